@@ -7,11 +7,19 @@ bench.py -- DV-Pari prover hot path on MI355X.
       per GPU over RCCL) BEFORE it touches a GPU, relays rank 0's JSON line and exits with the ranks' status.  Under a
       launcher (WORLD_SIZE set, e.g. the driver's torch.distributed.run) it is one of the ranks.
   python bench.py --gpus N --inproc          ONE process, in-library multi-GPU: dvp_set_devices(0..N-1)
+  --full                                     also everything below the headline (see "plain and --full")
+  --dump-outputs DIR                         write the last timed step's proof to DIR/*.npy (see "outputs")
 
 One "step" = one full Proof::prove (src/proving.rs:426-688) of a synthetic dense R1CS with 2^20 constraints (BASELINE
 config #4, the configuration the metric "R1CS constraints/sec (prove) at 2^20" is quoted on), witness already resident
 in HBM.  The K steps run ONE PROOF AT A TIME and that is `value` / `ms_per_step` (= the latency of a proof): the quantity
 the reference's prove() defines, and the loop the stage breakdown, the roofline block and the committed profiles describe.
+
+plain and --full: a plain run sets up, warms up, times the K steps, writes its outputs if asked and prints the line
+(`metric`, `value`, `unit`, `ms_per_step`, `dtype`, the configuration; with N > 1 also `rccl_ranks`, `backend` and every
+rank's own ms per step).  Its timed loop records no event scopes.  Everything else is --full, which runs as the benchmark
+always has: the dominant kernel's event scope in the timed loop, the stage pass, the roofline block, the CPU baseline, the
+verifier check of the last proof, the sidecar, and the legs described below.
 After the timed loop, outside it, the same proof is also run with two provers in flight on the GPU (own host thread and
 stream each, every proof byte-compared): `throughput_two_in_flight` -- a proving service's sustained rate, never `value`
 (--in-flight 1 skips that leg).  With N > 1 the two MSMs of the proof are sharded by index range over the ranks and combined by all-gather +
@@ -20,6 +28,10 @@ rank's own ms per step) and, beside it, the in-library figure for the same devic
 dvp_set_devices: one process, one host thread per device, peer copies -- measured by a child process after the ranks
 have released their GPUs).  Rank 0 prints ONE JSON line; the proof of the last step is checked with the
 designated-verifier equation (src/srs.rs:374-428) outside the timed region.
+
+outputs: --dump-outputs DIR writes the four fields of the last timed step's proof (what a caller of Proof::prove receives) as
+DIR/proof_commit_p.npy, proof_kzg_k.npy, proof_a0.npy, proof_b0.npy: one float64 per byte, little-endian byte order as in
+Proof::to_bytes.  The circuit, witness and trapdoor are seeded, so the same arguments give the same inputs on every run.
 
 roofline (dominant kernel = dvp::k_affine_round<true>, the first batched-affine pair round of each MSM: it gathers every
 base once per window).  `achieved` / `peak` / `frac` are the contract's figure -- algorithmic bytes (96 B per (scalar,
@@ -46,6 +58,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 PROFILE_TAG = "r06"
+TRAPDOOR = (0x1234567 + (1 << 200), 0x7654321 + (1 << 190), 0xABCDEF + (1 << 180))  # (tau, delta, epsilon) of every run
 LINE_LIMIT = 6000  # the driver keeps an 8 126-character tail of stdout: the ONE line must fit with room to spare
 LAUNCHER_VARS = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "ROLE_WORLD_SIZE", "GROUP_WORLD_SIZE",
                  "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID", "TORCHELASTIC_RESTART_COUNT", "TORCHELASTIC_MAX_RESTARTS",
@@ -133,19 +146,21 @@ def headline(full, detail_path=None):
         out["config"]["msm_windows"] = {k: _pick(v, ("c_bits", "windows", "table_gb")) for k, v in cfg["msm_windows"].items()}
     if isinstance(cfg.get("sharding"), str):
         out["config"]["sharding"] = cfg["sharding"][:120]
-    out["roofline"] = {"kernel": str(roof.get("kernel", ""))[:64], "bound": roof.get("bound"), "achieved": roof.get("achieved"), "peak": roof.get("peak"),
-                       "unit": roof.get("unit"), "frac": roof.get("frac"), "traffic": roof.get("traffic"),
-                       "avg_launch_ms": roof.get("avg_launch_ms"), "launches": roof.get("launches"),
-                       "algorithmic_bytes_per_launch": roof.get("algorithmic_bytes_per_launch"), "limiter": roof.get("limiter"),
-                       "work_model_frac": wm.get("frac"), "gather_model_frac": gm.get("frac"),
-                       "later_rounds": _pick(lr, ("ms_per_step", "launches_per_step", "achieved_gb_s", "frac_of_hbm_peak", "work_model_frac"))}
+    if roof:  # (a plain run measures no roofline: --full)
+        out["roofline"] = {"kernel": str(roof.get("kernel", ""))[:64], "bound": roof.get("bound"), "achieved": roof.get("achieved"), "peak": roof.get("peak"),
+                           "unit": roof.get("unit"), "frac": roof.get("frac"), "traffic": roof.get("traffic"),
+                           "avg_launch_ms": roof.get("avg_launch_ms"), "launches": roof.get("launches"),
+                           "algorithmic_bytes_per_launch": roof.get("algorithmic_bytes_per_launch"), "limiter": roof.get("limiter"),
+                           "work_model_frac": wm.get("frac"), "gather_model_frac": gm.get("frac"),
+                           "later_rounds": _pick(lr, ("ms_per_step", "launches_per_step", "achieved_gb_s", "frac_of_hbm_peak", "work_model_frac"))}
     if roof.get("per_msm"):
         out["roofline"]["per_msm"] = [_pick(p_, ("pairs", "avg_launch_ms", "frac", "work_model_frac")) for p_ in roof["per_msm"]]
     if cpu:
         out["cpu_baseline"] = _pick(cpu, ("value", "unit", "cores", "kind", "end_to_end_s", "composed_value", "msm_points_per_s",
                                           "best_cpu_pippenger_constraints_per_s"))
         out["cpu_baseline"]["sample"] = str(cpu.get("sample", ""))[:400]
-    out["stages_ms_per_step"] = full.get("stages_ms_per_step")
+    if "stages_ms_per_step" in full:
+        out["stages_ms_per_step"] = full["stages_ms_per_step"]
     if full.get("msm_standalone"):
         out["msm_standalone"] = full["msm_standalone"]
     by = {}
@@ -192,6 +207,15 @@ def write_detail(full):
     return name
 
 
+def dump_outputs(path, proof):
+    """--dump-outputs: the four fields of `proof` (Proof::to_bytes order) as DIR/proof_<field>.npy, one float64 per byte (exact)"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name in ("commit_p", "kzg_k", "a0", "b0"):
+        np.save(os.path.join(path, f"proof_{name}.npy"), np.frombuffer(bytes(getattr(proof, name)), dtype=np.uint8).astype(np.float64))
+
+
 def launch_ranks(args):
     """--gpus N > 1 and no launcher around us: start the ranks as children of a process that has not touched the GPU"""
     import socket
@@ -225,7 +249,7 @@ def run_inproc_child(args, share_gpu):
     """the in-library multi-GPU figure (dvp_set_devices) for the same device count, from a child process"""
     env = {k: v for k, v in os.environ.items() if k not in LAUNCHER_VARS}
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--inproc", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--log-m", str(args.log_m), "--no-cpu-baseline"]
+           "--log-m", str(args.log_m), "--no-cpu-baseline", "--full"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=float(os.environ.get("DVP_BENCH_INPROC_TIMEOUT", "150")))
     except subprocess.TimeoutExpired:
@@ -253,7 +277,12 @@ def main():
     ap.add_argument("--inproc", action="store_true", help="one process, in-library multi-GPU over devices 0..gpus-1 (dvp_set_devices)")
     ap.add_argument("--in-flight", type=int, default=2, help="2 (default): the extras leg after the timed loop also measures throughput with two proofs in flight "
                     "(throughput_two_in_flight); 1 skips it.  `value` is always one proof at a time")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: stage pass, roofline, CPU baseline, extras legs, "
+                    "N > 1 replicas and in-library legs, proof verification, sidecar.  The options above that shape those legs act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's proof to DIR/<name>.npy (float64, one value per byte)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and not args.inproc and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)  # never returns; nothing above this line touches the GPU
@@ -292,7 +321,7 @@ def main():
     # ---------------- untimed setup: circuit, witness, SRS (same seeds on every rank) ----------------------
     t0 = time.time()
     inst, pub, prv = dvp.gnark_r1cs.synthetic_dense(log_m)
-    td = dvp.srs.Trapdoor(0x1234567 + (1 << 200), 0x7654321 + (1 << 190), 0xABCDEF + (1 << 180))
+    td = dvp.srs.Trapdoor(*TRAPDOOR)
     pv = dvp.proving.Prover(inst)
     srs = dvp.srs.verifier_runs_setup(pv, inst, td)
     pv.set_srs(srs)
@@ -329,12 +358,13 @@ def main():
 
     for _ in range(args.warmup):
         proof = step()
-    # In the timed loop only the dominant kernel (the first pair round of each MSM) is bracketed by HIP events -- the roofline block's
+    # --full: in the timed loop only the dominant kernel (the first pair round of each MSM) is bracketed by HIP events -- the roofline block's
     # live launch time.  The stage breakdown (seven more event scopes per MSM, each a packet of its own that puts ~10 us between two
     # kernels) is measured in a pass of its own after the timed loop (DVP_BENCH_STAGE_EVENTS=1: everything in the timed loop, as in rounds 1-5)
     stage_events_in_loop = os.environ.get("DVP_BENCH_STAGE_EVENTS") == "1"
-    dvp.lib.dvp_profile_reset()
-    dvp.lib.dvp_profile_enable(1 if stage_events_in_loop else 2)
+    if args.full:  # a plain run times the prover without event scopes
+        dvp.lib.dvp_profile_reset()
+        dvp.lib.dvp_profile_enable(1 if stage_events_in_loop else 2)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -346,6 +376,62 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    rank_ms = [own_elapsed / args.steps * 1e3]
+    dist_info = None
+    if world > 1:
+        t = torch.tensor([elapsed, own_elapsed], dtype=torch.float64, device=dev)
+        allt = [torch.empty_like(t) for _ in range(world)]
+        dist.all_gather(allt, t)
+        elapsed = max(float(x[0].item()) for x in allt)
+        rank_ms = [float(x[1].item()) / args.steps * 1e3 for x in allt]
+        dist_info = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend()}
+    if world > 1 and args.replicas:
+        dist_info["replicas"] = {"n": world, "constraints_per_s": m * args.steps * world / elapsed, "ms_per_proof_each": rank_ms}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proof)
+    ms_per_step = elapsed / args.steps * 1e3
+    value = m * args.steps / elapsed * (world if (args.replicas and world > 1) else 1)
+    head = {
+        "metric": "R1CS constraints/sec (prove)",
+        "value": value,
+        "unit": "constraints/s",
+        "n_gpus": args.gpus,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak" if (args.replicas and world > 1) else "strong",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic",
+    }
+    head_config = {
+        "workload": f"Proof::prove, synthetic dense R1CS, 2^{log_m} constraints" + (" (BASELINE config #4)" if log_m == 20 else ""),
+        "log2_constraints": log_m,
+        "n_wires": inst.n_wires,
+        "msm_pairs_per_proof": inst.n_wires + 5 * m,
+        "sharding": ("in-library (dvp_set_devices): MSM index ranges per device, one host thread each, partial points added on device 0"
+                     if n_dev_inproc > 1 else
+                     "independent replicas: one whole proof per rank per step, no data-path collective" if (args.replicas and world > 1) else
+                     "MSM index ranges per rank, all-gather of partial points + local add; extends by vector among the ranks that need q2 / r2 "
+                     "(from three such ranks up: one broadcast per vector); challenge "
+                     "phase (inversions, barycentric sums, K scalars) by index with one all-gather of 128-byte records" if world > 1 else "single GPU"),
+    }
+    head_entry = ("dvp_prove_dev (Proof::prove with the witness resident)" if (args.inproc or world == 1 or args.replicas)
+                  else "phased entries, MSMs sharded over the ranks")
+    if not args.full:
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+            if rank != 0:
+                return
+        out = {**head, "config": {**head_config, "witness": "resident in HBM", "entry": head_entry, "proofs_in_flight": 1}}
+        if dist_info:
+            out.update(dist_info)
+            out["ms_per_step_ranks"] = rank_ms
+        out["scaling_measured"] = bool(world > 1 or n_dev_inproc > 1)
+        print(json.dumps(headline(out)), flush=True)
+        return
     dvp.lib.dvp_profile_enable(0)
     torch.cuda.synchronize()
     # the dominant kernel's figures belong to the TIMED loop: read them before the stage pass resets the slots
@@ -366,18 +452,7 @@ def main():
             step()
         torch.cuda.synchronize()
         dvp.lib.dvp_profile_enable(0)
-    rank_ms = [own_elapsed / args.steps * 1e3]
-    dist_info = None
-    if world > 1:
-        t = torch.tensor([elapsed, own_elapsed], dtype=torch.float64, device=dev)
-        allt = [torch.empty_like(t) for _ in range(world)]
-        dist.all_gather(allt, t)
-        elapsed = max(float(x[0].item()) for x in allt)
-        rank_ms = [float(x[1].item()) / args.steps * 1e3 for x in allt]
-        dist_info = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend()}
-    if world > 1 and args.replicas:
-        dist_info["replicas"] = {"n": world, "constraints_per_s": m * args.steps * world / elapsed, "ms_per_proof_each": rank_ms}
-    elif world > 1:
+    if world > 1 and not args.replicas:
         # every rank's own stage times (HIP events of its own launches) and its slice of the plan, so that a bad plan shows in one run
         mine = {"rank": rank}
         for nm in ("msm_total", "msm_sort", "msm_affine_round0", "msm_affine_rest", "msm_tail", "extend_total"):
@@ -472,8 +547,6 @@ def main():
     # correctness of what was timed: the proof must verify
     assert dvp.srs.verify(td, pub, proof), "bench proof does not verify"
     n_shards = (1 if args.replicas else world) * n_dev_inproc
-    ms_per_step = elapsed / args.steps * 1e3
-    value = m * args.steps / elapsed * (world if (args.replicas and world > 1) else 1)
     single = world == 1 and n_dev_inproc == 1
     # `value` / `ms_per_step` are ONE PROOF AT A TIME: the quantity BASELINE's metric measures (the reference's prove() is one proof
     # per call), and the loop that stages_ms_per_step, the roofline block and every committed profile describe.  Throughput with
@@ -796,33 +869,13 @@ def main():
         roof["request_size_experiment"] = {"source": f"profiles/{g64['_profile_tag']}_gather64_load_forms.json (tools/ubench/gather64.hip under rocprofv3 --pmc)",
                                            "fabric_read_bytes_per_64_byte_point": {v["variant"]: round(v["fabric_read_bytes_per_point"], 1) for v in g64["variants"]}}
     out = {
-        "metric": "R1CS constraints/sec (prove)",
-        "value": value,
-        "unit": "constraints/s",
-        "n_gpus": args.gpus,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak" if (args.replicas and world > 1) else "strong",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic",
+        **head,
         "config": {
-            "workload": f"Proof::prove, synthetic dense R1CS, 2^{log_m} constraints" + (" (BASELINE config #4)" if log_m == 20 else ""),
-            "log2_constraints": log_m,
-            "n_wires": inst.n_wires,
-            "msm_pairs_per_proof": inst.n_wires + 5 * m,
-            "sharding": ("in-library (dvp_set_devices): MSM index ranges per device, one host thread each, partial points added on device 0"
-                         if n_dev_inproc > 1 else
-                         "independent replicas: one whole proof per rank per step, no data-path collective" if (args.replicas and world > 1) else
-                         "MSM index ranges per rank, all-gather of partial points + local add; extends by vector among the ranks that need q2 / r2 "
-                         "(from three such ranks up: one broadcast per vector); challenge "
-                         "phase (inversions, barycentric sums, K scalars) by index with one all-gather of 128-byte records" if world > 1 else "single GPU"),
+            **head_config,
             "msm_windows": {"commit_msm": {"c_bits": plans[0][0], "windows": plans[0][1], "signed_windows": tables[0][1], "table_gb": round(tables[0][0] / 1e9, 2)},
                             "k_msm": {"c_bits": plans[1][0], "windows": plans[1][1], "signed_windows": tables[1][1], "table_gb": round(tables[1][0] / 1e9, 2)}},
             "witness": "resident in HBM",
-            "entry": "dvp_prove_dev (Proof::prove with the witness resident)" if (args.inproc or world == 1 or args.replicas) else "phased entries, MSMs sharded over the ranks",
+            "entry": head_entry,
             "proofs_in_flight": 1,
             "latency_ms_one_proof": ms_per_step,
             "ms_per_step_one_shot_msm": ms_one_shot,

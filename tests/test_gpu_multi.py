@@ -93,7 +93,7 @@ def test_bench_self_launch_rehearsal(dvp):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     n = 4
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--log-m", "14"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--log-m", "14"],
                          capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -128,7 +128,7 @@ def test_bench_replicas_mode_rehearsal(dvp):
     env = dict(os.environ, DVP_BENCH_SHARE_GPU="1", DVP_DIST_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--replicas", "--steps", "3", "--warmup", "1", "--log-m", "12"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--replicas", "--steps", "3", "--warmup", "1", "--log-m", "12"],
                          capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -143,6 +143,42 @@ def test_bench_replicas_mode_rehearsal(dvp):
     assert "ms_per_step_inproc" not in d and "replicas_error" not in d
     full = json.load(open(os.path.join(ROOT, d["detail"])))
     assert "shard_plan" not in full
+
+
+def test_bench_plain_sharded_rehearsal(dvp, tmp_path):
+    """a plain `python bench.py --gpus 2` (no --full): the ranks time the sharded proof, leave the group, and rank 0 alone prints
+    the line -- what ran and every rank's own ms per step, nothing measured under --full -- and dumps the last proof, which is
+    the single-GPU proof of the same instance.  Rehearsed with both ranks on cuda:0 over gloo."""
+    import json
+    import subprocess
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    env = dict(os.environ, DVP_BENCH_SHARE_GPU="1", DVP_DIST_BACKEND="gloo")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out_dir = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-m", "12",
+                          "--dump-outputs", str(out_dir)], capture_output=True, text=True, env=env, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["backend"] == "gloo" and d["scaling"] == "strong"
+    assert len(d["ms_per_step_ranks"]) == 2 and all(ms > 0 for ms in d["ms_per_step_ranks"]) and d["ms_per_step"] > 0
+    assert d["scaling_measured"] is True and d["config"]["entry"] == "phased entries, MSMs sharded over the ranks"
+    for k in ("roofline", "shard_plan", "replicas", "ms_per_step_inproc", "stages_ms_per_step"):
+        assert k not in d, k
+    assert d["detail"] is None
+    got = b"".join(np.load(out_dir / f"proof_{n}.npy").astype(np.uint8).tobytes() for n in ("commit_p", "kzg_k", "a0", "b0"))
+    inst, pub, prv = dvp.gnark_r1cs.synthetic_dense(12)
+    pv = dvp.proving.Prover(inst)
+    try:
+        pv.set_srs(dvp.srs.verifier_runs_setup(pv, inst, dvp.srs.Trapdoor(*bench.TRAPDOOR)))
+        assert got == pv.prove(pub, prv).to_bytes()
+    finally:
+        pv.close()
 
 
 @pytest.mark.parametrize("world", [2])

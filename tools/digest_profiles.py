@@ -76,7 +76,7 @@ alg = b["roofline"]["algorithmic_bytes_per_launch"]
 f_kb, w_kb = avg(fetch, "FETCH_SIZE"), avg(write, "WRITE_SIZE")
 traffic = {
     "kernel": "dvp::k_affine_round<true>, first pair round of each MSM",
-    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes, counters + --kernel-trace only) -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline",
+    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes, counters + --kernel-trace only) -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline",
     "launches": len(fetch),
     "avg_FETCH_SIZE_KB": f_kb,
     "avg_WRITE_SIZE_KB": w_kb,
@@ -127,7 +127,7 @@ valu, lds = avg(sq, "SQ_INSTS_VALU"), avg(sq, "SQ_INSTS_LDS")
 issue = {
     "kernel": traffic["kernel"],
     "source": "rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --kernel-trace "
-              "-- python bench.py --steps 2 --warmup 1 --no-cpu-baseline (averages over the first-round launches)",
+              "-- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline (averages over the first-round launches)",
     "launches": len(sq),
     "avg_duration_ms_under_pmc": avg(sq, "ms"),
     "counters_per_launch": {k: avg(sq, k) for k in ("SQ_INSTS_VALU", "SQ_INSTS_LDS", "SQ_WAVE_CYCLES", "SQ_BUSY_CYCLES", "SQ_WAVES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "GRBM_GUI_ACTIVE")},

@@ -62,7 +62,7 @@ def by_round():
     m = 1 << cfg["log2_constraints"]
     pairs = [cfg["n_wires"] + m, 4 * m]
     windows = [cfg["msm_windows"]["commit_msm"]["windows"], cfg["msm_windows"]["k_msm"]["windows"]]
-    out = {"source": "four separate rocprofv3 --pmc passes (counters + --kernel-trace only) of `python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras "
+    out = {"source": "four separate rocprofv3 --pmc passes (counters + --kernel-trace only) of `python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras "
                      "--in-flight 1`: TCC_EA0_RDREQ_sum/_32B/_64B/_128B; TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_DRAM_sum TCC_REQ_sum; TCC_EA0_WRREQ_sum "
                      "TCC_EA0_WRREQ_64B_sum WRITE_SIZE; SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE.  "
                      "Rows = the pair rounds of the LAST proof of each pass, matched by position (the launch sequence is deterministic).",
