@@ -136,6 +136,10 @@ _SIGS = {
     "dvp_cache_dir_prover": (C.c_int, [C.c_char_p, u32, C.POINTER(vp)]),
     "dvp_transcript_challenge": (C.c_int, [u8p, u64p, u32, u64p]),
     "dvp_blake3": (C.c_int, [u8p, sz, u8p]),
+    "dvp_verify": (C.c_int, [u64p, u64p, u64p, u64p, u32, u8p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "dvp_verify_batch": (C.c_int, [u64p, u64p, u64p, u64p, u32, u8p, sz, u8p]),
+    "dvp_verify_batch_dev": (C.c_int, [u64p, u64p, u64p, vp, u32, vp, sz, vp, vp]),
+    "dvp_sp1_public_input": (C.c_int, [C.c_uint64, u64p]),
 }
 EXPORTED = []
 for _name, (_res, _args) in _SIGS.items():

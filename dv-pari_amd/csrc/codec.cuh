@@ -1,6 +1,7 @@
 // The 30-byte presentation of an encoded point (shared by codec.hip's kernels and the MSM tail, which encodes its own result).
 #pragma once
 #include "k233.cuh"
+#include "tau.cuh"
 
 namespace dvp {
 
@@ -44,5 +45,56 @@ __device__ __forceinline__ Gf load30(const uint8_t* src, uint32_t* top_bits, int
   *top_bits = w.w[7] >> 9;
   return w;
 }
+
+// P in E[r] (affine, x != 0)?  E[r] = 4E: Tr(x) = 0 and a half of P has Tr(x_half) = 0.
+// half-trace through the byte table (30 lookups instead of 232 squarings)
+__device__ __forceinline__ bool k233_in_subgroup(const Aff& p, const GfSqrTables& T, const GfLdsK& L) {
+  if (gf_is_zero(p.x)) return false;
+  if (gf_trace(p.x)) return false;
+  Gf lam = gf_sqr_tab(p.x, T.th);                   // lam^2 + lam = x
+  Gf u2 = gf_add(p.y, gf_mul(gf_add(lam, gf_one()), p.x, L));  // x_half^2
+  return gf_trace(u2) == 0;
+}
+
+// One 30-byte encoding -> the E[r] representative (codec.hip's k_decode and verify.hip's k_verify).  Returns false for an
+// invalid encoding (spare top bits set, no curve point, or no root in E[r]); then r = 0 and is_inf is left false.  A valid
+// encoding decodes to the unique point whose encoding (k_encode) is these 30 bytes again.
+__device__ __forceinline__ bool codec_decode(const uint8_t* enc, int rule, const GfSqrTables& T, const GfLdsK& L, Aff& r, bool& is_inf) {
+  uint32_t top;
+  Gf w = load30(enc, &top, rule);
+  r.x = gf_zero();
+  r.y = gf_zero();
+  bool ok = (top == 0);
+  is_inf = false;
+  if (ok && gf_is_zero(w)) {
+    is_inf = true;
+  } else if (ok) {
+    if (rule) w = codec_absorb(w, rule, T);
+    Gf w2 = gf_sqr(w);
+    Gf e = gf_add(w2, w);
+    ok = !gf_is_zero(e);
+    if (ok) {
+      Gf einv = gf_inv_fast(e, T, L);
+      Gf cst = gf_sqr(einv);  // 1/e^2
+      ok = gf_trace(cst) == 0;
+      if (ok) {
+        Gf z = gf_sqr_tab(cst, T.th);   // half-trace: z^2 + z = 1/e^2
+        Gf lam = gf_add(w2, gf_one());  // x + y/x
+        Aff c0, c1;
+        c0.x = gf_mul(e, z, L);
+        c1.x = gf_add(c0.x, e);
+        c0.y = gf_mul(c0.x, gf_add(lam, c0.x), L);
+        c1.y = gf_mul(c1.x, gf_add(lam, c1.x), L);
+        bool s0 = k233_in_subgroup(c0, T, L), s1 = k233_in_subgroup(c1, T, L);
+        if (s0) r = c0; else if (s1) r = c1; else ok = false;
+      }
+    }
+  }
+  return ok;
+}
+
+// ---- fixed-base tables of the generator (codec.hip: gen_table): tab[w][d] = sum_t d_t tau^(c w + t)(G), affine ----------
+constexpr int GEN_C = 16;  // 15 windows, 63 MB table (L2 / Infinity-Cache resident): 15 mixed additions per scalar
+constexpr int GEN_W = TAU_DIGITS / GEN_C;  // 15
 
 }  // namespace dvp

@@ -34,16 +34,6 @@ __constant__ uint32_t K233_GX[8] = {0xefad6126u, 0x0a4c9d6eu, 0x19c26bf5u, 0x149
 __constant__ uint32_t K233_GY[8] = {0x56fae6a3u, 0x56e0c110u, 0xf18aeb9bu, 0x27a8cd9bu,
                                     0x555a67c4u, 0x19b7f70fu, 0x537dece8u, 0x000001dbu};
 
-// P in E[r] (affine, x != 0)?  E[r] = 4E: Tr(x) = 0 and a half of P has Tr(x_half) = 0.
-// half-trace through the byte table (30 lookups instead of 232 squarings)
-__device__ __forceinline__ bool k233_in_subgroup(const Aff& p, const GfSqrTables& T, const GfLdsK& L) {
-  if (gf_is_zero(p.x)) return false;
-  if (gf_trace(p.x)) return false;
-  Gf lam = gf_sqr_tab(p.x, T.th);                   // lam^2 + lam = x
-  Gf u2 = gf_add(p.y, gf_mul(gf_add(lam, gf_one()), p.x, L));  // x_half^2
-  return gf_trace(u2) == 0;
-}
-
 __device__ __forceinline__ bool k233_on_curve(const Aff& p) {
   // y^2 + xy = x^3 + 1
   Gf lhs = gf_add(gf_sqr(p.y), gf_mul(p.x, p.y));
@@ -91,36 +81,9 @@ k_decode(const uint8_t* __restrict__ enc, size_t n, GfSqrTables T, Aff* __restri
   GfLdsK L = gf_ldsk_init(lds_raw);
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint32_t top;
-  Gf w = load30(enc + i * 30, &top, rule);
   Aff r;
-  r.x = gf_zero();
-  r.y = gf_zero();
-  bool ok = (top == 0), is_inf = false;
-  if (ok && gf_is_zero(w)) {
-    is_inf = true;
-  } else if (ok) {
-    if (rule) w = codec_absorb(w, rule, T);
-    Gf w2 = gf_sqr(w);
-    Gf e = gf_add(w2, w);
-    ok = !gf_is_zero(e);
-    if (ok) {
-      Gf einv = gf_inv_fast(e, T, L);
-      Gf cst = gf_sqr(einv);  // 1/e^2
-      ok = gf_trace(cst) == 0;
-      if (ok) {
-        Gf z = gf_sqr_tab(cst, T.th);   // half-trace: z^2 + z = 1/e^2
-        Gf lam = gf_add(w2, gf_one());  // x + y/x
-        Aff c0, c1;
-        c0.x = gf_mul(e, z, L);
-        c1.x = gf_add(c0.x, e);
-        c0.y = gf_mul(c0.x, gf_add(lam, c0.x), L);
-        c1.y = gf_mul(c1.x, gf_add(lam, c1.x), L);
-        bool s0 = k233_in_subgroup(c0, T, L), s1 = k233_in_subgroup(c1, T, L);
-        if (s0) r = c0; else if (s1) r = c1; else ok = false;
-      }
-    }
-  }
+  bool is_inf;
+  bool ok = codec_decode(enc + i * 30, rule, T, L, r, is_inf);
   if (!ok) {
     atomicMin(err, (unsigned long long)i);
     is_inf = true;
@@ -130,8 +93,6 @@ k_decode(const uint8_t* __restrict__ enc, size_t n, GfSqrTables T, Aff* __restri
 }
 
 // ---- fixed-base tables: tab[w][d] = sum_t d_t tau^(c w + t)(G), affine ------------------------------
-constexpr int GEN_C = 16;  // 15 windows, 63 MB table (L2 / Infinity-Cache resident): 15 mixed additions per scalar
-constexpr int GEN_W = TAU_DIGITS / GEN_C;  // 15
 
 __global__ void __launch_bounds__(256) k_gen_table(Aff* __restrict__ tab) {
   uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -212,6 +173,8 @@ static int codec_rule() {
   }
   return r;
 }
+
+int codec_rule_now() { return codec_rule(); }  // verify.hip
 
 static std::mutex g_gen_mu;
 static Aff* g_gen_tab[16] = {nullptr};

@@ -1,0 +1,375 @@
+// The designated verifier's check, SRS::verify (src/srs.rs:374-428), for a batch of proofs against one trapdoor: one lane per
+// proof, ONE launch per batch (k_verify) once the generator table exists.
+//
+//   CurvePoint::from_bytes of commit_p / kzg_k   src/srs.rs:380-382       -> codec_decode (codec.cuh, shared with k_decode)
+//   Transcript (empty SRS / circuit, pub, P)     src/srs.rs:384-410       -> b3d (blake3_dev.cuh, shared with k_transcript)
+//   evaluate_monomial_basis_poly                 src/gnark_r1cs.rs:391-399 -> Horner in Montgomery Fr
+//   FrBits::to_fr of a0 / b0                     src/curve.rs:43-59       -> fr_below_p
+//   multi_scalar_mul(&[v0, u0], &[K, G]) == P    src/srs.rs:418-424       -> tau-adic v0 K + fixed-base u0 G, compared with P
+//
+// Per lane: v0 K runs right to left over the tau-adic digits of v0 (tau.cuh: the partial reduction and sixteen digits per step,
+// as the one-shot MSM recodes), with the running point tau^i(K) kept AFFINE -- a Frobenius step is two squarings -- and added into
+// a Lopez-Dahab accumulator by the complete mixed addition (ld_madd_ip: P = Q, P = -Q and the neutral element on either side, so
+// adversarial K and P cannot trip it).  u0 G continues in the same accumulator through the process-wide generator table
+// (gen_table: 15 windows of 16 digits, the 15 mixed additions of k_mulgen).  The sum is compared with P by cross-multiplication:
+// X == x(P) Z and Y == y(P) Z^2, no inversion.
+//
+// Public inputs: n_public <= 35 is one BLAKE3 chunk; larger counts are hashed multi-chunk on the device, per lane, with the
+// chaining values of complete subtrees kept in registers (VERIFY_B3_LEVELS levels: up to 2^8 chunks = DVP_VERIFY_MAX_PUBLIC
+// public inputs).  The 30 bytes of commit_p are hashed as they arrive: a valid encoding is the unique encoding of the point it
+// decodes to (codec_decode), so they equal witness_commitment_hash's re-encoding, and an invalid one rejects the proof anyway.
+#include <cstring>
+
+#include "blake3.h"
+#include "blake3_dev.cuh"
+#include "codec.cuh"
+#include "common.h"
+#include "fr.cuh"
+#include "k233.cuh"
+#include "tau.cuh"
+
+namespace dvp {
+
+int gen_table(const Aff** out, hipStream_t st);
+int gf_sqr_tables(GfSqrTables* out, hipStream_t st);
+int codec_rule_now();
+
+constexpr uint32_t VERIFY_B3_LEVELS = 8;
+constexpr uint32_t VERIFY_MAX_PUBLIC = DVP_VERIFY_MAX_PUBLIC;
+static_assert((size_t)VERIFY_MAX_PUBLIC * 29 <= ((size_t)1024 << VERIFY_B3_LEVELS), "public inputs beyond the subtree levels");
+
+struct VerifyConsts {
+  Fr tau;       // canonical
+  Fr delta_m;   // delta * R
+  Fr delta2_m;  // delta^2 * R
+  Fr eps_m;     // epsilon * R
+  b3d::Words8 h_ct;  // H(H(empty) || H(empty)): the compile-time half of the transcript (src/srs.rs:386-404)
+};
+
+// a < p for 8 little-endian 32-bit limbs (FrBits::to_fr's validity flag when the top limb holds byte 28 only)
+__device__ __forceinline__ bool fr_below_p(const Fr& a) {
+  uint64_t borrow = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    uint64_t t = (uint64_t)a.v[k] - fr_p_limb(k) - borrow;
+    borrow = (t >> 63) & 1;
+  }
+  return borrow != 0;
+}
+
+// 29 little-endian bytes (FrBits) -> 8 limbs
+__device__ __forceinline__ Fr load29(const uint8_t* src) {
+  Fr a;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) a.v[k] = 0;
+#pragma unroll
+  for (int b = 0; b < 29; ++b) a.v[b >> 2] |= (uint32_t)src[b] << (8 * (b & 3));
+  return a;
+}
+
+// 16 message words of block `blk_off` (byte offset) of the public-input buffer: each Fr as its 29-byte LE (src/proving.rs:147-150)
+__device__ __forceinline__ void pub_block(const uint8_t* pub, uint32_t len, uint32_t blk_off, uint32_t m[16]) {
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const uint32_t off = blk_off + 4 * k + b;
+      if (off < len) {
+        const uint32_t j = off / 29u, r = off - 29u * j;
+        w |= (uint32_t)pub[32 * (size_t)j + r] << (8 * b);
+      }
+    }
+    m[k] = w;
+  }
+}
+
+// BLAKE3 of the n_pub x 29 public-input bytes (any length up to 2^VERIFY_B3_LEVELS chunks): the BLAKE3 tree with the chaining
+// values of complete subtrees in lv[level] -- indexed only by compile-time constants (selects), so the stack stays in registers
+__device__ __forceinline__ void pub_digest(const uint8_t* pub, uint32_t npub, uint32_t out[8]) {
+  constexpr uint32_t IV[8] = {0x6A09E667u, 0xBB67AE85u, 0x3C6EF372u, 0xA54FF53Au, 0x510E527Fu, 0x9B05688Cu, 0x1F83D9ABu, 0x5BE0CD19u};
+  constexpr uint32_t CHUNK_START = 1, CHUNK_END = 2, PARENT = 4, ROOT = 8;
+  const uint32_t len = 29u * npub;
+  const uint32_t nchunks = len ? (len + 1023) / 1024 : 1;
+  uint32_t lv[VERIFY_B3_LEVELS][8];
+#pragma unroll
+  for (uint32_t l = 0; l < VERIFY_B3_LEVELS; ++l)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) lv[l][i] = 0;
+  uint32_t cv[8], m[16];
+#pragma unroll 1
+  for (uint32_t c = 0; c < nchunks; ++c) {
+    const uint32_t c_off = 1024 * c, c_len = min(1024u, len - c_off);
+    const uint32_t nblocks = c_len ? (c_len + 63) / 64 : 1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) cv[i] = IV[i];
+#pragma unroll 1
+    for (uint32_t b = 0; b < nblocks; ++b) {
+      pub_block(pub, len, c_off + 64 * b, m);
+      const bool last = b + 1 == nblocks;
+      const uint32_t fl = (b == 0 ? CHUNK_START : 0u) | (last ? CHUNK_END : 0u) | (last && nchunks == 1 ? ROOT : 0u);
+      b3d::compress(cv, m, last ? c_len - 64 * b : 64u, fl, c);
+    }
+    if (c + 1 == nchunks) break;
+    // more chunks follow: merge the complete subtrees below this one (binary increment of the chunk count)
+    uint32_t l = 0;
+#pragma unroll 1
+    while ((c >> l) & 1u) {
+#pragma unroll
+      for (uint32_t q = 0; q < VERIFY_B3_LEVELS; ++q)
+        if (q == l) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) { m[i] = lv[q][i]; m[8 + i] = cv[i]; }
+        }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) cv[i] = IV[i];
+      b3d::compress(cv, m, 64, PARENT);
+      ++l;
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < VERIFY_B3_LEVELS; ++q)
+      if (q == l) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) lv[q][i] = cv[i];
+      }
+  }
+  // finalise: the last chunk folded into the pending subtrees, smallest first; the last parent is the root
+  const uint32_t rest = nchunks - 1;
+#pragma unroll 1
+  for (uint32_t l = 0; rest >> l; ++l) {
+    if (!((rest >> l) & 1u)) continue;
+#pragma unroll
+    for (uint32_t q = 0; q < VERIFY_B3_LEVELS; ++q)
+      if (q == l) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { m[i] = lv[q][i]; m[8 + i] = cv[i]; }
+      }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) cv[i] = IV[i];
+    b3d::compress(cv, m, 64, PARENT | ((rest >> (l + 1)) ? 0u : ROOT));
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out[i] = cv[i];
+}
+
+// acc += q (q affine, finite), complete and without branches: the Lopez-Dahab mixed addition, whose Z3 = (Z1 B)^2 is already 0
+// (the neutral element) for acc = -q; acc = q selects 2q instead (from q alone, Z = 1: 1M + 3S), acc = O selects q.  Branches here
+// (ld_madd_ip's inlined doubling) put the accumulator in scratch: k_mulgen keeps 272 B per lane.
+template <class LT>
+__device__ __forceinline__ void madd_complete(Ld& acc, const Aff& q, const LT& L) {
+  const bool acc_inf = gf_is_zero(acc.Z);
+  const Gf A = gf_add(acc.Y, gf_mul(q.y, gf_sqr(acc.Z), L));
+  const Gf B = gf_add(acc.X, gf_mul(q.x, acc.Z, L));
+  const bool dbl = !acc_inf && gf_is_zero(B) && gf_is_zero(A);
+  const Gf C = gf_mul(B, acc.Z, L);
+  Gf D, E;
+  gf_mul2(gf_sqr(B), A, C, L, D, E);
+  const Gf Z3 = gf_sqr(C);
+  const Gf X3 = gf_add(gf_add(gf_sqr(A), D), E);
+  const Gf F = gf_add(X3, gf_mul(q.x, Z3, L));
+  const Gf G = gf_mul(gf_add(q.x, q.y), gf_sqr(Z3), L);
+  const Gf Y3 = gf_add(gf_mul(gf_add(E, Z3), F, L), G);
+  // 2q: Z = x^2, X = x^4 + 1, Y = Z + X (y^2 + 1)   (ld_dbl with Z1 = 1)
+  const Gf dZ = gf_sqr(q.x);
+  const Gf dX = gf_add(gf_sqr(dZ), gf_one());
+  const Gf dY = gf_add(dZ, gf_mul(dX, gf_add(gf_sqr(q.y), gf_one()), L));
+  acc.X = gf_select(acc_inf, q.x, gf_select(dbl, dX, X3));
+  acc.Y = gf_select(acc_inf, q.y, gf_select(dbl, dY, Y3));
+  acc.Z = gf_select(acc_inf, gf_one(), gf_select(dbl, dZ, Z3));
+}
+
+// one wave per SIMD: the 256 architectural VGPRs plus accumulation registers for what does not fit (no scratch); at two waves per
+// SIMD the tau-adic loop spills ~300 B per lane to scratch
+__global__ void __launch_bounds__(256, 1)
+k_verify(const uint8_t* __restrict__ proofs, size_t n, const Fr* __restrict__ pub, uint32_t npub, VerifyConsts K, const Aff* __restrict__ tab,
+         GfSqrTables T, int rule, uint8_t* __restrict__ verdicts) {
+  extern __shared__ char lds_raw[];
+  GfLdsK L = gf_ldsk_init(lds_raw);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* pr = proofs + 118 * i;
+  const Fr* pi = pub + (size_t)npub * i;
+  uint32_t bad = 0;
+  Aff P, Kp;
+  bool p_inf, k_inf;
+  if (!codec_decode(pr, rule, T, L, P, p_inf)) bad |= DVP_VERIFY_BAD_COMMIT_P;
+  if (!codec_decode(pr + 30, rule, T, L, Kp, k_inf)) bad |= DVP_VERIFY_BAD_KZG_K;
+  const Fr a0 = load29(pr + 60), b0 = load29(pr + 89);
+  if (!fr_below_p(a0)) bad |= DVP_VERIFY_BAD_A0;
+  if (!fr_below_p(b0)) bad |= DVP_VERIFY_BAD_B0;
+#pragma unroll 1
+  for (uint32_t j = 0; j < npub; ++j)
+    if (!fr_below_p(pi[j])) bad |= DVP_VERIFY_BAD_PUBLIC;
+  if (bad) {
+    verdicts[i] = (uint8_t)bad;
+    return;
+  }
+  // alpha = Transcript::output: H(H_ct || H(H(commit_p) || H(pub))), top four bytes cleared (src/proving.rs:164-197)
+  Fr alpha;
+  {
+    uint32_t blk[16], h_wc[8], h_pi[8], h_rt[8], out[8];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) blk[k] = 0;
+#pragma unroll
+    for (int b = 0; b < 30; ++b) blk[b >> 2] |= (uint32_t)pr[b] << (8 * (b & 3));
+    b3d::hash_chunk(blk, 30, h_wc);
+    pub_digest((const uint8_t*)pi, npub, h_pi);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { blk[k] = h_wc[k]; blk[8 + k] = h_pi[k]; }
+    b3d::hash_chunk(blk, 64, h_rt);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { blk[k] = K.h_ct.w[k]; blk[8 + k] = h_rt[k]; }
+    b3d::hash_chunk(blk, 64, out);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) alpha.v[k] = out[k];
+    alpha.v[7] = 0;  // 224 bits, always < p
+  }
+  // scalars (canonical throughout: mont_mul(x, c R) = x c)
+  const Fr alpha_m = fr_to_mont(alpha);
+  Fr i0 = fr_zero();
+#pragma unroll 1
+  for (uint32_t j = npub; j-- > 0;) i0 = fr_add(fr_mul(i0, alpha_m), pi[j]);  // sum_j pub_j alpha^j by Horner
+  const Fr r0 = fr_sub(fr_mul(a0, fr_to_mont(b0)), i0);
+  const Fr u0 = fr_mul(fr_add(fr_add(a0, fr_mul(b0, K.delta_m)), fr_mul(r0, K.delta2_m)), K.eps_m);
+  const Fr v0 = fr_mul(fr_sub(K.tau, alpha), K.eps_m);
+
+  Ld acc = ld_infinity();
+  uint32_t r0t[5], r1t[5];
+  // v0 K: sum_i d_i tau^i(K), digits low to high, tau^i(K) affine
+  if (!k_inf) {
+    tau_partial_reduce(v0.v, r0t, r1t);
+    Aff q = Kp;
+#pragma unroll 1
+    for (int s = 0; s < TAU_DIGITS / 16; ++s) {
+      const uint32_t dw = tau_step16(r0t, r1t);
+#pragma unroll 1
+      for (int t = 0; t < 16; ++t) {
+        if ((dw >> t) & 1u) madd_complete(acc, q, L);
+        q.x = gf_sqr(q.x);
+        q.y = gf_sqr(q.y);
+      }
+    }
+  }
+  // + u0 G through the generator table (k_mulgen's loop)
+  tau_partial_reduce(u0.v, r0t, r1t);
+#pragma unroll 1
+  for (int w = 0; w < GEN_W; ++w) {
+    const uint32_t d = tau_step16(r0t, r1t);
+    if (d) madd_complete(acc, tab[((size_t)w << GEN_C) + d], L);
+  }
+  bool eq;
+  if (ld_is_inf(acc) || p_inf) {
+    eq = ld_is_inf(acc) && p_inf;
+  } else {
+    eq = gf_eq(acc.X, gf_mul(P.x, acc.Z, L)) && gf_eq(acc.Y, gf_mul(P.y, gf_sqr(acc.Z), L));
+  }
+  verdicts[i] = eq ? 0 : (uint8_t)DVP_VERIFY_EQUATION;
+}
+
+static void fr_from_u64(const uint64_t* v, Fr* out) { memcpy(out->v, v, 32); }
+
+static bool fr_host_canonical(const uint64_t* v) {
+  for (int k = 3; k >= 0; --k) {
+    const uint64_t pk = (uint64_t)fr_p_limb(2 * k) | ((uint64_t)fr_p_limb(2 * k + 1) << 32);
+    if (v[k] != pk) return v[k] < pk;
+  }
+  return false;
+}
+
+static int verify_consts(const uint64_t tau[4], const uint64_t delta[4], const uint64_t eps[4], VerifyConsts* c) {
+  if (!tau || !delta || !eps) return DVP_EINVAL;
+  if (!fr_host_canonical(tau) || !fr_host_canonical(delta) || !fr_host_canonical(eps)) return DVP_EINVAL;
+  Fr t, d, e;
+  fr_from_u64(tau, &t);
+  fr_from_u64(delta, &d);
+  fr_from_u64(eps, &e);
+  c->tau = t;
+  c->delta_m = fr_to_mont(d);
+  c->delta2_m = fr_to_mont(fr_mul(c->delta_m, d));  // delta^2 (canonical), then times R
+  c->eps_m = fr_to_mont(e);
+  uint8_t h_empty[32], buf[64], h[32];
+  b3::hash(nullptr, 0, h_empty);
+  memcpy(buf, h_empty, 32);
+  memcpy(buf + 32, h_empty, 32);
+  b3::hash(buf, 64, h);
+  memcpy(c->h_ct.w, h, 32);
+  return DVP_OK;
+}
+
+static int verify_enqueue(const VerifyConsts& c, const void* d_pub, uint32_t npub, const void* d_proofs, size_t n, void* d_verdicts,
+                          hipStream_t st) {
+  const Aff* tab;
+  DVP_TRY(gen_table(&tab, st));
+  GfSqrTables T;
+  DVP_TRY(gf_sqr_tables(&T, st));
+  hipLaunchKernelGGL(k_verify, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
+                     (const Fr*)d_pub, npub, c, tab, T, codec_rule_now(), (uint8_t*)d_verdicts);
+  DVP_HIP(hipGetLastError());
+  return DVP_OK;
+}
+
+}  // namespace dvp
+
+using namespace dvp;
+
+extern "C" int dvp_verify_batch_dev(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const void* d_public_inputs,
+                                    uint32_t n_public, const void* d_proofs, size_t n, void* d_verdicts, void* stream) {
+  VerifyConsts c;
+  DVP_TRY(verify_consts(tau, delta, epsilon, &c));
+  if (n_public > VERIFY_MAX_PUBLIC) return DVP_EINVAL;
+  if (!n) return DVP_OK;
+  if (!d_proofs || !d_verdicts || (n_public && !d_public_inputs)) return DVP_EINVAL;
+  return verify_enqueue(c, d_public_inputs, n_public, d_proofs, n, d_verdicts, (hipStream_t)stream);
+}
+
+extern "C" int dvp_verify_batch(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const uint64_t* public_inputs,
+                                uint32_t n_public, const uint8_t* proofs, size_t n, uint8_t* verdicts) {
+  VerifyConsts c;
+  DVP_TRY(verify_consts(tau, delta, epsilon, &c));
+  if (n_public > VERIFY_MAX_PUBLIC) return DVP_EINVAL;
+  if (!n) return DVP_OK;
+  if (!proofs || !verdicts || (n_public && !public_inputs)) return DVP_EINVAL;
+  const size_t npub_all = (size_t)n_public * n;
+  for (size_t k = 0; k < npub_all; ++k)
+    if (!fr_host_canonical(public_inputs + 4 * k)) {
+      g_last_error_index = (int64_t)k;
+      return DVP_EINVAL;
+    }
+  DevBuf dp, dpub, dv;
+  DVP_TRY(dp.alloc(n * 118));
+  DVP_TRY(dpub.alloc(npub_all * 32));
+  DVP_TRY(dv.alloc(n));
+  DVP_HIP(hipMemcpy(dp.p, proofs, n * 118, hipMemcpyHostToDevice));
+  if (npub_all) DVP_HIP(hipMemcpy(dpub.p, public_inputs, npub_all * 32, hipMemcpyHostToDevice));
+  DVP_TRY(verify_enqueue(c, dpub.p, n_public, dp.p, n, dv.p, 0));
+  DVP_HIP(hipMemcpy(verdicts, dv.p, n, hipMemcpyDeviceToHost));
+  return DVP_OK;
+}
+
+extern "C" int dvp_verify(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const uint64_t* public_inputs,
+                          uint32_t n_public, const uint8_t proof[118], int* accepted, uint32_t* reasons) {
+  if (!proof || !accepted) return DVP_EINVAL;
+  uint8_t v = 0xff;
+  DVP_TRY(dvp_verify_batch(tau, delta, epsilon, public_inputs, n_public, proof, 1, &v));
+  *accepted = v == 0;
+  if (reasons) *reasons = v;
+  return DVP_OK;
+}
+
+// sp1_generate_scalar_from_raw_public_input (src/gnark_r1cs.rs:214-229): BLAKE3 of the 8-byte LE raw value, bytes 0..3 of the digest
+// cleared, the 32 bytes read BIG-endian -- a value < 2^224 < p (the loop multiplies by 256 per byte, whatever its comment says)
+extern "C" int dvp_sp1_public_input(uint64_t raw, uint64_t out[4]) {
+  if (!out) return DVP_EINVAL;
+  uint8_t le[8], h[32];
+  for (int b = 0; b < 8; ++b) le[b] = (uint8_t)(raw >> (8 * b));
+  b3::hash(le, 8, h);
+  for (int k = 0; k < 4; ++k) {
+    uint64_t w = 0;
+    for (int b = 0; b < 8; ++b) {
+      const int idx = 31 - (8 * k + b);  // byte 8k + b of the little-endian result
+      w |= (uint64_t)(idx < 4 ? 0 : h[idx]) << (8 * b);
+    }
+    out[k] = w;
+  }
+  return DVP_OK;
+}

@@ -171,3 +171,85 @@ def verify(td: Trapdoor, public_inputs, proof) -> bool:
     if lhs_inf or inf[0]:
         return bool(lhs_inf) and bool(inf[0])
     return bool((lhs == pts[0]).all())
+
+
+# ---- the verifier on the GPU (csrc/verify.hip): SRS::verify for many proofs at once, one verdict per proof ------------------
+VERIFY_BAD_COMMIT_P, VERIFY_BAD_KZG_K, VERIFY_BAD_A0, VERIFY_BAD_B0, VERIFY_BAD_PUBLIC, VERIFY_EQUATION = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+
+
+def _raw_limbs(v) -> np.ndarray:
+    """an int as 4 x u64 LE WITHOUT reduction (the C entries reject values >= p themselves)"""
+    return np.frombuffer(int(v).to_bytes(32, "little"), dtype="<u8").copy()
+
+
+def _trapdoor_args(td: Trapdoor):
+    from ._native import ptr
+
+    arrs = [_raw_limbs(x) for x in (td.tau, td.delta, td.epsilon)]
+    return arrs, [ptr(a) for a in arrs]
+
+
+def _proofs_array(proofs) -> np.ndarray:
+    from .proving import Proof
+
+    if isinstance(proofs, np.ndarray):
+        return np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, 118)
+    raw = b"".join(p.to_bytes() if isinstance(p, Proof) else bytes(p) for p in proofs)
+    return np.frombuffer(raw, dtype=np.uint8).reshape(-1, 118).copy()
+
+
+def _public_array(public_inputs, n: int) -> np.ndarray:
+    """n rows of public inputs -> n x n_public x 4 u64 (values taken as given: the C entry checks them)"""
+    if isinstance(public_inputs, np.ndarray) and public_inputs.dtype == np.uint64 and public_inputs.ndim == 3:
+        return np.ascontiguousarray(public_inputs)
+    rows = [list(r) for r in public_inputs]
+    assert len(rows) == n, (len(rows), n)
+    k = len(rows[0]) if rows else 0
+    assert all(len(r) == k for r in rows), "every proof needs the same number of public inputs"
+    out = np.zeros((n, k, 4), dtype=np.uint64)
+    if n and k:
+        buf = b"".join(int(v).to_bytes(32, "little") for r in rows for v in r)
+        out[:] = np.frombuffer(buf, dtype="<u8").reshape(n, k, 4)
+    return out
+
+
+def verify_batch(td: Trapdoor, public_inputs, proofs) -> np.ndarray:
+    """SRS::verify (src/srs.rs:374-428) for n proofs against one trapdoor on the GPU (dvp_verify_batch): proofs = a list of
+    Proof (or 118-byte strings) or an n x 118 uint8 array; public_inputs = one row per proof (list of lists, n x n_public ints
+    or n x n_public x 4 uint64 limbs).  Returns n uint8 verdicts: 0 = accepted, else VERIFY_* bits."""
+    from ._native import lib, check, ptr
+
+    pa = _proofs_array(proofs)
+    n = pa.shape[0]
+    pub = _public_array(public_inputs, n)
+    keep, (t, d, e) = _trapdoor_args(td)
+    out = np.zeros(n, dtype=np.uint8)
+    if n == 0:
+        return out
+    pub_buf = pub if pub.size else np.zeros(4, dtype=np.uint64)
+    check(lib.dvp_verify_batch(t, d, e, ptr(pub_buf), pub.shape[1], ptr(pa), n, ptr(out)), "dvp_verify_batch")
+    return out
+
+
+def verify_device(td: Trapdoor, public_inputs, proof) -> bool:
+    """SRS::verify for one proof through dvp_verify (the same kernel as verify_batch)"""
+    import ctypes as C
+
+    from ._native import lib, check, ptr
+
+    pa = _proofs_array([proof])
+    pub = _public_array([list(public_inputs)], 1)
+    pub_buf = pub if pub.size else np.zeros(4, dtype=np.uint64)
+    keep, (t, d, e) = _trapdoor_args(td)
+    acc, why = C.c_int(0), C.c_uint32(0)
+    check(lib.dvp_verify(t, d, e, ptr(pub_buf), pub.shape[1], ptr(pa), C.byref(acc), C.byref(why)), "dvp_verify")
+    return bool(acc.value)
+
+
+def sp1_public_input(raw: int) -> int:
+    """sp1_generate_scalar_from_raw_public_input, src/gnark_r1cs.rs:214-229 (dvp_sp1_public_input)"""
+    from ._native import lib, check, ptr
+
+    out = np.zeros(4, dtype=np.uint64)
+    check(lib.dvp_sp1_public_input(int(raw), ptr(out)), "dvp_sp1_public_input")
+    return fr.to_int(out)

@@ -1,0 +1,88 @@
+// Host program over the C ABI only (include/dvpari.h): the designated verifier's half of the reference's lifecycle,
+// `SRS::verify(secrets, public_inputs, proof)` (src/srs.rs:374-428), from files and the command line alone:
+//
+//   dvp_verify_cli <proof.bin> <tau> <delta> <epsilon> [<public input>...]
+//
+// proof.bin holds the 118 bytes of Proof::to_bytes (what dvp_prove_cli writes); the trapdoor values and the public inputs are
+// canonical field elements in hex (an optional 0x prefix).  Exit status: 0 accepted, 2 rejected (the DVP_VERIFY_* reason bits
+// are printed), 1 usage or I/O error, 3 no GPU.
+//
+// build:  g++ -O2 -std=c++17 -Iinclude examples/dvp_verify_cli.cpp -Ldv-pari_amd -ldvpari_hip -Wl,-rpath,$PWD/dv-pari_amd -o dvp_verify_cli
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "dvpari.h"
+
+// hex -> 4 x u64 little-endian limbs; false for anything that is not 1..64 hex digits
+static bool parse_hex(const char* s, uint64_t out[4]) {
+  if (s[0] == '0' && (s[1] == 'x' || s[1] == 'X')) s += 2;
+  const size_t len = strlen(s);
+  if (len == 0 || len > 64) return false;
+  memset(out, 0, 32);
+  for (size_t i = 0; i < len; ++i) {
+    const char c = s[len - 1 - i];
+    uint64_t v;
+    if (c >= '0' && c <= '9') v = (uint64_t)(c - '0');
+    else if (c >= 'a' && c <= 'f') v = (uint64_t)(c - 'a' + 10);
+    else if (c >= 'A' && c <= 'F') v = (uint64_t)(c - 'A' + 10);
+    else return false;
+    out[i / 16] |= v << (4 * (i % 16));
+  }
+  return true;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 5) {
+    fprintf(stderr, "usage: %s <proof.bin> <tau> <delta> <epsilon> [<public input>...]   (hex, canonical)\n", argv[0]);
+    return 1;
+  }
+  uint64_t td[3][4];
+  for (int k = 0; k < 3; ++k)
+    if (!parse_hex(argv[2 + k], td[k])) {
+      fprintf(stderr, "not a hex value: %s\n", argv[2 + k]);
+      return 1;
+    }
+  std::vector<uint64_t> pub(4 * (size_t)(argc - 5) + 4);
+  for (int k = 5; k < argc; ++k)
+    if (!parse_hex(argv[k], pub.data() + 4 * (size_t)(k - 5))) {
+      fprintf(stderr, "not a hex value: %s\n", argv[k]);
+      return 1;
+    }
+  uint8_t proof[119];
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) {
+    fprintf(stderr, "%s: cannot open\n", argv[1]);
+    return 1;
+  }
+  const size_t got = fread(proof, 1, sizeof(proof), f);
+  fclose(f);
+  if (got != 118) {
+    fprintf(stderr, "%s: %zu bytes, a proof has 118\n", argv[1], got);
+    return 1;
+  }
+  if (dvp_device_count() <= 0) {
+    fprintf(stderr, "no HIP device visible\n");
+    return 3;
+  }
+  int accepted = 0;
+  uint32_t reasons = 0;
+  const int rc = dvp_verify(td[0], td[1], td[2], pub.data(), (uint32_t)(argc - 5), proof, &accepted, &reasons);
+  if (rc != DVP_OK) {
+    fprintf(stderr, "dvp_verify: %s (index %lld)\n", dvp_strerror(rc), (long long)dvp_last_error_index());
+    return 1;
+  }
+  if (accepted) {
+    printf("accepted\n");
+    return 0;
+  }
+  std::string why;
+  const struct { uint32_t bit; const char* name; } names[] = {
+      {DVP_VERIFY_BAD_COMMIT_P, "bad_commit_p"}, {DVP_VERIFY_BAD_KZG_K, "bad_kzg_k"}, {DVP_VERIFY_BAD_A0, "bad_a0"},
+      {DVP_VERIFY_BAD_B0, "bad_b0"}, {DVP_VERIFY_BAD_PUBLIC, "bad_public"}, {DVP_VERIFY_EQUATION, "equation"}};
+  for (const auto& n : names)
+    if (reasons & n.bit) why += std::string(why.empty() ? "" : ",") + n.name;
+  printf("rejected 0x%02x %s\n", reasons, why.c_str());
+  return 2;
+}

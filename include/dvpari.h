@@ -246,6 +246,36 @@ int dvp_ecfft_domain_tables(dvp_ecfft* tree2n, int which, uint64_t* bar_weights,
 int dvp_transcript_challenge(const uint8_t commit_p[30], const uint64_t* public_inputs, uint32_t n_public, uint64_t out[4]);
 int dvp_blake3(const uint8_t* data, size_t len, uint8_t out[32]);
 
+/* SRS::verify(secrets, public_inputs, proof) (src/srs.rs:374-428) on the GPU: the designated verifier's check, one lane per proof,
+ * sharing the codec (dvp_codec_set_rule), the transcript and the curve code with the prover.  Proof bytes: Proof::to_bytes,
+ * commit_p[30] | kzg_k[30] | a0[29] | b0[29].  A proof is accepted (verdict 0) exactly when the reference returns true; otherwise
+ * the verdict is an OR of DVP_VERIFY_* bits: the reference's four validity flags, a non-canonical public input (the _dev flavour
+ * only), and DVP_VERIFY_EQUATION, set only when every input was valid and v0 K + u0 G != P.  Bad proof bytes never give an error
+ * status.  tau, delta, epsilon: canonical host values (>= p: DVP_EINVAL; zero is allowed, as in the reference).  The host
+ * flavours reject a non-canonical public input with DVP_EINVAL, dvp_last_error_index() = its flat index.  n_public <=
+ * DVP_VERIFY_MAX_PUBLIC (hashed on the device, multi-chunk beyond 35); n = 0 is DVP_OK. */
+#define DVP_VERIFY_BAD_COMMIT_P 0x01u
+#define DVP_VERIFY_BAD_KZG_K 0x02u
+#define DVP_VERIFY_BAD_A0 0x04u
+#define DVP_VERIFY_BAD_B0 0x08u
+#define DVP_VERIFY_BAD_PUBLIC 0x10u
+#define DVP_VERIFY_EQUATION 0x20u
+#define DVP_VERIFY_MAX_PUBLIC 8192u
+/* one proof: *accepted = 1 / 0, *reasons (optional) = DVP_VERIFY_* bits */
+int dvp_verify(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const uint64_t* public_inputs,
+               uint32_t n_public, const uint8_t proof[118], int* accepted, uint32_t* reasons);
+/* n proofs (n x 118 B) against one trapdoor; public_inputs: n x n_public canonical Fr (row i for proof i); verdicts: n bytes */
+int dvp_verify_batch(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const uint64_t* public_inputs,
+                     uint32_t n_public, const uint8_t* proofs, size_t n, uint8_t* verdicts);
+/* the same on device buffers, enqueued on `stream` on the current device (one kernel launch once the generator table of the
+ * device exists; the first call on a device builds it and waits for it).  A non-canonical public input is the verdict bit
+ * DVP_VERIFY_BAD_PUBLIC of its proof. */
+int dvp_verify_batch_dev(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const void* d_public_inputs,
+                         uint32_t n_public, const void* d_proofs, size_t n, void* d_verdicts, void* stream);
+/* sp1_generate_scalar_from_raw_public_input (src/gnark_r1cs.rs:214-229), host only: BLAKE3 of the 8-byte LE raw value, digest
+ * bytes 0..3 cleared, read big-endian (< 2^224, canonical) */
+int dvp_sp1_public_input(uint64_t raw, uint64_t out[4]);
+
 /* ------------------------------------------------------------------------------------------ */
 /* cache_dir formats: the files the reference's setup / prover exchange.          */
 /* Host-only code; the counted readers take out == NULL to query the element count.            */
