@@ -18,7 +18,14 @@
 // chaining values of complete subtrees kept in registers (VERIFY_B3_LEVELS levels: up to 2^8 chunks = DVP_VERIFY_MAX_PUBLIC
 // public inputs).  The 30 bytes of commit_p are hashed as they arrive: a valid encoding is the unique encoding of the point it
 // decodes to (codec_decode), so they equal witness_commitment_hash's re-encoding, and an invalid one rejects the proof anyway.
+//
+// dvp_verify_batch_rlc*: the same verdicts through one random-linear-combination MSM of the whole batch, with k_verify<true> as the
+// fallback when that MSM is not O (the section "batch check by one random linear combination" below).
+#include <algorithm>
 #include <cstring>
+#include <memory>
+#include <mutex>
+#include <vector>
 
 #include "blake3.h"
 #include "blake3_dev.cuh"
@@ -33,6 +40,8 @@ namespace dvp {
 int gen_table(const Aff** out, hipStream_t st);
 int gf_sqr_tables(GfSqrTables* out, hipStream_t st);
 int codec_rule_now();
+int msm_affine_dev_enc(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf,
+                       void* d_out_enc, void* h_copy, const void* d_copy, size_t copy_bytes, hipStream_t st, unsigned long long* d_err_defer);
 
 constexpr uint32_t VERIFY_B3_LEVELS = 8;
 constexpr uint32_t VERIFY_MAX_PUBLIC = DVP_VERIFY_MAX_PUBLIC;
@@ -178,11 +187,71 @@ __device__ __forceinline__ void madd_complete(Ld& acc, const Aff& q, const LT& L
   acc.Z = gf_select(acc_inf, gf_one(), gf_select(dbl, dZ, Z3));
 }
 
+// The front half of SRS::verify for one proof (k_verify_rlc_prep): decode P and K, the FrBits range checks of a0 and b0, canonical
+// public inputs, then (only for a well-formed proof) the transcript alpha and the scalars u0, v0.  The DVP_VERIFY_* validity bits
+// are k_verify's; f.h_pi is H(public inputs), which the random-linear-combination coefficient binds as well.  This is a
+// copy of k_verify's first half, not shared with it: k_verify calling a shared function compiles to another register allocation
+// (70 -> 33 AGPRs, 69 -> 104 spilled SGPRs), so k_verify keeps its own text and the two must be changed together.
+// It comes in two parts so that the caller can store the decoded points before the transcript: verify_decode, then (for a
+// well-formed proof only) verify_scalars.
+struct VerifyFront {
+  Fr u0, v0;
+  uint32_t h_pi[8];
+};
+
+__device__ __forceinline__ uint32_t verify_decode(const uint8_t* pr, const Fr* pi, uint32_t npub, const GfSqrTables& T, const GfLdsK& L,
+                                                  int rule, Aff& P, bool& p_inf, Aff& Kp, bool& k_inf) {
+  uint32_t bad = 0;
+  if (!codec_decode(pr, rule, T, L, P, p_inf)) bad |= DVP_VERIFY_BAD_COMMIT_P;
+  if (!codec_decode(pr + 30, rule, T, L, Kp, k_inf)) bad |= DVP_VERIFY_BAD_KZG_K;
+  if (!fr_below_p(load29(pr + 60))) bad |= DVP_VERIFY_BAD_A0;
+  if (!fr_below_p(load29(pr + 89))) bad |= DVP_VERIFY_BAD_B0;
+#pragma unroll 1
+  for (uint32_t j = 0; j < npub; ++j)
+    if (!fr_below_p(pi[j])) bad |= DVP_VERIFY_BAD_PUBLIC;
+  return bad;
+}
+
+__device__ __forceinline__ void verify_scalars(const uint8_t* pr, const Fr* pi, uint32_t npub, const VerifyConsts& K, VerifyFront& f) {
+  const Fr a0 = load29(pr + 60), b0 = load29(pr + 89);
+  // alpha = Transcript::output: H(H_ct || H(H(commit_p) || H(pub))), top four bytes cleared (src/proving.rs:164-197)
+  Fr alpha;
+  {
+    uint32_t blk[16], h_wc[8], h_rt[8], out[8];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) blk[k] = 0;
+#pragma unroll
+    for (int b = 0; b < 30; ++b) blk[b >> 2] |= (uint32_t)pr[b] << (8 * (b & 3));
+    b3d::hash_chunk(blk, 30, h_wc);
+    pub_digest((const uint8_t*)pi, npub, f.h_pi);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { blk[k] = h_wc[k]; blk[8 + k] = f.h_pi[k]; }
+    b3d::hash_chunk(blk, 64, h_rt);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { blk[k] = K.h_ct.w[k]; blk[8 + k] = h_rt[k]; }
+    b3d::hash_chunk(blk, 64, out);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) alpha.v[k] = out[k];
+    alpha.v[7] = 0;  // 224 bits, always < p
+  }
+  // scalars (canonical throughout: mont_mul(x, c R) = x c)
+  const Fr alpha_m = fr_to_mont(alpha);
+  Fr i0 = fr_zero();
+#pragma unroll 1
+  for (uint32_t j = npub; j-- > 0;) i0 = fr_add(fr_mul(i0, alpha_m), pi[j]);  // sum_j pub_j alpha^j by Horner
+  const Fr r0 = fr_sub(fr_mul(a0, fr_to_mont(b0)), i0);
+  f.u0 = fr_mul(fr_add(fr_add(a0, fr_mul(b0, K.delta_m)), fr_mul(r0, K.delta2_m)), K.eps_m);
+  f.v0 = fr_mul(fr_sub(K.tau, alpha), K.eps_m);
+}
+
 // one wave per SIMD: the 256 architectural VGPRs plus accumulation registers for what does not fit (no scratch); at two waves per
-// SIMD the tau-adic loop spills ~300 B per lane to scratch
+// SIMD the tau-adic loop spills ~300 B per lane to scratch.  GATED (the fallback of dvp_verify_batch_rlc*): the launch is always
+// enqueued and ends at once when *gate != 0, i.e. when the combined check held or no proof was well formed.
+template <bool GATED>
 __global__ void __launch_bounds__(256, 1)
 k_verify(const uint8_t* __restrict__ proofs, size_t n, const Fr* __restrict__ pub, uint32_t npub, VerifyConsts K, const Aff* __restrict__ tab,
-         GfSqrTables T, int rule, uint8_t* __restrict__ verdicts) {
+         GfSqrTables T, int rule, uint8_t* __restrict__ verdicts, const uint32_t* __restrict__ gate) {
+  if (GATED && *gate) return;
   extern __shared__ char lds_raw[];
   GfLdsK L = gf_ldsk_init(lds_raw);
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -266,6 +335,161 @@ k_verify(const uint8_t* __restrict__ proofs, size_t n, const Fr* __restrict__ pu
   verdicts[i] = eq ? 0 : (uint8_t)DVP_VERIFY_EQUATION;
 }
 
+// ---- batch check by one random linear combination (dvp_verify_batch_rlc*) ------------------------------------------------------
+// For n proofs against one trapdoor, every well-formed proof j (the set W) satisfies v0_j K_j + u0_j G - P_j = O when it is valid.
+// With r_j = BLAKE3(key || LE64(j) || proof_j || H(pub_j))[0..16) | 2^127 the n checks become ONE MSM of 2n + 1 points:
+//   sum_W (r_j v0_j) K_j + sum_W (p - r_j) P_j + (sum_W r_j u0_j) G == O.
+// Layout of the MSM input: [K_0 .. K_{n-1} | P_0 .. P_{n-1} | G]; a proof outside W has zero scalars and infinity flags.
+//   k_verify_rlc_prep   one lane per proof: the front half of k_verify, the coefficient, the bases, scalars and r_j u0_j
+//   k_rlc_sum_blocks    block partials of sum r_j u0_j (and of |W|)
+//   k_rlc_sum_final     one block: the G scalar, the G base (generator table, window 0, digit 1), |W|
+//   msm_affine_dev_enc  the one-shot MSM, deferred completion (its scalar-range word stays on the device)
+//   k_rlc_check         report word and gate
+//   k_verify<true>      the per-lane check over the whole batch, unless the gate says the combination held
+
+// the 190-byte coefficient message, little-endian words: key[0..32) | LE64(j)[32..40) | proof[40..158) | H(pub)[158..190)
+__device__ __forceinline__ uint32_t rlc_msg_byte(uint32_t off, const b3d::Words8& key, uint64_t j, const uint8_t* pr, const uint32_t h_pi[8]) {
+  if (off < 32) return (key.w[off >> 2] >> (8 * (off & 3))) & 0xffu;
+  if (off < 40) return (uint32_t)(j >> (8 * (off - 32))) & 0xffu;
+  if (off < 158) return pr[off - 40];
+  if (off < 190) return (h_pi[(off - 158) >> 2] >> (8 * ((off - 158) & 3))) & 0xffu;
+  return 0;
+}
+
+// r_j: the first 16 digest bytes read little-endian, bit 127 set (nonzero, 127 random bits, < p)
+__device__ __forceinline__ Fr rlc_coeff(const b3d::Words8& key, uint64_t j, const uint8_t* pr, const uint32_t h_pi[8]) {
+  constexpr uint32_t IV[8] = {0x6A09E667u, 0xBB67AE85u, 0x3C6EF372u, 0xA54FF53Au, 0x510E527Fu, 0x9B05688Cu, 0x1F83D9ABu, 0x5BE0CD19u};
+  constexpr uint32_t CHUNK_START = 1, CHUNK_END = 2, ROOT = 8;
+  uint32_t cv[8], m[16];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) cv[i] = IV[i];
+#pragma unroll
+  for (uint32_t b = 0; b < 3; ++b) {  // one chunk of three blocks: 64 + 64 + 62 bytes
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k) {
+      uint32_t w = 0;
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q) w |= rlc_msg_byte(64 * b + 4 * k + q, key, j, pr, h_pi) << (8 * q);
+      m[k] = w;
+    }
+    b3d::compress(cv, m, b == 2 ? 62u : 64u, b == 0 ? CHUNK_START : (b == 2 ? CHUNK_END | ROOT : 0u));
+  }
+  Fr r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r.v[k] = cv[k];
+  r.v[3] |= 0x80000000u;
+#pragma unroll
+  for (int k = 4; k < 8; ++k) r.v[k] = 0;
+  return r;
+}
+
+// one lane per proof, no tau-adic chain: the decode's inversion and the transcript are the cost
+__global__ void __launch_bounds__(256, 2)
+k_verify_rlc_prep(const uint8_t* __restrict__ proofs, size_t n, const Fr* __restrict__ pub, uint32_t npub, VerifyConsts K, b3d::Words8 key,
+                  GfSqrTables T, int rule, Fr* __restrict__ sc, Aff* __restrict__ bases, uint8_t* __restrict__ inf, Fr* __restrict__ ur,
+                  uint8_t* __restrict__ verdicts) {
+  extern __shared__ char lds_raw[];
+  GfLdsK L = gf_ldsk_init(lds_raw);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* pr = proofs + 118 * i;
+  const Fr* pi = pub + (size_t)npub * i;
+  uint32_t bad;
+  {
+    Aff P, Kp;
+    bool p_inf, k_inf;
+    bad = verify_decode(pr, pi, npub, T, L, rule, P, p_inf, Kp, k_inf);
+    bases[i] = Kp;  // stored now: the points are not held across the transcript
+    bases[n + i] = P;
+    inf[i] = (bad || k_inf) ? 1 : 0;
+    inf[n + i] = (bad || p_inf) ? 1 : 0;
+  }
+  Fr sk = fr_zero(), sp = fr_zero(), su = fr_zero();
+  if (!bad) {
+    VerifyFront f;
+    verify_scalars(pr, pi, npub, K, f);
+    const Fr r = rlc_coeff(key, (uint64_t)i, pr, f.h_pi);
+    const Fr r_m = fr_to_mont(r);
+    sk = fr_mul(f.v0, r_m);
+    sp = fr_sub(fr_zero(), r);  // p - r: r != 0
+    su = fr_mul(f.u0, r_m);
+  }
+  sc[i] = sk;
+  sc[n + i] = sp;
+  ur[i] = su;
+  verdicts[i] = (uint8_t)bad;
+}
+
+constexpr uint32_t RLC_SUM_TPB = 256;
+constexpr uint32_t RLC_SUM_BLOCKS = 1024;  // level-1 blocks at most: level 2 is one block over their partials
+
+// sum mod p of a block's values and count of its well-formed proofs; the tree over the block's lanes is fixed, and Fr addition is
+// exact, so the result does not depend on the order in which blocks run
+__device__ __forceinline__ void rlc_block_sum(Fr s, uint32_t w, Fr* out, uint32_t* out_w) {
+  __shared__ Fr ls[RLC_SUM_TPB];
+  __shared__ uint32_t lw[RLC_SUM_TPB];
+  ls[threadIdx.x] = s;
+  lw[threadIdx.x] = w;
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t h = RLC_SUM_TPB / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h) {
+      ls[threadIdx.x] = fr_add(ls[threadIdx.x], ls[threadIdx.x + h]);
+      lw[threadIdx.x] += lw[threadIdx.x + h];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    *out = ls[0];
+    *out_w = lw[0];
+  }
+}
+
+// level 1: block b sums lanes b, b + B, b + 2B, ... in strides of the whole grid
+__global__ void __launch_bounds__(RLC_SUM_TPB)
+k_rlc_sum_blocks(const Fr* __restrict__ ur, const uint8_t* __restrict__ verdicts, size_t n, Fr* __restrict__ part, uint32_t* __restrict__ part_w) {
+  Fr s = fr_zero();
+  uint32_t w = 0;
+#pragma unroll 1
+  for (size_t i = (size_t)blockIdx.x * RLC_SUM_TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * RLC_SUM_TPB) {
+    s = fr_add(s, ur[i]);
+    w += verdicts[i] == 0 ? 1u : 0u;
+  }
+  rlc_block_sum(s, w, part + blockIdx.x, part_w + blockIdx.x);
+}
+
+// level 2 (one block): the G entry of the MSM -- scalar sum_W r_j u0_j, base G = tab[window 0, digit 1] -- and |W|
+__global__ void __launch_bounds__(RLC_SUM_TPB)
+k_rlc_sum_final(const Fr* __restrict__ part, const uint32_t* __restrict__ part_w, uint32_t nparts, const Aff* __restrict__ tab, Fr* __restrict__ g_sc,
+                Aff* __restrict__ g_base, uint8_t* __restrict__ g_inf, uint32_t* __restrict__ n_w) {
+  Fr s = fr_zero();
+  uint32_t w = 0;
+#pragma unroll 1
+  for (uint32_t i = threadIdx.x; i < nparts; i += RLC_SUM_TPB) {
+    s = fr_add(s, part[i]);
+    w += part_w[i];
+  }
+  rlc_block_sum(s, w, g_sc, n_w);
+  if (threadIdx.x == 0) {
+    *g_base = tab[1];
+    *g_inf = 0;
+  }
+}
+
+// the MSM is O (and its scalars were in range): COMBINED; else FALLBACK.  No well-formed proof: no bit, the prep verdicts stand.
+// gate != 0 skips the fallback launch.
+__global__ void __launch_bounds__(64)
+k_rlc_check(const uint32_t* __restrict__ out_inf, const unsigned long long* __restrict__ err, const uint32_t* __restrict__ n_w,
+            uint32_t* __restrict__ gate, uint32_t* __restrict__ report, uint32_t* __restrict__ user_report) {
+  if (threadIdx.x != 0) return;
+  const bool any = *n_w != 0;
+  const bool held = *out_inf == 1u && *err == ~0ull;
+  const uint32_t rep = !any ? 0u : (held ? DVP_VERIFY_RLC_COMBINED : DVP_VERIFY_RLC_FALLBACK);
+  *gate = (!any || held) ? 1u : 0u;
+  *report = rep;
+  if (user_report) *user_report = rep;
+}
+
 static void fr_from_u64(const uint64_t* v, Fr* out) { memcpy(out->v, v, 32); }
 
 static bool fr_host_canonical(const uint64_t* v) {
@@ -302,8 +526,150 @@ static int verify_enqueue(const VerifyConsts& c, const void* d_pub, uint32_t npu
   DVP_TRY(gen_table(&tab, st));
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
-  hipLaunchKernelGGL(k_verify, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
-                     (const Fr*)d_pub, npub, c, tab, T, codec_rule_now(), (uint8_t*)d_verdicts);
+  hipLaunchKernelGGL(k_verify<false>, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
+                     (const Fr*)d_pub, npub, c, tab, T, codec_rule_now(), (uint8_t*)d_verdicts, (const uint32_t*)nullptr);
+  DVP_HIP(hipGetLastError());
+  return DVP_OK;
+}
+
+
+// ---- workspaces of the combined check: per device, one per host thread in flight ----------------------------------------------
+// A call holds its workspace while it enqueues and then marks the end of its kernels with `ev`; the next call on that workspace
+// orders itself behind them on the GPU (hipStreamWaitEvent), so nothing here waits on the host.  Growing happens before the call
+// enqueues anything (after the previous kernels on it ended): no hipMalloc / hipFree between enqueued kernels.
+struct RlcWs {
+  int device = -1;
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;
+  bool used = false;  // ev was recorded
+  bool held = false;  // a call is enqueuing on it (under g_rlc_mu)
+};
+static std::mutex g_rlc_mu;
+static std::vector<std::unique_ptr<RlcWs>> g_rlc_ws;
+
+struct RlcHold {
+  RlcWs* ws = nullptr;
+  hipStream_t st = nullptr;
+  bool enqueued = false;
+  ~RlcHold() {
+    if (!ws) return;
+    if (enqueued) ws->used = hipEventRecord(ws->ev, st) == hipSuccess;
+    std::lock_guard<std::mutex> g(g_rlc_mu);
+    ws->held = false;
+  }
+};
+
+static int rlc_acquire(size_t need, hipStream_t st, RlcHold& h) {
+  int dev;
+  DVP_HIP(hipGetDevice(&dev));
+  {
+    std::lock_guard<std::mutex> g(g_rlc_mu);
+    for (auto& w : g_rlc_ws)
+      if (w->device == dev && !w->held) {
+        h.ws = w.get();
+        break;
+      }
+    if (!h.ws) {
+      g_rlc_ws.emplace_back(new RlcWs);
+      h.ws = g_rlc_ws.back().get();
+      h.ws->device = dev;
+    }
+    h.ws->held = true;
+  }
+  h.st = st;
+  RlcWs& w = *h.ws;
+  if (!w.ev) DVP_HIP(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+  if (w.bytes < need) {
+    if (w.used) DVP_HIP(hipEventSynchronize(w.ev));
+    if (w.p) (void)hipFree(w.p);
+    w.p = nullptr;
+    w.bytes = 0;
+    w.used = false;
+    DVP_HIP(hipMalloc(&w.p, need));
+    w.bytes = need;
+  } else if (w.used) {
+    DVP_HIP(hipStreamWaitEvent(st, w.ev, 0));
+  }
+  return DVP_OK;
+}
+
+// workspace layout for n proofs (N = 2n + 1 MSM entries: 97 B each, plus 32 B per proof for r_j u0_j)
+struct RlcLayout {
+  size_t sc, bases, inf, ur, part, part_w, ctrl, total;
+};
+static RlcLayout rlc_layout(size_t n) {
+  const size_t N = 2 * n + 1;
+  size_t o = 0;
+  auto carve = [&](size_t b) { const size_t r = o; o = (o + b + 255) & ~(size_t)255; return r; };
+  RlcLayout l;
+  l.sc = carve(32 * N);
+  l.bases = carve(64 * N);
+  l.inf = carve(N);
+  l.ur = carve(32 * n);
+  l.part = carve(32 * (size_t)RLC_SUM_BLOCKS);
+  l.part_w = carve(4 * (size_t)RLC_SUM_BLOCKS);
+  l.ctrl = carve(128);  // MSM x, y [0, 64) | MSM infinity u32 [64] | scalar-range word u64 [72] | |W| [80] | gate [84] | report [88]
+  l.total = o;
+  return l;
+}
+
+// key = seed, or BLAKE3("dv-pari verify rlc v1" || tau || delta || epsilon), each as 32 little-endian bytes
+static void rlc_key(const uint64_t tau[4], const uint64_t delta[4], const uint64_t eps[4], const uint8_t* seed, uint8_t key[32]) {
+  if (seed) {
+    memcpy(key, seed, 32);
+    return;
+  }
+  static const char tag[] = "dv-pari verify rlc v1";
+  constexpr size_t T = sizeof(tag) - 1;
+  uint8_t buf[T + 96];
+  memcpy(buf, tag, T);
+  const uint64_t* v[3] = {tau, delta, eps};
+  for (int s = 0; s < 3; ++s)
+    for (int b = 0; b < 32; ++b) buf[T + 32 * s + b] = (uint8_t)(v[s][b >> 3] >> (8 * (b & 7)));
+  b3::hash(buf, sizeof buf, key);
+}
+
+static int rlc_enqueue(const VerifyConsts& c, const uint8_t key[32], const void* d_pub, uint32_t npub, const void* d_proofs, size_t n,
+                       void* d_verdicts, void* d_report, hipStream_t st) {
+  const Aff* tab;
+  DVP_TRY(gen_table(&tab, st));
+  GfSqrTables T;
+  DVP_TRY(gf_sqr_tables(&T, st));
+  const RlcLayout lay = rlc_layout(n);
+  RlcHold h;
+  DVP_TRY(rlc_acquire(lay.total, st, h));
+  char* ws = (char*)h.ws->p;
+  Fr* sc = (Fr*)(ws + lay.sc);
+  Aff* bases = (Aff*)(ws + lay.bases);
+  uint8_t* inf = (uint8_t*)(ws + lay.inf);
+  Fr* ur = (Fr*)(ws + lay.ur);
+  Fr* part = (Fr*)(ws + lay.part);
+  uint32_t* part_w = (uint32_t*)(ws + lay.part_w);
+  char* ctrl = ws + lay.ctrl;
+  uint32_t* out_xy = (uint32_t*)ctrl;
+  uint32_t* out_inf = (uint32_t*)(ctrl + 64);
+  unsigned long long* err = (unsigned long long*)(ctrl + 72);
+  uint32_t* n_w = (uint32_t*)(ctrl + 80);
+  uint32_t* gate = (uint32_t*)(ctrl + 84);
+  uint32_t* report = (uint32_t*)(ctrl + 88);
+  b3d::Words8 kw;
+  memcpy(kw.w, key, 32);
+  const int rule = codec_rule_now();
+  uint8_t* verdicts = (uint8_t*)d_verdicts;
+  h.enqueued = true;
+  hipLaunchKernelGGL(k_verify_rlc_prep, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
+                     (const Fr*)d_pub, npub, c, kw, T, rule, sc, bases, inf, ur, verdicts);
+  const uint32_t nparts = std::min<uint32_t>(cdiv(n, RLC_SUM_TPB), RLC_SUM_BLOCKS);
+  hipLaunchKernelGGL(k_rlc_sum_blocks, dim3(nparts), dim3(RLC_SUM_TPB), 0, st, (const Fr*)ur, (const uint8_t*)verdicts, n, part, part_w);
+  hipLaunchKernelGGL(k_rlc_sum_final, dim3(1), dim3(RLC_SUM_TPB), 0, st, (const Fr*)part, (const uint32_t*)part_w, nparts, tab, sc + 2 * n,
+                     bases + 2 * n, inf + 2 * n, n_w);
+  DVP_HIP(hipGetLastError());
+  DVP_TRY(msm_affine_dev_enc(sc, bases, inf, 2 * n + 1, out_xy, out_inf, nullptr, nullptr, nullptr, 0, st, err));
+  hipLaunchKernelGGL(k_rlc_check, dim3(1), dim3(64), 0, st, (const uint32_t*)out_inf, (const unsigned long long*)err, (const uint32_t*)n_w, gate,
+                     report, (uint32_t*)d_report);
+  hipLaunchKernelGGL(k_verify<true>, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
+                     (const Fr*)d_pub, npub, c, tab, T, rule, verdicts, (const uint32_t*)gate);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
@@ -346,6 +712,53 @@ extern "C" int dvp_verify_batch(const uint64_t tau[4], const uint64_t delta[4], 
   return DVP_OK;
 }
 
+extern "C" int dvp_verify_batch_rlc_dev(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const void* d_public_inputs,
+                                        uint32_t n_public, const void* d_proofs, size_t n, const uint8_t seed[32], void* d_verdicts,
+                                        void* d_report, void* stream) {
+  VerifyConsts c;
+  DVP_TRY(verify_consts(tau, delta, epsilon, &c));
+  if (n_public > VERIFY_MAX_PUBLIC) return DVP_EINVAL;
+  if (!n) return DVP_OK;
+  if (!d_proofs || !d_verdicts || (n_public && !d_public_inputs) || n > DVP_VERIFY_RLC_MAX_PROOFS) return DVP_EINVAL;
+  uint8_t key[32];
+  rlc_key(tau, delta, epsilon, seed, key);
+  return rlc_enqueue(c, key, d_public_inputs, n_public, d_proofs, n, d_verdicts, d_report, (hipStream_t)stream);
+}
+
+extern "C" int dvp_verify_batch_rlc(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const uint64_t* public_inputs,
+                                    uint32_t n_public, const uint8_t* proofs, size_t n, const uint8_t seed[32], uint8_t* verdicts,
+                                    uint32_t* report) {
+  VerifyConsts c;
+  DVP_TRY(verify_consts(tau, delta, epsilon, &c));
+  if (n_public > VERIFY_MAX_PUBLIC) return DVP_EINVAL;
+  if (!n) {
+    if (report) *report = 0;
+    return DVP_OK;
+  }
+  if (!proofs || !verdicts || (n_public && !public_inputs) || n > DVP_VERIFY_RLC_MAX_PROOFS) return DVP_EINVAL;
+  const size_t npub_all = (size_t)n_public * n;
+  for (size_t k = 0; k < npub_all; ++k)
+    if (!fr_host_canonical(public_inputs + 4 * k)) {
+      g_last_error_index = (int64_t)k;
+      return DVP_EINVAL;
+    }
+  uint8_t key[32];
+  rlc_key(tau, delta, epsilon, seed, key);
+  DevBuf dp, dpub, dv, drep;
+  DVP_TRY(dp.alloc(n * 118));
+  DVP_TRY(dpub.alloc(npub_all * 32));
+  DVP_TRY(dv.alloc(n));
+  DVP_TRY(drep.alloc(4));
+  DVP_HIP(hipMemcpy(dp.p, proofs, n * 118, hipMemcpyHostToDevice));
+  if (npub_all) DVP_HIP(hipMemcpy(dpub.p, public_inputs, npub_all * 32, hipMemcpyHostToDevice));
+  DVP_TRY(rlc_enqueue(c, key, dpub.p, n_public, dp.p, n, dv.p, drep.p, 0));
+  DVP_HIP(hipMemcpy(verdicts, dv.p, n, hipMemcpyDeviceToHost));
+  uint32_t rep = 0;
+  DVP_HIP(hipMemcpy(&rep, drep.p, 4, hipMemcpyDeviceToHost));
+  if (report) *report = rep;
+  return DVP_OK;
+}
+
 extern "C" int dvp_verify(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const uint64_t* public_inputs,
                           uint32_t n_public, const uint8_t proof[118], int* accepted, uint32_t* reasons) {
   if (!proof || !accepted) return DVP_EINVAL;
@@ -373,3 +786,4 @@ extern "C" int dvp_sp1_public_input(uint64_t raw, uint64_t out[4]) {
   }
   return DVP_OK;
 }
+

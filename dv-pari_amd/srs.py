@@ -175,6 +175,7 @@ def verify(td: Trapdoor, public_inputs, proof) -> bool:
 
 # ---- the verifier on the GPU (csrc/verify.hip): SRS::verify for many proofs at once, one verdict per proof ------------------
 VERIFY_BAD_COMMIT_P, VERIFY_BAD_KZG_K, VERIFY_BAD_A0, VERIFY_BAD_B0, VERIFY_BAD_PUBLIC, VERIFY_EQUATION = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+VERIFY_RLC_COMBINED, VERIFY_RLC_FALLBACK = 0x1, 0x2
 
 
 def _raw_limbs(v) -> np.ndarray:
@@ -229,6 +230,34 @@ def verify_batch(td: Trapdoor, public_inputs, proofs) -> np.ndarray:
     pub_buf = pub if pub.size else np.zeros(4, dtype=np.uint64)
     check(lib.dvp_verify_batch(t, d, e, ptr(pub_buf), pub.shape[1], ptr(pa), n, ptr(out)), "dvp_verify_batch")
     return out
+
+
+def verify_batch_rlc(td: Trapdoor, public_inputs, proofs, seed=None):
+    """verify_batch by one random linear combination (dvp_verify_batch_rlc): the well-formed proofs are checked together by one
+    MSM, and only when that check fails does the per-lane check run over the batch.  seed: 32 bytes, or None for the key derived
+    from the trapdoor.  Returns (verdicts, report): verdicts as verify_batch's (equal to them except with probability <= 2^-127),
+    report = VERIFY_RLC_COMBINED, VERIFY_RLC_FALLBACK, or 0 when no proof was well formed."""
+    import ctypes as C
+
+    from ._native import lib, check, ptr
+
+    pa = _proofs_array(proofs)
+    n = pa.shape[0]
+    pub = _public_array(public_inputs, n)
+    keep, (t, d, e) = _trapdoor_args(td)
+    out = np.zeros(n, dtype=np.uint8)
+    rep = C.c_uint32(0)
+    if seed is not None:
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+    sd = None if seed is None else np.frombuffer(seed, dtype=np.uint8).copy()
+    pub_buf = pub if pub.size else np.zeros(4, dtype=np.uint64)
+    pa_buf = pa if n else np.zeros((1, 118), dtype=np.uint8)
+    out_buf = out if n else np.zeros(1, dtype=np.uint8)
+    check(lib.dvp_verify_batch_rlc(t, d, e, ptr(pub_buf), pub.shape[1], ptr(pa_buf), n, None if sd is None else ptr(sd), ptr(out_buf),
+                                   C.byref(rep)), "dvp_verify_batch_rlc")
+    return out, int(rep.value)
 
 
 def verify_device(td: Trapdoor, public_inputs, proof) -> bool:
