@@ -104,6 +104,9 @@ _SIGS = {
     "dvp_prover_msm_size": (C.c_size_t, [vp, C.c_int]),
     "dvp_prover_msm_plan": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dvp_prover_msm_table_bytes": (C.c_uint64, [vp, C.c_int, C.POINTER(C.c_int)]),
+    "dvp_prover_set_table_budget": (C.c_int, [vp, C.c_uint64]),
+    "dvp_prover_msm_coverage": (C.c_int, [vp, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "dvp_table_plan": (C.c_int, [sz, sz, C.c_uint64, C.POINTER(C.c_size_t * 2), C.POINTER(C.c_uint64 * 2)]),
     "dvp_prover_msm_partial": (C.c_int, [vp, C.c_int, sz, sz, vp, vp, vp]),
     "dvp_prove_challenge": (C.c_int, [vp, vp, vp, vp]),
     "dvp_prove_challenge_partial": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp]),
@@ -153,11 +156,17 @@ for _name, (_res, _args) in _SIGS.items():
     EXPORTED.append(_name)
 
 
+STATUS_NAMES = {0: "DVP_OK", -1: "DVP_EINVAL", -2: "DVP_EDECODE", -3: "DVP_EUNSAT", -4: "DVP_EHIP", -6: "DVP_EIO", -7: "DVP_ENOMEM",
+                -8: "DVP_ECHALLENGE"}  # enum dvp_status, include/dvpari.h
+ENOMEM = -7
+
+
 class DvpError(RuntimeError):
     def __init__(self, status, where=""):
         self.status = status
+        self.name = STATUS_NAMES.get(status, "unknown")
         self.index = lib.dvp_last_error_index()
-        super().__init__(f"{where}: {lib.dvp_strerror(status).decode()} (status {status}, index {self.index})")
+        super().__init__(f"{where}: {self.name}: {lib.dvp_strerror(status).decode()} (status {status}, index {self.index})")
 
 
 def check(status, where=""):
@@ -194,6 +203,18 @@ class tune:
             lib.dvp_tune_set(k.encode(), v)
         self.saved = {}
         return False
+
+
+NO_TABLE_LIMIT = (1 << 64) - 1  # UINT64_MAX: dvp_prover_set_table_budget's "no limit"
+
+
+def table_plan(size0: int, size1: int, budget: int):
+    """dvp_table_plan, the table-budget planner (host only): ((covered0, covered1), (bytes0, bytes1)) for a prover whose two MSMs
+    have size0 / size1 terms and whose tables may hold `budget` bytes (None = no limit)"""
+    cov, nbytes = (C.c_size_t * 2)(), (C.c_uint64 * 2)()
+    b = NO_TABLE_LIMIT if budget is None else min(int(budget), NO_TABLE_LIMIT)
+    check(lib.dvp_table_plan(size0, size1, b, C.byref(cov), C.byref(nbytes)), "dvp_table_plan")
+    return (int(cov[0]), int(cov[1])), (int(nbytes[0]), int(nbytes[1]))
 
 
 # ---- int <-> limb helpers (canonical little-endian 4 x u64) ----------------------------------------

@@ -7,6 +7,7 @@
 #include <vector>
 #include <cstring>
 #include <cstdlib>
+#include <climits>
 
 namespace dvp {
 thread_local int64_t g_last_error_index = -1;
@@ -86,6 +87,11 @@ static void tune_from_env(Tune& t) {
   t.fr_bi_shape = geti("DVP_FR_BI_SHAPE", t.fr_bi_shape);
   t.msm_aligned_signed = geti("DVP_MSM_ALIGNED_SIGNED", t.msm_aligned_signed);
   t.prove_host_transcript = geti("DVP_PROVE_HOST_TRANSCRIPT", t.prove_host_transcript);
+  t.msm_table_refuse = geti("DVP_MSM_TABLE_REFUSE", t.msm_table_refuse);
+  if (const char* e = getenv("DVP_TABLE_BUDGET_BYTES")) {  // the full u64 range: UINT64_MAX and anything above LLONG_MAX read as "no limit"
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    t.table_budget_bytes = v > (unsigned long long)LLONG_MAX ? -1 : (long long)v;
+  }
 }
 static std::mutex g_dev_mu;
 static std::vector<int> g_devices;
@@ -105,7 +111,8 @@ static long long* tune_slot(const char* name) {
       {"DVP_MSM_C", &t.msm_c}, {"DVP_MSM_K", &t.msm_k}, {"DVP_MSM_FIXED_C", &t.msm_fixed_c}, {"DVP_FX_HI", &t.fx_hi},
       {"DVP_MSM_PROJ", &t.msm_proj}, {"DVP_MSM_AFF_MIN", &t.msm_aff_min}, {"DVP_MSM_HEX_MAX", &t.msm_hex_max}, {"DVP_MSM_ROUND_PIPELINE", &t.msm_round_pipeline}, {"DVP_MSM_SORT_FUSED", &t.msm_sort_fused}, {"DVP_MSM_BUCKET_PAIRS_MAX", &t.msm_bucket_pairs_max}, {"DVP_MSM_AFF_BMAX", &t.msm_aff_bmax}, {"DVP_MSM_AFF_BMIN", &t.msm_aff_bmin}, {"DVP_ECFFT_RADIX4", &t.ecfft_radix4}, {"DVP_ECFFT_FOLD", &t.ecfft_fold}, {"DVP_MSM_ACCUM_FAST", &t.msm_accum_fast}, {"DVP_MSM_TAIL_GROUPS", &t.msm_tail_groups}, {"DVP_MSM_ACCUM_HEX_MAX", &t.msm_accum_hex_max}, {"DVP_GF_INV_TABS", &t.gf_inv_tabs}, {"DVP_MSM_WS_SLOTS", &t.msm_ws_slots}, {"DVP_MSM_GATE_MIN", &t.msm_gate_min}, {"DVP_MSM_AFF_TPB", &t.msm_aff_tpb}, {"DVP_CACHE_REPLICAS", &t.cache_replicas},
       {"DVP_MSM_QUAD_MAX", &t.msm_quad_max}, {"DVP_MSM_ACCUM_QUAD_MAX", &t.msm_accum_quad_max}, {"DVP_MSM_FIXED_MIN", &t.msm_fixed_min}, {"DVP_HORNER_MAX_PUB", &t.horner_max_pub}, {"DVP_FR_BI_SHAPE", &t.fr_bi_shape},
-      {"DVP_MSM_ALIGNED_SIGNED", &t.msm_aligned_signed}, {"DVP_PROVE_HOST_TRANSCRIPT", &t.prove_host_transcript}};
+      {"DVP_MSM_ALIGNED_SIGNED", &t.msm_aligned_signed}, {"DVP_PROVE_HOST_TRANSCRIPT", &t.prove_host_transcript},
+      {"DVP_TABLE_BUDGET_BYTES", &t.table_budget_bytes}, {"DVP_MSM_TABLE_REFUSE", &t.msm_table_refuse}};
   for (auto& e : tab)
     if (!strcmp(name, e.n)) return e.v;
   return nullptr;

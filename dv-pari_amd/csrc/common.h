@@ -16,6 +16,13 @@ extern thread_local hipError_t g_last_hip_error;
 inline int hip_fail(hipError_t e, const char* what, const char* file, int line) {
   g_last_hip_error = e;
   fprintf(stderr, "[dvpari] HIP error %d (%s) at %s:%d: %s\n", (int)e, hipGetErrorString(e), file, line, what);
+  // out of memory is the one HIP error a host can act on (a smaller table budget, fewer provers): it gets its own status.  A refused
+  // allocation is an answer, not a fault: the runtime's sticky last-error is cleared, so that the hipGetLastError() check behind the
+  // next kernel launch of this thread does not report it a second time (g_last_hip_error keeps it)
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return DVP_ENOMEM;
+  }
   return DVP_EHIP;
 }
 
@@ -93,6 +100,8 @@ struct Tune {
   long long fr_bi_shape = 6;           // DVP_FR_BI_SHAPE: workgroup x elements per thread of k_batch_inverse: 0 = 512 x 16 (rounds 3-4), 1 = 256 x 8, 2 = 256 x 4, 3 = 512 x 8, 4 = 128 x 8, 5 = 128 x 4, 6 = 256 x 16 (default: 2^21 elements 128 us against 139), 7 = 1024 x 8
   long long horner_max_pub = -1;       // DVP_HORNER_MAX_PUB: public-input count up to which i(X) on D' is evaluated by Horner (-1 = default)
   long long prove_host_transcript = 0; // DVP_PROVE_HOST_TRANSCRIPT: 1 = dvp_prove_dev waits for the commitment MSM and hashes the transcript on the host (rounds 1-4); 0 = on the device, one stream wait per proof
+  long long table_budget_bytes = -1;   // DVP_TABLE_BUDGET_BYTES: HBM per device the fixed-base tables of a NEW prover may hold (-1 = no limit; dvp_prover_set_table_budget changes it per prover)
+  long long msm_table_refuse = 0;      // DVP_MSM_TABLE_REFUSE: TEST ONLY, 1 = msm_fixed_build behaves as if its table allocation had returned hipErrorOutOfMemory, without asking the runtime
   long long msm_aligned_signed = 1;    // DVP_MSM_ALIGNED_SIGNED: the aligned-window tables hold 2^(c w) P and the windows are signed binary digits (0 = the tau-adic aligned windows over rows tau^(o_w) P)
 };
 Tune& tune();

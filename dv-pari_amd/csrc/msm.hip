@@ -1785,6 +1785,66 @@ __global__ void __launch_bounds__(64) k_sum_points(const char* __restrict__ pts,
   *out_inf = fin ? 0u : 1u;
 }
 
+// The join of a MIXED MSM (a prover whose table budget covers only a prefix of the bases: prove.hip): the fixed-base MSM over the
+// prefix and the one-shot MSM over the suffix each left an affine partial point and a scalar-range word; this launch writes what the
+// tail kernel of a single MSM would have written for the whole sum -- the affine sum (complete addition: either part neutral, P = Q,
+// P = -Q), its 30-byte encoding under `rule` from the same shared inversion 1 / (X Z) as k_tail, and the merged range word: the
+// prefix's word wins (its indices come first), the suffix's first bad index is rebased by `covered` to the whole vector.  One row of
+// 16 lanes (the mixed addition and the inversion are one dependent chain of ~300 products); LDS: one wave's tables.
+__global__ void __launch_bounds__(64) k_join_points(const Aff* __restrict__ pa, const uint32_t* __restrict__ inf_a, const unsigned long long* __restrict__ err_a,
+                                                    const Aff* __restrict__ pb, const uint32_t* __restrict__ inf_b, const unsigned long long* __restrict__ err_b,
+                                                    uint32_t covered, GfSqrTables T, uint32_t* __restrict__ out_xy, uint32_t* __restrict__ out_inf,
+                                                    uint8_t* __restrict__ out_enc, int rule, unsigned long long* __restrict__ err_dst) {
+  extern __shared__ char lds_raw[];
+  GfLdsH H = gf_ldsh_init(lds_raw);
+  if (threadIdx.x >= 16 || blockIdx.x != 0) return;
+  Ld p = ld_infinity();
+  if (!*inf_a) {
+    const Aff q = *pa;
+    p.X = q.x; p.Y = q.y; p.Z = gf_one();
+  }
+  if (!*inf_b) {
+    const Aff q = *pb;
+    ld_madd_ip(p, q, H);
+  }
+  Aff a;
+  const bool fin = !ld_is_inf(p);
+  a.x = gf_zero();
+  a.y = gf_zero();
+  Gf w = gf_zero();
+  if (fin) {
+    if (out_enc && !gf_is_zero(p.X)) {
+      // x = X / Z, y = Y / Z^2, y / x = Y / (X Z): everything from inv = 1 / (X Z), as in k_tail
+      const Gf inv = gf_inv_fast(gf_mul(p.X, p.Z, H), T, H);
+      const Gf zi = gf_mul(inv, p.X, H);
+      a.x = gf_mul(p.X, zi, H);
+      a.y = gf_mul(p.Y, gf_sqr(zi), H);
+      const Gf lam1 = gf_add(gf_add(a.x, gf_mul(p.Y, inv, H)), gf_one());
+      w = gf_sqr_tab_wide(gf_sqr_tab_wide(lam1, T.t116), T.t116);
+      if (rule) w = codec_present(w, rule, T);
+    } else {
+      Gf zi = gf_inv_fast(p.Z, T, H);
+      a.x = gf_mul(p.X, zi, H);
+      a.y = gf_mul(p.Y, gf_sqr(zi), H);
+      if (out_enc) {  // x = 0 (the point of order two): the same formula as k_encode_point, where 1 / 0 reads 0
+        const Gf lam1 = gf_add(gf_add(a.x, gf_mul(a.y, gf_inv_fast(a.x, T, H), H)), gf_one());
+        w = gf_sqr_tab_wide(gf_sqr_tab_wide(lam1, T.t116), T.t116);
+        if (rule) w = codec_present(w, rule, T);
+      }
+    }
+  }
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    out_xy[k] = a.x.w[k];
+    out_xy[8 + k] = a.y.w[k];
+  }
+  *out_inf = fin ? 0u : 1u;
+  if (out_enc) store30(out_enc, w, rule);
+  const unsigned long long ea = *err_a, eb = *err_b;
+  *err_dst = ea != ~0ull ? ea : (eb != ~0ull ? eb + (unsigned long long)covered : ~0ull);
+}
+
 // multiplier microbenchmark (bench.py's roofline leg runs it OUTSIDE the timed loop): a dependent chain of products per
 // lane through the Karatsuba LDS multiplier at the occupancy of k_affine_round (256-thread blocks, 3 waves per SIMD)
 __global__ void __launch_bounds__(EC_TPB) __attribute__((amdgpu_waves_per_eu(3, 3))) k_ubench_mul(Gf* __restrict__ out, int reps) {
@@ -2599,6 +2659,20 @@ int msm_sum_points_dev(const void* d_pts, uint32_t pt_stride_bytes, const void* 
   return DVP_OK;
 }
 
+// the join of a mixed MSM (k_join_points), enqueued on `st`: d_a / d_b = the two partial points, each with its u32 infinity flag and
+// its scalar-range word; d_out_enc (optional) receives the sum's 30-byte encoding, d_err_out the merged range word
+int msm_join_points_dev(const void* d_a_xy, const void* d_a_inf, const unsigned long long* d_a_err, const void* d_b_xy, const void* d_b_inf,
+                        const unsigned long long* d_b_err, uint32_t covered, void* d_out_xy, void* d_out_inf, void* d_out_enc,
+                        unsigned long long* d_err_out, hipStream_t st) {
+  GfSqrTables Tsq;
+  DVP_TRY(gf_sqr_tables(&Tsq, st));
+  hipLaunchKernelGGL(k_join_points, dim3(1), dim3(64), GF_LDS_BYTES_PER_WAVE, st, (const Aff*)d_a_xy, (const uint32_t*)d_a_inf, d_a_err, (const Aff*)d_b_xy,
+                     (const uint32_t*)d_b_inf, d_b_err, covered, Tsq, (uint32_t*)d_out_xy, (uint32_t*)d_out_inf, (uint8_t*)d_out_enc,
+                     d_out_enc ? dvp_codec_get_rule() : 0, d_err_out);
+  DVP_HIP(hipGetLastError());
+  return DVP_OK;
+}
+
 int msm_affine_dev(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, void* d_out_xy,
                    void* d_out_inf, hipStream_t st) {
   return msm_core(d_scalars, d_bases, d_inf, n, nullptr, 0, d_out_xy, d_out_inf, st);
@@ -2615,9 +2689,9 @@ void msm_fixed_destroy(MsmFixedCtx* c);
 // tests.  (Rounds 2-3 also carried two SLIDING-window flavours over a multiple of every base for every digit position, 94-97 GB
 // of tables at 2^20; the signed aligned windows matched their speed at a twentieth of the memory -- 23.54 against 23.57 / 23.98 ms
 // -- and they were removed in round 4 together with their recoders, table builders and test matrix.)
-static int msm_fixed_build(const Aff* d_bases, uint32_t n_total, size_t range_hint, MsmFixedCtx** out, hipError_t* alloc_err) {
-  MsmFixedCtx* c = new MsmFixedCtx();
-  c->n_total = n_total;
+// window size, window count and sort split of a context that typically serves `range_hint` bases per call -- everything about a
+// context that does not need the device (the table-budget planner reads the row count from here)
+static void msm_fixed_settle(MsmFixedCtx* c, size_t range_hint) {
   double best = 1e300;
   int best_c = 8;
   const bool signed_aligned = tune().msm_aligned_signed != 0;
@@ -2649,7 +2723,19 @@ static int msm_fixed_build(const Aff* d_bases, uint32_t n_total, size_t range_hi
   const int kb = c->key_bits();
   c->hi_bits = kb / 2;  // even split: both levels have <= 2^10 bins and use the LDS-staged scatters
   if (int h = (int)tune().fx_hi; h >= 0 && h <= 10 && kb - h <= 15 && kb - h >= 1) c->hi_bits = h;
-  hipError_t e = hipMalloc((void**)&c->table, (size_t)c->rows() * n_total * sizeof(Aff));
+}
+// rows of the table msm_fixed_build would settle on for a context of `count` bases used whole (range_hint = count)
+int msm_fixed_rows_for(size_t count) {
+  MsmFixedCtx probe;
+  msm_fixed_settle(&probe, count);
+  return probe.rows();
+}
+static int msm_fixed_build(const Aff* d_bases, uint32_t n_total, size_t range_hint, MsmFixedCtx** out, hipError_t* alloc_err) {
+  MsmFixedCtx* c = new MsmFixedCtx();
+  c->n_total = n_total;
+  msm_fixed_settle(c, range_hint);
+  // DVP_MSM_TABLE_REFUSE = 1 (tests): as if the runtime had refused the table, without asking it
+  hipError_t e = tune().msm_table_refuse == 1 ? hipErrorOutOfMemory : hipMalloc((void**)&c->table, (size_t)c->rows() * n_total * sizeof(Aff));
   *alloc_err = e;
   if (e == hipSuccess) {
     if (c->signed_digits) {
@@ -2675,7 +2761,7 @@ static int msm_fixed_build(const Aff* d_bases, uint32_t n_total, size_t range_hi
   if (e != hipSuccess) {
     c->table = *alloc_err == hipSuccess ? c->table : nullptr;
     msm_fixed_destroy(c);
-    return hip_fail(e, "msm_fixed_create", __FILE__, __LINE__);
+    return hip_fail(e, "msm_fixed_create", __FILE__, __LINE__);  // DVP_ENOMEM for a refused table or scratch allocation
   }
   *out = c;
   return DVP_OK;
@@ -2725,6 +2811,38 @@ int msm_affine_dev_enc(const void* d_scalars, const void* d_bases, const void* d
 }  // namespace dvp
 
 using namespace dvp;
+
+// ---- the table-budget planner (include/dvpari_internal.h: dvp_table_plan) ------------------------------------------------------
+// largest count <= total whose table -- rows x count x 64 bytes, rows as msm_fixed_build settles them for THAT count -- fits `budget`;
+// 0 when that is fewer than fixed_min bases.  rows(count) only falls as count grows (more bases favour wider windows), so from an
+// upper bound the iteration n <- budget / (64 rows(n)) comes down onto the largest fixed point; the final test holds whatever
+// rows() does.
+static size_t table_max_prefix(size_t total, uint64_t budget, size_t fixed_min, uint64_t* bytes) {
+  *bytes = 0;
+  if (total == 0 || total < fixed_min || total >= ((size_t)1 << 27)) return 0;
+  size_t n = total;
+  for (int it = 0; it < 64 && n > 0; ++it) {
+    const uint64_t per = (uint64_t)msm_fixed_rows_for(n) * sizeof(Aff);
+    const uint64_t fit = budget / per;
+    if (fit >= n) break;
+    n = (size_t)fit;
+  }
+  while (n > 0 && (uint64_t)msm_fixed_rows_for(n) * n * sizeof(Aff) > budget) --n;  // never taken when rows() is monotone
+  if (n < fixed_min || n == 0) return 0;
+  *bytes = (uint64_t)msm_fixed_rows_for(n) * n * sizeof(Aff);
+  return n;
+}
+extern "C" int dvp_table_plan(size_t size0, size_t size1, uint64_t budget_bytes, size_t covered[2], uint64_t bytes[2]) {
+  if (!covered || !bytes) return DVP_EINVAL;
+  const size_t fixed_min = (size_t)(tune().msm_fixed_min > 0 ? tune().msm_fixed_min : 1);
+  covered[0] = 0;
+  bytes[0] = 0;
+  covered[1] = table_max_prefix(size1, budget_bytes, fixed_min, &bytes[1]);  // the K MSM (4m terms) first
+  // the commitment MSM only once the K MSM is served whole (or takes no table at any budget): at most one of the two is partly covered
+  if (covered[1] == size1 || size1 < fixed_min || size1 >= ((size_t)1 << 27))
+    covered[0] = table_max_prefix(size0, budget_bytes - bytes[1], fixed_min, &bytes[0]);
+  return DVP_OK;
+}
 
 extern "C" int dvp_msm_affine_dev(const void* d_scalars, const void* d_bases_xy, const void* d_bases_inf, size_t n,
                                   void* d_out_xy, void* d_out_inf, void* stream) {

@@ -56,6 +56,10 @@ int msm_affine_dev_enc(const void* d_scalars, const void* d_bases, const void* d
                        void* d_out_enc, void* h_copy, const void* d_copy, size_t copy_bytes, hipStream_t st, unsigned long long* d_err_defer);
 int msm_fixed_dev(const MsmFixedCtx* c, const void* d_scalars, const void* d_inf, uint32_t lo, uint32_t hi, void* d_out_xy,
                   void* d_out_inf, hipStream_t st);
+int msm_fixed_rows_for(size_t count);
+int msm_join_points_dev(const void* d_a_xy, const void* d_a_inf, const unsigned long long* d_a_err, const void* d_b_xy, const void* d_b_inf,
+                        const unsigned long long* d_b_err, uint32_t covered, void* d_out_xy, void* d_out_inf, void* d_out_enc,
+                        unsigned long long* d_err_out, hipStream_t st);
 
 // ---- domain tables from the isogeny chain ---------------------------------------------------------
 // For S = even leaves (D) of the 2m-leaf tree, Z_S = U - c0 V with (U,V) the projective image under
@@ -426,6 +430,7 @@ static constexpr size_t FIN_BYTES = FIN_OFF_MSMERR + 16;
 static constexpr size_t DEV_OFF_ALPHA_M = FIN_BYTES;           // device only: alpha (Montgomery), -Z_D(alpha) (Montgomery)
 static constexpr size_t DEV_OFF_NEGZ = DEV_OFF_ALPHA_M + 32;
 static constexpr size_t DEV_BLOCK_BYTES = DEV_OFF_NEGZ + 32;
+static constexpr size_t MIX_OFF_INF = 128, MIX_OFF_ERR = 136, MIX_OFF_ERR_OUT = 152, MIX_BYTES = 160;  // dvp_prover::mix
 struct dvp_prover {
   uint32_t log_m = 0, m = 0, n_pub = 0, n_wires = 0;
   dvp_ecfft* tree = nullptr;  // 2m leaves (tree2n)
@@ -445,6 +450,12 @@ struct dvp_prover {
   // lazily once the SRS is complete (12 x the base storage: 4.8 GB at m = 2^20 -- HBM is not the scarce resource)
   MsmFixedCtx* fx[2] = {nullptr, nullptr};
   size_t fx_lo[2] = {0, 0}, fx_hi[2] = {0, 0};  // index range of the bases the context of MSM `which` was built for
+  // dvp_prover_set_table_budget: the most HBM the tables may hold per device (UINT64_MAX = no limit).  Under a limit the table of MSM
+  // `which` covers exactly the prefix [0, covered) dvp_table_plan allots it, and the rest of the sum goes through the one-shot MSM
+  uint64_t table_budget = UINT64_MAX;
+  bool table_refused[2] = {false, false};  // the runtime refused this MSM's table: one-shot until the next dvp_prover_set_table_budget
+  // the two halves of a mixed MSM: [prefix point 64 | suffix point 64 | their infinity flags 2 x u32 | their range words 2 x u64 | merged word u64]
+  char* mix = nullptr;
   bool last_begin_extended = false;            // dvp_prove_begin_partial(need_extend): q2 / k_r are valid only if true
   uint32_t ext_filled = 0;                     // bit v: extended vector v of this proof is in E2 (extended here, or received and marked)
   // in-library multi-GPU (dvp_set_devices): one shard per listed device, each with its slice of both base vectors
@@ -558,7 +569,9 @@ static int prover_init(dvp_prover* p, uint32_t log2_m, uint32_t n_public, uint32
   p->alpha_dev = (Fr*)((char*)p->abir0 + FIN_OFF_ALPHA);
   p->msm_err = (unsigned long long*)((char*)p->abir0 + FIN_OFF_MSMERR);
   p->chal_dev = (Fr*)((char*)p->abir0 + DEV_OFF_ALPHA_M);
-  DVP_HIP(hipHostMalloc((void**)&p->fin_host, FIN_BYTES + 64, hipHostMallocDefault));
+  DVP_HIP(hipHostMalloc((void**)&p->fin_host, FIN_BYTES + 64 + 16, hipHostMallocDefault));  // + the merged range word of a mixed MSM
+  DVP_TRY(A((void**)&p->mix, MIX_BYTES));
+  p->table_budget = tune().table_budget_bytes < 0 ? UINT64_MAX : (uint64_t)tune().table_budget_bytes;
   DVP_HIP(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
   DVP_HIP(hipEventCreateWithFlags(&p->ev_alpha, hipEventDisableTiming));
   DVP_HIP(hipEventCreateWithFlags(&p->ev_negz, hipEventDisableTiming));
@@ -590,7 +603,7 @@ extern "C" void dvp_prover_destroy(dvp_prover* p) {
   if (!p) return;
   void* ptrs[] = {p->dD, p->dD2, p->barw, p->z2inv, p->coeffs_m, p->bases_a, p->inf_a, p->bases_k, p->inf_k, p->w, p->E,
                   p->E2, p->r2, p->SA, p->den, p->SK, p->partial, p->abir0 /* + flags + enc */, p->pts, p->pts_inf32,
-                  p->pts_inf8};
+                  p->pts_inf8, p->mix};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (p->fin_host) (void)hipHostFree(p->fin_host);
@@ -933,23 +946,90 @@ static int prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, vo
   // fixed-base mode pays off once the shared 2^c-bucket set is well filled.  The pre-rotated table covers only the index
   // range this prover is asked for (a rank of a multi-process prove always asks for the same slice: W x slice x 64 B of
   // HBM instead of W x everything); a call outside the covered range rebuilds it for the new range.
+  // A table the runtime refuses (DVP_ENOMEM) does not fail the call: the MSM goes through the one-shot path, and the allocation
+  // is not tried again before the next dvp_prover_set_table_budget.
   const size_t fixed_min = (size_t)(tune().msm_fixed_min > 0 ? tune().msm_fixed_min : 1);
-  if (hi - lo >= fixed_min && total < ((size_t)1 << 27)) {
-    if (p->fx[which] && (lo < p->fx_lo[which] || hi > p->fx_hi[which])) {
-      msm_fixed_destroy(p->fx[which]);
-      p->fx[which] = nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  void* h_copy = d_out_enc && !d_err_defer ? p->fin_host : nullptr;
+  if (p->table_budget == UINT64_MAX) {
+    if (hi - lo >= fixed_min && total < ((size_t)1 << 27) && !p->table_refused[which]) {
+      if (p->fx[which] && (lo < p->fx_lo[which] || hi > p->fx_hi[which])) {
+        msm_fixed_destroy(p->fx[which]);
+        p->fx[which] = nullptr;
+      }
+      int rc = DVP_OK;
+      if (!p->fx[which]) {
+        rc = msm_fixed_create(bs + lo, (uint32_t)(hi - lo), hi - lo, &p->fx[which]);
+        if (rc != DVP_OK && rc != DVP_ENOMEM) return rc;
+        p->fx_lo[which] = lo;
+        p->fx_hi[which] = hi;
+      }
+      if (rc == DVP_OK) {
+        const size_t o = p->fx_lo[which];
+        return msm_fixed_dev_enc(p->fx[which], sc + lo, inf + lo, (uint32_t)(lo - o), (uint32_t)(hi - o), d_out_xy, d_out_inf, d_out_enc, h_copy, p->abir0,
+                                 FIN_BYTES, st, d_err_defer);
+      }
+      p->table_refused[which] = true;
     }
-    if (!p->fx[which]) {
-      DVP_TRY(msm_fixed_create(bs + lo, (uint32_t)(hi - lo), hi - lo, &p->fx[which]));
-      p->fx_lo[which] = lo;
-      p->fx_hi[which] = hi;
-    }
-    const size_t o = p->fx_lo[which];
-    return msm_fixed_dev_enc(p->fx[which], sc + lo, inf + lo, (uint32_t)(lo - o), (uint32_t)(hi - o), d_out_xy, d_out_inf, d_out_enc,
-                             d_out_enc && !d_err_defer ? p->fin_host : nullptr, p->abir0, FIN_BYTES, (hipStream_t)stream, d_err_defer);
+    return msm_affine_dev_enc(sc + lo, bs + lo, inf + lo, hi - lo, d_out_xy, d_out_inf, d_out_enc, h_copy, p->abir0, FIN_BYTES, st, d_err_defer);
   }
-  return msm_affine_dev_enc(sc + lo, bs + lo, inf + lo, hi - lo, d_out_xy, d_out_inf, d_out_enc, d_out_enc && !d_err_defer ? p->fin_host : nullptr, p->abir0,
-                            FIN_BYTES, (hipStream_t)stream, d_err_defer);
+  // Under a budget the table is the planned prefix [0, cov) of the WHOLE vector, whatever range is asked for: [lo, min(hi, cov))
+  // comes out of it, the rest of [lo, hi) out of the one-shot MSM, and k_join_points adds the two (a mixed MSM).
+  size_t cov = 0;
+  if (!p->table_refused[which]) {
+    size_t pc[2];
+    uint64_t pb[2];
+    DVP_TRY(dvp_table_plan(dvp_prover_msm_size(p, 0), dvp_prover_msm_size(p, 1), p->table_budget, pc, pb));
+    cov = pc[which];
+  }
+  if (p->fx[which] && (p->fx_lo[which] != 0 || p->fx_hi[which] != cov)) {
+    msm_fixed_destroy(p->fx[which]);
+    p->fx[which] = nullptr;
+  }
+  const size_t a = hi < cov ? hi : cov;  // end of the part the table serves
+  if (cov > 0 && a > lo && a - lo >= fixed_min) {
+    int rc = DVP_OK;
+    if (!p->fx[which]) {
+      rc = msm_fixed_create(bs, (uint32_t)cov, cov, &p->fx[which]);
+      if (rc != DVP_OK && rc != DVP_ENOMEM) return rc;
+      p->fx_lo[which] = 0;
+      p->fx_hi[which] = cov;
+    }
+    if (rc == DVP_ENOMEM) {
+      p->table_refused[which] = true;
+    } else if (a == hi) {
+      return msm_fixed_dev_enc(p->fx[which], sc + lo, inf + lo, (uint32_t)lo, (uint32_t)hi, d_out_xy, d_out_inf, d_out_enc, h_copy, p->abir0, FIN_BYTES, st,
+                               d_err_defer);
+    } else {
+      // both halves with deferred completion on the caller's stream (the second one queues behind the first in the same workspace),
+      // then the join: it writes what a single MSM's tail kernel would have -- point, encoding, range word -- so the call ends as
+      // the single path does: deferred, or with the block copied to pinned memory ahead of ONE synchronisation
+      char* mx = p->mix;
+      unsigned long long* e2 = (unsigned long long*)(mx + MIX_OFF_ERR);
+      unsigned long long* e_out = d_err_defer ? d_err_defer : (unsigned long long*)(mx + MIX_OFF_ERR_OUT);
+      DVP_TRY(msm_fixed_dev_enc(p->fx[which], sc + lo, inf + lo, (uint32_t)lo, (uint32_t)a, mx, mx + MIX_OFF_INF, nullptr, nullptr, nullptr, 0, st, e2));
+      rc = msm_affine_dev_enc(sc + a, bs + a, inf + a, hi - a, mx + 64, mx + MIX_OFF_INF + 4, nullptr, nullptr, nullptr, 0, st, e2 + 1);
+      if (rc == DVP_OK)
+        rc = msm_join_points_dev(mx, mx + MIX_OFF_INF, e2, mx + 64, mx + MIX_OFF_INF + 4, e2 + 1, (uint32_t)(a - lo), d_out_xy, d_out_inf, d_out_enc, e_out, st);
+      if (rc != DVP_OK) {
+        (void)hipStreamSynchronize(st);  // the first half is in flight in its workspace
+        return rc;
+      }
+      if (d_err_defer) return DVP_OK;
+      volatile unsigned long long* h_err = (volatile unsigned long long*)(p->fin_host + FIN_BYTES + 64);
+      if (h_copy) DVP_HIP(hipMemcpyAsync(h_copy, p->abir0, FIN_BYTES, hipMemcpyDeviceToHost, st));
+      DVP_HIP(hipMemcpyAsync((void*)h_err, e_out, 8, hipMemcpyDeviceToHost, st));
+      DVP_HIP(hipStreamSynchronize(st));
+      count_host_wait(0);
+      const unsigned long long e = *h_err;
+      if (e != ~0ull) {
+        g_last_error_index = (int64_t)(e & 0xffffffffull);
+        return DVP_EINVAL;
+      }
+      return DVP_OK;
+    }
+  }
+  return msm_affine_dev_enc(sc + lo, bs + lo, inf + lo, hi - lo, d_out_xy, d_out_inf, d_out_enc, h_copy, p->abir0, FIN_BYTES, st, d_err_defer);
 }
 extern "C" int dvp_prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, void* d_out_xy, void* d_out_inf, void* stream) {
   if (p && (which == 0 || which == 1) && d_out_xy == (void*)(p->pts + which)) p->enc_fused[which] = false;  // the point changes, its encoding does not follow
@@ -1024,8 +1104,22 @@ static int shards_build(dvp_prover* p, const std::vector<int>& devs) {
           DVP_HIP(hipMemcpyPeer(sh.bases[w], sh.device, src_b, p->home_device, cnt * sizeof(Aff)));
           DVP_HIP(hipMemcpyPeer(sh.inf[w], sh.device, src_i, p->home_device, cnt));
         }
-        const size_t fixed_min = (size_t)(tune().msm_fixed_min > 0 ? tune().msm_fixed_min : 1);
-        if (cnt >= fixed_min) DVP_TRY(msm_fixed_create(sh.bases[w], (uint32_t)cnt, cnt, &sh.fx[w]));
+      }
+      // tables: the device's budget split evenly among the shards that name it, the K MSM first, all or nothing per MSM; a shard
+      // whose table does not fit, or is refused by the runtime, runs one-shot (mgpu_msm: sh.fx[w] == nullptr)
+      const size_t fixed_min = (size_t)(tune().msm_fixed_min > 0 ? tune().msm_fixed_min : 1);
+      size_t sharing = 0;
+      for (int d : devs) sharing += d == sh.device ? 1 : 0;
+      uint64_t left = p->table_budget == UINT64_MAX ? UINT64_MAX : p->table_budget / sharing;
+      for (int w = 1; w >= 0; --w) {
+        const size_t cnt = sh.hi[w] - sh.lo[w];
+        if (cnt < fixed_min || p->table_refused[w]) continue;
+        const uint64_t need = (uint64_t)msm_fixed_rows_for(cnt) * cnt * sizeof(Aff);
+        if (need > left) continue;
+        const int rc_t = msm_fixed_create(sh.bases[w], (uint32_t)cnt, cnt, &sh.fx[w]);
+        if (rc_t == DVP_ENOMEM) { p->table_refused[w] = true; continue; }
+        DVP_TRY(rc_t);
+        if (left != UINT64_MAX) left -= need;
       }
       return DVP_OK;
     };
@@ -1125,6 +1219,44 @@ extern "C" uint64_t dvp_prover_msm_table_bytes(const dvp_prover* p, int which, i
     if (s && signed_windows) *signed_windows = 1;
   }
   return total;
+}
+// dvp_prover_set_table_budget: tables that no longer fit are released now, the rest follows the new plan at the next proof
+extern "C" int dvp_prover_set_table_budget(dvp_prover* p, uint64_t bytes) {
+  if (!p) return DVP_EINVAL;
+  p->table_budget = bytes;
+  p->table_refused[0] = p->table_refused[1] = false;  // a new budget is the one occasion to ask the runtime again
+  shards_release(p);                                  // rebuilt under the new budget by the next sharded proof
+  size_t pc[2] = {0, 0};
+  uint64_t pb[2] = {UINT64_MAX, UINT64_MAX};
+  if (bytes != UINT64_MAX) DVP_TRY(dvp_table_plan(dvp_prover_msm_size(p, 0), dvp_prover_msm_size(p, 1), bytes, pc, pb));
+  for (int w = 0; w < 2; ++w)
+    if (p->fx[w] && msm_fixed_table_bytes(p->fx[w], nullptr) > pb[w]) {
+      msm_fixed_destroy(p->fx[w]);
+      p->fx[w] = nullptr;
+    }
+  return DVP_OK;
+}
+extern "C" int dvp_prover_msm_coverage(const dvp_prover* p, int which, size_t* covered, size_t* total, int* reason) {
+  if (!p || (which != 0 && which != 1) || !covered || !total || !reason) return DVP_EINVAL;
+  const size_t n = dvp_prover_msm_size(p, which);
+  const size_t fixed_min = (size_t)(tune().msm_fixed_min > 0 ? tune().msm_fixed_min : 1);
+  const size_t full = n >= fixed_min && n < ((size_t)1 << 27) ? n : 0;  // what no budget at all would put into tables
+  size_t pc[2];
+  uint64_t pb[2];
+  DVP_TRY(dvp_table_plan(dvp_prover_msm_size(p, 0), dvp_prover_msm_size(p, 1), p->table_budget, pc, pb));
+  size_t cov = pc[which];
+  if (!p->shards.empty()) {  // in-library multi-GPU: the leading shards that hold a table
+    cov = 0;
+    for (const auto& sh : p->shards) {
+      if (!sh.fx[which]) break;
+      cov += sh.hi[which] - sh.lo[which];
+    }
+  }
+  if (p->table_refused[which] && p->shards.empty()) cov = 0;
+  *covered = cov;
+  *total = n;
+  *reason = p->table_refused[which] ? 2 : (cov >= full ? 0 : 1);
+  return DVP_OK;
 }
 // the table the first pair round of MSM `which` gathers from on the home device (bench.py points dvp_ubench_gather at it)
 extern "C" int dvp_prover_msm_table_ptr(const dvp_prover* p, int which, const void** d_table, uint64_t* bytes) {

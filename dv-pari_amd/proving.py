@@ -252,6 +252,19 @@ class Prover:
         b = int(lib.dvp_prover_msm_table_bytes(self._h, which, C.byref(s)))
         return b, bool(s.value)
 
+    def set_table_budget(self, nbytes):
+        """the most HBM per device the fixed-base tables of this prover may hold (None = no limit, 0 = no tables); tables that no
+        longer fit are released at once, the next proof follows the new plan (dvp_prover_set_table_budget)"""
+        b = (1 << 64) - 1 if nbytes is None else min(int(nbytes), (1 << 64) - 1)
+        check(lib.dvp_prover_set_table_budget(self._h, b), "dvp_prover_set_table_budget")
+
+    def msm_coverage(self, which: int):
+        """(covered, total, reason): leading bases of MSM `which` served from tables, its size, and why not all of it --
+        0 not limited, 1 the budget, 2 an allocation the runtime refused (dvp_prover_msm_coverage)"""
+        cov, tot, why = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+        check(lib.dvp_prover_msm_coverage(self._h, which, C.byref(cov), C.byref(tot), C.byref(why)), "dvp_prover_msm_coverage")
+        return int(cov.value), int(tot.value), int(why.value)
+
     def msm_partial(self, which: int, lo: int, hi: int, d_out_xy: int, d_out_inf: int, stream: int = 0):
         check(lib.dvp_prover_msm_partial(self._h, which, lo, hi, d_out_xy, d_out_inf, stream), "dvp_prover_msm_partial")
 

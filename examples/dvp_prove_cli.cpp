@@ -2,7 +2,10 @@
 // against.  It mirrors the reference's `Proof::prove(cache_dir, public_inputs, private_inputs)` call
 // (src/proving.rs:426) from files alone:
 //
-//   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3]
+//   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3] [--table-budget <bytes>]
+//
+// --table-budget <bytes>: the most HBM per device the prover's fixed-base tables may hold (dvp_prover_set_table_budget; 0 = no
+// tables).  What does not fit runs through the one-shot MSM; the proof bytes do not depend on it.  The coverage goes to stderr.
 //
 // --devices d0,d1,..: in-library multi-GPU (dvp_set_devices): the two MSMs of the proof are sharded over the listed
 // devices, one host thread each; d0 is the home device.  An id may repeat.  The proof bytes do not depend on the list.
@@ -27,8 +30,19 @@ int main(int argc, char** argv) {
   std::vector<int> devices;
   int repeat = 0, threads = 1;  // --repeat N --threads T: N more proofs through dvp_prove_cache_dir from T host threads
   std::vector<char*> pos;
+  bool have_budget = false;
+  uint64_t budget = UINT64_MAX;
   for (int i = 1; i < argc; ++i) {
-    if (std::string(argv[i]) == "--devices" && i + 1 < argc) {
+    if (std::string(argv[i]) == "--table-budget" && i + 1 < argc) {
+      char* end = nullptr;
+      const unsigned long long v = strtoull(argv[++i], &end, 10);
+      if (end == argv[i] || *end != 0 || argv[i][0] == '-') {
+        fprintf(stderr, "--table-budget: expected a number of bytes, got '%s'\n", argv[i]);
+        return 2;
+      }
+      budget = (uint64_t)v;
+      have_budget = true;
+    } else if (std::string(argv[i]) == "--devices" && i + 1 < argc) {
       for (char* tok = argv[++i]; *tok;) {
         char* end = tok;
         const long id = strtol(tok, &end, 10);
@@ -53,7 +67,7 @@ int main(int argc, char** argv) {
     }
   }
   if (pos.size() < 2) {
-    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--repeat N --threads T]\n", argv[0]);
+    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--repeat N --threads T]\n", argv[0]);
     return 2;
   }
   argc = (int)pos.size() + 1;
@@ -105,7 +119,24 @@ int main(int argc, char** argv) {
     dvp_prover_destroy(p);
     return 1;
   }
+  if (have_budget) {
+    rc = dvp_prover_set_table_budget(p, budget);
+    if (rc != DVP_OK) {
+      fprintf(stderr, "--table-budget: %s\n", dvp_strerror(rc));
+      dvp_prover_destroy(p);
+      return 1;
+    }
+  }
   rc = dvp_prove(p, w.data() + 4, n_public, w.data() + 4 * (1 + (size_t)n_public), (uint32_t)(n_wires - 1 - n_public), proof);
+  if (have_budget && rc == DVP_OK)
+    for (int which = 1; which >= 0; --which) {
+      size_t covered = 0, total = 0;
+      int reason = 0;
+      if (dvp_prover_msm_coverage(p, which, &covered, &total, &reason) == DVP_OK)
+        fprintf(stderr, "MSM %d: %zu of %zu bases from tables (%llu bytes)%s\n", which, covered, total,
+                (unsigned long long)dvp_prover_msm_table_bytes(p, which, nullptr),
+                reason == 1 ? ", limited by the budget" : reason == 2 ? ", table refused by the runtime" : "");
+    }
   dvp_prover_destroy(p);
   if (rc != DVP_OK) {
     fprintf(stderr, "prove: %s (index %lld)\n", dvp_strerror(rc), (long long)dvp_last_error_index());
@@ -121,6 +152,15 @@ int main(int argc, char** argv) {
     const uint64_t* prv = w.data() + 4 * (1 + (size_t)n_public);
     const uint32_t n_prv = (uint32_t)(n_wires - 1 - n_public);
     uint8_t warm[118];
+    if (have_budget) {  // the prover dvp_prove_cache_dir keeps for this directory (a second one, DVP_CACHE_REPLICAS=2, starts from DVP_TABLE_BUDGET_BYTES)
+      dvp_prover* cp = nullptr;
+      rc = dvp_cache_dir_prover(dir.c_str(), n_public, &cp);
+      if (rc == DVP_OK) rc = dvp_prover_set_table_budget(cp, budget);
+      if (rc != DVP_OK) {
+        fprintf(stderr, "--table-budget: %s\n", dvp_strerror(rc));
+        return 1;
+      }
+    }
     for (int t = 0; t < 2; ++t) {  // opens the cache_dir entry (and, below, its second prover) outside the timed part
       rc = dvp_prove_cache_dir(dir.c_str(), pub, n_public, prv, n_prv, warm);
       if (rc != DVP_OK || memcmp(warm, proof, 118)) {

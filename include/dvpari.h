@@ -37,11 +37,13 @@ typedef enum dvp_status {
   DVP_EINVAL = -1,  /* bad size / null pointer / non-canonical scalar */
   DVP_EDECODE = -2, /* invalid 30-byte point (assert!(valid), src/io_utils.rs:223) */
   DVP_EUNSAT = -3,  /* R1CS row unsatisfied (assert_eq!, src/proving.rs:389-395) */
-  DVP_EHIP = -4,    /* HIP runtime error */
+  DVP_EHIP = -4,    /* HIP runtime error other than out of memory */
   /* -5 is unused: no entry point of this library calls RCCL -- partial MSM results are combined by the host
    * (one process per GPU: torch.distributed all-gather + dvp_points_sum_dev) or by peer copies (dvp_set_devices) */
   DVP_EIO = -6,
-  DVP_ENOMEM = -7,
+  DVP_ENOMEM = -7,  /* the HIP runtime refused an allocation (hipErrorOutOfMemory, and only that): retry with a smaller plan --
+                     * dvp_prover_set_table_budget, fewer provers per device.  A prover does not return it for its tables (it proves
+                     * without them), only when the working set of a proof itself does not fit */
   DVP_ECHALLENGE = -8 /* Fiat-Shamir challenge fell inside D u D' (assert!, src/proving.rs:548-556) */
 } dvp_status;
 
@@ -128,6 +130,8 @@ int dvp_msm_affine_dev(const void* d_scalars, const void* d_bases_xy, const void
  * (W x the storage) and all windows then share one bucket set.  range_hint = bases a typical call covers
  * (the per-GPU shard; 0 = n).  run: sum over i in [lo, hi) of scalars[i - lo] * base[i]. */
 typedef struct dvp_msm_ctx dvp_msm_ctx;
+/* DVP_ENOMEM: the table does not fit the device.  There is no fallback inside a context -- the context IS the table -- so the caller
+ * uses dvp_msm_affine (the one-shot MSM, no table) for these bases then. */
 int dvp_msm_ctx_create(const uint64_t* bases_xy, const uint8_t* bases_inf, size_t n, size_t range_hint, dvp_msm_ctx** out);
 void dvp_msm_ctx_destroy(dvp_msm_ctx* ctx);
 /* window bits c and window count the context settled on (all W windows share one bucket set: 2^(c-1) buckets of |digit| for the
@@ -218,8 +222,23 @@ int dvp_prove_quotient(dvp_prover* p, void* stream);
 size_t dvp_prover_msm_size(const dvp_prover* p, int which);
 /* window bits / window count chosen for MSM `which` (0,0 until its fixed-base tables exist) */
 int dvp_prover_msm_plan(const dvp_prover* p, int which, int* c_bits, int* windows);
-/* HBM held by the fixed-base tables of MSM `which` on all devices (see dvp_msm_ctx_table_bytes) */
+/* HBM held by the fixed-base tables of MSM `which` on all devices (see dvp_msm_ctx_table_bytes): what is actually allocated now --
+ * 0 before the first proof, and never more per device than dvp_prover_set_table_budget allows */
 uint64_t dvp_prover_msm_table_bytes(const dvp_prover* p, int which, int* signed_windows);
+/* The most HBM per device the fixed-base tables of this prover (both MSMs together) may hold.  UINT64_MAX = no limit (the default);
+ * 0 = no tables.  New provers, those of dvp_prove_cache_dir included, start from DVP_TABLE_BUDGET_BYTES in the environment (read
+ * once).  May be called at any time between proofs: tables that no longer fit are released at once, and the next proof follows the
+ * new plan.  The plan is deterministic: MSM 1 ([k_a | k_b | k_r], 4m terms) is served first, then MSM 0; at most one of the two is
+ * partly covered, by a table over a PREFIX [0, covered) of its bases -- the rest of that sum runs through the one-shot MSM and one
+ * point addition joins the two; a prefix shorter than DVP_MSM_FIXED_MIN gets no table.  Proof bytes do not depend on the budget.
+ * With dvp_set_devices the budget of a device is split evenly among the shards that name it, and a shard's table is all or
+ * nothing per MSM.  A table the runtime refuses although the budget allows it is not an error either: that MSM runs one-shot
+ * (dvp_prover_msm_coverage: reason 2) and the allocation is tried again only after the next call of this function. */
+int dvp_prover_set_table_budget(dvp_prover* p, uint64_t bytes);
+/* *covered = leading bases of MSM `which` served from tables on the home device (with dvp_set_devices: by the leading shards that
+ * hold one), *total = dvp_prover_msm_size, *reason = 0 not limited (everything DVP_MSM_FIXED_MIN lets into a table is in one),
+ * 1 limited by the budget, 2 an allocation was refused by the runtime.  Before the first proof this is the plan, not zeros. */
+int dvp_prover_msm_coverage(const dvp_prover* p, int which, size_t* covered, size_t* total, int* reason);
 int dvp_prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, void* d_out_xy, void* d_out_inf, void* stream);
 int dvp_prove_challenge(dvp_prover* p, const void* d_commit_xy, const void* d_commit_inf, void* stream);
 /* The same phase for provers that share one proof by INDEX (one process per GPU): the pointwise stages, the batch

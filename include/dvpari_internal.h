@@ -56,6 +56,13 @@ int dvp_ubench_gather(const void* d_table, size_t table_bytes, int reps, double*
  * (NULL / 0 before the first proof) -- what dvp_ubench_gather is pointed at */
 int dvp_prover_msm_table_ptr(const dvp_prover* p, int which, const void** d_table, uint64_t* bytes);
 
+/* The table-budget planner of dvp_prover_set_table_budget as a pure host function (no device is touched): size0 / size1 = the
+ * terms of MSM 0 / MSM 1 of a prover, budget_bytes = its budget.  covered[w] = leading bases of MSM w that get a table, bytes[w] =
+ * that table's size: rows x covered[w] x 64 with the row count the fixed-base context settles on for that many bases
+ * (DVP_MSM_FIXED_C, DVP_MSM_ALIGNED_SIGNED and DVP_MSM_FIXED_MIN apply as they do to a prover).  bytes[0] + bytes[1] <= budget_bytes;
+ * MSM 1 is served first and at most one of the two is partly covered. */
+int dvp_table_plan(size_t size0, size_t size1, uint64_t budget_bytes, size_t covered[2], uint64_t bytes[2]);
+
 /* parity-test access to the recode of the default fixed-base flavour alone (signed aligned windows): out_words[w * n + i] = 0 (digit 0) or 0x80000000 | 0x10000000 when the
  * digit is negative | w << 20 | |digit| (|digit| = 2^(c-1) is stored as key 0); *windows = ceil(234 / c_bits) */
 int dvp_debug_recode_signed(const uint64_t* scalars, size_t n, int c_bits, uint32_t* out_words, int* windows);
