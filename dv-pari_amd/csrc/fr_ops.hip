@@ -388,11 +388,16 @@ extern "C" int dvp_fr_vec_scalar_sub(const uint64_t s[4], const uint64_t* a, siz
   return DVP_OK;
 }
 extern "C" int dvp_fr_vec_dot(const uint64_t* a, const uint64_t* b, size_t n, uint64_t out[4]) {
-  if (!a || !b || !out) return DVP_EINVAL;
+  if (!out) return DVP_EINVAL;
+  if (!n) {  // the empty sum: nothing of a or b is read
+    memset(out, 0, 32);
+    return DVP_OK;
+  }
+  if (!a || !b) return DVP_EINVAL;
   DevBuf da, db, part, o;
-  DVP_TRY(up(da, a, (n ? n : 1) * 32));
-  DVP_TRY(up(db, b, (n ? n : 1) * 32));
-  uint32_t nb = cdiv(n ? n : 1, 256);
+  DVP_TRY(up(da, a, n * 32));
+  DVP_TRY(up(db, b, n * 32));
+  uint32_t nb = cdiv(n, 256);
   if (nb > 1024) nb = 1024;
   DVP_TRY(part.alloc(nb * sizeof(Fr)));
   DVP_TRY(o.alloc(sizeof(Fr)));
@@ -406,13 +411,22 @@ extern "C" int dvp_fr_spmv(const uint32_t* row_ptr, const uint32_t* col, const u
                            const uint64_t* coeffs, uint32_t n_coeffs, const uint64_t* x, uint32_t n_cols, uint64_t* out) {
   if (!n_rows) return DVP_OK;
   if (!row_ptr || !coeffs || !x || !out) return DVP_EINVAL;
-  size_t nnz = row_ptr[n_rows];
+  // k_spmv walks [row_ptr[r], row_ptr[r + 1]) of col / coeff_ids: every row must lie inside [0, nnz], in order
+  const size_t nnz = row_ptr[n_rows];
+  for (uint32_t r = 0; r < n_rows; ++r)
+    if (row_ptr[r] > row_ptr[r + 1] || row_ptr[r + 1] > nnz) { g_last_error_index = (int64_t)r; return DVP_EINVAL; }
+  if (nnz && (!col || !coeff_ids)) return DVP_EINVAL;
   for (size_t k = 0; k < nnz; ++k)
     if (col[k] >= n_cols || coeff_ids[k] >= n_coeffs) { g_last_error_index = (int64_t)k; return DVP_EINVAL; }
   DevBuf rp, c, id, cf, dx, o;
   DVP_TRY(up(rp, row_ptr, ((size_t)n_rows + 1) * 4));
-  DVP_TRY(up(c, col, (nnz ? nnz : 1) * 4));
-  DVP_TRY(up(id, coeff_ids, (nnz ? nnz : 1) * 4));
+  if (nnz) {
+    DVP_TRY(up(c, col, nnz * 4));
+    DVP_TRY(up(id, coeff_ids, nnz * 4));
+  } else {  // all rows empty: the kernel reads neither, and the host arrays may be empty or null
+    DVP_TRY(c.alloc(4));
+    DVP_TRY(id.alloc(4));
+  }
   DVP_TRY(up(cf, coeffs, (size_t)n_coeffs * 32));
   DVP_TRY(up(dx, x, (size_t)n_cols * 32));
   DVP_TRY(o.alloc((size_t)n_rows * 32));

@@ -76,6 +76,30 @@ def batch_inverse(a):
     return a
 
 
+# enum dvp_fr_op (include/dvpari_internal.h): name -> (number, inputs, outputs)
+DEBUG_OPS = {name: (k, n_in, n_out) for k, (name, n_in, n_out) in enumerate([
+    ("add", 2, 1), ("sub", 2, 1), ("neg", 1, 1), ("dbl", 1, 1), ("cond_sub_p", 1, 1), ("is_canonical", 1, 1), ("mul", 2, 1),
+    ("sqr", 1, 1), ("to_mont", 1, 1), ("from_mont", 1, 1), ("dot2", 4, 1), ("muladd29", 3, 1), ("mul29", 2, 1), ("roundtrip29", 1, 1),
+    ("roundtrip30", 1, 1), ("const30", 1, 1), ("canon30", 1, 1), ("sub_lazy30", 2, 1), ("muladd30", 3, 1), ("muladd30_x2", 6, 2),
+    ("inv", 1, 1), ("inv_gcd_raw", 1, 1), ("inv_fermat", 1, 1), ("pow_u64", 2, 1), ("limbs29", 1, 1), ("limbs30", 1, 1)])}
+
+
+def debug_op(name: str, inputs, on_device: bool):
+    """dvp_debug_fr_op: one function of csrc/fr.cuh per element.  inputs: one bytes object of n x 32 bytes (raw little-endian 256-bit
+    values) per operand; returns the outputs the same way.  on_device=False runs the host build of the function, without a GPU."""
+    import ctypes as C
+
+    op, n_in, n_out = DEBUG_OPS[name]
+    assert len(inputs) == n_in and len({len(b) for b in inputs}) == 1 and len(inputs[0]) % 32 == 0
+    n = len(inputs[0]) // 32
+    ins = [np.frombuffer(bytes(b), dtype="<u8") for b in inputs]
+    outs = [np.zeros(4 * n, dtype=np.uint64) for _ in range(n_out)]
+    pin = (C.c_void_p * 6)(*[a.ctypes.data for a in ins])
+    pout = (C.c_void_p * 2)(*[a.ctypes.data for a in outs])
+    check(lib.dvp_debug_fr_op(op, pin, n, 1 if on_device else 0, pout), f"dvp_debug_fr_op({name})")
+    return [a.tobytes() for a in outs]
+
+
 def spmv(row_ptr, col, coeff_ids, coeffs, x):
     row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint32)
     col = np.ascontiguousarray(col, dtype=np.uint32)

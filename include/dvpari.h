@@ -106,7 +106,10 @@ int dvp_fr_vec_scale(const uint64_t* a, const uint64_t s[4], size_t n, uint64_t*
 /* out[i] = a[i] + s * b[i]: the (A + delta B + delta^2 C) combination of accumulate_m_values' three sums (src/srs.rs:73-80) */
 int dvp_fr_vec_axpy(const uint64_t* a, const uint64_t s[4], const uint64_t* b, size_t n, uint64_t* out);
 int dvp_fr_vec_scalar_sub(const uint64_t s[4], const uint64_t* a, size_t n, uint64_t* out);
-int dvp_fr_vec_dot(const uint64_t* a, const uint64_t* b, size_t n, uint64_t out[4]);
+int dvp_fr_vec_dot(const uint64_t* a, const uint64_t* b, size_t n, uint64_t out[4]); /* n = 0: out = 0, a and b are not read */
+/* CSR rows: row_ptr holds n_rows + 1 non-decreasing offsets into col / coeff_ids, the last one their length.  DVP_EINVAL, before any
+ * device work, for a row r with row_ptr[r] > row_ptr[r + 1] or row_ptr[r + 1] > row_ptr[n_rows] (dvp_last_error_index() = r) and
+ * for an entry k with col[k] >= n_cols or coeff_ids[k] >= n_coeffs (index k); col / coeff_ids may be NULL only when there is no entry */
 int dvp_fr_spmv(const uint32_t* row_ptr, const uint32_t* col, const uint32_t* coeff_ids, uint32_t n_rows,
                 const uint64_t* coeffs, uint32_t n_coeffs, const uint64_t* x, uint32_t n_cols, uint64_t* out);
 int dvp_barycentric_eval(const uint64_t* domain, const uint64_t* bar_weights, const uint64_t z_at_alpha[4],

@@ -101,6 +101,45 @@ int dvp_debug_ecfft_matrices(dvp_ecfft* ctx, int to_even, int which, uint64_t* o
 /* layer d of the isogeny chain (FFTree::f.get_layers()[d]): leaves >> d canonical Fr, d = 0 .. log2_leaves */
 int dvp_debug_ecfft_layer(const dvp_ecfft* ctx, uint32_t d, uint64_t* out);
 
+/* TEST ONLY: one function of the Fr arithmetic (csrc/fr.cuh) per element, for the carry-boundary tests (tests/fr_cases.py holds the
+ * integer reference).  Every value is a raw 256-bit integer (4 x u64, little-endian) handed to the function untouched: "Montgomery
+ * in / out" functions see their operand as it is, e.g. MUL gives a b / 2^232 mod p.  in[k] / out[k]: n values each; pointers beyond an
+ * op's count are not read.  on_device = 1: a kernel, one element per lane, 256-thread workgroups -- the device build of the function
+ * as the kernels get it; on_device = 0: a host loop over the same functions that makes no HIP call (runs without a GPU).  An element
+ * outside the op's precondition -> DVP_EINVAL, dvp_last_error_index() = its index, before anything is computed.  R = 2^232, R' = 2^240;
+ * 29- and 30-bit-limb operands are sliced from the 256-bit value inside the op (fr29_from / fr30_from) and lazy results are re-sliced
+ * with fr30_to_fr. */
+enum dvp_fr_op {
+  DVP_FROP_ADD = 0,      /* in a, b < p: fr_add */
+  DVP_FROP_SUB,          /* a, b < p: fr_sub */
+  DVP_FROP_NEG,          /* a < p: fr_neg */
+  DVP_FROP_DBL,          /* a < p: fr_dbl */
+  DVP_FROP_COND_SUB_P,   /* a < 2p: fr_cond_sub_p */
+  DVP_FROP_IS_CANONICAL, /* any a: 1 if a < p else 0 */
+  DVP_FROP_MUL,          /* a, b < p: fr_mul = a b / R mod p */
+  DVP_FROP_SQR,          /* a < p: fr_sqr */
+  DVP_FROP_TO_MONT,      /* a < p: a R mod p */
+  DVP_FROP_FROM_MONT,    /* a < p: a / R mod p */
+  DVP_FROP_DOT2,         /* a0, b0, a1, b1 < p: fr_dot2 = (a0 b0 + a1 b1) / R mod p */
+  DVP_FROP_MULADD29,     /* a, b, c < p: fr_muladd29 = a b / R + c mod p */
+  DVP_FROP_MUL29,        /* a, b < p: fr_mul29 */
+  DVP_FROP_ROUNDTRIP29,  /* a < 2^232: fr_from29(fr_to29(a)) */
+  DVP_FROP_ROUNDTRIP30,  /* a < 2^240: fr30_to_fr(fr30_from(a)) */
+  DVP_FROP_CONST30,      /* a < p (it goes through fr_mul, which drops bit 232): fr30_const = a 2^8 mod p, fully reduced */
+  DVP_FROP_CANON30,      /* a < 2p: fr30_canon */
+  DVP_FROP_SUB_LAZY30,   /* e0 < 2^239, e1 < 128 p: fr30_sub_lazy = e0 - e1 + 128 p exactly */
+  DVP_FROP_MULADD30,     /* a < p; b, c < 2^240 with the exact result (a b + m p) / R' + c < 2^240: fr30_muladd */
+  DVP_FROP_MULADD30_X2,  /* (a0, b0, c0, a1, b1, c1), each triple as MULADD30: fr30_muladd_x2 -> out[0], out[1] */
+  DVP_FROP_INV,          /* a < p: fr_inv = R^2 / a mod p; 0 -> 0 */
+  DVP_FROP_INV_GCD_RAW,  /* a < p: fr_inv_gcd_raw = 1 / a mod p; 0 -> 0 */
+  DVP_FROP_INV_FERMAT,   /* a < p: fr_inv_fermat = R^2 / a mod p; 0 -> 0 */
+  DVP_FROP_POW_U64,      /* a < p, e < 2^64: fr_pow_u64 = a^e R^(1 - e) mod p */
+  DVP_FROP_LIMBS29,      /* a < 2^232: the eight 29-bit limbs of fr_to29, one per 32-bit word of the output */
+  DVP_FROP_LIMBS30,      /* a < 2^240: the eight limbs of fr30_from likewise (limb 7 keeps bits 210 and up) */
+  DVP_FROP_COUNT
+};
+int dvp_debug_fr_op(int op, const uint64_t* const in[6], size_t n, int on_device, uint64_t* const out[2]);
+
 #ifdef __cplusplus
 }
 #endif

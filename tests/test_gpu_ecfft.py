@@ -85,6 +85,46 @@ def test_multiblock_extend_enter_exit_vs_oracle(dvp, log_n, shifted):
     t.close()
 
 
+def _edge_vectors(n, seed):
+    """name -> n canonical values that push the lazy values of the butterflies away from their mean"""
+    import fr_cases as fc
+
+    top = o.P - 1
+    rnd = random.Random(seed)
+    e = fc.edge_values()
+    out = {"all p-1": [top] * n, "alternating 0 / p-1": [0, top] * (n // 2), "alternating p-1 / 0": [top, 0] * (n // 2),
+           "edge set": [e[rnd.randrange(len(e))] for _ in range(n)]}
+    for name, pos in (("first", 0), ("middle", n // 2), ("last", n - 1)):
+        v = [0] * n
+        v[pos] = top
+        out[f"spike p-1 {name}"] = v
+    return {k: to_limbs(v) for k, v in out.items()}
+
+
+@pytest.mark.parametrize("log_n", [12, 13])
+def test_multiblock_edge_vectors_vs_oracle(dvp, log_n):
+    """The same multi-block kernels on inputs random vectors never produce: all p - 1, alternating 0 / p - 1, a single p - 1 spike at
+    the first, middle and last position, and a vector drawn from the carry-boundary values of fr_cases.py.  Inside an extend a value is
+    only congruent to the field element and bounded by 64 p (csrc/fr.cuh, csrc/ecfft.hip); uniform inputs keep it near the middle of
+    that range, these push it to the ends.  extend (one batch of all vectors), enter and exit, element for element against the
+    oracle."""
+    n = 1 << log_n
+    m = n // 2
+    t = dvp.ec_fft.FFTree(n)
+    ot = co.FFTree(log_n)
+    half = _edge_vectors(m, log_n)
+    out = t.extend(np.stack(list(half.values())))
+    for k, (name, ev) in enumerate(half.items()):
+        assert np.array_equal(out[k], ot.extend(ev)), name
+    for name, v in _edge_vectors(n, 50 + log_n).items():
+        e = t.enter(v)
+        assert np.array_equal(e, ot.enter(v)), name
+        assert np.array_equal(t.exit(e), v), name
+        assert np.array_equal(t.exit(v), ot.exit(v)), name
+    ot.close()
+    t.close()
+
+
 @pytest.mark.parametrize("log_m", [12, 13, 14, 15, 16, 17, 18, 19, 21])
 def test_extend_pass_groupings_agree(dvp, nat, log_m):
     """The unfused top of an extend runs three layers per pass (k_butterfly8), then two (k_butterfly4) or one (k_butterfly) for
