@@ -68,6 +68,7 @@ _SIGS = {
     "dvp_fr_vec_dot": (C.c_int, [u64p, u64p, sz, u64p]),
     "dvp_fr_spmv": (C.c_int, [vp, vp, vp, u32, u64p, u32, u64p, u32, u64p]),
     "dvp_debug_fr_op": (C.c_int, [C.c_int, C.POINTER(vp), sz, C.c_int, C.POINTER(vp)]),
+    "dvp_debug_gf_op": (C.c_int, [C.c_int, C.c_int, C.POINTER(vp), sz, C.c_uint64, C.POINTER(vp)]),
     "dvp_barycentric_eval": (C.c_int, [u64p, u64p, u64p, u64p, sz, u64p, u64p]),
     "dvp_msm_affine": (C.c_int, [u64p, u64p, u8p, sz, u64p, C.POINTER(C.c_int)]),
     "dvp_msm_affine_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, vp]),

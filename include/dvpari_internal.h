@@ -140,6 +140,60 @@ enum dvp_fr_op {
 };
 int dvp_debug_fr_op(int op, const uint64_t* const in[6], size_t n, int on_device, uint64_t* const out[2]);
 
+/* TEST ONLY: one function of the GF(2^233) arithmetic (csrc/gf233.cuh) or of the K-233 point formulas (csrc/k233.cuh) per element, on
+ * the device (tests/gf_cases.py holds the case sets; oracle/pyref.py is the reference).  Every value is a raw 256-bit integer (4 x u64,
+ * little-endian: bit i = coefficient of z^i); a point is two affine fields (x, y) or three projective ones (X, Y, Z), one in[] each.
+ * `form` selects the multiplier the function runs on; an (op, form) pair the list below does not name is DVP_EINVAL.  The kernels launch
+ * as production does (256-thread workgroups, GF_LDSK_BYTES_PER_WAVE / GF_LDS_BYTES_PER_WAVE of dynamic LDS per wave, the tables of
+ * gf_sqr_tables()), and a lane (group) works through several elements one after the other in the same LDS region: element e belongs to
+ * group e mod S of the S groups launched, S = 64 / G x max(1, ceil(n G / 128)).  For the quad and row forms one element occupies a
+ * group of G = 4 / 16 lanes and out[k] holds n x G values, value e G + r from lane r of the group: the test sees every lane's copy.
+ * A group without an element retires as a whole before any cross-lane operation.
+ * Preconditions are checked on the host before any device call (nothing out of range reaches a kernel): a field operand >= 2^233 (every
+ * input but REDUCE16's), or word 15 of REDUCE16_14's input non-zero -> DVP_EINVAL, dvp_last_error_index() = the element; a `param` out of
+ * range (k > 232, an unknown table, a table the current DVP_GF_INV_TABS does not provide) -> DVP_EINVAL, dvp_last_error_index() = -1.
+ * Flags (0 / 1 in word 0) go to out[3]; out[] beyond an op's values (and out[3] without a flag) is not written and may be NULL. */
+enum dvp_gf_form {
+  DVP_GFFORM_REG = 0, /* gf_mul(a, b): registers only (the k233.cuh functions without a multiplier argument) */
+  DVP_GFFORM_LDS,     /* GfLds: the 16 KB comb */
+  DVP_GFFORM_LDSQ,    /* GfLdsQ: a quad of lanes per product */
+  DVP_GFFORM_LDSH,    /* GfLdsH: a row of 16 lanes per product */
+  DVP_GFFORM_LDSK,    /* GfLdsK: Karatsuba over 8 KB half tables */
+  DVP_GFFORM_COUNT
+};
+enum dvp_gf_op {
+  /* field: forms REG only unless stated */
+  DVP_GFOP_ADD = 0,     /* a, b -> a + b */
+  DVP_GFOP_MUL,         /* a, b -> a b; every form */
+  DVP_GFOP_MUL2,        /* a1, a2, b -> a1 b, a2 b (gf_mul2); the four LDS forms */
+  DVP_GFOP_SQR,         /* a -> a^2 */
+  DVP_GFOP_SQR_N,       /* a -> a^(2^param), param <= 232 (gf_sqr_n) */
+  DVP_GFOP_REDUCE16_15, /* (low 256 bits, high 256 bits) of a 512-bit polynomial -> gf_reduce16<15> */
+  DVP_GFOP_REDUCE16_14, /* the same through gf_reduce16<14>: word 15 must be zero */
+  DVP_GFOP_SQR_TAB,     /* a -> one table pass: param & 0xff = 0 t29, 1 t58, 2 t116, 3 half-trace, 4 t14, 5 t7; param & 0x100: gf_sqr_tab_wide */
+  DVP_GFOP_SQR_N_FAST,  /* a -> a^(2^param), param <= 232 (gf_sqr_n_fast) */
+  DVP_GFOP_INV,         /* a -> 1 / a, 0 -> 0 (gf_inv, the register chain) */
+  DVP_GFOP_INV_FAST,    /* a -> 1 / a, 0 -> 0 (gf_inv_fast: honours DVP_GF_INV_TABS); the four LDS forms */
+  DVP_GFOP_SQRT,        /* a -> sqrt(a) */
+  DVP_GFOP_TRACE,       /* a -> Tr(a) in word 0 */
+  DVP_GFOP_HALFTRACE,   /* a -> H(a) (gf_halftrace, the squaring loop) */
+  /* points: p = in[0..2] (X, Y, Z), q = in[3..4] (x, y) or in[3..5] (X, Y, Z); result (X, Y, Z) -> out[0..2] */
+  DVP_GFOP_LD_DBL,         /* p -> 2 p; every form */
+  DVP_GFOP_LD_MADD,        /* p, q affine -> p + q (ld_madd; the LDS forms go through ld_madd_ip); every form */
+  DVP_GFOP_LD_MADD_FAST,   /* p, q affine -> p + q, flag = 1; p == +-q: p untouched, flag = 0; LDS forms */
+  DVP_GFOP_LD_ADD_AFF_AFF, /* p = in[0..1], q = in[2..3], both affine, p.x != q.x -> p + q; LDS forms */
+  DVP_GFOP_LD_ADD,         /* p, q -> p + q (ld_add; the LDS forms go through ld_add_ip); every form */
+  DVP_GFOP_LD_ADD_NODBL,   /* p, q -> p + q, flag = 1; p == q: p untouched, flag = 0; LDS forms */
+  DVP_GFOP_LAM_FROM_LD,    /* Lopez-Dahab -> lambda-projective; LDS forms */
+  DVP_GFOP_LAM_TO_LD,      /* lambda-projective -> Lopez-Dahab; LDS forms */
+  DVP_GFOP_LAM_DBL,        /* lambda-projective doubling; LDS forms */
+  DVP_GFOP_LAM_ADD,        /* lambda-projective p, q -> p + q, flag = 1; p == q: p untouched, flag = 0; LDS forms */
+  DVP_GFOP_LD_FROB_N,      /* p -> tau^param p, param <= 232; REG */
+  DVP_GFOP_LD_TO_AFF,      /* p -> (x, y) in out[0..1], flag = 0 for infinity; REG */
+  DVP_GFOP_COUNT
+};
+int dvp_debug_gf_op(int op, int form, const uint64_t* const in[6], size_t n, uint64_t param, uint64_t* const out[4]);
+
 #ifdef __cplusplus
 }
 #endif

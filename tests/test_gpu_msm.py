@@ -231,14 +231,10 @@ def test_msm_heavy_skew_2_18(dvp):
     assert np_to_pt(xy, is_inf) == co.k233_mulgen(np_dot_mod(s, k))
 
 
-def test_bucket_reduction_exceptional_pairs(dvp):
-    """what the pair rounds leave (k_bucket_pairs / k_bucket_rest): bases drawn from eight points and their negatives,
-    scalars from five values, so that the buckets the rounds hand over hold equal points (P + P), opposite points
-    (P - P) and the infinity markers earlier rounds made of them -- the pairs the fast formulas refuse and the list
-    redoes.  Fixed-base and one-shot, the rounds stopped at several depths, against the fan-in-K reducer route
-    (DVP_MSM_BUCKET_PAIRS_MAX=0) and the oracle."""
+def exceptional_pairs_input(n=4096):
+    """bases drawn from eight points and their negatives, scalars from five values: (bases, scalars, the scalars and the bases'
+    discrete logs as integers, the expected sum)"""
     rnd = random.Random(777)
-    n = 4096
     k8 = [rnd.randrange(1, o.P) for _ in range(8)]
     p8 = [co.k233_mulgen(x) for x in k8]
     vals = [rnd.randrange(o.P) for _ in range(4)] + [1]
@@ -248,8 +244,16 @@ def test_bucket_reduction_exceptional_pairs(dvp):
         pts.append(o.k233_neg(p8[j]) if neg else p8[j])
         ks.append(o.P - k8[j] if neg else k8[j])
         sv.append(rnd.choice(vals))
-    bases, s = pts_to_np(pts), to_limbs(sv)
-    exp = co.k233_mulgen(sum(a * b for a, b in zip(sv, ks)) % o.P)
+    return pts_to_np(pts), to_limbs(sv), sv, ks, co.k233_mulgen(sum(a * b for a, b in zip(sv, ks)) % o.P)
+
+
+def test_bucket_reduction_exceptional_pairs(dvp):
+    """what the pair rounds leave (k_bucket_pairs / k_bucket_rest): bases drawn from eight points and their negatives,
+    scalars from five values, so that the buckets the rounds hand over hold equal points (P + P), opposite points
+    (P - P) and the infinity markers earlier rounds made of them -- the pairs the fast formulas refuse and the list
+    redoes.  Fixed-base and one-shot, the rounds stopped at several depths, against the fan-in-K reducer route
+    (DVP_MSM_BUCKET_PAIRS_MAX=0) and the oracle."""
+    bases, s, sv, ks, exp = exceptional_pairs_input()
     lo, hi = 100, 3000
     exp_part = co.k233_mulgen(sum(a * b for a, b in zip(sv[lo:hi], ks[lo:hi])) % o.P)
     for c in (8, 11):
@@ -269,6 +273,61 @@ def test_bucket_reduction_exceptional_pairs(dvp):
                             assert np_to_pt(*fb.run(s)) == exp, (c, aff_min, knob)
                             assert gpu_msm(dvp, s, bases) == exp, (c, aff_min, knob)
         fb.close()
+
+
+def test_msm_multiplier_form_knobs(dvp):
+    """the knobs that choose a multiplier form or a launch shape and that no other test sets, each at a value that really switches the
+    path where msm_core reads it, on the exceptional-pair input above and on 3 000 random points, fixed-base and one-shot, against
+    the oracle:
+      DVP_GF_INV_TABS 0 / 2 -- gf_sqr_tables(): the inversion's runs of 14 and 7 squarings plain / both as table passes;
+      DVP_MSM_HEX_MAX=0 -- no merge level and no tail on rows of 16 lanes (quads up to DVP_MSM_QUAD_MAX additions instead);
+      DVP_MSM_QUAD_MAX=2^30 with HEX_MAX=0 -- EVERY merge level on quads; =1 with HEX_MAX=0 -- every level of more than one addition
+        one lane per addition (the Karatsuba form);
+      DVP_MSM_ACCUM_QUAD_MAX=2^30 / 1 -- the fan-in reducer (forced with DVP_MSM_BUCKET_PAIRS_MAX=0; its row-of-16 last level off) all
+        quads / none, on table entries (no pair rounds) and on the affine output of a few pair rounds (DVP_MSM_AFF_MIN=4096), there
+        with and without the exception-free first level (k_accum_affine_fast / k_accum_affine);
+      DVP_MSM_AFF_TPB 64 / 128, DVP_MSM_AFF_BMIN 1 / 136 (= DVP_MSM_AFF_BMAX, the most it accepts) -- the pair rounds, which
+        DVP_MSM_AFF_MIN=32 makes run at this size;
+      DVP_FX_HI at both ends of what msm_fixed_settle accepts (0 <= h <= 10, 1 <= key bits - h <= 15): 0 / 9 for c = 11 (10 key bits),
+        2 / 10 for c = 18 (17 key bits); read when the context is created."""
+    big = 1 << 30
+    xb, xs, _, _, xexp = exceptional_pairs_input()
+    n = 3000
+    k, s = rand_fr_np(n, 4101), rand_fr_np(n, 4102)
+    rb, _ = dvp.curve.point_scalar_mul_gen_batch(k)
+    rexp = co.k233_mulgen(np_dot_mod(s, k))
+    inputs = ((xb, xs, xexp), (rb, s, rexp))
+    reducer = dict(DVP_MSM_BUCKET_PAIRS_MAX=0, DVP_MSM_ACCUM_HEX_MAX=0)
+    rounds = dict(DVP_MSM_AFF_MIN=32)
+    settings = [
+        dict(DVP_GF_INV_TABS=0, **rounds), dict(DVP_GF_INV_TABS=2, **rounds), dict(DVP_GF_INV_TABS=0), dict(DVP_GF_INV_TABS=2),
+        dict(DVP_MSM_HEX_MAX=0), dict(DVP_MSM_HEX_MAX=0, DVP_MSM_QUAD_MAX=big), dict(DVP_MSM_HEX_MAX=0, DVP_MSM_QUAD_MAX=1),
+        dict(DVP_MSM_ACCUM_QUAD_MAX=big, **reducer), dict(DVP_MSM_ACCUM_QUAD_MAX=1, **reducer),
+        dict(DVP_MSM_ACCUM_QUAD_MAX=big, DVP_MSM_ACCUM_FAST=0, DVP_MSM_AFF_MIN=4096, **reducer),
+        dict(DVP_MSM_ACCUM_QUAD_MAX=1, DVP_MSM_ACCUM_FAST=0, DVP_MSM_AFF_MIN=4096, **reducer),
+        dict(DVP_MSM_ACCUM_QUAD_MAX=big, DVP_MSM_AFF_MIN=4096, **reducer), dict(DVP_MSM_ACCUM_QUAD_MAX=1, DVP_MSM_AFF_MIN=4096, **reducer),
+        dict(DVP_MSM_AFF_TPB=64, **rounds), dict(DVP_MSM_AFF_TPB=128, **rounds),
+        dict(DVP_MSM_AFF_BMIN=1, **rounds), dict(DVP_MSM_AFF_BMIN=136, **rounds),
+    ]
+    for knob in ("DVP_GF_INV_TABS", "DVP_MSM_HEX_MAX", "DVP_MSM_QUAD_MAX", "DVP_MSM_ACCUM_QUAD_MAX", "DVP_MSM_AFF_TPB", "DVP_MSM_AFF_BMIN"):
+        assert any(knob in st for st in settings)
+    for bases, sc, exp in inputs:
+        with dvp.tune(DVP_MSM_FIXED_C=11):
+            fb = dvp.curve.FixedBaseMsm(bases)
+        assert np_to_pt(*fb.run(sc)) == exp and gpu_msm(dvp, sc, bases) == exp  # the defaults
+        for st in settings:
+            with dvp.tune(DVP_MSM_C=11, **st):
+                assert np_to_pt(*fb.run(sc)) == exp, st
+                assert gpu_msm(dvp, sc, bases) == exp, st
+        fb.close()
+        for c, his in ((11, (0, 9)), (18, (2, 10))):
+            for h in his:
+                with dvp.tune(DVP_MSM_FIXED_C=c, DVP_FX_HI=h):
+                    fb = dvp.curve.FixedBaseMsm(bases)
+                for aff_min in (32, 1 << 19):
+                    with dvp.tune(DVP_MSM_AFF_MIN=aff_min):
+                        assert np_to_pt(*fb.run(sc)) == exp, (c, h, aff_min)
+                fb.close()
 
 
 def test_merge_tree_equal_and_opposite_buckets(dvp):
