@@ -141,6 +141,16 @@ _SIGS = {
     "dvp_cache_dir_prover": (C.c_int, [C.c_char_p, u32, C.POINTER(vp)]),
     "dvp_transcript_challenge": (C.c_int, [u8p, u64p, u32, u64p]),
     "dvp_blake3": (C.c_int, [u8p, sz, u8p]),
+    "dvp_blake3_dev": (C.c_int, [vp, sz, vp, vp]),
+    "dvp_debug_blake3_tree_run": (u32, []),
+    "dvp_debug_blake3_leaves_dev": (C.c_int, [vp, sz, C.c_uint64, vp, vp]),
+    "dvp_debug_blake3_reduce_dev": (C.c_int, [vp, sz, vp, vp, vp]),
+    "dvp_prover_srs_hash": (C.c_int, [vp, u8p]),
+    "dvp_prover_set_transcript_binding": (C.c_int, [vp, u8p, u8p]),
+    "dvp_transcript_challenge_bound": (C.c_int, [u8p, u64p, u32, u8p, u8p, u64p]),
+    "dvp_verify_set_binding": (C.c_int, [u8p, u8p]),
+    "dvp_verify_get_binding": (C.c_int, [u8p, u8p]),
+    "dvp_cache_dir_set_binding": (C.c_int, [C.c_char_p, u32, u8p, u8p, C.c_int]),
     "dvp_verify": (C.c_int, [u64p, u64p, u64p, u64p, u32, u8p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dvp_verify_batch": (C.c_int, [u64p, u64p, u64p, u64p, u32, u8p, sz, u8p]),
     "dvp_verify_batch_dev": (C.c_int, [u64p, u64p, u64p, vp, u32, vp, sz, vp, vp]),

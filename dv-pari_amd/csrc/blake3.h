@@ -96,5 +96,15 @@ static inline void hash(const uint8_t* data, size_t len, uint8_t out32[32]) {
   for (int i = 0; i < 8; ++i) { out32[4 * i] = (uint8_t)out[i]; out32[4 * i + 1] = (uint8_t)(out[i] >> 8); out32[4 * i + 2] = (uint8_t)(out[i] >> 16); out32[4 * i + 3] = (uint8_t)(out[i] >> 24); }
 }
 
+// the compile-time half of the transcript, H(srs_hash || circuit_hash) (src/proving.rs:164-176); a NULL hash stands for BLAKE3(""),
+// what the reference hashes today (:86-105,113-132)
+static inline void compile_hash(const uint8_t* srs_hash, const uint8_t* circuit_hash, uint8_t out32[32]) {
+  uint8_t h_empty[32], buf[64];
+  hash(nullptr, 0, h_empty);
+  memcpy(buf, srs_hash ? srs_hash : h_empty, 32);
+  memcpy(buf + 32, circuit_hash ? circuit_hash : h_empty, 32);
+  hash(buf, 64, out32);
+}
+
 }  // namespace b3
 }  // namespace dvp

@@ -230,6 +230,11 @@ struct OpenEntry {
   bool busy[2] = {false, false};
   uint64_t proofs_done = 0;
   uint64_t room_retry_at = 1;  // a second prover is considered once proofs_done reaches this (first: after one completed proof)
+  // dvp_cache_dir_set_binding (under slot_mu): a proof applies it to the prover it took when that prover's generation is behind, so a
+  // prover opened later inherits it
+  bool bind_has[2] = {false, false};
+  uint8_t bind_hash[2][32];
+  uint64_t bind_gen = 0, applied_gen[2] = {0, 0};
   ~OpenEntry() {
     if (p) dvp_prover_destroy(p);
     if (p2) dvp_prover_destroy(p2);
@@ -476,7 +481,22 @@ extern "C" int dvp_prove_cache_dir(const char* cache_dir, const uint64_t* public
     }
     e->busy[slot] = true;
   }
-  rc = dvp_prove(slot == 0 ? e->p : e->p2, public_inputs, n_public, private_inputs, n_private, proof);
+  dvp_prover* pv = slot == 0 ? e->p : e->p2;
+  rc = DVP_OK;
+  {
+    std::unique_lock<std::mutex> g(e->slot_mu);
+    if (e->applied_gen[slot] != e->bind_gen) {
+      const uint64_t gen = e->bind_gen;
+      uint8_t h[2][32];
+      const bool has[2] = {e->bind_has[0], e->bind_has[1]};
+      memcpy(h, e->bind_hash, sizeof(h));
+      g.unlock();
+      rc = dvp_prover_set_transcript_binding(pv, has[0] ? h[0] : nullptr, has[1] ? h[1] : nullptr);
+      g.lock();
+      if (rc == DVP_OK) e->applied_gen[slot] = gen;
+    }
+  }
+  if (rc == DVP_OK) rc = dvp_prove(pv, public_inputs, n_public, private_inputs, n_private, proof);
   {
     std::lock_guard<std::mutex> g(e->slot_mu);
     e->busy[slot] = false;
@@ -484,6 +504,38 @@ extern "C" int dvp_prove_cache_dir(const char* cache_dir, const uint64_t* public
   }
   e->slot_cv.notify_one();
   return rc;
+}
+
+extern "C" int dvp_cache_dir_set_binding(const char* cache_dir, uint32_t n_public, const uint8_t* srs_hash, const uint8_t* circuit_hash,
+                                         int bind_srs) {
+  if (!cache_dir) return DVP_EINVAL;
+  std::shared_ptr<OpenEntry> e;
+  int rc = open_entry(cache_dir, n_public, &e);
+  if (rc) return rc;
+  uint8_t computed[32];
+  if (bind_srs && !srs_hash) {  // the first prover's own SRS hash: take its turn like a proof
+    {
+      std::unique_lock<std::mutex> g(e->slot_mu);
+      e->slot_cv.wait(g, [&] { return !e->busy[0]; });
+      e->busy[0] = true;
+    }
+    rc = dvp_prover_srs_hash(e->p, computed);
+    {
+      std::lock_guard<std::mutex> g(e->slot_mu);
+      e->busy[0] = false;
+    }
+    e->slot_cv.notify_all();
+    if (rc) return rc;
+    srs_hash = computed;
+  }
+  std::lock_guard<std::mutex> g(e->slot_mu);
+  const uint8_t* h[2] = {srs_hash, circuit_hash};
+  for (int k = 0; k < 2; ++k) {
+    e->bind_has[k] = h[k] != nullptr;
+    if (h[k]) memcpy(e->bind_hash[k], h[k], 32);
+  }
+  ++e->bind_gen;
+  return DVP_OK;
 }
 
 // the prover dvp_prove_cache_dir uses for (cache_dir, n_public) on the current device, opened if need be: BORROWED --

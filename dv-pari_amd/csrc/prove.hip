@@ -41,6 +41,10 @@ int decode_dev(const uint8_t* d_enc, size_t n, Aff* d_out, uint8_t* d_inf, hipSt
 int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out, hipStream_t st);
 int encode_point_dev(const Aff* d_pt, const uint32_t* d_inf32, uint8_t* d_out, hipStream_t st);
 int batch_inverse_dev(Fr* d, size_t n, hipStream_t st);
+int b3_leaves_dev(const uint8_t* d_data, size_t len, uint64_t chunk_base, uint32_t* d_cvs, hipStream_t st);  // blake3_tree.hip
+int b3_single_chunk_dev(const uint8_t* d_data, size_t len, uint32_t* d_out32, hipStream_t st);
+size_t b3_reduce_tmp_bytes(size_t n);
+int b3_reduce_dev(uint32_t* d_cvs, size_t n, uint32_t* d_tmp, uint32_t* d_out32, hipStream_t st);
 struct MsmFixedCtx;
 int msm_fixed_create(const Aff* d_bases, uint32_t n_total, size_t range_hint, MsmFixedCtx** out);
 int msm_sum_points_dev(const void* d_pts, uint32_t pt_stride_bytes, const void* d_inf32, uint32_t n, uint32_t inf_stride, void* d_out_xy,
@@ -349,7 +353,7 @@ k_kscalars_range(const Fr* __restrict__ E, const Fr* __restrict__ r2, const Fr* 
 
 // ---- the Fiat-Shamir transcript on the device (round 5) ----------------------------------------------------------------
 // Transcript::output (src/proving.rs:164-197) needs four single-chunk BLAKE3 hashes once commit_p exists -- H(commit_p),
-// H(public inputs as 29-byte LE), H(H_wc || H_pi), H(H_ct || H_rt); H_ct = H(H(empty) || H(empty)) is a constant the host passes in --
+// H(public inputs as 29-byte LE), H(H_wc || H_pi), H(H_ct || H_rt); H_ct = H(srs_hash || circuit_hash) is a value the host passes in (dvp_prover::h_ct) --
 // and alpha is the result with its top four bytes cleared (:192).  One lane of one wave does that right behind the commitment MSM's
 // tail kernel, so dvp_prove_dev has no host round trip between its two MSMs (the host is already enqueueing the second MSM's sort while
 // the first one's rounds run).  Written from the BLAKE3 specification like blake3.h (the host flavour, which the phased entries and
@@ -496,7 +500,9 @@ struct dvp_prover {
   // side stream + events of the device transcript: -Z(alpha) is computed beside the challenge phase's vector kernels
   hipStream_t side = nullptr;
   hipEvent_t ev_alpha = nullptr, ev_negz = nullptr;
-  b3d::Words8 h_ct;             // H(H(empty) || H(empty)): srs / circuit hashes are hashes of empty buffers (src/proving.rs:86-105,113-132)
+  // H(srs_hash || circuit_hash), the compile-time half of the transcript.  Default: both are hashes of empty buffers, as in the
+  // reference (src/proving.rs:86-105,113-132); dvp_prover_set_transcript_binding replaces them.  Every path that derives alpha reads it.
+  b3d::Words8 h_ct;
 };
 
 static const int PT = 256;
@@ -576,10 +582,8 @@ static int prover_init(dvp_prover* p, uint32_t log2_m, uint32_t n_public, uint32
   DVP_HIP(hipEventCreateWithFlags(&p->ev_alpha, hipEventDisableTiming));
   DVP_HIP(hipEventCreateWithFlags(&p->ev_negz, hipEventDisableTiming));
   {
-    uint8_t h_empty[32], buf[64], h[32];
-    b3::hash(nullptr, 0, h_empty);
-    memcpy(buf, h_empty, 32); memcpy(buf + 32, h_empty, 32);
-    b3::hash(buf, 64, h);
+    uint8_t h[32];
+    b3::compile_hash(nullptr, nullptr, h);
     memcpy(p->h_ct.w, h, 32);
   }
   DVP_TRY(A((void**)&p->pts, 2 * sizeof(Aff)));
@@ -740,16 +744,14 @@ extern "C" int dvp_prover_set_srs_affine_dev(dvp_prover* p, int which, const voi
   return DVP_OK;
 }
 
-// Transcript::output, src/proving.rs:164-197 (srs/circuit hashes are hashes of EMPTY buffers, :86-105,113-132)
-static void transcript_challenge(const uint8_t commit_p[30], const uint64_t* pub, uint32_t npub, uint8_t out32[32]) {
-  uint8_t h_empty[32], h_wc[32], h_pi[32], h_ct[32], h_rt[32], buf[64];
-  b3::hash(nullptr, 0, h_empty);
+// Transcript::output, src/proving.rs:164-197; h_ct = H(srs_hash || circuit_hash) (b3::compile_hash: hashes of EMPTY buffers in the
+// reference, :86-105,113-132)
+static void transcript_challenge(const uint8_t commit_p[30], const uint64_t* pub, uint32_t npub, const uint8_t h_ct[32], uint8_t out32[32]) {
+  uint8_t h_wc[32], h_pi[32], h_rt[32], buf[64];
   b3::hash(commit_p, 30, h_wc);
   std::vector<uint8_t> pi((size_t)npub * 29);
   for (uint32_t j = 0; j < npub; ++j) memcpy(pi.data() + 29 * (size_t)j, (const uint8_t*)(pub + 4 * (size_t)j), 29);
   b3::hash(pi.data(), pi.size(), h_pi);
-  memcpy(buf, h_empty, 32); memcpy(buf + 32, h_empty, 32);
-  b3::hash(buf, 64, h_ct);
   memcpy(buf, h_wc, 32); memcpy(buf + 32, h_pi, 32);
   b3::hash(buf, 64, h_rt);
   memcpy(buf, h_ct, 32); memcpy(buf + 32, h_rt, 32);
@@ -759,9 +761,61 @@ static void transcript_challenge(const uint8_t commit_p[30], const uint64_t* pub
 
 extern "C" int dvp_transcript_challenge(const uint8_t commit_p[30], const uint64_t* public_inputs, uint32_t n_public, uint64_t out[4]) {
   if (!commit_p || (n_public && !public_inputs) || !out) return DVP_EINVAL;
-  uint8_t h[32];
-  transcript_challenge(commit_p, public_inputs, n_public, h);
+  return dvp_transcript_challenge_bound(commit_p, public_inputs, n_public, nullptr, nullptr, out);
+}
+extern "C" int dvp_transcript_challenge_bound(const uint8_t commit_p[30], const uint64_t* public_inputs, uint32_t n_public,
+                                              const uint8_t srs_hash[32], const uint8_t circuit_hash[32], uint64_t out[4]) {
+  if (!commit_p || (n_public && !public_inputs) || !out) return DVP_EINVAL;
+  uint8_t h_ct[32], h[32];
+  b3::compile_hash(srs_hash, circuit_hash, h_ct);
+  transcript_challenge(commit_p, public_inputs, n_public, h_ct, h);
   memcpy(out, h, 32);
+  return DVP_OK;
+}
+extern "C" int dvp_prover_set_transcript_binding(dvp_prover* p, const uint8_t srs_hash[32], const uint8_t circuit_hash[32]) {
+  if (!p) return DVP_EINVAL;
+  uint8_t h[32];
+  b3::compile_hash(srs_hash, circuit_hash, h);
+  memcpy(p->h_ct.w, h, 32);
+  return DVP_OK;
+}
+
+// BLAKE3 of the stream the commented-out loop of Transcript::srs_hash would build (src/proving.rs:91-101): to_bytes() of g_k[0], g_k[1],
+// g_k[2], g_q, g_m -- on the device encode_dev over bases_k[0, 4m), bases_a[n_wires, n_wires + m), bases_a[0, n_wires).  The stream
+// (1.3 GB at 2^23 constraints) is never materialised: it is encoded into a window of whole points AND whole chunks (a multiple of
+// lcm(30, 1024) = 15360 bytes), each window's chunks are hashed with their position in the stream as the counter base, and the chaining
+// values are reduced once.  Reads the home device's copies, which shards_build leaves in place: the hash does not depend on the device list.
+static constexpr size_t SRS_HASH_WINDOW_POINTS = (size_t)512 * 4096;  // 60 MiB of encodings = 61440 chunks: 960 waves of k_b3_leaves
+extern "C" int dvp_prover_srs_hash(dvp_prover* p, uint8_t out[32]) {
+  if (!p || !out) return DVP_EINVAL;
+  for (int k = 0; k < 5; ++k)
+    if (!p->have_srs[k]) return DVP_EINVAL;
+  const size_t m = p->m, nw = p->n_wires;
+  struct Seg { const Aff* b; const uint8_t* inf; size_t n; };
+  const Seg seg[3] = {{p->bases_k, p->inf_k, 4 * m}, {p->bases_a + nw, p->inf_a + nw, m}, {p->bases_a, p->inf_a, nw}};
+  const size_t total_pts = 5 * m + nw, total_bytes = 30 * total_pts, nchunks = (total_bytes + 1023) / 1024;
+  const size_t win_pts = std::min(SRS_HASH_WINDOW_POINTS, total_pts);
+  hipStream_t st = nullptr;
+  DevBuf win, cvs, tmp, dout;
+  DVP_TRY(win.alloc(win_pts * 30));
+  DVP_TRY(dout.alloc(32));
+  if (nchunks > 1) {
+    DVP_TRY(cvs.alloc(nchunks * 32));
+    DVP_TRY(tmp.alloc(b3_reduce_tmp_bytes(nchunks)));
+  }
+  for (size_t lo = 0; lo < total_pts; lo += win_pts) {
+    const size_t hi = std::min(lo + win_pts, total_pts);
+    size_t s0 = 0;  // first stream index of segment k
+    for (int k = 0; k < 3; s0 += seg[k].n, ++k) {
+      const size_t a = std::max(lo, s0), b = std::min(hi, s0 + seg[k].n);
+      if (a < b) DVP_TRY(encode_dev(seg[k].b + (a - s0), seg[k].inf + (a - s0), b - a, win.as<uint8_t>() + 30 * (a - lo), st));
+    }
+    if (nchunks == 1) DVP_TRY(b3_single_chunk_dev(win.as<uint8_t>(), total_bytes, dout.as<uint32_t>(), st));
+    else DVP_TRY(b3_leaves_dev(win.as<uint8_t>(), 30 * (hi - lo), 30 * lo / 1024, cvs.as<uint32_t>() + 8 * (30 * lo / 1024), st));
+  }
+  if (nchunks > 1) DVP_TRY(b3_reduce_dev(cvs.as<uint32_t>(), nchunks, tmp.as<uint32_t>(), dout.as<uint32_t>(), st));
+  DVP_HIP(hipMemcpyAsync(out, dout.p, 32, hipMemcpyDeviceToHost, st));
+  DVP_HIP(hipStreamSynchronize(st));
   return DVP_OK;
 }
 
@@ -1316,7 +1370,7 @@ extern "C" int dvp_prove_challenge(dvp_prover* p, const void* d_commit_xy, const
   }
   p->enc_fused[0] = false;
   uint8_t ch[32];
-  transcript_challenge(p->commit_p_host, p->pub_host.data(), p->n_pub, ch);
+  transcript_challenge(p->commit_p_host, p->pub_host.data(), p->n_pub, (const uint8_t*)p->h_ct.w, ch);
   Fr alpha;
   memcpy(alpha.v, ch, 32);
   p->alpha_canon = alpha;
@@ -1353,7 +1407,7 @@ extern "C" int dvp_prove_challenge_partial(dvp_prover* p, const void* d_commit_x
   }
   p->enc_fused[0] = false;
   uint8_t ch[32];
-  transcript_challenge(p->commit_p_host, p->pub_host.data(), p->n_pub, ch);
+  transcript_challenge(p->commit_p_host, p->pub_host.data(), p->n_pub, (const uint8_t*)p->h_ct.w, ch);
   Fr alpha;
   memcpy(alpha.v, ch, 32);
   p->alpha_canon = alpha;

@@ -52,7 +52,7 @@ struct VerifyConsts {
   Fr delta_m;   // delta * R
   Fr delta2_m;  // delta^2 * R
   Fr eps_m;     // epsilon * R
-  b3d::Words8 h_ct;  // H(H(empty) || H(empty)): the compile-time half of the transcript (src/srs.rs:386-404)
+  b3d::Words8 h_ct;  // H(srs_hash || circuit_hash): the compile-time half of the transcript (src/srs.rs:386-404), dvp_verify_set_binding
 };
 
 // a < p for 8 little-endian 32-bit limbs (FrBits::to_fr's validity flag when the top limb holds byte 28 only)
@@ -500,6 +500,31 @@ static bool fr_host_canonical(const uint64_t* v) {
   return false;
 }
 
+// dvp_verify_set_binding: the two hashes of the transcript's compile-time half, process-wide like the codec rule.  NULL = BLAKE3(""),
+// the reference's value.  verify_consts reads them once per call, under the mutex: a call in flight keeps what it started with.
+static std::mutex g_bind_mu;
+static bool g_bind_has[2] = {false, false};
+static uint8_t g_bind_hash[2][32];
+extern "C" int dvp_verify_set_binding(const uint8_t srs_hash[32], const uint8_t circuit_hash[32]) {
+  std::lock_guard<std::mutex> g(g_bind_mu);
+  const uint8_t* h[2] = {srs_hash, circuit_hash};
+  for (int k = 0; k < 2; ++k) {
+    g_bind_has[k] = h[k] != nullptr;
+    if (h[k]) memcpy(g_bind_hash[k], h[k], 32);
+  }
+  return DVP_OK;
+}
+extern "C" int dvp_verify_get_binding(uint8_t srs_hash[32], uint8_t circuit_hash[32]) {
+  if (!srs_hash || !circuit_hash) return DVP_EINVAL;
+  std::lock_guard<std::mutex> g(g_bind_mu);
+  uint8_t* h[2] = {srs_hash, circuit_hash};
+  for (int k = 0; k < 2; ++k) {
+    if (g_bind_has[k]) memcpy(h[k], g_bind_hash[k], 32);
+    else b3::hash(nullptr, 0, h[k]);
+  }
+  return DVP_OK;
+}
+
 static int verify_consts(const uint64_t tau[4], const uint64_t delta[4], const uint64_t eps[4], VerifyConsts* c) {
   if (!tau || !delta || !eps) return DVP_EINVAL;
   if (!fr_host_canonical(tau) || !fr_host_canonical(delta) || !fr_host_canonical(eps)) return DVP_EINVAL;
@@ -511,11 +536,11 @@ static int verify_consts(const uint64_t tau[4], const uint64_t delta[4], const u
   c->delta_m = fr_to_mont(d);
   c->delta2_m = fr_to_mont(fr_mul(c->delta_m, d));  // delta^2 (canonical), then times R
   c->eps_m = fr_to_mont(e);
-  uint8_t h_empty[32], buf[64], h[32];
-  b3::hash(nullptr, 0, h_empty);
-  memcpy(buf, h_empty, 32);
-  memcpy(buf + 32, h_empty, 32);
-  b3::hash(buf, 64, h);
+  uint8_t h[32];
+  {
+    std::lock_guard<std::mutex> g(g_bind_mu);
+    b3::compile_hash(g_bind_has[0] ? g_bind_hash[0] : nullptr, g_bind_has[1] ? g_bind_hash[1] : nullptr, h);
+  }
   memcpy(c->h_ct.w, h, 32);
   return DVP_OK;
 }

@@ -98,12 +98,26 @@ def prover_prepares_precomputes(cache_dir, validate_precompute: bool = False) ->
     return rep.value
 
 
-def transcript_challenge(commit_p: bytes, public_inputs) -> int:
-    """Transcript::output, src/proving.rs:164-197."""
+def _hash_arg(h, name):
+    """a 32-byte hash (or None) as an array that outlives the call, and the pointer to pass"""
+    if h is None:
+        return None, None
+    b = bytes(h)
+    if len(b) != 32:
+        raise ValueError(f"{name} must be 32 bytes")
+    a = np.frombuffer(b, dtype=np.uint8).copy()
+    return a, ptr(a)
+
+
+def transcript_challenge(commit_p: bytes, public_inputs, srs_hash=None, circuit_hash=None) -> int:
+    """Transcript::output, src/proving.rs:164-197.  srs_hash / circuit_hash: the binding (dvp_transcript_challenge_bound); None is
+    BLAKE3(""), what the reference hashes."""
     cp = np.frombuffer(commit_p, dtype=np.uint8).copy()
     pub = fr.vec(public_inputs) if len(public_inputs) else np.zeros((1, 4), dtype=np.uint64)
     out = np.zeros(4, dtype=np.uint64)
-    check(lib.dvp_transcript_challenge(ptr(cp), ptr(pub), len(public_inputs), ptr(out)), "dvp_transcript_challenge")
+    ks, s = _hash_arg(srs_hash, "srs_hash")
+    kc, c = _hash_arg(circuit_hash, "circuit_hash")
+    check(lib.dvp_transcript_challenge_bound(ptr(cp), ptr(pub), len(public_inputs), s, c, ptr(out)), "dvp_transcript_challenge_bound")
     return fr.to_int(out)
 
 
@@ -112,6 +126,30 @@ def blake3(data: bytes) -> bytes:
     out = np.zeros(32, dtype=np.uint8)
     check(lib.dvp_blake3(ptr(d), len(data), ptr(out)), "dvp_blake3")
     return out.tobytes()
+
+
+def blake3_dev(d_ptr: int, nbytes: int, stream: int = 0) -> bytes:
+    """BLAKE3 of nbytes at the device address d_ptr (any byte alignment; 0 is allowed for nbytes = 0), chunk-parallel on the GPU
+    (dvp_blake3_dev).  The call itself only enqueues on `stream`; this wrapper then waits for the 32 bytes."""
+    import torch
+
+    out = torch.empty(32, dtype=torch.uint8, device="cuda")
+    check(lib.dvp_blake3_dev(d_ptr or None, nbytes, out.data_ptr(), stream or None), "dvp_blake3_dev")
+    if stream:
+        torch.cuda.ExternalStream(stream).synchronize()
+    else:
+        torch.cuda.synchronize()
+    return out.cpu().numpy().tobytes()
+
+
+def set_cache_dir_binding(cache_dir, num_public_inputs: int, srs_hash=None, circuit_hash=None, bind_srs: bool = False):
+    """dvp_cache_dir_set_binding: Prover.set_transcript_binding for the prover(s) Proof.prove(cache_dir, ..) keeps; bind_srs with
+    srs_hash None binds the opened prover's own Prover.srs_hash()"""
+    import os
+
+    ks, s = _hash_arg(srs_hash, "srs_hash")
+    kc, c = _hash_arg(circuit_hash, "circuit_hash")
+    check(lib.dvp_cache_dir_set_binding(os.fspath(cache_dir).encode(), num_public_inputs, s, c, int(bool(bind_srs))), "dvp_cache_dir_set_binding")
 
 
 class Prover:
@@ -162,6 +200,20 @@ class Prover:
         """payload of a reference point-vector file (n x 30 bytes, src/io_utils.rs:83-111)"""
         e = np.ascontiguousarray(enc, dtype=np.uint8).reshape(-1, 30)
         check(lib.dvp_prover_set_srs_encoded(self._h, which, ptr(e), e.shape[0]), "dvp_prover_set_srs_encoded")
+
+    def srs_hash(self) -> bytes:
+        """BLAKE3 of to_bytes() of g_k[0], g_k[1], g_k[2], g_q, g_m in that order (the stream Transcript::srs_hash would hash,
+        src/proving.rs:91-101), encoded and hashed on the device; depends on the codec rule in force (dvp_prover_srs_hash)"""
+        out = np.zeros(32, dtype=np.uint8)
+        check(lib.dvp_prover_srs_hash(self._h, ptr(out)), "dvp_prover_srs_hash")
+        return out.tobytes()
+
+    def set_transcript_binding(self, srs_hash=None, circuit_hash=None):
+        """bind this prover's challenges to (srs_hash, circuit_hash): the transcript's compile-time half becomes
+        H(srs_hash || circuit_hash), None = BLAKE3(""); (None, None) restores the reference's constant"""
+        ks, s = _hash_arg(srs_hash, "srs_hash")
+        kc, c = _hash_arg(circuit_hash, "circuit_hash")
+        check(lib.dvp_prover_set_transcript_binding(self._h, s, c), "dvp_prover_set_transcript_binding")
 
     # ---- domain data -------------------------------------------------------------------------------
     def domains(self):

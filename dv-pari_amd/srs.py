@@ -158,7 +158,7 @@ def verify(td: Trapdoor, public_inputs, proof) -> bool:
     b0, ok_b = pr.b0_fr()
     if not (ok_a and ok_b):
         return False
-    alpha = transcript_challenge(pr.commit_p, public_inputs)
+    alpha = transcript_challenge(pr.commit_p, public_inputs, *get_verify_binding())  # the binding the GPU verifier follows too
     i0 = evaluate_monomial_basis_poly(public_inputs, alpha)
     r0 = (a0 * b0 - i0) % P
     delta2 = td.delta * td.delta % P
@@ -212,6 +212,26 @@ def _public_array(public_inputs, n: int) -> np.ndarray:
         buf = b"".join(int(v).to_bytes(32, "little") for r in rows for v in r)
         out[:] = np.frombuffer(buf, dtype="<u8").reshape(n, k, 4)
     return out
+
+
+def set_verify_binding(srs_hash=None, circuit_hash=None):
+    """dvp_verify_set_binding: the (srs_hash, circuit_hash) pair every verify entry of this process checks proofs against from now on;
+    None = BLAKE3(""), (None, None) = the reference's unbound transcript"""
+    from ._native import lib, check
+    from .proving import _hash_arg
+
+    ks, s = _hash_arg(srs_hash, "srs_hash")
+    kc, c = _hash_arg(circuit_hash, "circuit_hash")
+    check(lib.dvp_verify_set_binding(s, c), "dvp_verify_set_binding")
+
+
+def get_verify_binding():
+    """(srs_hash, circuit_hash) in force for the verify entries (BLAKE3("") where none is set)"""
+    from ._native import lib, check, ptr
+
+    s, c = np.zeros(32, dtype=np.uint8), np.zeros(32, dtype=np.uint8)
+    check(lib.dvp_verify_get_binding(ptr(s), ptr(c)), "dvp_verify_get_binding")
+    return s.tobytes(), c.tobytes()
 
 
 def verify_batch(td: Trapdoor, public_inputs, proofs) -> np.ndarray:

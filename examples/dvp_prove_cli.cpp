@@ -2,7 +2,11 @@
 // against.  It mirrors the reference's `Proof::prove(cache_dir, public_inputs, private_inputs)` call
 // (src/proving.rs:426) from files alone:
 //
-//   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3] [--table-budget <bytes>]
+//   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3] [--table-budget <bytes>] [--bind-srs] [--circuit-hash <hex>]
+//
+// --bind-srs: bind the proof's challenge to the SRS (dvp_prover_srs_hash + dvp_prover_set_transcript_binding); the SRS hash used goes
+// to stderr -- the verifier needs it (dvp_verify_cli --srs-hash).  --circuit-hash <64 hex digits>: the circuit half of the binding
+// (whatever the host defines it to be).  Without either the transcript is the reference's, which binds neither.
 //
 // --table-budget <bytes>: the most HBM per device the prover's fixed-base tables may hold (dvp_prover_set_table_budget; 0 = no
 // tables).  What does not fit runs through the one-shot MSM; the proof bytes do not depend on it.  The coverage goes to stderr.
@@ -26,8 +30,26 @@
 
 #include "dvpari.h"
 
+// 64 hex digits (an optional 0x prefix) -> 32 bytes in the order written, as a digest is printed
+static bool parse_hash(const char* s, uint8_t out[32]) {
+  if (s[0] == '0' && (s[1] == 'x' || s[1] == 'X')) s += 2;
+  if (strlen(s) != 64) return false;
+  for (int i = 0; i < 64; ++i) {
+    const char c = s[i];
+    int v;
+    if (c >= '0' && c <= '9') v = c - '0';
+    else if (c >= 'a' && c <= 'f') v = c - 'a' + 10;
+    else if (c >= 'A' && c <= 'F') v = c - 'A' + 10;
+    else return false;
+    out[i / 2] = (uint8_t)((i & 1) ? (out[i / 2] | v) : (v << 4));
+  }
+  return true;
+}
+
 int main(int argc, char** argv) {
   std::vector<int> devices;
+  bool bind_srs = false, have_circuit = false;
+  uint8_t srs_hash[32] = {0}, circuit_hash[32] = {0};
   int repeat = 0, threads = 1;  // --repeat N --threads T: N more proofs through dvp_prove_cache_dir from T host threads
   std::vector<char*> pos;
   bool have_budget = false;
@@ -42,6 +64,14 @@ int main(int argc, char** argv) {
       }
       budget = (uint64_t)v;
       have_budget = true;
+    } else if (std::string(argv[i]) == "--bind-srs") {
+      bind_srs = true;
+    } else if (std::string(argv[i]) == "--circuit-hash" && i + 1 < argc) {
+      if (!parse_hash(argv[++i], circuit_hash)) {
+        fprintf(stderr, "--circuit-hash: expected 64 hex digits, got '%s'\n", argv[i]);
+        return 2;
+      }
+      have_circuit = true;
     } else if (std::string(argv[i]) == "--devices" && i + 1 < argc) {
       for (char* tok = argv[++i]; *tok;) {
         char* end = tok;
@@ -67,7 +97,7 @@ int main(int argc, char** argv) {
     }
   }
   if (pos.size() < 2) {
-    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--repeat N --threads T]\n", argv[0]);
+    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--circuit-hash HEX] [--repeat N --threads T]\n", argv[0]);
     return 2;
   }
   argc = (int)pos.size() + 1;
@@ -127,6 +157,20 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if (bind_srs || have_circuit) {
+    rc = bind_srs ? dvp_prover_srs_hash(p, srs_hash) : DVP_OK;
+    if (rc == DVP_OK) rc = dvp_prover_set_transcript_binding(p, bind_srs ? srs_hash : nullptr, have_circuit ? circuit_hash : nullptr);
+    if (rc != DVP_OK) {
+      fprintf(stderr, "--bind-srs / --circuit-hash: %s\n", dvp_strerror(rc));
+      dvp_prover_destroy(p);
+      return 1;
+    }
+    if (bind_srs) {
+      fprintf(stderr, "srs hash: ");
+      for (int i = 0; i < 32; ++i) fprintf(stderr, "%02x", srs_hash[i]);
+      fprintf(stderr, "\n");
+    }
+  }
   rc = dvp_prove(p, w.data() + 4, n_public, w.data() + 4 * (1 + (size_t)n_public), (uint32_t)(n_wires - 1 - n_public), proof);
   if (have_budget && rc == DVP_OK)
     for (int which = 1; which >= 0; --which) {
@@ -158,6 +202,13 @@ int main(int argc, char** argv) {
       if (rc == DVP_OK) rc = dvp_prover_set_table_budget(cp, budget);
       if (rc != DVP_OK) {
         fprintf(stderr, "--table-budget: %s\n", dvp_strerror(rc));
+        return 1;
+      }
+    }
+    if (bind_srs || have_circuit) {  // the same binding for the prover(s) dvp_prove_cache_dir keeps
+      rc = dvp_cache_dir_set_binding(dir.c_str(), n_public, bind_srs ? srs_hash : nullptr, have_circuit ? circuit_hash : nullptr, 0);
+      if (rc != DVP_OK) {
+        fprintf(stderr, "dvp_cache_dir_set_binding: %s\n", dvp_strerror(rc));
         return 1;
       }
     }

@@ -1,7 +1,10 @@
 // Host program over the C ABI only (include/dvpari.h): the designated verifier's half of the reference's lifecycle,
 // `SRS::verify(secrets, public_inputs, proof)` (src/srs.rs:374-428), from files and the command line alone:
 //
-//   dvp_verify_cli <proof.bin> <tau> <delta> <epsilon> [<public input>...]
+//   dvp_verify_cli <proof.bin> <tau> <delta> <epsilon> [<public input>...] [--srs-hash <hex>] [--circuit-hash <hex>]
+//
+// --srs-hash / --circuit-hash (64 hex digits each): the binding the proof was made under (dvp_verify_set_binding; what
+// dvp_prove_cli --bind-srs printed, and the host's circuit hash).  A hash that is not given is BLAKE3(""), the reference's transcript.
 //
 // proof.bin holds the 118 bytes of Proof::to_bytes (what dvp_prove_cli writes); the trapdoor values and the public inputs are
 // canonical field elements in hex (an optional 0x prefix).  Exit status: 0 accepted, 2 rejected (the DVP_VERIFY_* reason bits
@@ -33,9 +36,42 @@ static bool parse_hex(const char* s, uint64_t out[4]) {
   return true;
 }
 
+// 64 hex digits (an optional 0x prefix) -> 32 bytes in the order written, as a digest is printed
+static bool parse_hash(const char* s, uint8_t out[32]) {
+  if (s[0] == '0' && (s[1] == 'x' || s[1] == 'X')) s += 2;
+  if (strlen(s) != 64) return false;
+  for (int i = 0; i < 64; ++i) {
+    const char c = s[i];
+    int v;
+    if (c >= '0' && c <= '9') v = c - '0';
+    else if (c >= 'a' && c <= 'f') v = c - 'a' + 10;
+    else if (c >= 'A' && c <= 'F') v = c - 'A' + 10;
+    else return false;
+    out[i / 2] = (uint8_t)((i & 1) ? (out[i / 2] | v) : (v << 4));
+  }
+  return true;
+}
+
 int main(int argc, char** argv) {
+  bool have_hash[2] = {false, false};
+  uint8_t hashes[2][32] = {{0}, {0}};
+  std::vector<char*> pos;
+  for (int i = 1; i < argc; ++i) {
+    const int k = std::string(argv[i]) == "--srs-hash" ? 0 : std::string(argv[i]) == "--circuit-hash" ? 1 : -1;
+    if (k < 0) {
+      pos.push_back(argv[i]);
+    } else if (i + 1 >= argc || !parse_hash(argv[i + 1], hashes[k])) {
+      fprintf(stderr, "%s: expected 64 hex digits\n", argv[i]);
+      return 1;
+    } else {
+      have_hash[k] = true;
+      ++i;
+    }
+  }
+  argc = (int)pos.size() + 1;
+  for (size_t i = 0; i < pos.size(); ++i) argv[i + 1] = pos[i];
   if (argc < 5) {
-    fprintf(stderr, "usage: %s <proof.bin> <tau> <delta> <epsilon> [<public input>...]   (hex, canonical)\n", argv[0]);
+    fprintf(stderr, "usage: %s <proof.bin> <tau> <delta> <epsilon> [<public input>...] [--srs-hash HEX] [--circuit-hash HEX]   (hex, canonical)\n", argv[0]);
     return 1;
   }
   uint64_t td[3][4];
@@ -66,6 +102,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "no HIP device visible\n");
     return 3;
   }
+  if (dvp_verify_set_binding(have_hash[0] ? hashes[0] : nullptr, have_hash[1] ? hashes[1] : nullptr) != DVP_OK) return 1;
   int accepted = 0;
   uint32_t reasons = 0;
   const int rc = dvp_verify(td[0], td[1], td[2], pub.data(), (uint32_t)(argc - 5), proof, &accepted, &reasons);

@@ -267,6 +267,38 @@ int dvp_ecfft_domain_tables(dvp_ecfft* tree2n, int which, uint64_t* bar_weights,
 /* Transcript::output, src/proving.rs:164-197, and the BLAKE3 hash it is built on */
 int dvp_transcript_challenge(const uint8_t commit_p[30], const uint64_t* public_inputs, uint32_t n_public, uint64_t out[4]);
 int dvp_blake3(const uint8_t* data, size_t len, uint8_t out[32]);
+/* BLAKE3 of a DEVICE buffer, chunk-parallel: one lane per 1 KiB chunk, then the chaining values pairwise, nine levels per launch
+ * (csrc/blake3_tree.hip).  d_data may start at any byte address (nothing at or beyond d_data + len is read; up to three bytes in front
+ * of it are, the aligned dword its first byte lies in) and may be NULL only for len = 0; d_out32: 32 bytes on the device.  Enqueues on
+ * `stream` and does not wait; its scratch (len / 32 bytes of chaining values) is allocated and freed in stream order.  DVP_ENOMEM only
+ * when the runtime refuses that scratch; len > 2^40 is DVP_EINVAL (32-bit chunk counter). */
+int dvp_blake3_dev(const void* d_data, size_t len, void* d_out32, void* stream);
+
+/* Binding the transcript to the SRS and the circuit.  Transcript::srs_hash and ::circuit_info_hash (src/proving.rs:82-134) hash EMPTY
+ * buffers in the reference ("takes awfully long to hash this much data"), so a proof's challenge binds neither; that stays the default
+ * here, byte for byte.  On this device the SRS hash is milliseconds, so a host may opt in: the compile-time half of the transcript
+ * becomes H(srs_hash || circuit_hash), a NULL hash meaning BLAKE3("") (NULL, NULL = the reference's constant).  Prover and verifier
+ * must be given the same pair: a proof made under one binding fails under any other with DVP_VERIFY_EQUATION.
+ *
+ * dvp_prover_srs_hash: BLAKE3 of the stream the commented-out loop at src/proving.rs:91-101 would build -- to_bytes() of every point of
+ * g_k[0], g_k[1], g_k[2], then g_q, then g_m, i.e. the payloads of the files g_k_0, g_k_1, g_k_2, g_q, g_m in that order without their
+ * 8-byte counts -- encoded and hashed on the device through a bounded staging window.  It DEPENDS ON THE CODEC RULE IN FORCE
+ * (dvp_codec_set_rule): the same bases hash differently under another rule.  DVP_EINVAL until all five SRS vectors are set.  Under
+ * dvp_set_devices the home device's copies are hashed (they stay complete), so the device list does not change the result.  Waits
+ * for the result; call it between proofs.
+ * dvp_prover_set_transcript_binding: may be called between proofs; every path that derives alpha follows it (dvp_prove, dvp_prove_dev
+ * with the device or the host transcript, device lists, dvp_prove_challenge, dvp_prove_challenge_partial).  The circuit hash is the
+ * caller's: the reference has not settled what it is (:110); dvp_blake3 / dvp_blake3_dev hash whatever a host decides on.
+ * dvp_transcript_challenge_bound: dvp_transcript_challenge under a binding (host only). */
+int dvp_prover_srs_hash(dvp_prover* p, uint8_t out[32]);
+int dvp_prover_set_transcript_binding(dvp_prover* p, const uint8_t srs_hash[32], const uint8_t circuit_hash[32]);
+int dvp_transcript_challenge_bound(const uint8_t commit_p[30], const uint64_t* public_inputs, uint32_t n_public,
+                                   const uint8_t srs_hash[32], const uint8_t circuit_hash[32], uint64_t out[4]);
+/* The verifier's side: process-wide like dvp_codec_set_rule; every dvp_verify* entry reads it once per call (a call in flight keeps
+ * the value it started with).  NULL, NULL restores the default.  The seed-less key of dvp_verify_batch_rlc does not change (it covers
+ * the proof bytes already).  get: the pair in force, BLAKE3("") for a hash that is not set. */
+int dvp_verify_set_binding(const uint8_t srs_hash[32], const uint8_t circuit_hash[32]);
+int dvp_verify_get_binding(uint8_t srs_hash[32], uint8_t circuit_hash[32]);
 
 /* SRS::verify(secrets, public_inputs, proof) (src/srs.rs:374-428) on the GPU: the designated verifier's check, one lane per proof,
  * sharing the codec (dvp_codec_set_rule), the transcript and the curve code with the prover.  Proof bytes: Proof::to_bytes,
@@ -409,6 +441,11 @@ int dvp_prover_open_cache_dir(const char* cache_dir, uint32_t n_public, dvp_prov
 int dvp_prove_cache_dir(const char* cache_dir, const uint64_t* public_inputs, uint32_t n_public, const uint64_t* private_inputs,
                         uint32_t n_private, uint8_t proof[118]);
 void dvp_cache_dir_release(const char* cache_dir);
+/* dvp_prover_set_transcript_binding for the prover(s) dvp_prove_cache_dir keeps for (cache_dir, n_public), opened if need be:
+ * bind_srs != 0 with srs_hash == NULL computes dvp_prover_srs_hash of the opened prover and binds that; a second prover
+ * (DVP_CACHE_REPLICAS=2) inherits the binding.  Waits for a proof in flight on the entry's first prover when it has to compute the hash;
+ * takes effect with the next proof that starts; a release of the entry drops it. */
+int dvp_cache_dir_set_binding(const char* cache_dir, uint32_t n_public, const uint8_t* srs_hash, const uint8_t* circuit_hash, int bind_srs);
 /* the cached prover of (cache_dir, n_public), opened if need be -- borrowed, for inspection only (debug reads, plans) */
 int dvp_cache_dir_prover(const char* cache_dir, uint32_t n_public, dvp_prover** out);
 

@@ -89,6 +89,15 @@ int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delta[4], const
 int dvp_prover_debug_transcript_dev(dvp_prover* p, const uint8_t commit_p[30], const uint64_t* public_inputs, uint32_t n_public,
                                     uint64_t out_alpha[4], uint64_t out_neg_z_alpha[4]);
 
+/* TEST ONLY: the two halves of dvp_blake3_dev apart, so that a long stream can be hashed piecewise (what dvp_prover_srs_hash does with
+ * its staging windows).  leaves: the chaining values of the 1 KiB chunks of d_data[0, len), len > 0, a piece of a stream that starts at
+ * chunk `chunk_base` of it (so at a multiple of 1024 bytes; every piece but the last is a multiple of 1024 bytes long) -> d_cvs, 32
+ * bytes per chunk.  reduce: n >= 2 chaining values -> the digest; d_cvs is overwritten, d_tmp holds 32 bytes per tree_run values
+ * (rounded up).  tree_run: the chaining values one workgroup of the tree kernel reduces per launch. */
+uint32_t dvp_debug_blake3_tree_run(void);
+int dvp_debug_blake3_leaves_dev(const void* d_data, size_t len, uint64_t chunk_base, void* d_cvs, void* stream);
+int dvp_debug_blake3_reduce_dev(void* d_cvs, size_t n, void* d_tmp, void* d_out32, void* stream);
+
 /* intermediates of the last proof, for parity tests (names: see prove.hip) */
 int dvp_prover_debug_read(dvp_prover* p, const char* name, uint64_t* out, size_t n_elems);
 

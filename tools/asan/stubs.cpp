@@ -11,6 +11,8 @@ void dvp_prover_destroy(dvp_prover*) {}
 int dvp_prover_set_coeffs(dvp_prover*, const uint64_t*, uint32_t) { return DVP_EHIP; }
 int dvp_prover_set_matrix(dvp_prover*, int, uint32_t, const uint32_t*, const uint32_t*, const uint32_t*) { return DVP_EHIP; }
 int dvp_prover_set_srs_encoded(dvp_prover*, int, const uint8_t*, size_t) { return DVP_EHIP; }
+int dvp_prover_srs_hash(dvp_prover*, uint8_t*) { return DVP_EHIP; }
+int dvp_prover_set_transcript_binding(dvp_prover*, const uint8_t*, const uint8_t*) { return DVP_EHIP; }
 int dvp_prove(dvp_prover*, const uint64_t*, uint32_t, const uint64_t*, uint32_t, uint8_t*) { return DVP_EHIP; }
 int dvp_tune_get(const char*, long long* v) { if (v) *v = 1; return DVP_OK; }
 hipError_t hipGetDevice(int* d) { if (d) *d = 0; return hipSuccess; }
