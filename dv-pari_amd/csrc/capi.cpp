@@ -53,6 +53,8 @@ void prof_collect() {
 
 static std::atomic<uint64_t> g_host_waits[2];
 void count_host_wait(int kind) { g_host_waits[kind & 1].fetch_add(1, std::memory_order_relaxed); }
+static std::atomic<uint64_t> g_later_rounds[2];
+void count_later_round(bool dense) { g_later_rounds[dense ? 1 : 0].fetch_add(1, std::memory_order_relaxed); }
 
 static void tune_from_env(Tune& t) {
   t = Tune();
@@ -66,6 +68,7 @@ static void tune_from_env(Tune& t) {
   t.msm_aff_min = geti("DVP_MSM_AFF_MIN", t.msm_aff_min);
   t.msm_hex_max = geti("DVP_MSM_HEX_MAX", t.msm_hex_max);
   t.msm_round_pipeline = geti("DVP_MSM_ROUND_PIPELINE", t.msm_round_pipeline);
+  t.msm_round_dense = geti("DVP_MSM_ROUND_DENSE", t.msm_round_dense);
   t.msm_sort_fused = geti("DVP_MSM_SORT_FUSED", t.msm_sort_fused);
   t.msm_bucket_pairs_max = geti("DVP_MSM_BUCKET_PAIRS_MAX", t.msm_bucket_pairs_max);
   t.msm_aff_bmax = geti("DVP_MSM_AFF_BMAX", t.msm_aff_bmax);
@@ -109,7 +112,7 @@ static long long* tune_slot(const char* name) {
   dvp::Tune& t = dvp::tune();
   struct { const char* n; long long* v; } tab[] = {
       {"DVP_MSM_C", &t.msm_c}, {"DVP_MSM_K", &t.msm_k}, {"DVP_MSM_FIXED_C", &t.msm_fixed_c}, {"DVP_FX_HI", &t.fx_hi},
-      {"DVP_MSM_PROJ", &t.msm_proj}, {"DVP_MSM_AFF_MIN", &t.msm_aff_min}, {"DVP_MSM_HEX_MAX", &t.msm_hex_max}, {"DVP_MSM_ROUND_PIPELINE", &t.msm_round_pipeline}, {"DVP_MSM_SORT_FUSED", &t.msm_sort_fused}, {"DVP_MSM_BUCKET_PAIRS_MAX", &t.msm_bucket_pairs_max}, {"DVP_MSM_AFF_BMAX", &t.msm_aff_bmax}, {"DVP_MSM_AFF_BMIN", &t.msm_aff_bmin}, {"DVP_ECFFT_RADIX4", &t.ecfft_radix4}, {"DVP_ECFFT_FOLD", &t.ecfft_fold}, {"DVP_MSM_ACCUM_FAST", &t.msm_accum_fast}, {"DVP_MSM_TAIL_GROUPS", &t.msm_tail_groups}, {"DVP_MSM_ACCUM_HEX_MAX", &t.msm_accum_hex_max}, {"DVP_GF_INV_TABS", &t.gf_inv_tabs}, {"DVP_MSM_WS_SLOTS", &t.msm_ws_slots}, {"DVP_MSM_GATE_MIN", &t.msm_gate_min}, {"DVP_MSM_AFF_TPB", &t.msm_aff_tpb}, {"DVP_CACHE_REPLICAS", &t.cache_replicas},
+      {"DVP_MSM_PROJ", &t.msm_proj}, {"DVP_MSM_AFF_MIN", &t.msm_aff_min}, {"DVP_MSM_HEX_MAX", &t.msm_hex_max}, {"DVP_MSM_ROUND_PIPELINE", &t.msm_round_pipeline}, {"DVP_MSM_ROUND_DENSE", &t.msm_round_dense}, {"DVP_MSM_SORT_FUSED", &t.msm_sort_fused}, {"DVP_MSM_BUCKET_PAIRS_MAX", &t.msm_bucket_pairs_max}, {"DVP_MSM_AFF_BMAX", &t.msm_aff_bmax}, {"DVP_MSM_AFF_BMIN", &t.msm_aff_bmin}, {"DVP_ECFFT_RADIX4", &t.ecfft_radix4}, {"DVP_ECFFT_FOLD", &t.ecfft_fold}, {"DVP_MSM_ACCUM_FAST", &t.msm_accum_fast}, {"DVP_MSM_TAIL_GROUPS", &t.msm_tail_groups}, {"DVP_MSM_ACCUM_HEX_MAX", &t.msm_accum_hex_max}, {"DVP_GF_INV_TABS", &t.gf_inv_tabs}, {"DVP_MSM_WS_SLOTS", &t.msm_ws_slots}, {"DVP_MSM_GATE_MIN", &t.msm_gate_min}, {"DVP_MSM_AFF_TPB", &t.msm_aff_tpb}, {"DVP_CACHE_REPLICAS", &t.cache_replicas},
       {"DVP_MSM_QUAD_MAX", &t.msm_quad_max}, {"DVP_MSM_ACCUM_QUAD_MAX", &t.msm_accum_quad_max}, {"DVP_MSM_FIXED_MIN", &t.msm_fixed_min}, {"DVP_HORNER_MAX_PUB", &t.horner_max_pub}, {"DVP_FR_BI_SHAPE", &t.fr_bi_shape},
       {"DVP_MSM_ALIGNED_SIGNED", &t.msm_aligned_signed}, {"DVP_PROVE_HOST_TRANSCRIPT", &t.prove_host_transcript},
       {"DVP_TABLE_BUDGET_BYTES", &t.table_budget_bytes}, {"DVP_MSM_TABLE_REFUSE", &t.msm_table_refuse}};
@@ -145,6 +148,8 @@ extern "C" void dvp_profile_reset(void) {
   dvp::g_prof_round0.clear();
   dvp::g_host_waits[0] = 0;
   dvp::g_host_waits[1] = 0;
+  dvp::g_later_rounds[0] = 0;
+  dvp::g_later_rounds[1] = 0;
 }
 // the "msm_affine_round0" slot split by launch shape: one entry per distinct MSM size seen since the last reset
 extern "C" int dvp_profile_round0_shapes(uint64_t* pairs, double* total_ms, uint64_t* launches, int cap) {
@@ -163,6 +168,11 @@ extern "C" int dvp_profile_read(const char* name, double* total_ms, uint64_t* la
   if (!strcmp(name, "host_waits_stream") || !strcmp(name, "host_waits_side")) {  // counts since the last dvp_profile_reset
     *total_ms = 0;
     *launches = dvp::g_host_waits[name[11] == 's' && name[12] == 'i' ? 1 : 0].load();
+    return DVP_OK;
+  }
+  if (!strcmp(name, "later_rounds_word") || !strcmp(name, "later_rounds_dense")) {  // launches since the last dvp_profile_reset
+    *total_ms = 0;
+    *launches = dvp::g_later_rounds[name[13] == 'd' ? 1 : 0].load();
     return DVP_OK;
   }
   dvp::prof_collect();

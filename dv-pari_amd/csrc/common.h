@@ -94,6 +94,7 @@ struct Tune {
   long long msm_bucket_pairs_max = 12;  // DVP_MSM_BUCKET_PAIRS_MAX: what the pair rounds leave goes through k_bucket_pairs / k_bucket_rest (one thread per bucket) when no bucket holds more points than this; above it, and with 0, through the fan-in-K reducer
   long long msm_sort_fused = 1;  // DVP_MSM_SORT_FUSED: level 1 of the signed flavour's sort recomputes the entry words from the scalars (0 = k_recode_signed writes them to HBM first)
   long long msm_round_pipeline = 2;  // DVP_MSM_ROUND_PIPELINE: bookkeeping of the pair rounds (counts / offsets / descriptors): 2 = all rounds at once, four launches on the caller's stream before the first round (default); 1 = the same on a side stream behind the sort's last scatter (equal one proof at a time, 1 ms slower with two in flight); 0 = per round, between the rounds
+  long long msm_round_dense = 0;     // DVP_MSM_ROUND_DENSE: 1 = with the all-rounds bookkeeping (DVP_MSM_ROUND_PIPELINE 1 / 2) a later pair round holds its additions in slots [0, A) and its odd leftovers behind them, two descriptor words per slot: the rows of leftovers copy and multiply nothing.  0 (default) = bucket order, one word per slot, as the per-round bookkeeping always does: alone the dense order measured 0.11-0.17 ms per 2^20 proof, within the parent's own spread (recorded negatives)
   long long msm_hex_max = -1;   // DVP_MSM_HEX_MAX: merge levels up to this many additions use a row of 16 lanes each (-1 = default, 0 = never)
   long long msm_quad_max = 0;   // DVP_MSM_QUAD_MAX: merge levels up to this many additions use a quad of lanes each (0 = default)
   long long msm_fixed_min = 1ll << 16; // DVP_MSM_FIXED_MIN: smallest shard the prover sends through the fixed-base tables
@@ -129,5 +130,8 @@ void prof_collect();
 // of the caller's stream (the GPU idles until the host has reacted), kind 1 = the largest-bucket read of an MSM, taken on a side
 // stream while the first pair round runs (the host waits, the GPU does not)
 void count_host_wait(int kind);
+// launches of the pair rounds after the first, counted always, by descriptor form (dvp_profile_read "later_rounds_word" /
+// "later_rounds_dense"): the tests read which form ran
+void count_later_round(bool dense);
 
 }  // namespace dvp

@@ -1099,7 +1099,8 @@ int gf_sqr_tables(GfSqrTables* out, hipStream_t st) {
 // bases (HBM misses in the first round: the pre-rotated table is 5 GB) are off the critical path.
 constexpr uint32_t AFF_NONE = 0xffffffffu;
 // slot descriptor of the rounds after the first: the slot adds points i and i + 1 of the previous round's output (DESC_PAIR set) or
-// passes point i on (a bucket's odd leftover); i < 2^31.  The first round reads the sorted item list as (a, b) pairs instead.
+// passes point i on (a bucket's odd leftover); i < 2^31.  The first round reads the sorted item list as (a, b) pairs instead; the
+// dense order of the all-rounds bookkeeping (k_round_desc_all) adds a second word, the index the slot's result goes to.
 constexpr uint32_t DESC_PAIR = 0x80000000u;
 
 // Both sorts lay every bucket out from an EVEN position of the item list (scan of the counts rounded up to
@@ -1246,7 +1247,11 @@ __global__ void __launch_bounds__(SCAN_TPB) k_mscan_add(uint32_t* __restrict__ r
 struct DescPlan {
   unsigned long long at[40];  // round r's descriptors start at desc + at[r]
 };
-template <int LPK>
+// DENSE (Tune::msm_round_dense): a round's additions fill slots [0, A_r) and its odd leftovers [A_r, total_r), two words per slot
+// {input index | DESC_PAIR, output index} -- the rows of k_affine_round that hold leftovers alone then copy and multiply nothing.
+// The dense positions need no scan of their own: exclusive scans are linear, so the pairs of a key start at o_r - o_(r+1) (the scan
+// of floor(c_r / 2)), its leftover sits at 2 o_(r+1) - o_r (the scan of c_r & 1) behind the A_r = o_r[nkeys] - o_(r+1)[nkeys] pairs.
+template <int LPK, bool DENSE>
 __global__ void __launch_bounds__(1024)
 k_round_desc_all(const uint32_t* __restrict__ rp, uint32_t nkeys, int R, DescPlan plan, uint32_t* __restrict__ desc) {
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1256,7 +1261,7 @@ k_round_desc_all(const uint32_t* __restrict__ rp, uint32_t nkeys, int R, DescPla
   // the counts and offsets of up to eight rounds are asked for at once and the descriptors written afterwards: a round's three loads
   // used to sit in front of its stores, round after round
   for (int r0 = 1; r0 < R; r0 += 8) {
-    uint32_t cr[8], o[8], oo[8];
+    uint32_t cr[8], o[8], oo[8], A[8];  // A: the round's additions (DENSE only)
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int r = r0 + q;
@@ -1265,8 +1270,9 @@ k_round_desc_all(const uint32_t* __restrict__ rp, uint32_t nkeys, int R, DescPla
         cr[q] = c[key];
         o[q] = c[stride + key];
         oo[q] = c[3 * stride + key];
+        A[q] = DENSE ? c[stride + nkeys] - c[3 * stride + nkeys] : 0u;
       } else {
-        cr[q] = 0; o[q] = 0; oo[q] = 0;
+        cr[q] = 0; o[q] = 0; oo[q] = 0; A[q] = 0;
       }
     }
 #pragma unroll
@@ -1275,6 +1281,13 @@ k_round_desc_all(const uint32_t* __restrict__ rp, uint32_t nkeys, int R, DescPla
       if (r >= R) break;
       const uint32_t nout = (cr[q] + 1) >> 1;
       uint32_t* d = desc + plan.at[r];
+      if (DENSE) {
+        const uint32_t npair = cr[q] >> 1, a = o[q] - oo[q];
+        uint2* d2 = (uint2*)d;
+        for (uint32_t j = lane; j < npair; j += LPK) d2[a + j] = make_uint2((o[q] + 2 * j) | DESC_PAIR, oo[q] + j);
+        if ((cr[q] & 1u) && lane == npair % LPK) d2[A[q] + (2 * oo[q] - o[q])] = make_uint2(o[q] + cr[q] - 1, oo[q] + npair);
+        continue;
+      }
       for (uint32_t j = lane; j < nout; j += LPK) d[oo[q] + j] = (o[q] + 2 * j) | ((2 * j + 1 < cr[q]) ? DESC_PAIR : 0u);
     }
   }
@@ -1311,6 +1324,12 @@ k_round_desc(const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ off,
 #ifndef AFF_XY
 #define AFF_XY 1
 #endif
+// 1: pass 1 multiplies the slope's NUMERATOR into the prefix as well -- run * num and run * den are one gf_mul2 against one table of
+// `run` --, and pass 2 gets lam = (run num) * inv and the stripped inverse den * inv from one gf_mul2 against `inv`: three table
+// builds per addition.  0: the arithmetic of rounds 1-6 (run * den; then pre * inv | den * inv; then num * dinv: four tables).
+#ifndef AFF_NUM1
+#define AFF_NUM1 1
+#endif
 __device__ __forceinline__ void aff_set_prio(uint32_t v) {
   switch (v % 3u) {
     case 0: __builtin_amdgcn_s_setprio(0); break;
@@ -1343,7 +1362,13 @@ struct WaveTrace {
   unsigned long long* buf;  // [0] = records written, records from word 8
   uint32_t cap, tag;
 };
-template <bool FIRST, bool TRACE = false>
+// a slot as the kernel sees it: the points it adds (b = NONE: a is passed on; a = NONE: no such slot) and, on the DENSE path, the
+// index its result goes to (elsewhere that is the slot's own number)
+struct AffSlot {
+  uint32_t a, b, o;
+};
+// DENSE (later rounds whose bookkeeping k_round_desc_all<.., true> did): two-word descriptors, additions first, leftovers last
+template <bool FIRST, bool TRACE = false, bool DENSE = false>
 __global__ void __launch_bounds__(EC_TPB) __attribute__((amdgpu_waves_per_eu(3, 3)))
 k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, const uint32_t* __restrict__ total_ptr /* ooff[nkeys] */,
                uint32_t cap, uint32_t bmax, GfSqrTables T, Gf* __restrict__ prefix, Aff* __restrict__ out, uint32_t sign_mask, WaveTrace wt) {
@@ -1372,41 +1397,73 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
   // (round 6: the load is unconditional from a clamped index and the VALUE is selected.  Returning `none` from the early exits made
   // hipcc select between two ADDRESSES -- &desc[sk] and a private copy of `none`: 16 B of scratch per lane and, worse, a FLAT load per
   // descriptor, which counts on lgkmcnt beside the multiplier's LDS reads)
-  auto ld_desc = [&](int k) -> uint2 {
+  auto ld_desc = [&](int k) -> AffSlot {
     const uint32_t sk = (uint32_t)k * nthr + tid;
     const bool ok = k >= 0 && k < B && sk < total;
     if (FIRST) {
       uint2 v = none;
       if (ok) v = desc[sk];
-      return v;
+      return AffSlot{v.x, v.y, 0u};
     }
-    const uint32_t d = ((const uint32_t*)desc)[ok ? sk : 0u], a = d & ~DESC_PAIR;  // later rounds: one word per slot
-    return make_uint2(ok ? a : AFF_NONE, (ok && (d & DESC_PAIR)) ? a + 1 : AFF_NONE);
+    // later rounds: one word per slot, or two on the DENSE path
+    const uint2 d = DENSE ? desc[ok ? sk : 0u] : make_uint2(((const uint32_t*)desc)[ok ? sk : 0u], 0u);
+    const uint32_t a = d.x & ~DESC_PAIR;
+    return AffSlot{ok ? a : AFF_NONE, (ok && (d.x & DESC_PAIR)) ? a + 1 : AFF_NONE, d.y};
   };
   const Gf one = gf_one();
-  // pass 1: denominators and running product (x-coordinates only; y is touched when x1 == x2)
+  // pass 1: the running product of the denominators; AFF_NUM1: and every slot's numerator times the product before it (x and y of a
+  // point share a 64-byte half line: no request more than for x alone).  Without AFF_NUM1 y is touched only when x1 == x2.
+  // A slot that adds nothing (no partner, an infinity, P - P) multiplies the product by one; a wave whose lanes all hold leftovers
+  // -- the top rows of a DENSE round -- skips the product.  Only pairs park a prefix: pass 2 reads it for them alone.
   Gf run = one;
   {
-    uint2 d0 = ld_desc(0), d1 = ld_desc(1);
+    AffSlot d0 = ld_desc(0), d1 = ld_desc(1);
     Gf xa = gf_zero(), xb = gf_zero();
-    if (d0.y != AFF_NONE) { xa = ldx(d0.x); xb = ldx(d0.y); }
+    if (d0.b != AFF_NONE) { xa = ldx(d0.a); xb = ldx(d0.b); }
+#if AFF_NUM1
+    Gf ya = gf_zero(), yb = gf_zero();
+    if (d0.b != AFF_NONE) { ya = ldy(d0.a, xa); yb = ldy(d0.b, xb); }
+#endif
 #pragma unroll 1
     for (int k = 0; k < B; ++k) {
 #if AFF_PRIO
       aff_set_prio(wslot + (uint32_t)k);
 #endif
-      const uint2 d2 = ld_desc(k + 2);
+      const AffSlot d2 = ld_desc(k + 2);
       Gf nxa = gf_zero(), nxb = gf_zero();
-      if (d1.y != AFF_NONE) { nxa = ldx(d1.x); nxb = ldx(d1.y); }
-      Gf den = one;
-      if (d0.y != AFF_NONE && !gf_is_zero(xa) && !gf_is_zero(xb)) {
-        Gf dd = gf_add(xa, xb);
-        if (!gf_is_zero(dd)) den = dd;
-        else if (gf_eq(ldy(d0.x, xa), ldy(d0.y, xb))) den = xa;  // doubling: lambda = x + y/x
+      if (d1.b != AFF_NONE) { nxa = ldx(d1.a); nxb = ldx(d1.b); }
+#if AFF_NUM1
+      Gf nya = gf_zero(), nyb = gf_zero();
+      if (d1.b != AFF_NONE) { nya = ldy(d1.a, nxa); nyb = ldy(d1.b, nxb); }
+#endif
+      const bool pair = d0.b != AFF_NONE;
+      if (!DENSE || __any(pair)) {
+        Gf den = one;
+#if AFF_NUM1
+        Gf num = gf_zero();
+        if (pair && !gf_is_zero(xa) && !gf_is_zero(xb)) {
+          const Gf dd = gf_add(xa, xb), ys = gf_add(ya, yb);
+          if (!gf_is_zero(dd)) { den = dd; num = ys; }
+          else if (gf_is_zero(ys)) { den = xa; num = ya; }  // doubling: lambda = x + y/x
+        }
+        Gf np, nrun;
+        gf_mul2(num, den, run, L, np, nrun);
+        if (pair) prefix[(size_t)k * nthr + tid] = np;
+        run = nrun;
+#else
+        if (pair && !gf_is_zero(xa) && !gf_is_zero(xb)) {
+          Gf dd = gf_add(xa, xb);
+          if (!gf_is_zero(dd)) den = dd;
+          else if (gf_eq(ldy(d0.a, xa), ldy(d0.b, xb))) den = xa;  // doubling: lambda = x + y/x
+        }
+        if (pair) prefix[(size_t)k * nthr + tid] = run;
+        run = gf_mul(run, den, L);
+#endif
       }
-      prefix[(size_t)k * nthr + tid] = run;
-      run = gf_mul(run, den, L);
       d0 = d1; d1 = d2; xa = nxa; xb = nxb;
+#if AFF_NUM1
+      ya = nya; yb = nyb;
+#endif
     }
   }
   if (TRACE) tr_t1 = wall_clock64();
@@ -1414,55 +1471,79 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
   if (TRACE) tr_t2 = wall_clock64();
   // pass 2 (backwards): recover each inverse and finish the addition
   {
-    uint2 e0 = ld_desc(B - 1), e1 = ld_desc(B - 2);
+    AffSlot e0 = ld_desc(B - 1), e1 = ld_desc(B - 2);
     Gf px = gf_zero(), qx = gf_zero(), pre = one;
-    if (e0.x != AFF_NONE) px = ldx(e0.x);
-    if (e0.y != AFF_NONE) { qx = ldx(e0.y); pre = prefix[(size_t)(B - 1) * nthr + tid]; }
+    if (e0.a != AFF_NONE) px = ldx(e0.a);
+    if (e0.b != AFF_NONE) { qx = ldx(e0.b); pre = prefix[(size_t)(B - 1) * nthr + tid]; }
+    // AFF_NUM1: the numerator is in the prefix already, so q's y-coordinate is wanted only where p is infinity or x1 == x2 and is
+    // fetched there (q_y below) instead of riding the pipeline
 #if AFF_XY
-    Gf py = gf_zero(), qy = gf_zero();
-    if (e0.x != AFF_NONE) py = ldy(e0.x, px);
-    if (e0.y != AFF_NONE) qy = ldy(e0.y, qx);
+    Gf py = gf_zero();
+    if (e0.a != AFF_NONE) py = ldy(e0.a, px);
+#if !AFF_NUM1
+    Gf qy = gf_zero();
+    if (e0.b != AFF_NONE) qy = ldy(e0.b, qx);
+#endif
 #endif
 #pragma unroll 1
     for (int k = B - 1; k >= 0; --k) {
 #if AFF_PRIO
       aff_set_prio(wslot + (uint32_t)k);
 #endif
-      const uint2 e2 = ld_desc(k - 2);
+      const AffSlot e2 = ld_desc(k - 2);
 #if AFF_XY
       // the next slot's WHOLE points and prefix product: x and y of a point share a 128-byte line, and a y fetched one slot
       // after its x (the round-3 pipeline) found the line evicted from the L2 again: 6.3 line requests per addition, 4.3 now
-      Gf npx = gf_zero(), nqx = gf_zero(), npy = gf_zero(), nqy = gf_zero(), npre = one;
-      if (e1.x != AFF_NONE) { npx = ldx(e1.x); npy = ldy(e1.x, npx); }
-      if (e1.y != AFF_NONE) { nqx = ldx(e1.y); nqy = ldy(e1.y, nqx); npre = prefix[(size_t)(k - 1) * nthr + tid]; }
+      Gf npx = gf_zero(), nqx = gf_zero(), npy = gf_zero(), npre = one;
+      if (e1.a != AFF_NONE) { npx = ldx(e1.a); npy = ldy(e1.a, npx); }
+#if AFF_NUM1
+      if (e1.b != AFF_NONE) { nqx = ldx(e1.b); npre = prefix[(size_t)(k - 1) * nthr + tid]; }
+#else
+      Gf nqy = gf_zero();
+      if (e1.b != AFF_NONE) { nqx = ldx(e1.b); nqy = ldy(e1.b, nqx); npre = prefix[(size_t)(k - 1) * nthr + tid]; }
+#endif
 #else
       // this slot's y-coordinates (needed after the two products of the inverse recovery) ...
-      Gf py = gf_zero(), qy = gf_zero();
-      if (e0.x != AFF_NONE) py = ldy(e0.x, px);
-      if (e0.y != AFF_NONE) qy = ldy(e0.y, qx);
+      Gf py = gf_zero();
+      if (e0.a != AFF_NONE) py = ldy(e0.a, px);
+#if !AFF_NUM1
+      Gf qy = gf_zero();
+      if (e0.b != AFF_NONE) qy = ldy(e0.b, qx);
+#endif
       // ... and the next slot's x-coordinates and prefix product
       Gf npx = gf_zero(), nqx = gf_zero(), npre = one;
-      if (e1.x != AFF_NONE) npx = ldx(e1.x);
-      if (e1.y != AFF_NONE) { nqx = ldx(e1.y); npre = prefix[(size_t)(k - 1) * nthr + tid]; }
+      if (e1.a != AFF_NONE) npx = ldx(e1.a);
+      if (e1.b != AFF_NONE) { nqx = ldx(e1.b); npre = prefix[(size_t)(k - 1) * nthr + tid]; }
 #endif
-      if (e0.x != AFF_NONE) {
-        const uint32_t sidx = (uint32_t)k * nthr + tid;
+#if AFF_NUM1
+      auto q_y = [&]() -> Gf { return ldy(e0.b, qx); };
+#else
+      auto q_y = [&]() -> Gf { return qy; };
+#endif
+      if (e0.a != AFF_NONE) {
+        const uint32_t sidx = DENSE ? e0.o : (uint32_t)k * nthr + tid;
         Gf ox = px, oy = py;  // odd leftover, or q == infinity: pass p through
-        if (e0.y != AFF_NONE) {
-          if (gf_is_zero(px)) { ox = qx; oy = qy; }
+        if (e0.b != AFF_NONE) {
+          if (gf_is_zero(px)) { ox = qx; oy = q_y(); }
           else if (!gf_is_zero(qx)) {
             Gf dd = gf_add(px, qx);
             const bool same_x = gf_is_zero(dd);
-            const bool dbl = same_x && gf_eq(py, qy);
+            const bool dbl = same_x && gf_eq(py, q_y());
             if (same_x && !dbl) {  // p == -q
               ox = gf_zero(); oy = gf_zero();
             } else {
               Gf den = dbl ? px : dd;
+#if AFF_NUM1
+              Gf lam, inv_next;
+              gf_mul2(pre, den, inv, L, lam, inv_next);  // num/den (pre = num times the product before this slot), and the running inverse stripped of this slot's factor
+              inv = inv_next;
+#else
               Gf dinv, inv_next;
               gf_mul2(pre, den, inv, L, dinv, inv_next);  // 1/den, and the running inverse stripped of this slot's factor
               inv = inv_next;
               Gf num = dbl ? py : gf_add(py, qy);
               Gf lam = gf_mul(num, dinv, L);
+#endif
               if (dbl) lam = gf_add(lam, px);
               ox = gf_add(gf_add(gf_sqr(lam), lam), dd);  // dd == 0 when doubling (curve a = 0)
               // y3 = lam (x1 + x3) + x3 + y1   (the same expression covers the doubling)
@@ -1474,7 +1555,10 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
       }
       e0 = e1; e1 = e2; px = npx; qx = nqx; pre = npre;
 #if AFF_XY
-      py = npy; qy = nqy;
+      py = npy;
+#if !AFF_NUM1
+      qy = nqy;
+#endif
 #endif
     }
   }
@@ -2128,7 +2212,8 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
                           (const void*)k_accum_affine_fast<false, true>, (const void*)k_accum_affine_rest<true>, (const void*)k_accum_affine_rest<false>,
                           (const void*)k_tail_groups, (const void*)k_merge<1, false>, (const void*)k_merge<4, false>, (const void*)k_merge<16, false>, (const void*)k_merge<1, true>, (const void*)k_merge<4, true>, (const void*)k_merge<16, true>,
                           (const void*)k_affine_round<true, false>, (const void*)k_affine_round<false, false>, (const void*)k_affine_round<true, true>,
-                          (const void*)k_affine_round<false, true>, (const void*)k_sum_points, (const void*)k_tail<false>, (const void*)k_tail<true>,
+                          (const void*)k_affine_round<false, true>, (const void*)k_affine_round<false, false, true>, (const void*)k_affine_round<false, true, true>,
+                          (const void*)k_sum_points, (const void*)k_tail<false>, (const void*)k_tail<true>,
                           (const void*)k_bucket_pairs, (const void*)k_bucket_rest};
       for (const void* f : ec)
         if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, EC_LDS_Q);
@@ -2202,18 +2287,20 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
   // descriptors, so nothing the side stream writes is ever read by a round still in flight
   const bool pipelined = affine_mode && tn.msm_round_pipeline != 0 && ra_plan >= 2 && e_est >= 4 * (size_t)p.nkeys;
   const bool side_stream = pipelined && tn.msm_round_pipeline == 1;
-  std::vector<size_t> desc_at((size_t)ra_plan + 1, 0);  // round r's descriptors start at gdesc + desc_at[r] (r >= 1)
+  // the all-rounds bookkeeping lays a round out densely (additions first, leftovers behind them), two descriptor words per slot
+  const bool dense = pipelined && tn.msm_round_dense != 0;
+  std::vector<size_t> desc_at((size_t)ra_plan + 1, 0);  // round r's descriptors start at gdesc + desc_at[r] (r >= 1; even: uint2 on the dense path)
   size_t desc_n = affA_n + 64;
   if (pipelined) {
     size_t cap_r = p.e_max + p.nkeys, at = 0;
     for (int r = 0; r < ra_plan; ++r) {
       const size_t out_max = cap_r / 2 + p.nkeys + 1;
-      if (r >= 1) { desc_at[r] = at; at += out_max + 64; }
+      if (r >= 1) { desc_at[r] = at; at += (dense ? 2 : 1) * (out_max + 64); }
       cap_r = out_max;
     }
     if (at > desc_n) desc_n = at;
   }
-  size_t o_gdesc = carve(affine_mode ? desc_n * sizeof(uint32_t) : 16);  // one descriptor word per output slot
+  size_t o_gdesc = carve(affine_mode ? desc_n * sizeof(uint32_t) : 16);  // one descriptor word per output slot (dense: two)
   size_t o_rp = carve(pipelined ? (size_t)ra_plan * 2 * ((size_t)p.nkeys + 1) * 4 : 16);  // (counts, offsets) of rounds 1 .. ra_plan
   size_t o_bsum2 = carve(((size_t)((ra_plan > 0 ? ra_plan : 1) + 1) * ((size_t)p.nkeys / SCAN_BLK + 1) + 8) * 4);  // scan scratch of the side stream: a row of block sums per round
   size_t o_bkt = carve((size_t)p.nkeys * sizeof(Ld));
@@ -2317,12 +2404,11 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
     DescPlan plan;
     for (int q = 0; q < 40; ++q) plan.at[q] = q < ra_plan ? desc_at[q] : 0;
     const size_t per_key = (e_est >> 2) / nk;  // round 1's outputs per bucket
-    if (per_key >= 48)
-      hipLaunchKernelGGL((k_round_desc_all<64>), dim3(cdiv((size_t)nk * 64, 1024)), dim3(1024), 0, bk, rp, nk, ra_plan, plan, gdesc);
-    else if (per_key >= 8)
-      hipLaunchKernelGGL((k_round_desc_all<16>), dim3(cdiv((size_t)nk * 16, 1024)), dim3(1024), 0, bk, rp, nk, ra_plan, plan, gdesc);
-    else
-      hipLaunchKernelGGL((k_round_desc_all<4>), dim3(cdiv((size_t)nk * 4, 1024)), dim3(1024), 0, bk, rp, nk, ra_plan, plan, gdesc);
+    const int lpk = per_key >= 48 ? 64 : per_key >= 8 ? 16 : 4;
+    auto desc_all = lpk == 64 ? (dense ? k_round_desc_all<64, true> : k_round_desc_all<64, false>)
+                  : lpk == 16 ? (dense ? k_round_desc_all<16, true> : k_round_desc_all<16, false>)
+                              : (dense ? k_round_desc_all<4, true> : k_round_desc_all<4, false>);
+    hipLaunchKernelGGL(desc_all, dim3(cdiv((size_t)nk * lpk, 1024)), dim3(1024), 0, bk, rp, nk, ra_plan, plan, gdesc);
     if (side_stream) DVP_HIP(hipEventRecord(g_ws.ev_side[0], g_ws.side));
     DVP_HIP(hipGetLastError());
     prepared = ra_plan;
@@ -2416,6 +2502,7 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
   // so smaller workgroups only change how soon a finished wave's slot is handed to the next workgroup
   const uint32_t aff_tpb = (tn.msm_aff_tpb == 64 || tn.msm_aff_tpb == 128 || tn.msm_aff_tpb == 256) ? (uint32_t)tn.msm_aff_tpb : (uint32_t)EC_TPB;
   const uint32_t aff_lds = (aff_tpb / 64) * GF_LDSK_BYTES_PER_WAVE;
+  // (asked of one instantiation for all of them: amdgpu_waves_per_eu(3, 3) pins every flavour -- first, later, dense, traced -- to three waves per SIMD)
   DVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blk_per_cu, (const void*)k_affine_round<false, false>, (int)aff_tpb, aff_lds));
   if (blk_per_cu < 1) blk_per_cu = 1;
   const uint32_t aff_cap = (uint32_t)n_cu * (uint32_t)blk_per_cu * aff_tpb;
@@ -2443,11 +2530,16 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
         hipLaunchKernelGGL((k_affine_round<true, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, sign_mask, wt);
       else if (r == 0)
         hipLaunchKernelGGL((k_affine_round<true, false>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, sign_mask, wt);
+      else if (dense && wt.buf)
+        hipLaunchKernelGGL((k_affine_round<false, true, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
+      else if (dense)
+        hipLaunchKernelGGL((k_affine_round<false, false, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
       else if (wt.buf)
         hipLaunchKernelGGL((k_affine_round<false, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
       else
         hipLaunchKernelGGL((k_affine_round<false, false>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
       ps0.stop();
+      if (r > 0) count_later_round(dense);
     }
     pts_in = outp;
     cap = out_max;
