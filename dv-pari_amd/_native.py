@@ -87,6 +87,11 @@ _SIGS = {
     "dvp_codec_set_rule": (C.c_int, [C.c_int]),
     "dvp_codec_get_rule": (C.c_int, []),
     "dvp_points_add": (C.c_int, [u64p, u8p, u64p, u8p, sz, u64p, u8p]),
+    "dvp_points_check": (C.c_int, [u64p, u8p, sz, u8p, C.POINTER(C.c_size_t)]),
+    "dvp_points_check_dev": (C.c_int, [vp, vp, sz, vp, vp, vp]),
+    "dvp_points_set_strict": (C.c_int, [C.c_int]),
+    "dvp_points_get_strict": (C.c_int, []),
+    "dvp_ubench_points_check": (C.c_int, [vp, vp, vp, sz, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dvp_prover_create": (C.c_int, [u32, u32, u32, C.POINTER(vp)]),
     "dvp_prover_destroy": (None, [vp]),
     "dvp_prover_set_coeffs": (C.c_int, [vp, u64p, u32]),
@@ -169,8 +174,9 @@ for _name, (_res, _args) in _SIGS.items():
 
 
 STATUS_NAMES = {0: "DVP_OK", -1: "DVP_EINVAL", -2: "DVP_EDECODE", -3: "DVP_EUNSAT", -4: "DVP_EHIP", -6: "DVP_EIO", -7: "DVP_ENOMEM",
-                -8: "DVP_ECHALLENGE"}  # enum dvp_status, include/dvpari.h
+                -8: "DVP_ECHALLENGE", -9: "DVP_EPOINT"}  # enum dvp_status, include/dvpari.h
 ENOMEM = -7
+EPOINT = -9
 
 
 class DvpError(RuntimeError):

@@ -192,6 +192,7 @@ extern "C" const char* dvp_strerror(int s) {
     case DVP_EIO: return "I/O error";
     case DVP_ENOMEM: return "out of memory";
     case DVP_ECHALLENGE: return "Fiat-Shamir challenge lies in the evaluation domain";
+    case DVP_EPOINT: return "affine point unreduced, off the curve or outside the prime-order subgroup";
     default: return "unknown status";
   }
 }

@@ -13,6 +13,7 @@
 //   P = (x,y) that is  w = sqrt(x + y/x + 1)  (lambda-coordinate of P plus one); neutral -> 0.
 //   Decoding: e = w^2 + w, solve x^2 + e x + 1 = 0 (half-trace), roots are x(P) and x(P+N) = 1/x;
 //   y = x (w^2 + 1 + x); keep the root whose point lies in E[r] = 4E (two trace tests).
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
@@ -90,6 +91,48 @@ k_decode(const uint8_t* __restrict__ enc, size_t n, GfSqrTables T, Aff* __restri
   }
   out[i] = r;
   inf[i] = is_inf ? 1 : 0;
+}
+
+// One affine point per lane -> one class byte (include/dvpari.h: DVP_POINT_*), for the entries that take affine points from a caller:
+// the kernels behind them assume reduced coordinates and points of E[r].  The classes partition the curve's affine points: E = E[r] x
+// Z/4, so a point is in E[r], in E[r] + N (N = (0,1), the point of order 2: xsk233's own view of a group element), or -- Tr(x) = 1 --
+// outside 2E.  Tr(x) = 0 puts P in 2E; of 2E = E[r] u (E[r] + N) the half's trace test (k233_in_subgroup) keeps E[r].
+// The three products x y, x x^2 (curve equation) and (lambda + 1) x (the half) share the operand x and so ONE build of its half tables
+// (gf_mul3); lambda is a table pass over x alone, so all three multipliers are known before the first lookup.  An unreduced
+// coordinate never reaches the multiplier (gf_k_split / gf_k_combine assume reduced operands): such a lane is classified first and
+// skips the arithmetic, as do the lanes of points at infinity.
+// summary = { first bad index (atomicMin), number of bad points }: both from the lowest bad lane of a wave only, so clean input pays
+// for no atomic at all.
+__global__ void __launch_bounds__(256, 2)
+k_points_check(const Aff* __restrict__ pts, const uint8_t* __restrict__ inf, size_t n, GfSqrTables T, uint8_t* __restrict__ classes,
+               unsigned long long* __restrict__ summary) {
+  extern __shared__ char lds_raw[];
+  GfLdsK L = gf_ldsk_init(lds_raw);
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t cls = 0;
+  if (i < n && !(inf && inf[i])) {
+    Aff p = pts[i];
+    if ((p.x.w[7] | p.y.w[7]) >> 9) {
+      cls = DVP_POINT_UNREDUCED;
+    } else {
+      Gf lam1 = gf_sqr_tab(p.x, T.th);  // lam^2 + lam = x when Tr(x) = 0 (some reduced element otherwise: unused then)
+      lam1.w[0] ^= 1u;
+      Gf xy, x3, lx;
+      gf_mul3(p.y, gf_sqr(p.x), lam1, p.x, L, xy, x3, lx);
+      Gf d = gf_add(gf_add(gf_sqr(p.y), xy), x3);  // y^2 + xy + x^3 + 1
+      d.w[0] ^= 1u;
+      if (!gf_is_zero(d)) cls = DVP_POINT_OFF_CURVE;
+      else if (gf_is_zero(p.x)) cls = DVP_POINT_COSET_N;  // N itself
+      else if (gf_trace(p.x)) cls = DVP_POINT_ORDER4;
+      else if (gf_trace(gf_add(p.y, lx))) cls = DVP_POINT_COSET_N;  // x_half^2 = y + (lambda + 1) x
+    }
+  }
+  if (i < n && classes) classes[i] = (uint8_t)cls;
+  const unsigned long long bad = __ballot(cls != 0);
+  if (bad && (threadIdx.x & 63) == (unsigned)__ffsll((long long)bad) - 1) {  // lanes hold ascending indices: the lowest bad lane has the wave's first
+    atomicMin(summary, (unsigned long long)i);
+    atomicAdd(summary + 1, (unsigned long long)__popcll(bad));
+  }
 }
 
 // ---- fixed-base tables: tab[w][d] = sum_t d_t tau^(c w + t)(G), affine ------------------------------
@@ -250,6 +293,52 @@ int decode_dev(const uint8_t* d_enc, size_t n, Aff* d_out, uint8_t* d_inf, hipSt
   return read_err(err.as<unsigned long long>(), st, DVP_EDECODE);
 }
 
+// enqueue only: d_summary (16 bytes) is reset here, then k_points_check fills it
+int points_check_dev(const void* d_xy, const void* d_inf, size_t n, void* d_classes, void* d_summary, hipStream_t st) {
+  DVP_HIP(hipMemsetAsync(d_summary, 0xff, 8, st));
+  DVP_HIP(hipMemsetAsync((char*)d_summary + 8, 0, 8, st));
+  if (!n) return DVP_OK;
+  GfSqrTables T;
+  DVP_TRY(gf_sqr_tables(&T, st));
+  hipLaunchKernelGGL(k_points_check, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const Aff*)d_xy, (const uint8_t*)d_inf, n, T,
+                     (uint8_t*)d_classes, (unsigned long long*)d_summary);
+  DVP_HIP(hipGetLastError());
+  return DVP_OK;
+}
+
+// the check and its verdict: waits for `st`.  DVP_EPOINT with g_last_error_index = the first bad point
+int points_check_wait(const void* d_xy, const void* d_inf, size_t n, void* d_classes, size_t* n_bad, hipStream_t st) {
+  DevBuf sum;
+  DVP_TRY(sum.alloc(16));
+  DVP_TRY(points_check_dev(d_xy, d_inf, n, d_classes, sum.p, st));
+  unsigned long long s[2];
+  DVP_HIP(hipMemcpyAsync(s, sum.p, 16, hipMemcpyDeviceToHost, st));
+  DVP_HIP(hipStreamSynchronize(st));
+  if (n_bad) *n_bad = (size_t)s[1];
+  if (s[0] != ~0ull) {
+    g_last_error_index = (int64_t)s[0];
+    return DVP_EPOINT;
+  }
+  return DVP_OK;
+}
+
+// strict mode: DVP_POINTS_STRICT from the environment at first use, dvp_points_set_strict at run time
+static std::atomic<int> g_points_strict{-1};
+static int points_strict() {
+  int s = g_points_strict.load();
+  if (s < 0) {
+    const char* e = getenv("DVP_POINTS_STRICT");
+    s = (e && atoi(e) != 0) ? 1 : 0;
+    g_points_strict.store(s);
+  }
+  return s;
+}
+// what the entries that copy affine points from a caller run on their device copy (msm.hip, prove.hip and below): nothing when strict is off
+int points_check_strict(const void* d_xy, const void* d_inf, size_t n, hipStream_t st) {
+  if (!n || !points_strict()) return DVP_OK;
+  return points_check_wait(d_xy, d_inf, n, nullptr, nullptr, st);
+}
+
 // CurvePoint::add over two vectors (src/curve.rs:84-90): out[i] = a[i] + b[i] on the E[r] representative; complete
 // (doubling, inverses and the neutral element are handled), register-only arithmetic -- a convenience entry, not a hot path.
 __global__ void __launch_bounds__(128)
@@ -309,6 +398,7 @@ extern "C" int dvp_points_encode(const uint64_t* xy, const uint8_t* inf, size_t 
     DVP_TRY(di.alloc(n));
     DVP_HIP(hipMemcpy(di.p, inf, n, hipMemcpyHostToDevice));
   }
+  DVP_TRY(points_check_strict(dp.p, di.p, n, 0));
   DVP_TRY(encode_dev(dp.as<Aff>(), di.as<uint8_t>(), n, de.as<uint8_t>(), 0));
   DVP_HIP(hipMemcpy(out_enc, de.p, n * 30, hipMemcpyDeviceToHost));
   return DVP_OK;
@@ -333,6 +423,8 @@ extern "C" int dvp_points_add(const uint64_t* a_xy, const uint8_t* a_inf, const 
     DVP_TRY(dbi.alloc(n));
     DVP_HIP(hipMemcpy(dbi.p, b_inf, n, hipMemcpyHostToDevice));
   }
+  DVP_TRY(points_check_strict(da.p, dai.p, n, 0));  // operand a first: the index is b's only when a is clean
+  DVP_TRY(points_check_strict(db.p, dbi.p, n, 0));
   hipLaunchKernelGGL(k_points_add, dim3(cdiv(n, 128)), dim3(128), 0, 0, da.as<Aff>(), dai.as<uint8_t>(), db.as<Aff>(), dbi.as<uint8_t>(), n,
                      dout.as<Aff>(), doi.as<uint8_t>());
   DVP_HIP(hipGetLastError());
@@ -353,6 +445,73 @@ extern "C" int dvp_points_decode(const uint8_t* enc, size_t n, uint64_t* out_xy,
   DVP_HIP(hipMemcpy(out_xy, dp.p, n * 64, hipMemcpyDeviceToHost));
   DVP_HIP(hipMemcpy(out_inf, di.p, n, hipMemcpyDeviceToHost));
   return rc;
+}
+
+extern "C" int dvp_points_check(const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* classes, size_t* n_bad) {
+  if (!n) return DVP_OK;
+  if (!xy) return DVP_EINVAL;
+  DevBuf dp, di, dc;
+  DVP_TRY(dp.alloc(n * 64));
+  DVP_HIP(hipMemcpy(dp.p, xy, n * 64, hipMemcpyHostToDevice));
+  if (inf) {
+    DVP_TRY(di.alloc(n));
+    DVP_HIP(hipMemcpy(di.p, inf, n, hipMemcpyHostToDevice));
+  }
+  if (classes) DVP_TRY(dc.alloc(n));
+  int rc = points_check_wait(dp.p, di.p, n, dc.p, n_bad, 0);
+  if (classes && (rc == DVP_OK || rc == DVP_EPOINT)) DVP_HIP(hipMemcpy(classes, dc.p, n, hipMemcpyDeviceToHost));
+  return rc;
+}
+
+extern "C" int dvp_points_check_dev(const void* d_xy, const void* d_inf, size_t n, void* d_classes, void* d_summary, void* stream) {
+  if ((n && !d_xy) || !d_summary) return DVP_EINVAL;
+  return points_check_dev(d_xy, d_inf, n, d_classes, d_summary, (hipStream_t)stream);
+}
+
+extern "C" int dvp_points_set_strict(int on) {
+  g_points_strict.store(on ? 1 : 0);
+  return DVP_OK;
+}
+extern "C" int dvp_points_get_strict(void) { return points_strict(); }
+
+// k_points_check and k_decode alone on the same count, device events, median of `reps` after one warm-up launch each (tools/points_check.py)
+extern "C" int dvp_ubench_points_check(const void* d_xy, const void* d_inf, const void* d_enc, size_t n, void* d_scratch, int reps,
+                                       double* check_ms, double* decode_ms) {
+  if (!d_xy || !d_enc || !d_scratch || !n || reps < 1 || reps > 99 || !(reps & 1) || !check_ms || !decode_ms) return DVP_EINVAL;
+  GfSqrTables T;
+  DVP_TRY(gf_sqr_tables(&T, 0));
+  DevBuf sum;
+  DVP_TRY(sum.alloc(16));
+  DVP_HIP(hipMemset(sum.p, 0xff, 16));
+  hipEvent_t e0, e1;
+  DVP_HIP(hipEventCreate(&e0));
+  DVP_HIP(hipEventCreate(&e1));
+  const int rule = codec_rule();
+  float t[2][99];
+  hipError_t err = hipSuccess;
+  for (int k = 0; k < 2 && err == hipSuccess; ++k)
+    for (int r = -1; r < reps && err == hipSuccess; ++r) {
+      (void)hipEventRecord(e0, 0);
+      if (k == 0)
+        hipLaunchKernelGGL(k_points_check, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const Aff*)d_xy, (const uint8_t*)d_inf, n, T,
+                           (uint8_t*)nullptr, sum.as<unsigned long long>());
+      else
+        hipLaunchKernelGGL(k_decode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint8_t*)d_enc, n, T, (Aff*)d_scratch,
+                           (uint8_t*)d_scratch + n * 64, sum.as<unsigned long long>(), rule);
+      err = hipGetLastError();
+      (void)hipEventRecord(e1, 0);
+      if (err == hipSuccess) err = hipEventSynchronize(e1);
+      float ms = 0;
+      if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+      if (r >= 0) t[k][r] = ms;
+    }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (err != hipSuccess) return hip_fail(err, "dvp_ubench_points_check", __FILE__, __LINE__);
+  for (int k = 0; k < 2; ++k) std::sort(t[k], t[k] + reps);
+  *check_ms = t[0][reps / 2];
+  *decode_ms = t[1][reps / 2];
+  return DVP_OK;
 }
 
 // scalars: n x 32 B canonical LE; bases: n x 30 B xsk233 encodings; out: 30 B encoding of the sum

@@ -668,6 +668,35 @@ GF_DEV void gf_mul2(const Gf& a1, const Gf& a2, const Gf& b, const GfLdsK& c, Gf
   r1 = gf_k_combine(L1, H1, M1);
   r2 = gf_k_combine(L2, H2, M2);
 }
+// a1 * b, a2 * b and a3 * b against ONE build of each half table of b (k_points_check: x y, x x^2 and (lambda + 1) x).  Each product is
+// combined as soon as its M is there, so at most seven half products are live at a time
+GF_DEV void gf_mul3(const Gf& a1, const Gf& a2, const Gf& a3, const Gf& b, const GfLdsK& c, Gf& r1, Gf& r2, Gf& r3) {
+  uint32_t p0[4], p1[4], q0[4], q1[4], s0[4], s1[4], b0[4], b1[4];
+  gf_k_split(a1, p0, p1);
+  gf_k_split(a2, q0, q1);
+  gf_k_split(a3, s0, s1);
+  gf_k_split(b, b0, b1);
+  uint32_t L1[8], H1[8], L2[8], H2[8], L3[8], H3[8], M[8];
+  gf_k_tab_build_mul(L1, p0, b0, c);
+  gf_k_mul_tab(L2, q0, c);
+  gf_k_mul_tab(L3, s0, c);
+  gf_k_tab_build_mul(H1, p1, b1, c);
+  gf_k_mul_tab(H2, q1, c);
+  gf_k_mul_tab(H3, s1, c);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    p0[i] ^= p1[i];
+    q0[i] ^= q1[i];
+    s0[i] ^= s1[i];
+    b0[i] ^= b1[i];
+  }
+  gf_k_tab_build_mul(M, p0, b0, c);
+  r1 = gf_k_combine(L1, H1, M);
+  gf_k_mul_tab(M, q0, c);
+  r2 = gf_k_combine(L2, H2, M);
+  gf_k_mul_tab(M, s0, c);
+  r3 = gf_k_combine(L3, H3, M);
+}
 
 // 16 bits -> 32 bits with zeros interleaved
 GF_DEV uint32_t gf_spread16(uint32_t x) {

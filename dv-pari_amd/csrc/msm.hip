@@ -3078,6 +3078,9 @@ extern "C" int dvp_debug_recode_signed(const uint64_t* scalars, size_t n, int c,
   return DVP_OK;
 }
 
+namespace dvp {
+int points_check_strict(const void* d_xy, const void* d_inf, size_t n, hipStream_t st);  // codec.hip: a no-op unless strict mode is on
+}
 extern "C" int dvp_msm_affine(const uint64_t* scalars, const uint64_t* bases_xy, const uint8_t* bases_inf, size_t n,
                               uint64_t out_xy[8], int* out_is_infinity) {
   if ((n && (!scalars || !bases_xy)) || !out_xy || !out_is_infinity) return DVP_EINVAL;
@@ -3093,6 +3096,7 @@ extern "C" int dvp_msm_affine(const uint64_t* scalars, const uint64_t* bases_xy,
     DVP_TRY(di.alloc(n));
     DVP_HIP(hipMemcpy(di.p, bases_inf, n, hipMemcpyHostToDevice));
   }
+  DVP_TRY(points_check_strict(db.p, di.p, n, 0));
   DVP_TRY(msm_affine_dev(ds.p, db.p, di.p, n, dout.p, (char*)dout.p + 64, 0));
   uint32_t inf;
   DVP_HIP(hipMemcpy(out_xy, dout.p, 64, hipMemcpyDeviceToHost));
@@ -3121,7 +3125,9 @@ extern "C" int dvp_msm_ctx_create(const uint64_t* bases_xy, const uint8_t* bases
   hipError_t e = hipMalloc((void**)&c->d_inf, n);
   if (e == hipSuccess) e = bases_inf ? hipMemcpy(c->d_inf, bases_inf, n, hipMemcpyHostToDevice) : hipMemset(c->d_inf, 0, n);
   if (e != hipSuccess) return fail(hip_fail(e, "dvp_msm_ctx_create", __FILE__, __LINE__));
-  int rc = msm_fixed_create(db.as<Aff>(), (uint32_t)n, range_hint, &c->fx);
+  int rc = points_check_strict(db.p, c->d_inf, n, 0);
+  if (rc != DVP_OK) return fail(rc);
+  rc = msm_fixed_create(db.as<Aff>(), (uint32_t)n, range_hint, &c->fx);
   if (rc != DVP_OK) return fail(rc);
   *out = c;
   return DVP_OK;

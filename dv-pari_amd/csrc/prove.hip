@@ -40,6 +40,7 @@ int msm_affine_dev(const void* d_scalars, const void* d_bases, const void* d_inf
 int decode_dev(const uint8_t* d_enc, size_t n, Aff* d_out, uint8_t* d_inf, hipStream_t st);
 int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out, hipStream_t st);
 int encode_point_dev(const Aff* d_pt, const uint32_t* d_inf32, uint8_t* d_out, hipStream_t st);
+int points_check_strict(const void* d_xy, const void* d_inf, size_t n, hipStream_t st);  // codec.hip: a no-op unless strict mode is on
 int batch_inverse_dev(Fr* d, size_t n, hipStream_t st);
 int b3_leaves_dev(const uint8_t* d_data, size_t len, uint64_t chunk_base, uint32_t* d_cvs, hipStream_t st);  // blake3_tree.hip
 int b3_single_chunk_dev(const uint8_t* d_data, size_t len, uint32_t* d_out32, hipStream_t st);
@@ -696,6 +697,17 @@ static int srs_slot(dvp_prover* p, int which, Aff** base, uint8_t** inf, size_t*
   }
   return DVP_EINVAL;
 }
+// strict mode (dvp_points_set_strict; a no-op otherwise): the vector just copied into the prover must hold reduced points of E[r].  The
+// slot has been overwritten by then, so a rejected vector leaves it UNSET and its tables stale -- a later proof fails as for a vector
+// that was never given (prover_ready), not on the rejected or the previous bases.  Waits on the default stream, as the setters do anyway.
+static int srs_strict_check(dvp_prover* p, int which, const Aff* base, const uint8_t* inf, size_t n) {
+  int rc = points_check_strict(base, inf, n, nullptr);
+  if (rc != DVP_OK) {
+    p->have_srs[which] = false;
+    srs_changed(p, which < 2 ? 0 : 1);
+  }
+  return rc;
+}
 extern "C" int dvp_prover_set_srs_encoded(dvp_prover* p, int which, const uint8_t* enc, size_t n) {
   if (!p || !enc) return DVP_EINVAL;
   Aff* base; uint8_t* inf; size_t want;
@@ -720,6 +732,7 @@ extern "C" int dvp_prover_set_srs_affine(dvp_prover* p, int which, const uint64_
   DVP_HIP(hipMemcpy(base, xy, n * sizeof(Aff), hipMemcpyHostToDevice));
   if (inf_in) DVP_HIP(hipMemcpy(inf, inf_in, n, hipMemcpyHostToDevice));
   else DVP_HIP(hipMemset(inf, 0, n));
+  DVP_TRY(srs_strict_check(p, which, base, inf, n));
   p->have_srs[which] = true;
   srs_changed(p, which < 2 ? 0 : 1);
   // the copies / fills above ran on the default stream; proofs run on other (non-blocking) streams, which do not order themselves
@@ -736,6 +749,7 @@ extern "C" int dvp_prover_set_srs_affine_dev(dvp_prover* p, int which, const voi
   DVP_HIP(hipMemcpy(base, d_xy, n * sizeof(Aff), hipMemcpyDeviceToDevice));
   if (d_inf) DVP_HIP(hipMemcpy(inf, d_inf, n, hipMemcpyDeviceToDevice));
   else DVP_HIP(hipMemset(inf, 0, n));
+  DVP_TRY(srs_strict_check(p, which, base, inf, n));
   p->have_srs[which] = true;
   srs_changed(p, which < 2 ? 0 : 1);
   // the copies / fills above ran on the default stream; proofs run on other (non-blocking) streams, which do not order themselves

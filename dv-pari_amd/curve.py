@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._native import lib, check, ptr
+from ._native import lib, check, ptr, EPOINT
 
 FR_MODULUS = 3450873173395281893717377931138512760570940988862252126328087024741343
 
@@ -76,8 +76,48 @@ def from_bytes(enc: np.ndarray):
     return xy, inf
 
 
+# classes of dvp_points_check (include/dvpari.h: DVP_POINT_*); 0 = a reduced point of E[r]
+POINT_UNREDUCED, POINT_OFF_CURVE, POINT_ORDER4, POINT_COSET_N = 0x01, 0x02, 0x04, 0x08
+
+
+def check_points(points_xy: np.ndarray, points_inf: np.ndarray = None):
+    """dvp_points_check: (classes uint8 [n], index of the first bad point or None).  Does not raise for bad points: a point whose
+    infinity flag is set is class 0 whatever its coordinates hold.  COSET_N is P + N with P in E[r], N = (0,1): the affine view
+    xs233 itself holds of a group element; this library takes the E[r] representative P (or the 30-byte encoding)."""
+    b = np.ascontiguousarray(points_xy, dtype=np.uint64).reshape(-1, 8)
+    n = b.shape[0]
+    inf_p = None
+    if points_inf is not None:
+        pi = np.ascontiguousarray(points_inf, dtype=np.uint8)
+        assert pi.shape == (n,)
+        inf_p = ptr(pi)
+    classes = np.zeros(n, dtype=np.uint8)
+    n_bad = C.c_size_t(0)
+    rc = lib.dvp_points_check(ptr(b), inf_p, n, ptr(classes), C.byref(n_bad))
+    if rc == EPOINT:
+        return classes, int(lib.dvp_last_error_index())
+    check(rc, "dvp_points_check")
+    return classes, None
+
+
+def check_points_dev(d_xy: int, d_inf: int, n: int, d_classes: int, d_summary: int, stream: int = 0):
+    """dvp_points_check_dev: enqueue only; d_summary (16 bytes) = {u64 first bad index or ~0, u64 bad points}, reset by the call"""
+    check(lib.dvp_points_check_dev(d_xy, d_inf, n, d_classes, d_summary, stream), "dvp_points_check_dev")
+
+
+def set_strict_points(on: bool):
+    """dvp_points_set_strict: process-wide; when on, the entries that take affine points from the host (multi_scalar_mul,
+    FixedBaseMsm, Prover.set_srs, add, to_bytes) check them first and raise DvpError(DVP_EPOINT) with .index = the first bad point"""
+    check(lib.dvp_points_set_strict(int(bool(on))), "dvp_points_set_strict")
+
+
+def strict_points() -> bool:
+    return bool(lib.dvp_points_get_strict())
+
+
 def add(a_xy, b_xy, a_inf=None, b_inf=None):
-    """CurvePoint::add over two vectors, src/curve.rs:84-90.  Returns (xy [n,8], inf [n])."""
+    """CurvePoint::add over two vectors, src/curve.rs:84-90.  Returns (xy [n,8], inf [n]).  In strict mode operand a is checked
+    first, then b: DvpError.index is the first bad point of a, and of b only when a is clean."""
     a = np.ascontiguousarray(a_xy, dtype=np.uint64).reshape(-1, 8)
     b = np.ascontiguousarray(b_xy, dtype=np.uint64).reshape(-1, 8)
     n = a.shape[0]

@@ -44,7 +44,8 @@ typedef enum dvp_status {
   DVP_ENOMEM = -7,  /* the HIP runtime refused an allocation (hipErrorOutOfMemory, and only that): retry with a smaller plan --
                      * dvp_prover_set_table_budget, fewer provers per device.  A prover does not return it for its tables (it proves
                      * without them), only when the working set of a proof itself does not fit */
-  DVP_ECHALLENGE = -8 /* Fiat-Shamir challenge fell inside D u D' (assert!, src/proving.rs:548-556) */
+  DVP_ECHALLENGE = -8, /* Fiat-Shamir challenge fell inside D u D' (assert!, src/proving.rs:548-556) */
+  DVP_EPOINT = -9      /* an affine point is unreduced, off the curve or outside E[r]; dvp_last_error_index() = the first such point */
 } dvp_status;
 
 const char* dvp_strerror(int status);
@@ -60,7 +61,7 @@ int dvp_set_device(int device_id);
  * extends, pointwise maps; < 15 % of a proof) stay on the home device.  An id may repeat (a one-GPU box can exercise
  * the path).  n <= 1 restores single-device proving.  Proof bytes are identical for every device list. */
 int dvp_set_devices(const int* device_ids, int n);
-/* last failing index for DVP_EDECODE / DVP_EUNSAT / DVP_EINVAL (thread-local), or -1 */
+/* last failing index for DVP_EDECODE / DVP_EUNSAT / DVP_EINVAL / DVP_EPOINT (thread-local), or -1 */
 int64_t dvp_last_error_index(void);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -171,6 +172,41 @@ int dvp_codec_get_rule(void);
  * CurvePoints (src/curve.rs:69-76) is equality of (x, y, infinity) on this representation. */
 int dvp_points_add(const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, size_t n, uint64_t* out_xy,
                    uint8_t* out_inf);
+
+/* Affine points checked on the device.  The kernels behind the affine entries assume points of E[r] (the prime-order subgroup) with
+ * reduced coordinates; the 30-byte path can only produce such points (dvp_points_decode), the affine path takes what it is given.
+ * Every point i with inf[i] == 0 (inf == NULL: every point) gets exactly one class; a point with inf[i] != 0 is class 0 whatever its
+ * coordinates hold.
+ *   0                    reduced, on y^2 + xy = x^3 + 1, in E[r]
+ *   DVP_POINT_UNREDUCED  a bit in 233 .. 255 of x or y is set
+ *   DVP_POINT_OFF_CURVE  reduced, but the curve equation fails ((0,0) and (0, y != 1) included)
+ *   DVP_POINT_ORDER4     on the curve, x != 0, Tr(x) = 1: not even in 2E
+ *   DVP_POINT_COSET_N    on the curve and P + N in E[r], N = (0,1) (N itself included): xsk233's OWN affine view of a group element
+ *                        (xsk233 = { P + N : P in E[r] }); this library takes the E[r] representative P or the 30-byte encoding
+ * dvp_points_check: DVP_OK when every point is class 0, else DVP_EPOINT with dvp_last_error_index() = the first bad point; classes
+ * (optional, n bytes) and *n_bad (optional) are filled either way.  n = 0: DVP_OK, nothing is touched.
+ * dvp_points_check_dev: enqueues on `stream` and returns DVP_OK; the verdict is d_summary = { u64 first bad index or ~0, u64 number
+ * of bad points }, which the call itself resets (it need not be initialised); d_inf and d_classes may be NULL.
+ *
+ * Strict mode (process-wide like dvp_codec_set_rule; initial value DVP_POINTS_STRICT from the environment, default 0 = off): when on,
+ * the entries that copy affine points from the caller -- dvp_msm_affine, dvp_msm_ctx_create, dvp_prover_set_srs_affine,
+ * dvp_prover_set_srs_affine_dev, dvp_points_add, dvp_points_encode -- run the check on their device copy before anything else uses
+ * it and return DVP_EPOINT with the index of the first bad point.  dvp_points_add checks operand a, then operand b: the index is that
+ * of the first bad point of a, and only when a is clean that of the first bad point of b (both count from 0).  After a failure
+ * dvp_msm_ctx_create has freed what it allocated and not written *out, and the SRS setters leave vector `which` UNSET: a later proof
+ * fails as it does for a vector that was never given, never on stale or rejected bases.
+ * NEVER checked, strict or not: the `_dev` run entries dvp_msm_affine_dev, dvp_msm_ctx_run_dev, dvp_points_sum_dev and the prover's own
+ * buffers -- they must not wait on the host; a caller who wants a check there enqueues dvp_points_check_dev itself. */
+#define DVP_POINT_UNREDUCED 0x01u
+#define DVP_POINT_OFF_CURVE 0x02u
+#define DVP_POINT_ORDER4 0x04u
+#define DVP_POINT_COSET_N 0x08u
+int dvp_points_check(const uint64_t* xy, const uint8_t* inf /* may be NULL */, size_t n, uint8_t* classes /* optional, n bytes */,
+                     size_t* n_bad /* optional */);
+int dvp_points_check_dev(const void* d_xy, const void* d_inf, size_t n, void* d_classes /* optional */,
+                         void* d_summary /* 16 bytes, written by the call */, void* stream);
+int dvp_points_set_strict(int on);
+int dvp_points_get_strict(void);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Prover -- Proof::prove(cache_dir, public_inputs, private_inputs), src/proving.rs:426-688,      */

@@ -43,6 +43,11 @@ int dvp_ubench_gf_mul(int reps, double* products_per_s);
  * independent chains, as the twisted butterflies issue them), whole chip: the ceiling of bench.py's work model for extend / enter /
  * exit (BASELINE configs #3 and #4) */
 int dvp_ubench_fr_mul(int reps, double* muladds_per_s);
+/* k_points_check against k_decode on the same count in one run (tools/points_check.py): device events around each kernel alone, one
+ * warm-up launch and then the median of `reps` (odd, 1 .. 99).  d_xy / d_inf: n affine points; d_enc: n x 30 B encodings; d_scratch:
+ * n x 65 bytes the decode kernel writes its points and flags into.  Waits for the result. */
+int dvp_ubench_points_check(const void* d_xy, const void* d_inf, const void* d_enc, size_t n, void* d_scratch, int reps,
+                            double* check_ms, double* decode_ms);
 /* Wave-level trace of the batched-affine pair rounds (dvp::k_affine_round, tools/wave_trace.py).  d_buf = device buffer of
  * 64 + 64 * n_records bytes zeroed by the caller, NULL = off.  While set, every pair round appends one 64-byte record per
  * wave (8 u64: s_memrealtime at wave start / after pass 1 / after the shared inversion / at the end; s_memtime at start / end;
