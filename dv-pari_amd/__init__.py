@@ -4,6 +4,7 @@ dv-pari_amd -- host-side mirror of the DV-Pari prover hot path over the MI355X-n
 
 The module names follow the reference (alpenlabs/dv-pari):
     curve.multi_scalar_mul / point_scalar_mul_gen      <- src/curve.rs:129-158
+    curve.point_scalar_mul (a vector of k_i P_i)      <- src/curve.rs:113-126
     ec_fft.FFTree(.extend/.enter/.exit)                 <- ecfft crate as used by src/ec_fft.rs, src/proving.rs:410-422
 There is no CPU fallback: importing the native library fails loudly when it is missing.
 

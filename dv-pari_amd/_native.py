@@ -87,11 +87,16 @@ _SIGS = {
     "dvp_codec_set_rule": (C.c_int, [C.c_int]),
     "dvp_codec_get_rule": (C.c_int, []),
     "dvp_points_add": (C.c_int, [u64p, u8p, u64p, u8p, sz, u64p, u8p]),
+    "dvp_points_mul": (C.c_int, [u64p, sz, u64p, u8p, sz, u64p, u8p]),
+    "dvp_points_mul_dev": (C.c_int, [vp, sz, vp, vp, sz, vp, vp, vp, vp]),
+    "dvp_points_mul_xsk233": (C.c_int, [u8p, sz, u8p, sz, u8p]),
+    "dvp_debug_recode_tnaf": (C.c_int, [vp, sz, C.c_int, vp, C.POINTER(C.c_int), vp]),
     "dvp_points_check": (C.c_int, [u64p, u8p, sz, u8p, C.POINTER(C.c_size_t)]),
     "dvp_points_check_dev": (C.c_int, [vp, vp, sz, vp, vp, vp]),
     "dvp_points_set_strict": (C.c_int, [C.c_int]),
     "dvp_points_get_strict": (C.c_int, []),
     "dvp_ubench_points_check": (C.c_int, [vp, vp, vp, sz, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "dvp_ubench_points_mul": (C.c_int, [vp, vp, sz, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dvp_prover_create": (C.c_int, [u32, u32, u32, C.POINTER(vp)]),
     "dvp_prover_destroy": (None, [vp]),
     "dvp_prover_set_coeffs": (C.c_int, [vp, u64p, u32]),

@@ -514,6 +514,52 @@ extern "C" int dvp_ubench_points_check(const void* d_xy, const void* d_inf, cons
   return DVP_OK;
 }
 
+// dvp_points_mul_dev (its two 8-byte fills and k_points_mul at the width in force) and k_mulgen alone on the same scalars and count, device
+// events, median of `reps` after one warm-up each (tools/points_mul.py)
+namespace dvp {
+int points_mul_dev(const void* d_scalars, size_t n_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf,
+                   void* d_summary, hipStream_t st);
+}
+extern "C" int dvp_ubench_points_mul(const void* d_scalars, const void* d_xy, size_t n, void* d_scratch, int reps, double* mul_ms, double* mulgen_ms) {
+  if (!d_scalars || !d_xy || !d_scratch || !n || reps < 1 || reps > 99 || !(reps & 1) || !mul_ms || !mulgen_ms) return DVP_EINVAL;
+  GfSqrTables T;
+  DVP_TRY(gf_sqr_tables(&T, 0));
+  const Aff* tab;
+  DVP_TRY(gen_table(&tab, 0));
+  DevBuf sum;
+  DVP_TRY(sum.alloc(16));
+  DVP_HIP(hipMemset(sum.p, 0xff, 16));
+  hipEvent_t e0, e1;
+  DVP_HIP(hipEventCreate(&e0));
+  DVP_HIP(hipEventCreate(&e1));
+  float t[2][99];
+  hipError_t err = hipSuccess;
+  int rc = DVP_OK;
+  for (int k = 0; k < 2 && err == hipSuccess && rc == DVP_OK; ++k)
+    for (int r = -1; r < reps && err == hipSuccess && rc == DVP_OK; ++r) {
+      (void)hipEventRecord(e0, 0);
+      if (k == 0)
+        rc = points_mul_dev(d_scalars, n, d_xy, nullptr, n, d_scratch, (uint8_t*)d_scratch + n * 64, sum.p, 0);
+      else
+        hipLaunchKernelGGL(k_mulgen, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint32_t*)d_scalars, n, tab, T, (Aff*)d_scratch,
+                           (uint8_t*)d_scratch + n * 64, sum.as<unsigned long long>());
+      err = hipGetLastError();
+      (void)hipEventRecord(e1, 0);
+      if (err == hipSuccess) err = hipEventSynchronize(e1);
+      float ms = 0;
+      if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+      if (r >= 0) t[k][r] = ms;
+    }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc != DVP_OK) return rc;
+  if (err != hipSuccess) return hip_fail(err, "dvp_ubench_points_mul", __FILE__, __LINE__);
+  for (int k = 0; k < 2; ++k) std::sort(t[k], t[k] + reps);
+  *mul_ms = t[0][reps / 2];
+  *mulgen_ms = t[1][reps / 2];
+  return DVP_OK;
+}
+
 // scalars: n x 32 B canonical LE; bases: n x 30 B xsk233 encodings; out: 30 B encoding of the sum
 extern "C" int dvp_msm_xsk233(const uint8_t* scalars, const uint8_t* bases_enc, size_t n, uint8_t out_enc[30]) {
   if ((n && (!scalars || !bases_enc)) || !out_enc) return DVP_EINVAL;

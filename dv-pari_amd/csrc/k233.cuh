@@ -280,6 +280,80 @@ GF_DEV bool ld_add_nodbl(Ld& p, const Ld& q, const LT& L) {
   return true;
 }
 
+// acc += q (q affine, finite), complete and without branches: the Lopez-Dahab mixed addition, whose Z3 = (Z1 B)^2 is already 0
+// (the neutral element) for acc = -q; acc = q selects 2q instead (from q alone, Z = 1: 1M + 3S), acc = O selects q.  Branches here
+// (ld_madd_ip's inlined doubling) put the accumulator in scratch: k_mulgen keeps 272 B per lane.
+template <class LT>
+__device__ __forceinline__ void madd_complete(Ld& acc, const Aff& q, const LT& L) {
+  const bool acc_inf = gf_is_zero(acc.Z);
+  const Gf A = gf_add(acc.Y, gf_mul(q.y, gf_sqr(acc.Z), L));
+  const Gf B = gf_add(acc.X, gf_mul(q.x, acc.Z, L));
+  const bool dbl = !acc_inf && gf_is_zero(B) && gf_is_zero(A);
+  const Gf C = gf_mul(B, acc.Z, L);
+  Gf D, E;
+  gf_mul2(gf_sqr(B), A, C, L, D, E);
+  const Gf Z3 = gf_sqr(C);
+  const Gf X3 = gf_add(gf_add(gf_sqr(A), D), E);
+  const Gf F = gf_add(X3, gf_mul(q.x, Z3, L));
+  const Gf G = gf_mul(gf_add(q.x, q.y), gf_sqr(Z3), L);
+  const Gf Y3 = gf_add(gf_mul(gf_add(E, Z3), F, L), G);
+  // 2q: Z = x^2, X = x^4 + 1, Y = Z + X (y^2 + 1)   (ld_dbl with Z1 = 1)
+  const Gf dZ = gf_sqr(q.x);
+  const Gf dX = gf_add(gf_sqr(dZ), gf_one());
+  const Gf dY = gf_add(dZ, gf_mul(dX, gf_add(gf_sqr(q.y), gf_one()), L));
+  acc.X = gf_select(acc_inf, q.x, gf_select(dbl, dX, X3));
+  acc.Y = gf_select(acc_inf, q.y, gf_select(dbl, dY, Y3));
+  acc.Z = gf_select(acc_inf, gf_one(), gf_select(dbl, dZ, Z3));
+}
+
+// p + q for a FINITE p and a finite affine q with p != +-q, no test at all: ld_madd_fast for a caller who knows
+template <class LT>
+GF_DEV void ld_madd_distinct(Ld& p, const Aff& q, const LT& L) {
+  const Gf A = gf_add(p.Y, gf_mul(q.y, gf_sqr(p.Z), L));
+  const Gf B = gf_add(p.X, gf_mul(q.x, p.Z, L));
+  const Gf C = gf_mul(B, p.Z, L);
+  Gf D, E;
+  gf_mul2(gf_sqr(B), A, C, L, D, E);
+  const Gf Z3 = gf_sqr(C);
+  const Gf X3 = gf_add(gf_add(gf_sqr(A), D), E);
+  const Gf F = gf_add(X3, gf_mul(q.x, Z3, L));
+  const Gf G = gf_mul(gf_add(q.x, q.y), gf_sqr(Z3), L);
+  p.Y = gf_add(gf_mul(gf_add(E, Z3), F, L), G);
+  p.X = X3;
+  p.Z = Z3;
+}
+// p + q, both projective, for FINITE p and q with p != +-q: the body of ld_add_nodbl without its branches (the table build of
+// k_points_mul, where the operands are known to differ).  Outside that precondition the result is some triple, never a fault.
+template <class LT>
+GF_DEV void ld_add_distinct(Ld& p, const Ld& q, const LT& L) {
+  Gf A1 = gf_mul(q.Y, gf_sqr(p.Z), L);
+  Gf A2 = gf_mul(p.Y, gf_sqr(q.Z), L);
+  Gf B1, E;
+  gf_mul2(q.X, q.Z, p.Z, L, B1, E);
+  Gf B2 = gf_mul(p.X, q.Z, L);
+  Gf C = gf_add(A1, A2);
+  Gf D = gf_add(B1, B2);
+  Gf Ds = gf_sqr(D);
+  Gf DB, DA;
+  gf_mul2(B1, A1, Ds, L, DB, DA);
+  Gf F, I;
+  gf_mul2(D, DB, E, L, F, I);
+  Gf G, H;
+  gf_mul2(Ds, C, F, L, G, H);
+  Gf Z3 = gf_sqr(F);
+  Gf X3 = gf_add(gf_add(gf_sqr(C), H), G);
+  I = gf_add(I, X3);
+  Gf J = gf_add(DA, X3);
+  p.Y = gf_add(gf_mul(I, H, L), gf_mul(J, Z3, L));
+  p.X = X3;
+  p.Z = Z3;
+}
+// -(X, Y, Z) = (X, Y + X Z, Z)
+template <class LT>
+GF_DEV void ld_neg_ip(Ld& p, const LT& L) {
+  p.Y = gf_add(p.Y, gf_mul(p.X, p.Z, L));
+}
+
 // ---- lambda-projective coordinates (Oliveira, Lopez, Aranha, Rodriguez-Henriquez 2013): (X, L, Z) with x = X / Z and
 // lambda = x + y / x = L / Z, kept in an Ld whose Y field holds L; Z == 0 is the point at infinity.  Full addition 11M + 2S against
 // Lopez-Dahab's 13M + 5S, doubling 4M + 4S against 3M + 5S: what the merge tree runs on (2^(c+1) full additions per MSM, no

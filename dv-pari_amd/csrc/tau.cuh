@@ -216,4 +216,168 @@ __device__ __forceinline__ uint32_t tau_step16(uint32_t* r0, uint32_t* r1) {
   return dw;
 }
 
+// ---- width-w tau-NAF (Solinas 2000, section 5.3/6, for mu = -1) of a partially reduced scalar: points_mul.hip ----------------------------
+// rho = sum_j s_j alpha_(u_j) tau^j with s_j in {+1, -1}, u_j odd < 2^(w-1), at most one non-zero digit among any w consecutive
+// positions.  alpha_u = beta_u + gamma_u tau = u mods tau^w: the element of least norm in u + tau^w Z[tau].  One step: rho odd (r0 odd)
+// -> u = (r0 + r1 t_w) mods 2^w, where t_w is the integer with tau = t_w (mod tau^w) (the EVEN root of t^2 + t + 2 mod 2^w: tau is
+// no unit modulo tau^w), rho <- rho - sign(u) alpha_|u|, which tau^w divides; then rho <- rho / tau (tau_step on an even r0).
+// Nothing here is typed in: t_w, alpha_u and the tail length below are derived from tau^2 = -tau - 2 at compile time.
+struct ZTau {
+  int a, b;  // a + b tau
+};
+constexpr ZTau ztau_mul(ZTau x, ZTau y) { return ZTau{x.a * y.a - 2 * x.b * y.b, x.a * y.b + x.b * y.a - x.b * y.b}; }
+constexpr int ztau_norm(ZTau x) { return x.a * x.a - x.a * x.b + 2 * x.b * x.b; }
+constexpr ZTau ztau_pow_tau(int w) {
+  ZTau x{1, 0};
+  for (int i = 0; i < w; ++i) x = ztau_mul(x, ZTau{0, 1});
+  return x;
+}
+constexpr int tnaf_tw(int w) {
+  for (int t = 0; t < (1 << w); t += 2)
+    if (((t * t + t + 2) & ((1 << w) - 1)) == 0) return t;
+  return -1;
+}
+constexpr int tnaf_iabs(int v) { return v < 0 ? -v : v; }
+constexpr int TNAF_MAX_ENTRIES = 8;  // w <= 5
+struct TnafTable {
+  int w, tw, entries;  // entries = 2^(w-2): entry e holds alpha_(2e+1)
+  int beta[TNAF_MAX_ENTRIES], gamma[TNAF_MAX_ENTRIES];
+  int max_norm;
+};
+// least norm over u - q tau^w, q in a box that holds the nearest lattice points; ties go to the smallest (|beta|, |gamma|, beta, gamma)
+constexpr TnafTable tnaf_make(int w) {
+  TnafTable t{};
+  t.w = w;
+  t.tw = tnaf_tw(w);
+  t.entries = 1 << (w - 2);
+  t.max_norm = 0;
+  const ZTau tp = ztau_pow_tau(w);
+  for (int e = 0; e < t.entries; ++e) {
+    const int u = 2 * e + 1;
+    bool have = false;
+    int bn = 0, bb = 0, bg = 0;
+    for (int q0 = -4; q0 <= 4; ++q0)
+      for (int q1 = -4; q1 <= 4; ++q1) {
+        const ZTau m = ztau_mul(ZTau{q0, q1}, tp);
+        const ZTau c{u - m.a, -m.b};
+        const int n = ztau_norm(c);
+        bool better = !have || n < bn;
+        if (have && n == bn) {
+          const int k0[4] = {tnaf_iabs(c.a), tnaf_iabs(c.b), c.a, c.b}, k1[4] = {tnaf_iabs(bb), tnaf_iabs(bg), bb, bg};
+          for (int i = 0; i < 4; ++i) {
+            if (k0[i] != k1[i]) {
+              better = k0[i] < k1[i];
+              break;
+            }
+          }
+        }
+        if (better) {
+          have = true;
+          bn = n;
+          bb = c.a;
+          bg = c.b;
+        }
+      }
+    t.beta[e] = bb;
+    t.gamma[e] = bg;
+    if (bn > t.max_norm) t.max_norm = bn;
+  }
+  return t;
+}
+// digits of the expansion of one small element (0 = the recoding did not end within `cap` steps)
+constexpr int tnaf_small_len(const TnafTable& t, ZTau rho, int cap) {
+  int n = 0;
+  while (rho.a != 0 || rho.b != 0) {
+    if (n == cap) return 0;
+    if (rho.a & 1) {
+      int u = (rho.a + rho.b * t.tw) & ((1 << t.w) - 1);
+      if (u >= (1 << (t.w - 1))) u -= 1 << t.w;
+      const int s = u > 0 ? 1 : -1, e = (tnaf_iabs(u) - 1) / 2;
+      rho.a -= s * t.beta[e];
+      rho.b -= s * t.gamma[e];
+    }
+    const int h = rho.a / 2;  // exact: rho.a is even here
+    rho = ZTau{rho.b - h, -h};
+    ++n;
+  }
+  return n;
+}
+// the longest expansion among the elements of norm <= nb (-1 = one of them does not end): N(a + b tau) >= 7 a^2 / 8 and >= 7 b^2 / 4,
+// so |a|, |b| <= 16 covers every norm up to 224
+constexpr int tnaf_tail_len(const TnafTable& t, int nb) {
+  int mx = 0;
+  for (int a = -16; a <= 16; ++a)
+    for (int b = -16; b <= 16; ++b) {
+      if (ztau_norm(ZTau{a, b}) > nb) continue;
+      if (a == 0 && b == 0) continue;
+      const int n = tnaf_small_len(t, ZTau{a, b}, 64);
+      if (n == 0) return -1;
+      if (n > mx) mx = n;
+    }
+  return mx;
+}
+// TnafDigits<W>::value is a PROVEN bound on the number of digit positions, in the style of TAU_DIGITS above:
+//   |rho_0| < 2^115.51 (the partial reduction: see TAU_DIGITS).  One step maps rho to (rho - d) / tau with d = 0 or +-alpha_u, so with
+//   A = sqrt(max_u N(alpha_u)) (max norm 2, 8, 16 for w = 3, 4, 5):  |rho_(k+1)| <= (|rho_k| + A) / sqrt 2, hence
+//   |rho_k| < |rho_0| 2^(-k/2) + A / (sqrt 2 - 1).  After k = 233 steps |rho_233| < 2^(-0.99) + 2.41422 A, i.e.
+//   N(rho_233) <= NB = (0.5035 + 2.41422 A)^2: 15, 53, 103 for w = 3, 4, 5 (tnaf_norm_bound rounds UP, to 16, 54, 104).
+//   Every element of norm <= NB has an expansion of at most TAIL = 6, 8, 9 digits: exhaustive enumeration at compile time
+//   (tnaf_tail_len, which also shows that each of them ends).  Total <= 233 + TAIL = 239, 241, 242; observed maximum 234.
+// The non-zero digits are at least w positions apart (tau^w divides rho after a subtraction), so there are at most
+// ceil(value / w) of them: TnafDigits<W>::max_nonzero.
+constexpr int tnaf_norm_bound(int max_norm) {
+  // ceil((0.5035 + 2.41422 sqrt(max_norm))^2) + 1 with sqrt rounded up by Newton's iteration from above
+  double s = max_norm > 1 ? (double)max_norm : 1.0;
+  for (int i = 0; i < 60; ++i) s = 0.5 * (s + (double)max_norm / s);
+  s *= 1.0 + 1e-12;
+  const double b = 0.5035 + 2.41422 * s;
+  return (int)(b * b) + 1;
+}
+template <int W>
+struct TnafDigits {
+  static_assert(W >= 3 && W <= 5, "window width");
+  static constexpr TnafTable table = tnaf_make(W);
+  static constexpr int tail = tnaf_tail_len(table, tnaf_norm_bound(table.max_norm));
+  static_assert(tail > 0, "an element of small norm whose tau-NAF does not end");
+  static constexpr int value = 233 + tail;
+  static constexpr int max_nonzero = (value + W - 1) / W;
+};
+static_assert(TnafDigits<3>::value == 239 && TnafDigits<4>::value == 241 && TnafDigits<5>::value == 242, "the bound the comment states");
+
+// one position of the width-W tau-NAF of rho = r0 + r1 tau (160-bit two's complement, as tau_partial_reduce leaves them): returns the
+// signed digit (0, or +-u with u odd < 2^(W-1)) and replaces rho by (rho - digit's alpha) / tau.  Branch-free.
+template <int W>
+__device__ __forceinline__ int tnaf_step(uint32_t* r0, uint32_t* r1) {
+  constexpr TnafTable t = TnafDigits<W>::table;
+  const uint32_t odd = r0[0] & 1u;
+  const uint32_t uu = (r0[0] + r1[0] * (uint32_t)t.tw) & ((1u << W) - 1);
+  const int su = ((int)uu - (int)((uu >> (W - 1)) << W)) * (int)odd;  // mods 2^W; 0 for an even rho
+  const int au = su < 0 ? -su : su;
+  int b = 0, g = 0;
+#pragma unroll
+  for (int e = 0; e < t.entries; ++e) {
+    if (au == 2 * e + 1) {
+      b = t.beta[e];
+      g = t.gamma[e];
+    }
+  }
+  if (su < 0) {
+    b = -b;
+    g = -g;
+  }
+  // rho -= (b + g tau): small signed integers into the five limbs
+  int64_t c0 = -(int64_t)b, c1 = -(int64_t)g;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    c0 += (int64_t)(uint64_t)r0[k];
+    r0[k] = (uint32_t)c0;
+    c0 >>= 32;
+    c1 += (int64_t)(uint64_t)r1[k];
+    r1[k] = (uint32_t)c1;
+    c1 >>= 32;
+  }
+  (void)tau_step(r0, r1);  // r0 is even now: the division alone
+  return su;
+}
+
 }  // namespace dvp

@@ -161,32 +161,6 @@ __device__ __forceinline__ void pub_digest(const uint8_t* pub, uint32_t npub, ui
   for (int i = 0; i < 8; ++i) out[i] = cv[i];
 }
 
-// acc += q (q affine, finite), complete and without branches: the Lopez-Dahab mixed addition, whose Z3 = (Z1 B)^2 is already 0
-// (the neutral element) for acc = -q; acc = q selects 2q instead (from q alone, Z = 1: 1M + 3S), acc = O selects q.  Branches here
-// (ld_madd_ip's inlined doubling) put the accumulator in scratch: k_mulgen keeps 272 B per lane.
-template <class LT>
-__device__ __forceinline__ void madd_complete(Ld& acc, const Aff& q, const LT& L) {
-  const bool acc_inf = gf_is_zero(acc.Z);
-  const Gf A = gf_add(acc.Y, gf_mul(q.y, gf_sqr(acc.Z), L));
-  const Gf B = gf_add(acc.X, gf_mul(q.x, acc.Z, L));
-  const bool dbl = !acc_inf && gf_is_zero(B) && gf_is_zero(A);
-  const Gf C = gf_mul(B, acc.Z, L);
-  Gf D, E;
-  gf_mul2(gf_sqr(B), A, C, L, D, E);
-  const Gf Z3 = gf_sqr(C);
-  const Gf X3 = gf_add(gf_add(gf_sqr(A), D), E);
-  const Gf F = gf_add(X3, gf_mul(q.x, Z3, L));
-  const Gf G = gf_mul(gf_add(q.x, q.y), gf_sqr(Z3), L);
-  const Gf Y3 = gf_add(gf_mul(gf_add(E, Z3), F, L), G);
-  // 2q: Z = x^2, X = x^4 + 1, Y = Z + X (y^2 + 1)   (ld_dbl with Z1 = 1)
-  const Gf dZ = gf_sqr(q.x);
-  const Gf dX = gf_add(gf_sqr(dZ), gf_one());
-  const Gf dY = gf_add(dZ, gf_mul(dX, gf_add(gf_sqr(q.y), gf_one()), L));
-  acc.X = gf_select(acc_inf, q.x, gf_select(dbl, dX, X3));
-  acc.Y = gf_select(acc_inf, q.y, gf_select(dbl, dY, Y3));
-  acc.Z = gf_select(acc_inf, gf_one(), gf_select(dbl, dZ, Z3));
-}
-
 // The front half of SRS::verify for one proof (k_verify_rlc_prep): decode P and K, the FrBits range checks of a0 and b0, canonical
 // public inputs, then (only for a well-formed proof) the transcript alpha and the scalars u0, v0.  The DVP_VERIFY_* validity bits
 // are k_verify's; f.h_pi is H(public inputs), which the random-linear-combination coefficient binds as well.  This is a

@@ -33,6 +33,40 @@ def multi_scalar_mul_dev(d_scalars: int, d_bases: int, d_inf: int, n: int, d_out
     check(lib.dvp_msm_affine_dev(d_scalars, d_bases, d_inf, n, d_out_xy, d_out_inf, stream), "dvp_msm_affine_dev")
 
 
+def point_scalar_mul(scalars: np.ndarray, points_xy: np.ndarray, points_inf: np.ndarray = None):
+    """point_scalar_mul over a vector, src/curve.rs:113-126: k_i P_i for n independent pairs in one launch.  scalars [n, 4], or
+    [1, 4] / [4] = one scalar for every point.  Returns (xy [n,8], inf [n]); raises DvpError(DVP_EINVAL) with .index = the first
+    non-canonical scalar, and in strict mode DvpError(DVP_EPOINT) for a bad point (points are checked before scalars)."""
+    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    b = np.ascontiguousarray(points_xy, dtype=np.uint64).reshape(-1, 8)
+    n = b.shape[0]
+    inf_p = None
+    if points_inf is not None:
+        pi = np.ascontiguousarray(points_inf, dtype=np.uint8)
+        assert pi.shape == (n,)
+        inf_p = ptr(pi)
+    xy = np.zeros((n, 8), dtype=np.uint64)
+    inf = np.zeros(n, dtype=np.uint8)
+    check(lib.dvp_points_mul(ptr(s), s.shape[0], ptr(b), inf_p, n, ptr(xy), ptr(inf)), "dvp_points_mul")
+    return xy, inf
+
+
+def point_scalar_mul_dev(d_scalars: int, n_scalars: int, d_xy: int, d_inf: int, n: int, d_out_xy: int, d_out_inf: int, d_summary: int,
+                         stream: int = 0):
+    """dvp_points_mul_dev: enqueue only; d_out_xy may be d_xy, d_inf may be 0; d_summary (16 bytes) = {u64 first non-canonical scalar
+    or ~0, u64 how many}, reset by the call.  Such a lane gives O."""
+    check(lib.dvp_points_mul_dev(d_scalars, n_scalars, d_xy, d_inf or None, n, d_out_xy, d_out_inf, d_summary, stream), "dvp_points_mul_dev")
+
+
+def point_scalar_mul_bytes(scalars32: np.ndarray, enc30: np.ndarray) -> np.ndarray:
+    """the same on the reference's wire formats: scalars [n, 32] (or one) little-endian bytes, points [n, 30] -> [n, 30]"""
+    s = np.ascontiguousarray(scalars32, dtype=np.uint8).reshape(-1, 32)
+    e = np.ascontiguousarray(enc30, dtype=np.uint8).reshape(-1, 30)
+    out = np.zeros((e.shape[0], 30), dtype=np.uint8)
+    check(lib.dvp_points_mul_xsk233(ptr(s), s.shape[0], ptr(e), e.shape[0], ptr(out)), "dvp_points_mul_xsk233")
+    return out
+
+
 def point_scalar_mul_gen_batch(scalars: np.ndarray):
     """point_scalar_mul_gen over a vector (src/curve.rs:129-137, loops at src/srs.rs:130-160).
     Returns (xy [n,8], inf [n])."""

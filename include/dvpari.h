@@ -173,6 +173,23 @@ int dvp_codec_get_rule(void);
 int dvp_points_add(const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, size_t n, uint64_t* out_xy,
                    uint8_t* out_inf);
 
+/* point_scalar_mul over a vector (src/curve.rs:113-126, the operation multi_scalar_mul is made of): out[i] = k_i P_i for n independent
+ * pairs, one launch.  scalars: canonical (< r), 4 u64 limbs each; n_scalars = n, or 1 = one scalar for every point; anything else is
+ * DVP_EINVAL.  xy / inf as everywhere (inf may be NULL); out_inf[i] = 1 with zero coordinates for O (k_i = 0 or P_i = O).
+ * dvp_points_mul / dvp_points_mul_xsk233: n = 0 is DVP_OK and touches nothing; a NULL scalars / xy / enc or a NULL output with n > 0 and
+ * a wrong n_scalars are DVP_EINVAL before any device call; a non-canonical scalar is DVP_EINVAL with dvp_last_error_index() = the
+ * first such scalar, and no output is written.  dvp_points_mul_xsk233 takes and gives the reference's wire formats (scalars 32 B LE,
+ * points 30 B, under the codec rule in force); a bad encoding is DVP_EDECODE with its index.
+ * dvp_points_mul_dev: enqueues on `stream` and returns, never waits on the host and never checks points; d_out_xy may equal d_xy,
+ * d_inf may be NULL.  A non-canonical scalar makes its lane produce O and is reported in d_summary = { u64 first such index or ~0,
+ * u64 their number }, which the call itself resets (the layout of dvp_points_check_dev). */
+int dvp_points_mul(const uint64_t* scalars, size_t n_scalars, const uint64_t* xy, const uint8_t* inf /* may be NULL */, size_t n,
+                   uint64_t* out_xy, uint8_t* out_inf);
+int dvp_points_mul_dev(const void* d_scalars, size_t n_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy,
+                       void* d_out_inf, void* d_summary /* 16 bytes, written by the call */, void* stream);
+int dvp_points_mul_xsk233(const uint8_t* scalars /* n_scalars x 32 B LE */, size_t n_scalars, const uint8_t* enc /* n x 30 B */,
+                          size_t n, uint8_t* out_enc /* n x 30 B */);
+
 /* Affine points checked on the device.  The kernels behind the affine entries assume points of E[r] (the prime-order subgroup) with
  * reduced coordinates; the 30-byte path can only produce such points (dvp_points_decode), the affine path takes what it is given.
  * Every point i with inf[i] == 0 (inf == NULL: every point) gets exactly one class; a point with inf[i] != 0 is class 0 whatever its
@@ -190,12 +207,13 @@ int dvp_points_add(const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b
  *
  * Strict mode (process-wide like dvp_codec_set_rule; initial value DVP_POINTS_STRICT from the environment, default 0 = off): when on,
  * the entries that copy affine points from the caller -- dvp_msm_affine, dvp_msm_ctx_create, dvp_prover_set_srs_affine,
- * dvp_prover_set_srs_affine_dev, dvp_points_add, dvp_points_encode -- run the check on their device copy before anything else uses
+ * dvp_prover_set_srs_affine_dev, dvp_points_add, dvp_points_encode, dvp_points_mul -- run the check on their device copy before anything else uses
  * it and return DVP_EPOINT with the index of the first bad point.  dvp_points_add checks operand a, then operand b: the index is that
- * of the first bad point of a, and only when a is clean that of the first bad point of b (both count from 0).  After a failure
+ * of the first bad point of a, and only when a is clean that of the first bad point of b (both count from 0).  dvp_points_mul checks its
+ * points before its scalars: a bad point together with a bad scalar is DVP_EPOINT.  After a failure
  * dvp_msm_ctx_create has freed what it allocated and not written *out, and the SRS setters leave vector `which` UNSET: a later proof
  * fails as it does for a vector that was never given, never on stale or rejected bases.
- * NEVER checked, strict or not: the `_dev` run entries dvp_msm_affine_dev, dvp_msm_ctx_run_dev, dvp_points_sum_dev and the prover's own
+ * NEVER checked, strict or not: the `_dev` run entries dvp_msm_affine_dev, dvp_msm_ctx_run_dev, dvp_points_sum_dev, dvp_points_mul_dev and the prover's own
  * buffers -- they must not wait on the host; a caller who wants a check there enqueues dvp_points_check_dev itself. */
 #define DVP_POINT_UNREDUCED 0x01u
 #define DVP_POINT_OFF_CURVE 0x02u

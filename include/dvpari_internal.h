@@ -48,6 +48,10 @@ int dvp_ubench_fr_mul(int reps, double* muladds_per_s);
  * n x 65 bytes the decode kernel writes its points and flags into.  Waits for the result. */
 int dvp_ubench_points_check(const void* d_xy, const void* d_inf, const void* d_enc, size_t n, void* d_scratch, int reps,
                             double* check_ms, double* decode_ms);
+/* dvp_points_mul_dev (at the DVP_POINTS_MUL_W in force) against its yardstick k_mulgen on the same scalars and count in one run
+ * (tools/points_mul.py): device events around each alone, one warm-up and then the median of `reps` (odd, 1 .. 99).  d_scalars: n x 32 B
+ * canonical; d_xy: n affine points of E[r]; d_scratch: n x 65 bytes both write their points and flags into.  Waits for the result. */
+int dvp_ubench_points_mul(const void* d_scalars, const void* d_xy, size_t n, void* d_scratch, int reps, double* mul_ms, double* mulgen_ms);
 /* Wave-level trace of the batched-affine pair rounds (dvp::k_affine_round, tools/wave_trace.py).  d_buf = device buffer of
  * 64 + 64 * n_records bytes zeroed by the caller, NULL = off.  While set, every pair round appends one 64-byte record per
  * wave (8 u64: s_memrealtime at wave start / after pass 1 / after the shared inversion / at the end; s_memtime at start / end;
@@ -71,6 +75,12 @@ int dvp_table_plan(size_t size0, size_t size1, uint64_t budget_bytes, size_t cov
 /* parity-test access to the recode of the default fixed-base flavour alone (signed aligned windows): out_words[w * n + i] = 0 (digit 0) or 0x80000000 | 0x10000000 when the
  * digit is negative | w << 20 | |digit| (|digit| = 2^(c-1) is stored as key 0); *windows = ceil(234 / c_bits) */
 int dvp_debug_recode_signed(const uint64_t* scalars, size_t n, int c_bits, uint32_t* out_words, int* windows);
+
+/* parity-test access to the width-w tau-NAF recoder of dvp_points_mul alone (w = 3, 4, 5), run on the device: digits[i * *n_digits + j] =
+ * the signed digit of scalar i at position j (+-u, u odd < 2^(w-1); 0 for none), *n_digits = the PROVEN bound on the positions (csrc/tau.cuh:
+ * TnafDigits), alpha[2 e], alpha[2 e + 1] = (beta, gamma) of the representative alpha_(2e+1) = beta + gamma tau the kernel's table holds,
+ * e < 2^(w-2).  digits == NULL: only *n_digits and alpha (no device call).  A non-canonical scalar: DVP_EINVAL and its index. */
+int dvp_debug_recode_tnaf(const uint64_t* scalars, size_t n, int w, int8_t* digits, int* n_digits, int32_t* alpha /* 2^(w-2) x (beta, gamma) */);
 
 /* TEST / HARNESS ONLY: the SRS scalars (discrete logs of the bases: trapdoor material) of an IN-MEMORY circuit -- CSR matrices L, R, O
  * over n_rows <= 2^log2_m rows (row_ptr[k]: n_rows + 1 entries), coefficient table (n_coeffs x 4 u64, canonical), n_wires -- in
