@@ -90,6 +90,10 @@ _SIGS = {
     "dvp_points_mul": (C.c_int, [u64p, sz, u64p, u8p, sz, u64p, u8p]),
     "dvp_points_mul_dev": (C.c_int, [vp, sz, vp, vp, sz, vp, vp, vp, vp]),
     "dvp_points_mul_xsk233": (C.c_int, [u8p, sz, u8p, sz, u8p]),
+    "dvp_msm_segments": (C.c_int, [u64p, u64p, u8p, sz, u64p, sz, u64p, u8p]),
+    "dvp_msm_segments_work_bytes": (sz, [sz, sz]),
+    "dvp_msm_segments_dev": (C.c_int, [vp, vp, vp, sz, u64p, sz, vp, vp, vp, sz, vp, vp]),
+    "dvp_msm_segments_xsk233": (C.c_int, [u8p, u8p, sz, u64p, sz, u8p]),
     "dvp_debug_recode_tnaf": (C.c_int, [vp, sz, C.c_int, vp, C.POINTER(C.c_int), vp]),
     "dvp_points_check": (C.c_int, [u64p, u8p, sz, u8p, C.POINTER(C.c_size_t)]),
     "dvp_points_check_dev": (C.c_int, [vp, vp, sz, vp, vp, vp]),

@@ -104,6 +104,7 @@ struct Tune {
   long long table_budget_bytes = -1;   // DVP_TABLE_BUDGET_BYTES: HBM per device the fixed-base tables of a NEW prover may hold (-1 = no limit; dvp_prover_set_table_budget changes it per prover)
   long long msm_table_refuse = 0;      // DVP_MSM_TABLE_REFUSE: TEST ONLY, 1 = msm_fixed_build behaves as if its table allocation had returned hipErrorOutOfMemory, without asking the runtime
   long long points_mul_w = 3;          // DVP_POINTS_MUL_W: window width of dvp_points_mul's tau-NAF (3, 4 or 5; anything else = the default)
+  long long msm_seg_piece = 4;         // DVP_MSM_SEG_PIECE: operands one lane of dvp_msm_segments' reduction sums per level, the piece length P (2 ..= 64; anything else = the default)
   long long msm_aligned_signed = 1;    // DVP_MSM_ALIGNED_SIGNED: the aligned-window tables hold 2^(c w) P and the windows are signed binary digits (0 = the tau-adic aligned windows over rows tau^(o_w) P)
 };
 Tune& tune();

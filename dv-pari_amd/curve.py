@@ -67,6 +67,59 @@ def point_scalar_mul_bytes(scalars32: np.ndarray, enc30: np.ndarray) -> np.ndarr
     return out
 
 
+def _seg_ptr(seg_ptr) -> np.ndarray:
+    sp = np.ascontiguousarray(seg_ptr, dtype=np.uint64).reshape(-1)
+    assert sp.shape[0] >= 1, "seg_ptr holds n_seg + 1 offsets"
+    return sp
+
+
+def multi_scalar_mul_segments(scalars: np.ndarray, points_xy: np.ndarray, seg_ptr, points_inf: np.ndarray = None):
+    """n_seg independent multi_scalar_mul (src/curve.rs:141-158) over consecutive slices in one call: out[j] = sum of k_i P_i for
+    seg_ptr[j] <= i < seg_ptr[j+1].  seg_ptr is CSR-style (n_seg + 1 offsets, 0 first, n last, non-decreasing); empty segments give
+    O.  Returns (xy [n_seg, 8], inf [n_seg]); errors as point_scalar_mul, plus DvpError(DVP_EINVAL) with .index = the first offending
+    segment for a bad seg_ptr."""
+    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    b = np.ascontiguousarray(points_xy, dtype=np.uint64).reshape(-1, 8)
+    sp = _seg_ptr(seg_ptr)
+    n, n_seg = b.shape[0], sp.shape[0] - 1
+    assert s.shape[0] == n, (s.shape, b.shape)
+    inf_p = None
+    if points_inf is not None:
+        pi = np.ascontiguousarray(points_inf, dtype=np.uint8)
+        assert pi.shape == (n,)
+        inf_p = ptr(pi)
+    xy = np.zeros((n_seg, 8), dtype=np.uint64)
+    inf = np.zeros(n_seg, dtype=np.uint8)
+    check(lib.dvp_msm_segments(ptr(s), ptr(b), inf_p, n, ptr(sp), n_seg, ptr(xy), ptr(inf)), "dvp_msm_segments")
+    return xy, inf
+
+
+def segments_work_bytes(n: int, n_seg: int) -> int:
+    """dvp_msm_segments_work_bytes: the d_work a multi_scalar_mul_segments_dev call of this shape needs (host arithmetic)"""
+    return int(lib.dvp_msm_segments_work_bytes(n, n_seg))
+
+
+def multi_scalar_mul_segments_dev(d_scalars: int, d_xy: int, d_inf: int, n: int, seg_ptr, d_out_xy: int, d_out_inf: int, d_work: int,
+                                  work_bytes: int, d_summary: int, stream: int = 0):
+    """dvp_msm_segments_dev: enqueue only.  seg_ptr is a HOST array, read during the call; d_inf may be 0; d_out_inf is n_seg bytes;
+    d_work holds segments_work_bytes(n, n_seg) bytes; d_summary (16 bytes) as point_scalar_mul_dev.  Outputs must not overlap the
+    inputs or d_work."""
+    sp = _seg_ptr(seg_ptr)
+    check(lib.dvp_msm_segments_dev(d_scalars or None, d_xy or None, d_inf or None, n, ptr(sp), sp.shape[0] - 1, d_out_xy, d_out_inf,
+                                   d_work or None, work_bytes, d_summary, stream), "dvp_msm_segments_dev")
+
+
+def multi_scalar_mul_segments_bytes(scalars32: np.ndarray, enc30: np.ndarray, seg_ptr) -> np.ndarray:
+    """the same on the reference's wire formats: scalars [n, 32] little-endian bytes, points [n, 30] -> [n_seg, 30]"""
+    s = np.ascontiguousarray(scalars32, dtype=np.uint8).reshape(-1, 32)
+    e = np.ascontiguousarray(enc30, dtype=np.uint8).reshape(-1, 30)
+    sp = _seg_ptr(seg_ptr)
+    assert s.shape[0] == e.shape[0]
+    out = np.zeros((sp.shape[0] - 1, 30), dtype=np.uint8)
+    check(lib.dvp_msm_segments_xsk233(ptr(s), ptr(e), e.shape[0], ptr(sp), sp.shape[0] - 1, ptr(out)), "dvp_msm_segments_xsk233")
+    return out
+
+
 def point_scalar_mul_gen_batch(scalars: np.ndarray):
     """point_scalar_mul_gen over a vector (src/curve.rs:129-137, loops at src/srs.rs:130-160).
     Returns (xy [n,8], inf [n])."""

@@ -190,6 +190,47 @@ int dvp_points_mul_dev(const void* d_scalars, size_t n_scalars, const void* d_xy
 int dvp_points_mul_xsk233(const uint8_t* scalars /* n_scalars x 32 B LE */, size_t n_scalars, const uint8_t* enc /* n x 30 B */,
                           size_t n, uint8_t* out_enc /* n x 30 B */);
 
+/* out[j] = sum over seg_ptr[j] <= i < seg_ptr[j+1] of k_i P_i, for j < n_seg: n_seg independent multi_scalar_mul
+ * (src/curve.rs:141-158) over consecutive slices of one scalar vector and one point vector, in one call.  Stage 1 is dvp_points_mul_dev
+ * over all n pairs; stage 2 sums the products of every segment with complete additions: pieces of at most P = DVP_MSM_SEG_PIECE
+ * consecutive operands, one lane each, level after level until every segment has one sum (at most
+ * P ceil(log_P(longest segment)) dependent additions and one inversion behind stage 1, whatever the cut).  Results are affine, so they
+ * do not depend on P or on DVP_POINTS_MUL_W.
+ * seg_ptr is CSR-style, as row_ptr of dvp_fr_spmv, and a HOST array in every flavour: seg_ptr[0] = 0, non-decreasing,
+ * seg_ptr[n_seg] = n.  DVP_EINVAL before any device call, with dvp_last_error_index() = the first offending j: 0 for seg_ptr[0] != 0,
+ * j for seg_ptr[j] > seg_ptr[j + 1] or seg_ptr[j + 1] > n, n_seg - 1 for seg_ptr[n_seg] < n.  Empty segments are allowed anywhere and
+ * give O (out_inf = 1, zero coordinates; the xsk233 flavour: the neutral element's encoding).  n_seg = 0 is DVP_OK and touches nothing;
+ * n = 0 with n_seg > 0 writes n_seg times O (the host flavours without a device).  NULL required pointers, n or n_seg >= 2^32 and a
+ * work_bytes below dvp_msm_segments_work_bytes(n, n_seg) are DVP_EINVAL before any device call.
+ * dvp_msm_segments / dvp_msm_segments_xsk233: as dvp_points_mul -- in strict mode the points are checked first (DVP_EPOINT with the
+ * index), then a non-canonical scalar is DVP_EINVAL with its index; no output is written in either case; a bad encoding is
+ * DVP_EDECODE with its index.
+ * dvp_msm_segments_dev: enqueues on `stream` and returns; never checks points; allocates nothing on the device.  A lane with a
+ * non-canonical scalar contributes O and is reported in d_summary (the layout of dvp_points_mul_dev; the call resets it); every
+ * segment is still written.  d_work is the caller's: dvp_msm_segments_work_bytes (pure host arithmetic, non-decreasing in both
+ * arguments, enough for every admissible DVP_MSM_SEG_PIECE) bytes that no other work in flight uses.  The outputs must not overlap the
+ * inputs or d_work.  The offsets of every level are computed on the host from seg_ptr -- O(n_seg) per level, seg_ptr is not read after
+ * the call returns -- and reach the device through a ring of four pinned staging buffers the library owns, one asynchronous copy on
+ * `stream` per call.  The call does not wait for work already on `stream`.  What it can block on: (1) the geometry copy of the call
+ * four calls before it, when that copy has not run yet because the work in front of it on ITS stream has not finished; (2) a pinned
+ * allocation, when the call needs more staging bytes than the slot it is given has held before (the runtime may synchronise the device
+ * there); (3) the first call on a device, which builds the inversion tables every entry of the group shares.
+ * When to call dvp_msm_affine per segment instead: the one-shot pipeline is ~33 dependent launches per call whatever its size, this
+ * entry pays ~58 additions per point whatever the cut; measured on one MI355X (tools/README.md, "Segmented MSM") a loop of
+ * dvp_msm_affine_dev overtakes this entry between 4096 and 65536 points per segment (loop / this entry = 2.9-4.7 at
+ * 4096 points, 0.3-0.5 at 65536; near 2^14-2^15 by interpolation): call dvp_msm_affine per segment for segments of 2^15 points and up.
+ * Out of scope here: gathered bases (a column index per term), a per-segment bucket method in LDS, fusing the reduction into the
+ * multiplication kernel, a device-resident seg_ptr, and use of this entry inside the prover. */
+int dvp_msm_segments(const uint64_t* scalars /* n x 4 */, const uint64_t* xy /* n x 8 */, const uint8_t* inf /* may be NULL */, size_t n,
+                     const uint64_t* seg_ptr /* n_seg + 1 */, size_t n_seg, uint64_t* out_xy /* n_seg x 8 */, uint8_t* out_inf /* n_seg */);
+size_t dvp_msm_segments_work_bytes(size_t n, size_t n_seg);
+int dvp_msm_segments_dev(const void* d_scalars, const void* d_xy, const void* d_inf /* may be NULL */, size_t n,
+                         const uint64_t* seg_ptr /* HOST, n_seg + 1, read only during the call */, size_t n_seg,
+                         void* d_out_xy, void* d_out_inf /* n_seg bytes */, void* d_work, size_t work_bytes,
+                         void* d_summary /* 16 bytes, written by the call */, void* stream);
+int dvp_msm_segments_xsk233(const uint8_t* scalars /* n x 32 B LE */, const uint8_t* enc /* n x 30 B */, size_t n,
+                            const uint64_t* seg_ptr, size_t n_seg, uint8_t* out_enc /* n_seg x 30 B */);
+
 /* Affine points checked on the device.  The kernels behind the affine entries assume points of E[r] (the prime-order subgroup) with
  * reduced coordinates; the 30-byte path can only produce such points (dvp_points_decode), the affine path takes what it is given.
  * Every point i with inf[i] == 0 (inf == NULL: every point) gets exactly one class; a point with inf[i] != 0 is class 0 whatever its
@@ -207,13 +248,13 @@ int dvp_points_mul_xsk233(const uint8_t* scalars /* n_scalars x 32 B LE */, size
  *
  * Strict mode (process-wide like dvp_codec_set_rule; initial value DVP_POINTS_STRICT from the environment, default 0 = off): when on,
  * the entries that copy affine points from the caller -- dvp_msm_affine, dvp_msm_ctx_create, dvp_prover_set_srs_affine,
- * dvp_prover_set_srs_affine_dev, dvp_points_add, dvp_points_encode, dvp_points_mul -- run the check on their device copy before anything else uses
+ * dvp_prover_set_srs_affine_dev, dvp_points_add, dvp_points_encode, dvp_points_mul, dvp_msm_segments -- run the check on their device copy before anything else uses
  * it and return DVP_EPOINT with the index of the first bad point.  dvp_points_add checks operand a, then operand b: the index is that
- * of the first bad point of a, and only when a is clean that of the first bad point of b (both count from 0).  dvp_points_mul checks its
- * points before its scalars: a bad point together with a bad scalar is DVP_EPOINT.  After a failure
+ * of the first bad point of a, and only when a is clean that of the first bad point of b (both count from 0).  dvp_points_mul and dvp_msm_segments check their
+ * points before their scalars: a bad point together with a bad scalar is DVP_EPOINT.  After a failure
  * dvp_msm_ctx_create has freed what it allocated and not written *out, and the SRS setters leave vector `which` UNSET: a later proof
  * fails as it does for a vector that was never given, never on stale or rejected bases.
- * NEVER checked, strict or not: the `_dev` run entries dvp_msm_affine_dev, dvp_msm_ctx_run_dev, dvp_points_sum_dev, dvp_points_mul_dev and the prover's own
+ * NEVER checked, strict or not: the `_dev` run entries dvp_msm_affine_dev, dvp_msm_ctx_run_dev, dvp_points_sum_dev, dvp_points_mul_dev, dvp_msm_segments_dev and the prover's own
  * buffers -- they must not wait on the host; a caller who wants a check there enqueues dvp_points_check_dev itself. */
 #define DVP_POINT_UNREDUCED 0x01u
 #define DVP_POINT_OFF_CURVE 0x02u
