@@ -121,14 +121,14 @@ __global__ void __launch_bounds__(B3_TREE_THREADS) k_b3_tree(const uint32_t* __r
 int b3_leaves_dev(const uint8_t* d_data, size_t len, uint64_t chunk_base, uint32_t* d_cvs, hipStream_t st) {
   const size_t nchunks = (len + B3_CHUNK - 1) / B3_CHUNK;
   if (!len || chunk_base + nchunks > (1ull << 32)) return DVP_EINVAL;  // compress carries a 32-bit chunk counter
-  hipLaunchKernelGGL(k_b3_leaves, dim3(cdiv(nchunks, 64)), dim3(64), 0, st, d_data, len, (uint32_t)chunk_base, nchunks, 0u, d_cvs);
+  DVP_LAUNCH(k_b3_leaves, dim3(cdiv(nchunks, 64)), dim3(64), 0, st, d_data, len, (uint32_t)chunk_base, nchunks, 0u, d_cvs);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
 // digest of a single chunk (len <= 1024; len = 0 is one empty chunk): ROOT on its own last block
 int b3_single_chunk_dev(const uint8_t* d_data, size_t len, uint32_t* d_out32, hipStream_t st) {
   if (len > B3_CHUNK) return DVP_EINVAL;
-  hipLaunchKernelGGL(k_b3_leaves, dim3(1), dim3(64), 0, st, d_data, len, 0u, (size_t)1, 1u, d_out32);
+  DVP_LAUNCH(k_b3_leaves, dim3(1), dim3(64), 0, st, d_data, len, 0u, (size_t)1, 1u, d_out32);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
@@ -140,7 +140,7 @@ int b3_reduce_dev(uint32_t* d_cvs, size_t n, uint32_t* d_tmp, uint32_t* d_out32,
   for (;;) {
     const size_t nb = (n + B3_TREE_RUN - 1) / B3_TREE_RUN;
     const bool last = nb == 1;
-    hipLaunchKernelGGL(k_b3_tree, dim3((unsigned)nb), dim3(B3_TREE_THREADS), 0, st, (const uint32_t*)src, n, last ? d_out32 : dst, last ? 1u : 0u);
+    DVP_LAUNCH(k_b3_tree, dim3((unsigned)nb), dim3(B3_TREE_THREADS), 0, st, (const uint32_t*)src, n, last ? d_out32 : dst, last ? 1u : 0u);
     DVP_HIP(hipGetLastError());
     if (last) return DVP_OK;
     n = nb;

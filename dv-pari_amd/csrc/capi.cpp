@@ -4,10 +4,12 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <string>
 #include <vector>
 #include <cstring>
 #include <cstdlib>
 #include <climits>
+#include <cxxabi.h>
 
 namespace dvp {
 thread_local int64_t g_last_error_index = -1;
@@ -55,6 +57,52 @@ static std::atomic<uint64_t> g_host_waits[2];
 void count_host_wait(int kind) { g_host_waits[kind & 1].fetch_add(1, std::memory_order_relaxed); }
 static std::atomic<uint64_t> g_later_rounds[2];
 void count_later_round(bool dense) { g_later_rounds[dense ? 1 : 0].fetch_add(1, std::memory_order_relaxed); }
+
+// the launch census (common.h): name -> counter, filled while the library is loaded (the counters' own static initialisers call
+// census_register, so the registry is built on first use) and only read afterwards
+struct Census {
+  std::mutex mu;
+  std::map<std::string, LaunchCounter*> by_name;
+};
+static Census& census() {
+  static Census* c = new Census;  // never destroyed: launches may still be counted while the process exits
+  return *c;
+}
+LaunchCounter* census_register(const char* file, const char* tag_type) {
+  // "dvp::LaunchTag<&(void dvp::k_merge<16, true>(Ld*, int, unsigned int, Ld*))>" or "dvp::LaunchTag<&dvp::k_post_sort>"
+  // -> "k_merge<16,true>", "k_post_sort"; the file without its directories
+  int st = 0;
+  char* dm = abi::__cxa_demangle(tag_type ? tag_type : "", nullptr, nullptr, &st);
+  std::string v = (st == 0 && dm) ? dm : (tag_type ? tag_type : "");
+  free(dm);
+  for (size_t at; (at = v.find("(anonymous namespace)::")) != std::string::npos;) v.erase(at, 23);
+  size_t a = v.find("<&");
+  if (a != std::string::npos) v = v.substr(a + 2);
+  if (!v.empty() && v[0] == '(') v = v.substr(1);
+  if (!v.compare(0, 5, "void ")) v = v.substr(5);
+  std::string name;
+  int depth = 0;
+  for (size_t i = 0; i < v.size(); ++i) {  // the qualified name and its balanced template arguments, up to the parameter list
+    const char ch = v[i];
+    if (ch == '<') ++depth;
+    if (depth == 0 && (ch == '(' || ch == ')' || ch == '>')) break;
+    if (ch == '>') --depth;
+    if (ch == ' ' && i > 0 && v[i - 1] == ',') continue;
+    name.push_back(ch);
+  }
+  const size_t lt = name.find('<');
+  const size_t ns = name.rfind("::", lt);  // kernels live in a namespace: the bare name
+  if (ns != std::string::npos) name = name.substr(ns + 2);
+  std::string f = file ? file : "";
+  size_t sl = f.find_last_of("/\\");
+  if (sl != std::string::npos) f = f.substr(sl + 1);
+  name = f + ":" + name;
+  Census& c = census();
+  std::lock_guard<std::mutex> g(c.mu);
+  LaunchCounter*& slot = c.by_name[name];
+  if (!slot) slot = new LaunchCounter;
+  return slot;
+}
 
 static void tune_from_env(Tune& t) {
   t = Tune();
@@ -153,6 +201,22 @@ extern "C" void dvp_profile_reset(void) {
   dvp::g_host_waits[1] = 0;
   dvp::g_later_rounds[0] = 0;
   dvp::g_later_rounds[1] = 0;
+  dvp::Census& c = dvp::census();
+  std::lock_guard<std::mutex> gc(c.mu);
+  for (auto& e : c.by_name) e.second->n.store(0, std::memory_order_relaxed);
+}
+// the census' names, one "file:variant" per line; returns the bytes needed (terminating NUL included), touches no device
+extern "C" int dvp_debug_launch_names(char* buf, size_t cap) {
+  dvp::Census& c = dvp::census();
+  std::lock_guard<std::mutex> g(c.mu);
+  std::string all;
+  for (auto& e : c.by_name) { all += e.first; all += '\n'; }
+  if (buf && cap) {
+    const size_t k = all.size() < cap - 1 ? all.size() : cap - 1;
+    memcpy(buf, all.data(), k);
+    buf[k] = 0;
+  }
+  return (int)(all.size() + 1);
 }
 // the "msm_affine_round0" slot split by launch shape: one entry per distinct MSM size seen since the last reset
 extern "C" int dvp_profile_round0_shapes(uint64_t* pairs, double* total_ms, uint64_t* launches, int cap) {
@@ -176,6 +240,15 @@ extern "C" int dvp_profile_read(const char* name, double* total_ms, uint64_t* la
   if (!strcmp(name, "later_rounds_word") || !strcmp(name, "later_rounds_dense")) {  // launches since the last dvp_profile_reset
     *total_ms = 0;
     *launches = dvp::g_later_rounds[name[13] == 'd' ? 1 : 0].load();
+    return DVP_OK;
+  }
+  if (!strncmp(name, "launch:", 7)) {  // the launch census: launches of one variant since the last dvp_profile_reset
+    dvp::Census& c = dvp::census();
+    std::lock_guard<std::mutex> g(c.mu);
+    auto it = c.by_name.find(name + 7);
+    if (it == c.by_name.end()) return DVP_EINVAL;
+    *total_ms = 0;
+    *launches = it->second->n.load(std::memory_order_relaxed);
     return DVP_OK;
   }
   dvp::prof_collect();

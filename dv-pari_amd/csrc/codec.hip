@@ -231,7 +231,7 @@ int gen_table(const Aff** out, hipStream_t st) {
     Aff* t;
     size_t cnt = (size_t)GEN_W << GEN_C;
     DVP_HIP(hipMalloc((void**)&t, cnt * sizeof(Aff)));
-    hipLaunchKernelGGL(k_gen_table, dim3(cdiv(cnt, 256)), dim3(256), 0, st, t);
+    DVP_LAUNCH(k_gen_table, dim3(cdiv(cnt, 256)), dim3(256), 0, st, t);
     DVP_HIP(hipGetLastError());
     DVP_HIP(hipStreamSynchronize(st));
     g_gen_tab[dev] = t;
@@ -259,7 +259,7 @@ int mulgen_dev(const void* d_scalars, size_t n, Aff* d_out, uint8_t* d_inf, hipS
   DVP_HIP(hipMemsetAsync(err.p, 0xff, 8, st));
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
-  hipLaunchKernelGGL(k_mulgen, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint32_t*)d_scalars, n, tab, T, d_out,
+  DVP_LAUNCH(k_mulgen, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint32_t*)d_scalars, n, tab, T, d_out,
                      d_inf, err.as<unsigned long long>());
   DVP_HIP(hipGetLastError());
   return read_err(err.as<unsigned long long>(), st, DVP_EINVAL);
@@ -268,7 +268,7 @@ int mulgen_dev(const void* d_scalars, size_t n, Aff* d_out, uint8_t* d_inf, hipS
 int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out, hipStream_t st) {
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
-  hipLaunchKernelGGL(k_encode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, d_pts, d_inf, n, T, d_out, codec_rule());
+  DVP_LAUNCH(k_encode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, d_pts, d_inf, n, T, d_out, codec_rule());
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
@@ -276,7 +276,7 @@ int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out,
 int encode_point_dev(const Aff* d_pt, const uint32_t* d_inf32, uint8_t* d_out, hipStream_t st) {
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
-  hipLaunchKernelGGL(k_encode_point, dim3(1), dim3(64), GF_LDS_BYTES_PER_WAVE, st, d_pt, d_inf32, T, d_out, codec_rule());
+  DVP_LAUNCH(k_encode_point, dim3(1), dim3(64), GF_LDS_BYTES_PER_WAVE, st, d_pt, d_inf32, T, d_out, codec_rule());
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
@@ -287,7 +287,7 @@ int decode_dev(const uint8_t* d_enc, size_t n, Aff* d_out, uint8_t* d_inf, hipSt
   DVP_HIP(hipMemsetAsync(err.p, 0xff, 8, st));
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
-  hipLaunchKernelGGL(k_decode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, d_enc, n, T, d_out, d_inf,
+  DVP_LAUNCH(k_decode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, d_enc, n, T, d_out, d_inf,
                      err.as<unsigned long long>(), codec_rule());
   DVP_HIP(hipGetLastError());
   return read_err(err.as<unsigned long long>(), st, DVP_EDECODE);
@@ -300,7 +300,7 @@ int points_check_dev(const void* d_xy, const void* d_inf, size_t n, void* d_clas
   if (!n) return DVP_OK;
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
-  hipLaunchKernelGGL(k_points_check, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const Aff*)d_xy, (const uint8_t*)d_inf, n, T,
+  DVP_LAUNCH(k_points_check, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const Aff*)d_xy, (const uint8_t*)d_inf, n, T,
                      (uint8_t*)d_classes, (unsigned long long*)d_summary);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
@@ -425,7 +425,7 @@ extern "C" int dvp_points_add(const uint64_t* a_xy, const uint8_t* a_inf, const 
   }
   DVP_TRY(points_check_strict(da.p, dai.p, n, 0));  // operand a first: the index is b's only when a is clean
   DVP_TRY(points_check_strict(db.p, dbi.p, n, 0));
-  hipLaunchKernelGGL(k_points_add, dim3(cdiv(n, 128)), dim3(128), 0, 0, da.as<Aff>(), dai.as<uint8_t>(), db.as<Aff>(), dbi.as<uint8_t>(), n,
+  DVP_LAUNCH(k_points_add, dim3(cdiv(n, 128)), dim3(128), 0, 0, da.as<Aff>(), dai.as<uint8_t>(), db.as<Aff>(), dbi.as<uint8_t>(), n,
                      dout.as<Aff>(), doi.as<uint8_t>());
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out_xy, dout.p, n * 64, hipMemcpyDeviceToHost));
@@ -493,10 +493,10 @@ extern "C" int dvp_ubench_points_check(const void* d_xy, const void* d_inf, cons
     for (int r = -1; r < reps && err == hipSuccess; ++r) {
       (void)hipEventRecord(e0, 0);
       if (k == 0)
-        hipLaunchKernelGGL(k_points_check, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const Aff*)d_xy, (const uint8_t*)d_inf, n, T,
+        DVP_LAUNCH(k_points_check, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const Aff*)d_xy, (const uint8_t*)d_inf, n, T,
                            (uint8_t*)nullptr, sum.as<unsigned long long>());
       else
-        hipLaunchKernelGGL(k_decode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint8_t*)d_enc, n, T, (Aff*)d_scratch,
+        DVP_LAUNCH(k_decode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint8_t*)d_enc, n, T, (Aff*)d_scratch,
                            (uint8_t*)d_scratch + n * 64, sum.as<unsigned long long>(), rule);
       err = hipGetLastError();
       (void)hipEventRecord(e1, 0);
@@ -541,7 +541,7 @@ extern "C" int dvp_ubench_points_mul(const void* d_scalars, const void* d_xy, si
       if (k == 0)
         rc = points_mul_dev(d_scalars, n, d_xy, nullptr, n, d_scratch, (uint8_t*)d_scratch + n * 64, sum.p, 0);
       else
-        hipLaunchKernelGGL(k_mulgen, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint32_t*)d_scalars, n, tab, T, (Aff*)d_scratch,
+        DVP_LAUNCH(k_mulgen, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint32_t*)d_scalars, n, tab, T, (Aff*)d_scratch,
                            (uint8_t*)d_scratch + n * 64, sum.as<unsigned long long>());
       err = hipGetLastError();
       (void)hipEventRecord(e1, 0);

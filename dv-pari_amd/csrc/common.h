@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+#include <typeinfo>
 #include <vector>
 
 #include "../../include/dvpari_internal.h"
@@ -135,5 +137,35 @@ void count_host_wait(int kind);
 // launches of the pair rounds after the first, counted always, by descriptor form (dvp_profile_read "later_rounds_word" /
 // "later_rounds_dense"): the tests read which form ran
 void count_later_round(bool dense);
+
+// ---- launch census: every kernel launch of the library is counted per variant, always -------------------------------------
+// A variant is one kernel with its instantiated template arguments; its name is "<file>:<kernel><args>" as the compiler spells the
+// instantiation, blanks removed ("msm.hip:k_merge<16,false>"), so a launch inside templated host code carries the arguments it was
+// instantiated with.  The counter of a variant is a static member of a template over the kernel's address: sites that launch the same
+// variant share it, and it registers its name when the library is loaded, so dvp_debug_launch_names (dvpari_internal.h) knows every
+// variant host code can launch without launching anything.  dvp_profile_read("launch:<name>") reads a count, dvp_profile_reset
+// zeroes them all.  The wrapper adds one relaxed host increment to a launch: no HIP call, no event, no synchronisation.
+struct LaunchCounter {
+  std::atomic<uint64_t> n{0};
+};
+LaunchCounter* census_register(const char* file, const char* tag_type);  // capi.cpp; tag_type = typeid(LaunchTag<&kernel<args>>).name()
+template <auto K>
+struct LaunchTag {};  // its mangled type name spells the kernel with every template argument; the registry demangles it
+template <auto K>
+struct LaunchSite {
+  static LaunchCounter* const counter;
+};
+template <auto K>
+LaunchCounter* const LaunchSite<K>::counter = census_register(__BASE_FILE__, typeid(LaunchTag<K>).name());
+template <auto K>
+struct Launch;
+template <class... P, void (*K)(P...)>
+struct Launch<K> {  // the kernel's own parameter types: arguments convert at the call, as they would in a direct launch
+  static void go(dim3 grid, dim3 block, size_t lds, hipStream_t st, P... p) {
+    LaunchSite<K>::counter->n.fetch_add(1, std::memory_order_relaxed);
+    hipLaunchKernelGGL(K, grid, block, (unsigned)lds, st, p...);
+  }
+};
+#define DVP_LAUNCH(kernel, grid, block, lds, stream, ...) ::dvp::Launch<(kernel)>::go(grid, block, lds, stream, __VA_ARGS__)
 
 }  // namespace dvp

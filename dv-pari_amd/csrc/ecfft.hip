@@ -707,7 +707,7 @@ static int build_matset(dvp_ecfft* c, int sl, int to_even, MatSet** out, hipStre
     for (int d = 0; d < ln; ++d) {
       uint32_t nd = n >> d;
       size_t off = 2 * (size_t)(n - nd);
-      hipLaunchKernelGGL(k_build_twiddles, dim3(cdiv(nd >> 1, TPB)), dim3(TPB), 0, st, c->layer(d), sl, nd, src, dst, ms.dec + off, ms.rec + off);
+      DVP_LAUNCH(k_build_twiddles, dim3(cdiv(nd >> 1, TPB)), dim3(TPB), 0, st, c->layer(d), sl, nd, src, dst, ms.dec + off, ms.rec + off);
     }
     // the twists, bottom up: W_d from W_{d+1} (ping-pong), once per parity
     DevBuf wa, wb, ws, wd;
@@ -723,12 +723,12 @@ static int build_matset(dvp_ecfft* c, int sl, int to_even, MatSet** out, hipStre
       for (int d = ln - 1; d >= 0; --d) {
         uint32_t nd = n >> d;
         Fr* outp = d == 0 ? (par == 0 ? ws.as<Fr>() : wd.as<Fr>()) : cur;
-        hipLaunchKernelGGL(k_twist_layer, dim3(cdiv(nd, TPB)), dim3(TPB), 0, st, c->layer(d), sl, nd, c->x0[d], parity, prev, outp);
+        DVP_LAUNCH(k_twist_layer, dim3(cdiv(nd, TPB)), dim3(TPB), 0, st, c->layer(d), sl, nd, c->x0[d], parity, prev, outp);
         prev = outp;
         Fr* t = cur; cur = nxt; nxt = t;
       }
     }
-    hipLaunchKernelGGL(k_twist_finish, dim3(cdiv(n, TPB)), dim3(TPB), 0, st, ws.as<Fr>(), wd.as<Fr>(), n, ms.win, ms.wout);
+    DVP_LAUNCH(k_twist_finish, dim3(cdiv(n, TPB)), dim3(TPB), 0, st, ws.as<Fr>(), wd.as<Fr>(), n, ms.win, ms.wout);
     DVP_HIP(hipGetLastError());
     DVP_HIP(hipStreamSynchronize(st));  // the scratch buffers go out of scope
   }
@@ -803,8 +803,8 @@ static int extend_io(dvp_ecfft* c, int sl, int to_even, const Fr* src_in, Fr* da
     const uint32_t nn = batch <= 4 && batch >= 2 ? n : (uint32_t)((size_t)batch * n);
     const dim3 g(cdiv(nn >> 1, TPB)), b(TPB);
 #define DVP_BF(B) \
-  do { if (dec) hipLaunchKernelGGL((k_butterfly<B, true>), g, b, 0, st, src, data, tws, lh, nn, pre, post, n); \
-       else hipLaunchKernelGGL((k_butterfly<B, false>), g, b, 0, st, src, data, tws, lh, nn, pre, post, n); } while (0)
+  do { if (dec) DVP_LAUNCH((k_butterfly<B, true>), g, b, 0, st, src, data, tws, lh, nn, pre, post, n); \
+       else DVP_LAUNCH((k_butterfly<B, false>), g, b, 0, st, src, data, tws, lh, nn, pre, post, n); } while (0)
     if (batch == 4) DVP_BF(4); else if (batch == 3) DVP_BF(3); else if (batch == 2) DVP_BF(2); else DVP_BF(1);
 #undef DVP_BF
     src = data;
@@ -820,8 +820,8 @@ static int extend_io(dvp_ecfft* c, int sl, int to_even, const Fr* src_in, Fr* da
     const uint32_t nn = batch <= 4 && batch >= 2 ? n : (uint32_t)((size_t)batch * n);
     const dim3 g1(cdiv(nn >> 2, TPB));
 #define DVP_BF4(B, GRID) \
-  do { if (dec) hipLaunchKernelGGL((k_butterfly4<B, true>), GRID, b, 0, st, src, data, wide, narrow, lh2, nn, pre, post, n); \
-       else hipLaunchKernelGGL((k_butterfly4<B, false>), GRID, b, 0, st, src, data, wide, narrow, lh2, nn, pre, post, n); } while (0)
+  do { if (dec) DVP_LAUNCH((k_butterfly4<B, true>), GRID, b, 0, st, src, data, wide, narrow, lh2, nn, pre, post, n); \
+       else DVP_LAUNCH((k_butterfly4<B, false>), GRID, b, 0, st, src, data, wide, narrow, lh2, nn, pre, post, n); } while (0)
     if (batch == 4) DVP_BF4(4, g); else if (batch == 3) DVP_BF4(3, g); else if (batch == 2) DVP_BF4(2, g); else DVP_BF4(1, g1);
 #undef DVP_BF4
     src = data;
@@ -838,8 +838,8 @@ static int extend_io(dvp_ecfft* c, int sl, int to_even, const Fr* src_in, Fr* da
     const uint32_t nn = batch <= 4 && batch >= 2 ? n : (uint32_t)((size_t)batch * n);
     const dim3 g1(cdiv(nn >> 3, TPB));
 #define DVP_BF8(B, GRID) \
-  do { if (dec) hipLaunchKernelGGL((k_butterfly8<B, true>), GRID, b, 0, st, src, data, t0, t1, t2, lh3, nn, pre, post, n); \
-       else hipLaunchKernelGGL((k_butterfly8<B, false>), GRID, b, 0, st, src, data, t0, t1, t2, lh3, nn, pre, post, n); } while (0)
+  do { if (dec) DVP_LAUNCH((k_butterfly8<B, true>), GRID, b, 0, st, src, data, t0, t1, t2, lh3, nn, pre, post, n); \
+       else DVP_LAUNCH((k_butterfly8<B, false>), GRID, b, 0, st, src, data, t0, t1, t2, lh3, nn, pre, post, n); } while (0)
     if (batch == 4) DVP_BF8(4, g); else if (batch == 3) DVP_BF8(3, g); else if (batch == 2) DVP_BF8(2, g); else DVP_BF8(1, g1);
 #undef DVP_BF8
     src = data;
@@ -860,11 +860,11 @@ static int extend_io(dvp_ecfft* c, int sl, int to_even, const Fr* src_in, Fr* da
     if (dec) {
       ExtIo<0> e;
       fill(e, pre_of(), false);
-      hipLaunchKernelGGL((k_extend_top<true, 0>), g, b, 0, st, src, data, base, n, ln, d0, tl, batch, e);
+      DVP_LAUNCH((k_extend_top<true, 0>), g, b, 0, st, src, data, base, n, ln, d0, tl, batch, e);
     } else {
       (void)pre_of();
 #define DVP_TOP_LAST(SM_) \
-  do { ExtIo<SM_> e; fill(e, nullptr, last); hipLaunchKernelGGL((k_extend_top<false, SM_>), g, b, 0, st, src, data, base, n, ln, d0, tl, batch, e); } while (0)
+  do { ExtIo<SM_> e; fill(e, nullptr, last); DVP_LAUNCH((k_extend_top<false, SM_>), g, b, 0, st, src, data, base, n, ln, d0, tl, batch, e); } while (0)
       const int sm = last ? sm_last : 0;
       if (sm == 1) DVP_TOP_LAST(1); else if (sm == 2) DVP_TOP_LAST(2); else if (sm == 3) DVP_TOP_LAST(3); else DVP_TOP_LAST(0);
 #undef DVP_TOP_LAST
@@ -891,7 +891,7 @@ static int extend_io(dvp_ecfft* c, int sl, int to_even, const Fr* src_in, Fr* da
     const bool last = top == 0;
 #define DVP_FUSED(SM_) \
   do { ExtIo<SM_> e; fill(e, pre, last); \
-       hipLaunchKernelGGL((k_extend_fused<SM_>), dim3(cdiv(total, FUSE_ELEMS)), dim3(FUSE_TPB), 0, st, src, data, ms->dec, ms->rec, n, ln, lb, total, e); } while (0)
+       DVP_LAUNCH((k_extend_fused<SM_>), dim3(cdiv(total, FUSE_ELEMS)), dim3(FUSE_TPB), 0, st, src, data, ms->dec, ms->rec, n, ln, lb, total, e); } while (0)
     const int sm = last ? sm_last : 0;
     if (sm == 1) DVP_FUSED(1); else if (sm == 2) DVP_FUSED(2); else if (sm == 3) DVP_FUSED(3); else DVP_FUSED(0);
 #undef DVP_FUSED
@@ -920,7 +920,7 @@ static int get_xnn(dvp_ecfft* c, int sl, Fr** out, hipStream_t st) {
   uint32_t sz = c->n_leaves >> sl;
   Fr* p;
   DVP_HIP(hipMalloc((void**)&p, (size_t)sz * sizeof(Fr)));
-  hipLaunchKernelGGL(k_pow_table, dim3(cdiv(sz, TPB)), dim3(TPB), 0, st, c->layer(0), sl, sz, (uint64_t)(sz >> 1), p);
+  DVP_LAUNCH(k_pow_table, dim3(cdiv(sz, TPB)), dim3(TPB), 0, st, c->layer(0), sl, sz, (uint64_t)(sz >> 1), p);
   DVP_HIP(hipGetLastError());
   c->xnn[sl] = p;
   *out = p;
@@ -998,11 +998,11 @@ static int ecfft_init(dvp_ecfft* c, uint32_t log_n, int shifted, uint32_t base_l
     DVP_TRY(dy.alloc(log_n * sizeof(Fr)));
     DVP_HIP(hipMemcpy(dx.p, tx.data(), log_n * sizeof(Fr), hipMemcpyHostToDevice));
     DVP_HIP(hipMemcpy(dy.p, ty.data(), log_n * sizeof(Fr), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_leaves, dim3(cdiv(N, TPB)), dim3(TPB), 0, 0, dx.as<Fr>(), dy.as<Fr>(), C.x, C.y, (int)log_n,
+    DVP_LAUNCH(k_leaves, dim3(cdiv(N, TPB)), dim3(TPB), 0, 0, dx.as<Fr>(), dy.as<Fr>(), C.x, C.y, (int)log_n,
                        c->layer(0), N);
     for (uint32_t d = 0; d < log_n; ++d) {
       uint32_t half = (N >> d) >> 1;
-      hipLaunchKernelGGL(k_next_layer, dim3(cdiv(half, TPB)), dim3(TPB), 0, 0, c->layer(d), c->x0[d], c->t[d],
+      DVP_LAUNCH(k_next_layer, dim3(cdiv(half, TPB)), dim3(TPB), 0, 0, c->layer(d), c->x0[d], c->t[d],
                          c->layer(d + 1), half);
     }
     DVP_HIP(hipGetLastError());
@@ -1040,7 +1040,7 @@ extern "C" int dvp_ecfft_leaves(const dvp_ecfft* c, uint64_t* out) {
   size_t n = c->n_leaves;
   DevBuf tmp;
   DVP_TRY(tmp.alloc(n * sizeof(Fr)));
-  hipLaunchKernelGGL(k_from_mont, dim3(cdiv(n, TPB)), dim3(TPB), 0, 0, c->layer(0), tmp.as<Fr>(), n);
+  DVP_LAUNCH(k_from_mont, dim3(cdiv(n, TPB)), dim3(TPB), 0, 0, c->layer(0), tmp.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out, tmp.p, n * sizeof(Fr), hipMemcpyDeviceToHost));
   return DVP_OK;
@@ -1051,7 +1051,7 @@ static int check_canonical_dev(const Fr* d, size_t n, hipStream_t st) {
   DVP_TRY(bad.alloc(8));
   unsigned long long init = ~0ull;
   DVP_HIP(hipMemcpyAsync(bad.p, &init, 8, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_check_canonical, dim3(cdiv(n, TPB)), dim3(TPB), 0, st, d, n, bad.as<unsigned long long>());
+  DVP_LAUNCH(k_check_canonical, dim3(cdiv(n, TPB)), dim3(TPB), 0, st, d, n, bad.as<unsigned long long>());
   DVP_HIP(hipMemcpyAsync(&init, bad.p, 8, hipMemcpyDeviceToHost, st));
   DVP_HIP(hipStreamSynchronize(st));
   if (init != ~0ull) {
@@ -1229,7 +1229,7 @@ static int get_enter_tab(dvp_ecfft* c, int sl, EnterTab* out, hipStream_t st) {
   EnterTab tb;
   DVP_HIP(hipMalloc((void**)&tb.xe, (size_t)h * sizeof(Fr30)));
   DVP_HIP(hipMalloc((void**)&tb.t2, (size_t)h * sizeof(Fr30)));
-  hipLaunchKernelGGL(k_enter_fuse_tables, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, xnn, ms->wout, tb.xe, tb.t2, h);
+  DVP_LAUNCH(k_enter_fuse_tables, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, xnn, ms->wout, tb.xe, tb.t2, h);
   DVP_HIP(hipGetLastError());
   std::lock_guard<std::mutex> g(g_enter_mu);
   g_enter_tabs[c][sl] = tb;
@@ -1250,7 +1250,7 @@ static int enter_core(dvp_ecfft* c, int sl0, const Fr* d_coeffs, Fr* d_out, hipS
     Leaf8 l8;
     DVP_TRY(get_leaf8(c, &l8, st));
     Fr* dst = (c->log_n - 3 == sl0) ? d_out : bufs[nb];
-    hipLaunchKernelGGL(k_leaf_matmul8, dim3(cdiv(M / 8, TPB)), dim3(TPB), 0, st, d_coeffs, dst, l8.enter, M / 8);
+    DVP_LAUNCH(k_leaf_matmul8, dim3(cdiv(M / 8, TPB)), dim3(TPB), 0, st, d_coeffs, dst, l8.enter, M / 8);
     DVP_HIP(hipGetLastError());
     even = dst;
     nb ^= 1;
@@ -1275,7 +1275,7 @@ static int enter_core(dvp_ecfft* c, int sl0, const Fr* d_coeffs, Fr* d_out, hipS
       if (h > 1) DVP_TRY(extend_from(c, k, 0, even, odd, 2 * nsub, st));  // (h == 1: a constant is its own extension)
       Fr* xnn;
       DVP_TRY(get_xnn(c, k, &xnn, st));
-      hipLaunchKernelGGL(k_enter_combine, dim3(cdiv(nsub * h, TPB)), dim3(TPB), 0, st, even, h > 1 ? odd : even, xnn, dst, h, nsub * h);
+      DVP_LAUNCH(k_enter_combine, dim3(cdiv(nsub * h, TPB)), dim3(TPB), 0, st, even, h > 1 ? odd : even, xnn, dst, h, nsub * h);
       DVP_HIP(hipGetLastError());
     }
     even = dst;
@@ -1453,10 +1453,10 @@ static int ensure_exit_tables(dvp_ecfft* c, int sl_min, hipStream_t st) {
     Fr* xnn;
     DVP_TRY(get_xnn(c, sl, &xnn, st));
     // the even leaves of the stride-2^sl tree all map to layer-kk leaf 0 of the strided tree = layers[kk][0]
-    hipLaunchKernelGGL(k_exit_tables, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, c->layer(0), sl, h, xnn, c->d_x0, c->d_t, kk,
+    DVP_LAUNCH(k_exit_tables, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, c->layer(0), sl, h, xnn, c->d_x0, c->d_t, kk,
                        c->layer(kk), tb.xinv, tb.z0inv);
     if (h == 1) {
-      hipLaunchKernelGGL(k_c_base, dim3(1), dim3(1), 0, st, c->layer(0), tb.ctab);
+      DVP_LAUNCH(k_c_base, dim3(1), dim3(1), 0, st, c->layer(0), tb.ctab);
     } else {
       // (1) z = Z_0 - X^h in coefficient form: exit on the even subtree of the evaluations -leaf^h
       DevBuf zlow, lo, hi, A, B, rho;
@@ -1466,7 +1466,7 @@ static int ensure_exit_tables(dvp_ecfft* c, int sl_min, hipStream_t st) {
       DVP_TRY(A.alloc((size_t)h * sizeof(Fr)));
       DVP_TRY(B.alloc((size_t)h * sizeof(Fr)));
       DVP_TRY(rho.alloc((size_t)sz * sizeof(Fr)));
-      hipLaunchKernelGGL(k_neg_from_mont_even, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, xnn, lo.as<Fr>(), h);
+      DVP_LAUNCH(k_neg_from_mont_even, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, xnn, lo.as<Fr>(), h);
       DVP_TRY(exit_core(c, sl + 1, lo.as<Fr>(), zlow.as<Fr>(), st));
       // (2) z = z_lo + X^(h/2) z_hi;  Z_0^2 mod X^h = z_lo^2 + 2 X^(h/2) (z_lo z_hi mod X^(h/2))
       DVP_HIP(hipMemsetAsync(lo.p, 0, (size_t)h * sizeof(Fr), st));
@@ -1475,16 +1475,16 @@ static int ensure_exit_tables(dvp_ecfft* c, int sl_min, hipStream_t st) {
       DVP_HIP(hipMemcpyAsync(hi.p, zlow.as<Fr>() + h / 2, (size_t)(h / 2) * sizeof(Fr), hipMemcpyDeviceToDevice, st));
       DVP_TRY(enter_core(c, sl + 1, lo.as<Fr>(), A.as<Fr>(), st));  // <z_lo> on the even subtree
       DVP_TRY(enter_core(c, sl + 1, hi.as<Fr>(), B.as<Fr>(), st));  // <z_hi>
-      hipLaunchKernelGGL(k_mul_canon, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, A.as<Fr>(), B.as<Fr>(), hi.as<Fr>(), h);  // <z_lo z_hi>
-      hipLaunchKernelGGL(k_mul_canon, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, A.as<Fr>(), A.as<Fr>(), lo.as<Fr>(), h);  // <z_lo^2>
+      DVP_LAUNCH(k_mul_canon, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, A.as<Fr>(), B.as<Fr>(), hi.as<Fr>(), h);  // <z_lo z_hi>
+      DVP_LAUNCH(k_mul_canon, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, A.as<Fr>(), A.as<Fr>(), lo.as<Fr>(), h);  // <z_lo^2>
       DVP_TRY(exit_core(c, sl + 1, lo.as<Fr>(), A.as<Fr>(), st));
       DVP_TRY(exit_core(c, sl + 1, hi.as<Fr>(), B.as<Fr>(), st));
-      hipLaunchKernelGGL(k_rho, dim3(cdiv(sz, TPB)), dim3(TPB), 0, st, A.as<Fr>(), B.as<Fr>(), rho.as<Fr>(), h);
+      DVP_LAUNCH(k_rho, dim3(cdiv(sz, TPB)), dim3(TPB), 0, st, A.as<Fr>(), B.as<Fr>(), rho.as<Fr>(), h);
       // (3) evaluate on the whole subtree, keep in Montgomery form
       DevBuf ev;
       DVP_TRY(ev.alloc((size_t)sz * sizeof(Fr)));
       DVP_TRY(enter_core(c, sl, rho.as<Fr>(), ev.as<Fr>(), st));
-      hipLaunchKernelGGL(k_to_mont, dim3(cdiv(sz, TPB)), dim3(TPB), 0, st, ev.as<Fr>(), tb.ctab, sz);
+      DVP_LAUNCH(k_to_mont, dim3(cdiv(sz, TPB)), dim3(TPB), 0, st, ev.as<Fr>(), tb.ctab, sz);
       DVP_HIP(hipGetLastError());
       DVP_HIP(hipStreamSynchronize(st));  // DevBufs go out of scope
     }
@@ -1494,7 +1494,7 @@ static int ensure_exit_tables(dvp_ecfft* c, int sl_min, hipStream_t st) {
       DVP_TRY(build_matset(c, sl, 0, &ms, st));
       DVP_HIP(hipMalloc((void**)&tb.fused, (size_t)6 * h * sizeof(Fr30)));
       Fr30* f = tb.fused;
-      hipLaunchKernelGGL(k_exit_fuse_tables, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, ms->win, ms->wout, tb.xinv, tb.z0inv, xnn, tb.ctab, f, f + h, f + 2 * (size_t)h,
+      DVP_LAUNCH(k_exit_fuse_tables, dim3(cdiv(h, TPB)), dim3(TPB), 0, st, ms->win, ms->wout, tb.xinv, tb.z0inv, xnn, tb.ctab, f, f + h, f + 2 * (size_t)h,
                          f + 3 * (size_t)h, f + 4 * (size_t)h, f + 5 * (size_t)h, h);
       DVP_HIP(hipGetLastError());
     }
@@ -1538,9 +1538,9 @@ static int exit_core(dvp_ecfft* c, int sl0, const Fr* d_evals, Fr* d_out, hipStr
     DVP_TRY(get_xnn(c, k, &xnn, st));
     dim3 grid(cdiv(total, TPB)), blk(TPB);
     auto redc = [&](const Fr* ev) -> int {  // leaves h0 (even part) and h1 (odd part)
-      hipLaunchKernelGGL(k_exit_pre, grid, blk, 0, st, ev, tb.xinv, t0, h, total);
+      DVP_LAUNCH(k_exit_pre, grid, blk, 0, st, ev, tb.xinv, t0, h, total);
       DVP_TRY(extend_inplace(c, k, 0, t0, nsub, st));
-      hipLaunchKernelGGL(k_exit_mid, grid, blk, 0, st, ev, t0, xnn, tb.z0inv, h1, h, total);
+      DVP_LAUNCH(k_exit_mid, grid, blk, 0, st, ev, t0, xnn, tb.z0inv, h1, h, total);
       DVP_TRY(extend_from(c, k, 1, h1, h0, nsub, st));  // (h == 1: a copy)
       return DVP_OK;
     };
@@ -1561,12 +1561,12 @@ static int exit_core(dvp_ecfft* c, int sl0, const Fr* d_evals, Fr* d_out, hipStr
       b2.sm = 2; b2.out = nxt; b2.tb = XI; b2.aux = cur; b2.lh = lh;
       DVP_TRY(extend_io(c, k, 1, h1b, h0, nsub, st, &b2));
     } else if (h == 1 && tune().ecfft_fold != 0) {
-      hipLaunchKernelGGL(k_exit_leaf, grid, blk, 0, st, cur, tb.xinv, tb.z0inv, xnn, tb.ctab, nxt, nsub);
+      DVP_LAUNCH(k_exit_leaf, grid, blk, 0, st, cur, tb.xinv, tb.z0inv, xnn, tb.ctab, nxt, nsub);
     } else {
       DVP_TRY(redc(cur));
-      hipLaunchKernelGGL(k_exit_mulc, grid, blk, 0, st, h0, h1, tb.ctab, r1, h, total);
+      DVP_LAUNCH(k_exit_mulc, grid, blk, 0, st, h0, h1, tb.ctab, r1, h, total);
       DVP_TRY(redc(r1));
-      hipLaunchKernelGGL(k_exit_post, grid, blk, 0, st, cur, h0, tb.xinv, nxt, h, total);
+      DVP_LAUNCH(k_exit_post, grid, blk, 0, st, cur, h0, tb.xinv, nxt, h, total);
     }
     DVP_HIP(hipGetLastError());
     cur = nxt;
@@ -1575,7 +1575,7 @@ static int exit_core(dvp_ecfft* c, int sl0, const Fr* d_evals, Fr* d_out, hipStr
   if (leaf8) {
     Leaf8 l8;
     DVP_TRY(get_leaf8(c, &l8, st));
-    hipLaunchKernelGGL(k_leaf_matmul8, dim3(cdiv(M / 8, TPB)), dim3(TPB), 0, st, cur, d_out, l8.exit, M / 8);
+    DVP_LAUNCH(k_leaf_matmul8, dim3(cdiv(M / 8, TPB)), dim3(TPB), 0, st, cur, d_out, l8.exit, M / 8);
     DVP_HIP(hipGetLastError());
   }
   return DVP_OK;
@@ -1676,10 +1676,10 @@ extern "C" int dvp_debug_ecfft_matrices(dvp_ecfft* c, int to_even, int which, ui
   for (int d = 0; d < ln; ++d) {
     const uint32_t nd = nv >> d;
     const size_t off = 4 * (size_t)(nv - nd);
-    hipLaunchKernelGGL(k_build_mats, dim3(cdiv(nd >> 1, TPB)), dim3(TPB), 0, 0, c->layer(d), 0, nd, c->x0[d], src, dst, dec.as<Fr29>() + off,
+    DVP_LAUNCH(k_build_mats, dim3(cdiv(nd >> 1, TPB)), dim3(TPB), 0, 0, c->layer(d), 0, nd, c->x0[d], src, dst, dec.as<Fr29>() + off,
                        rec.as<Fr29>() + off);
   }
-  hipLaunchKernelGGL(k_mats_export, dim3(cdiv(n, TPB)), dim3(TPB), 0, 0, which ? rec.as<Fr29>() : dec.as<Fr29>(), tmp.as<Fr>(), n);
+  DVP_LAUNCH(k_mats_export, dim3(cdiv(n, TPB)), dim3(TPB), 0, 0, which ? rec.as<Fr29>() : dec.as<Fr29>(), tmp.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out, tmp.p, n * sizeof(Fr), hipMemcpyDeviceToHost));
   return DVP_OK;
@@ -1689,7 +1689,7 @@ extern "C" int dvp_debug_ecfft_layer(const dvp_ecfft* c, uint32_t d, uint64_t* o
   const size_t n = c->n_leaves >> d;
   DevBuf tmp;
   DVP_TRY(tmp.alloc(n * sizeof(Fr)));
-  hipLaunchKernelGGL(k_from_mont, dim3(cdiv(n, TPB)), dim3(TPB), 0, 0, c->layer((int)d), tmp.as<Fr>(), n);
+  DVP_LAUNCH(k_from_mont, dim3(cdiv(n, TPB)), dim3(TPB), 0, 0, c->layer((int)d), tmp.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out, tmp.p, n * sizeof(Fr), hipMemcpyDeviceToHost));
   return DVP_OK;

@@ -94,7 +94,7 @@ static void fr_debug_host(const uint64_t* const* in, size_t n, uint64_t* const* 
 
 template <int OP>
 static void fr_debug_launch(const FrDebugPtrs& p, size_t n) {
-  hipLaunchKernelGGL((k_fr_debug<OP>), dim3(cdiv(n, 256)), dim3(256), 0, 0, p, n);
+  DVP_LAUNCH((k_fr_debug<OP>), dim3(cdiv(n, 256)), dim3(256), 0, 0, p, n);
 }
 
 // ---- the preconditions, in plain integer compares on the host (no function under test decides them, bar one: see MULADD30) --------

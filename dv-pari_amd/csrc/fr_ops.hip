@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(256) k_ubench_fr30(Fr30* __restrict__ out, int
 
 int batch_inverse_dev(Fr* d, size_t n, hipStream_t st) {
   if (!n) return DVP_OK;
-#define DVP_BI(TPB, CH) hipLaunchKernelGGL((k_batch_inverse<TPB, CH>), dim3(cdiv(n, (size_t)TPB * CH)), dim3(TPB), 0, st, d, n)
+#define DVP_BI(TPB, CH) DVP_LAUNCH((k_batch_inverse<TPB, CH>), dim3(cdiv(n, (size_t)TPB * CH)), dim3(TPB), 0, st, d, n)
   switch ((int)tune().fr_bi_shape) {
     case 0: DVP_BI(512, 16); break;  // rounds 3-4
     case 1: DVP_BI(256, 8); break;
@@ -200,8 +200,8 @@ int barycentric_dev(const Fr* dom, const Fr* wts, const Fr* ev, size_t n, Fr alp
                     Fr* d_partial, Fr* d_out, hipStream_t st) {
   size_t threads = (n + INV_CHUNK - 1) / INV_CHUNK;
   uint32_t nb = cdiv(threads, 256);
-  hipLaunchKernelGGL(k_bary_partial, dim3(nb), dim3(256), 0, st, dom, wts, ev, n, alpha_m, tables_mont, d_partial);
-  hipLaunchKernelGGL(k_bary_final, dim3(1), dim3(256), 0, st, d_partial, nb, z_alpha_m, d_out);
+  DVP_LAUNCH(k_bary_partial, dim3(nb), dim3(256), 0, st, dom, wts, ev, n, alpha_m, tables_mont, d_partial);
+  DVP_LAUNCH(k_bary_final, dim3(1), dim3(256), 0, st, d_partial, nb, z_alpha_m, d_out);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
@@ -223,9 +223,9 @@ extern "C" int dvp_ubench_fr_mul(int reps, double* muladds_per_s) {
   hipEvent_t e0, e1;
   DVP_HIP(hipEventCreate(&e0));
   DVP_HIP(hipEventCreate(&e1));
-  hipLaunchKernelGGL(k_ubench_fr30, dim3(blocks), dim3(256), 0, 0, out.as<Fr30>(), 8);
+  DVP_LAUNCH(k_ubench_fr30, dim3(blocks), dim3(256), 0, 0, out.as<Fr30>(), 8);
   DVP_HIP(hipEventRecord(e0, 0));
-  hipLaunchKernelGGL(k_ubench_fr30, dim3(blocks), dim3(256), 0, 0, out.as<Fr30>(), reps);
+  DVP_LAUNCH(k_ubench_fr30, dim3(blocks), dim3(256), 0, 0, out.as<Fr30>(), reps);
   DVP_HIP(hipEventRecord(e1, 0));
   DVP_HIP(hipEventSynchronize(e1));
   float ms = 0;
@@ -342,7 +342,7 @@ extern "C" int dvp_fr_vec_mul(const uint64_t* a, const uint64_t* b, size_t n, ui
   DevBuf da, db;
   DVP_TRY(up(da, a, n * 32));
   DVP_TRY(up(db, b, n * 32));
-  hipLaunchKernelGGL(k_vec_mul, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), db.as<Fr>(), da.as<Fr>(), n);
+  DVP_LAUNCH(k_vec_mul, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), db.as<Fr>(), da.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out, da.p, n * 32, hipMemcpyDeviceToHost));
   return DVP_OK;
@@ -355,7 +355,7 @@ extern "C" int dvp_fr_vec_scale(const uint64_t* a, const uint64_t s[4], size_t n
   if (!fr_is_canonical(sc)) return DVP_EINVAL;
   DevBuf da;
   DVP_TRY(up(da, a, n * 32));
-  hipLaunchKernelGGL(k_vec_scale, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), fr_to_mont(sc), da.as<Fr>(), n);
+  DVP_LAUNCH(k_vec_scale, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), fr_to_mont(sc), da.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out, da.p, n * 32, hipMemcpyDeviceToHost));
   return DVP_OK;
@@ -369,7 +369,7 @@ extern "C" int dvp_fr_vec_axpy(const uint64_t* a, const uint64_t s[4], const uin
   DevBuf da, db;
   DVP_TRY(up(da, a, n * 32));
   DVP_TRY(up(db, b, n * 32));
-  hipLaunchKernelGGL(k_vec_axpy, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), fr_to_mont(sc), db.as<Fr>(), da.as<Fr>(), n);
+  DVP_LAUNCH(k_vec_axpy, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), fr_to_mont(sc), db.as<Fr>(), da.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out, da.p, n * 32, hipMemcpyDeviceToHost));
   return DVP_OK;
@@ -382,7 +382,7 @@ extern "C" int dvp_fr_vec_scalar_sub(const uint64_t s[4], const uint64_t* a, siz
   if (!fr_is_canonical(sc)) return DVP_EINVAL;
   DevBuf da;
   DVP_TRY(up(da, a, n * 32));
-  hipLaunchKernelGGL(k_vec_scalar_sub, dim3(cdiv(n, 256)), dim3(256), 0, 0, sc, da.as<Fr>(), da.as<Fr>(), n);
+  DVP_LAUNCH(k_vec_scalar_sub, dim3(cdiv(n, 256)), dim3(256), 0, 0, sc, da.as<Fr>(), da.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out, da.p, n * 32, hipMemcpyDeviceToHost));
   return DVP_OK;
@@ -401,8 +401,8 @@ extern "C" int dvp_fr_vec_dot(const uint64_t* a, const uint64_t* b, size_t n, ui
   if (nb > 1024) nb = 1024;
   DVP_TRY(part.alloc(nb * sizeof(Fr)));
   DVP_TRY(o.alloc(sizeof(Fr)));
-  hipLaunchKernelGGL(k_vec_dot_partial, dim3(nb), dim3(256), 0, 0, da.as<Fr>(), db.as<Fr>(), n, part.as<Fr>());
-  hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(256), 0, 0, part.as<Fr>(), nb, o.as<Fr>());
+  DVP_LAUNCH(k_vec_dot_partial, dim3(nb), dim3(256), 0, 0, da.as<Fr>(), db.as<Fr>(), n, part.as<Fr>());
+  DVP_LAUNCH(k_sum_final, dim3(1), dim3(256), 0, 0, part.as<Fr>(), nb, o.as<Fr>());
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out, o.p, 32, hipMemcpyDeviceToHost));
   return DVP_OK;
@@ -430,7 +430,7 @@ extern "C" int dvp_fr_spmv(const uint32_t* row_ptr, const uint32_t* col, const u
   DVP_TRY(up(cf, coeffs, (size_t)n_coeffs * 32));
   DVP_TRY(up(dx, x, (size_t)n_cols * 32));
   DVP_TRY(o.alloc((size_t)n_rows * 32));
-  hipLaunchKernelGGL(k_spmv, dim3(cdiv(n_rows, 256)), dim3(256), 0, 0, rp.as<uint32_t>(), c.as<uint32_t>(), id.as<uint32_t>(),
+  DVP_LAUNCH(k_spmv, dim3(cdiv(n_rows, 256)), dim3(256), 0, 0, rp.as<uint32_t>(), c.as<uint32_t>(), id.as<uint32_t>(),
                      cf.as<Fr>(), dx.as<Fr>(), n_rows, o.as<Fr>());
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out, o.p, (size_t)n_rows * 32, hipMemcpyDeviceToHost));

@@ -183,7 +183,7 @@ static int gf_debug_launch(const GfDebugPtrs& p, size_t n, uint32_t param, const
     const uint32_t groups = (waves ? waves : 1u) * 64u / F::G;
     const uint32_t lds = 4u * F::LDS_PER_WAVE;
     if (lds) DVP_HIP(hipFuncSetAttribute((const void*)k_gf_debug<OP, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_gf_debug<OP, FORM>), dim3(cdiv((size_t)groups * F::G, 256)), dim3(256), lds, 0, p, (uint32_t)n, groups, param, T);
+    DVP_LAUNCH((k_gf_debug<OP, FORM>), dim3(cdiv((size_t)groups * F::G, 256)), dim3(256), lds, 0, p, (uint32_t)n, groups, param, T);
     DVP_HIP(hipGetLastError());
     return DVP_OK;
   }

@@ -195,9 +195,8 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* t
   return block_scan_waves<SCAN_TPB / 64>(v, total, sh);  // sh: 256 entries
 }
 
-// PAD2: every count is rounded up to even first (fixed-base sort: buckets then start at even positions of the sorted
+// every count is rounded up to even first (both sorts: buckets then start at even positions of the sorted
 // item list, so the list read as uint2 pairs IS the first pair round's descriptor array, see k_post_sort)
-template <bool PAD2>
 __global__ void __launch_bounds__(SCAN_TPB) k_scan_local(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                          uint32_t* __restrict__ bsum, uint32_t m) {
   __shared__ uint32_t sh[SCAN_TPB];
@@ -206,7 +205,7 @@ __global__ void __launch_bounds__(SCAN_TPB) k_scan_local(const uint32_t* __restr
 #pragma unroll
   for (int k = 0; k < SCAN_EPT; ++k) {
     v[k] = (base + k < m) ? in[base + k] : 0;
-    if (PAD2) v[k] = (v[k] + 1u) & ~1u;
+    v[k] = (v[k] + 1u) & ~1u;
     s += v[k];
   }
   uint32_t tot;
@@ -279,18 +278,15 @@ __global__ void __launch_bounds__(SCAN_TPB) k_scan_add_fold(uint32_t* __restrict
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total_out = add + bsum_raw[blockIdx.x];
 }
 
-// out[0..m) = exclusive scan of in[0..m); out[m] = total
-static int scan_exclusive(const uint32_t* in, uint32_t* out, uint32_t m, uint32_t* bsum, hipStream_t st, bool pad2 = false) {
+// out[0..m) = exclusive scan of in[0..m) rounded up to even; out[m] = total
+static int scan_exclusive_pad2(const uint32_t* in, uint32_t* out, uint32_t m, uint32_t* bsum, hipStream_t st) {
   uint32_t nb = cdiv(m, SCAN_BLK);
-  if (pad2)
-    hipLaunchKernelGGL(k_scan_local<true>, dim3(nb), dim3(SCAN_TPB), 0, st, in, out, bsum, m);
-  else
-    hipLaunchKernelGGL(k_scan_local<false>, dim3(nb), dim3(SCAN_TPB), 0, st, in, out, bsum, m);
+  DVP_LAUNCH(k_scan_local, dim3(nb), dim3(SCAN_TPB), 0, st, in, out, bsum, m);
   if (nb <= SCAN_FOLD_NB)
-    hipLaunchKernelGGL(k_scan_add_fold, dim3(nb), dim3(SCAN_TPB), 0, st, out, bsum, m, out + m);
+    DVP_LAUNCH(k_scan_add_fold, dim3(nb), dim3(SCAN_TPB), 0, st, out, bsum, m, out + m);
   else {
-    hipLaunchKernelGGL(k_scan_bsums, dim3(1), dim3(SCAN_TPB), 0, st, bsum, nb, out + m);
-    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(SCAN_TPB), 0, st, out, bsum, m);
+    DVP_LAUNCH(k_scan_bsums, dim3(1), dim3(SCAN_TPB), 0, st, bsum, nb, out + m);
+    DVP_LAUNCH(k_scan_add, dim3(nb), dim3(SCAN_TPB), 0, st, out, bsum, m);
   }
   DVP_HIP(hipGetLastError());
   return DVP_OK;
@@ -299,12 +295,12 @@ static int scan_exclusive(const uint32_t* in, uint32_t* out, uint32_t m, uint32_
 // vout[i] = ceil(in[i] / K); out = exclusive scan of vout (out[m] = total): the per-round bookkeeping of the bucket reducers
 static int scan_exclusive_div(const uint32_t* in, uint32_t K, uint32_t* vout, uint32_t* out, uint32_t m, uint32_t* bsum, hipStream_t st) {
   uint32_t nb = cdiv(m, SCAN_BLK);
-  hipLaunchKernelGGL(k_scan_local_div, dim3(nb), dim3(SCAN_TPB), 0, st, in, K, vout, out, bsum, m);
+  DVP_LAUNCH(k_scan_local_div, dim3(nb), dim3(SCAN_TPB), 0, st, in, K, vout, out, bsum, m);
   if (nb <= SCAN_FOLD_NB)
-    hipLaunchKernelGGL(k_scan_add_fold, dim3(nb), dim3(SCAN_TPB), 0, st, out, bsum, m, out + m);
+    DVP_LAUNCH(k_scan_add_fold, dim3(nb), dim3(SCAN_TPB), 0, st, out, bsum, m, out + m);
   else {
-    hipLaunchKernelGGL(k_scan_bsums, dim3(1), dim3(SCAN_TPB), 0, st, bsum, nb, out + m);
-    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(SCAN_TPB), 0, st, out, bsum, m);
+    DVP_LAUNCH(k_scan_bsums, dim3(1), dim3(SCAN_TPB), 0, st, bsum, nb, out + m);
+    DVP_LAUNCH(k_scan_add, dim3(nb), dim3(SCAN_TPB), 0, st, out, bsum, m);
   }
   DVP_HIP(hipGetLastError());
   return DVP_OK;
@@ -1068,7 +1064,7 @@ int gf_sqr_tables(GfSqrTables* out, hipStream_t st) {
   if (!g_sqr_tab[dev]) {
     Gf* t;
     DVP_HIP(hipMalloc((void**)&t, (size_t)6 * 30 * 256 * sizeof(Gf)));
-    hipLaunchKernelGGL(k_build_sqr_tables, dim3(cdiv(6 * 30 * 256, 256)), dim3(256), 0, st, t);
+    DVP_LAUNCH(k_build_sqr_tables, dim3(cdiv(6 * 30 * 256, 256)), dim3(256), 0, st, t);
     DVP_HIP(hipGetLastError());
     DVP_HIP(hipStreamSynchronize(st));
     g_sqr_tab[dev] = t;
@@ -1106,7 +1102,7 @@ constexpr uint32_t DESC_PAIR = 0x80000000u;
 // Both sorts lay every bucket out from an EVEN position of the item list (scan of the counts rounded up to
 // even); an odd bucket's spare slot gets AFF_NONE.  The list read as uint2 pairs is then exactly the descriptor array of
 // the first pair round -- (a, b) table indices, b = NONE for the odd leftover -- so that round needs no descriptor
-// kernel and no scan: its output offsets are the item offsets halved (k_round0_offsets).
+// kernel and no scan: its output offsets are the item offsets halved (k_post_sort, or the all-rounds scan).
 // the three per-key passes between the sort and the first pair round of an MSM whose bookkeeping is not done by the all-rounds scan (small
 // one-shot MSMs) as ONE launch (round 6): the NONE behind every odd bucket, the first round's counts and offsets, the largest bucket
 __global__ void __launch_bounds__(256)
@@ -1126,14 +1122,6 @@ k_post_sort(uint32_t* __restrict__ items, const uint32_t* __restrict__ cnt, cons
   }
   for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
   if ((threadIdx.x & 63) == 0 && m) atomicMax(d_max, m);
-}
-__global__ void __launch_bounds__(256)
-k_round0_offsets(const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ off /* nkeys + 1, even */, uint32_t nkeys,
-                 uint32_t* __restrict__ ocnt, uint32_t* __restrict__ ooff /* nkeys + 1 */) {
-  uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k > nkeys) return;
-  ooff[k] = off[k] >> 1;
-  if (k < nkeys) ocnt[k] = (cnt[k] + 1) >> 1;
 }
 
 // ---- the bookkeeping of ALL pair rounds at once (round 4) --------------------------------------------------------------------
@@ -1725,7 +1713,7 @@ __global__ void __launch_bounds__(EC_TPB) k_tail_groups(const Ld* __restrict__ A
 template <bool HEX>
 __global__ void __launch_bounds__(EC_TPB) k_tail(const Ld* __restrict__ A, int c, int W, int n_narrow, GfSqrTables T, Ld* __restrict__ buf,
                                                  uint32_t* __restrict__ out_xy, uint32_t* __restrict__ out_inf, uint8_t* __restrict__ out_enc, int rule,
-                                                 unsigned long long* __restrict__ ctrl /* msm_core's control words: [0] err, [1] d_max | rest_n, [2] err_out */, unsigned long long* __restrict__ err_dst) {
+                                                 unsigned long long* __restrict__ ctrl /* msm_core's control words: [0] err, [1] d_max | rest_n, [2] err_out, [3] last MSM's [1] */, unsigned long long* __restrict__ err_dst) {
   using LT = typename std::conditional<HEX, GfLdsH, GfLdsQ>::type;
   constexpr int GS = HEX ? 4 : 2;             // log2 lanes per point
   constexpr uint32_t NG = EC_TPB >> GS;       // points in flight per pass
@@ -1833,6 +1821,7 @@ __global__ void __launch_bounds__(EC_TPB) k_tail(const Ld* __restrict__ A, int c
   const unsigned long long e = ctrl[0];
   if (err_dst) *err_dst = e;
   ctrl[2] = e;
+  ctrl[3] = ctrl[1];  // (d_max | rest_n) of this MSM, kept for dvp_debug_msm_rest_len
   ctrl[0] = ~0ull;
   ctrl[1] = 0ull;
 }
@@ -2036,6 +2025,12 @@ struct MsmWorkspace {
 constexpr int MSM_MAX_DEVICES = 16;
 constexpr int MSM_WS_SLOTS = 2;
 static MsmWorkspace g_ws_dev[MSM_MAX_DEVICES][MSM_WS_SLOTS];
+// where the calling thread's last MSM ran (dvp_debug_msm_rest_len)
+struct LastMsm {
+  int dev = -1, slot = 0;
+  hipStream_t st = nullptr;
+};
+static thread_local LastMsm g_last_msm;
 static std::atomic<size_t> g_ws_need[MSM_MAX_DEVICES];
 // Two MSMs on one device overlap everything EXCEPT their pair rounds: those fill the chip on their own (two of them side by side
 // only contend: measured 4 % slower than taking turns), while everything around them -- sort, reducer, merge levels, tail, the
@@ -2236,6 +2231,7 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
     }
   if (!g.owns_lock()) g = std::unique_lock<std::mutex>(g_ws_dev[cur_dev][0].mu);
   MsmWorkspace& g_ws = g_ws_dev[cur_dev][ws_slot];
+  g_last_msm = LastMsm{cur_dev, ws_slot, st};
   if (g_ws.busy_valid) {  // kernels of a deferred MSM may still be using this workspace
     if (g_ws.busy_stream != st) DVP_HIP(hipStreamWaitEvent(st, g_ws.ev_busy, 0));
     g_ws.busy_valid = false;
@@ -2243,7 +2239,7 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
   // carve the workspace
   size_t o = 0;
   auto carve = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes); return r; };
-  size_t o_err = carve(32);  // err (u64) | d_max, rest_n (u32 each) | err_out (u64): the tail kernel's copy of err for the host
+  size_t o_err = carve(32);  // err (u64) | d_max, rest_n (u32 each) | err_out (u64): the tail kernel's copy of err for the host | the tail kernel's copy of (d_max, rest_n)
   size_t o_digits = carve(fx ? 16 : (size_t)p.W * n * 2);
   // signed flavour: level 1 of the sort reads the scalars themselves (k_part_hist_signed), a block per fx_S scalars
   const bool fused1 = fx && fx->signed_digits && tune().msm_sort_fused != 0;
@@ -2305,7 +2301,8 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
   size_t o_bsum2 = carve(((size_t)((ra_plan > 0 ? ra_plan : 1) + 1) * ((size_t)p.nkeys / SCAN_BLK + 1) + 8) * 4);  // scan scratch of the side stream: a row of block sums per round
   size_t o_bkt = carve((size_t)p.nkeys * sizeof(Ld));
   // k_bucket_pairs' list of buckets that met an exceptional pair (<= nkeys), or k_accum_affine_fast's list of such TASKS (chunks of K entries)
-  const size_t rest_cap = (size_t)p.nkeys + 2 + p.e_max / (size_t)(p.K > 0 ? p.K : 1);
+  // (sized by the reducer's own bound on its first-level tasks at its largest, no pair round run: (e_max + nkeys) / K + nkeys + 1)
+  const size_t rest_cap = (size_t)p.nkeys + 2 + (p.e_max + (size_t)p.nkeys) / (size_t)(p.K > 0 ? p.K : 1);
   size_t o_rest = carve(rest_cap * 4);
   const uint32_t tail_groups = ((uint32_t)(p.W * p.c) + 15u) / 16u;  // k_tail_groups: workgroups of 16 points
   size_t o_tail = carve(((size_t)2 * p.W * p.c + 1 + 2 * (size_t)tail_groups) * sizeof(Ld));
@@ -2350,7 +2347,7 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
     DVP_TRY(scan_exclusive_div(ic, 2u, oc, oo, nk, bs, s));
     // descriptors: lanes per bucket by the average bucket size of this round
     const size_t per_key = (e_est >> (r + 1)) / nk;
-#define DVP_DESC_LAUNCH(LPK) hipLaunchKernelGGL((k_round_desc<LPK>), dim3(cdiv((size_t)nk * LPK, 256)), dim3(256), 0, s, ic, io, oo, nk, dsc)
+#define DVP_DESC_LAUNCH(LPK) DVP_LAUNCH((k_round_desc<LPK>), dim3(cdiv((size_t)nk * LPK, 256)), dim3(256), 0, s, ic, io, oo, nk, dsc)
     if (per_key >= 48) DVP_DESC_LAUNCH(64); else if (per_key >= 8) DVP_DESC_LAUNCH(16); else DVP_DESC_LAUNCH(4);
 #undef DVP_DESC_LAUNCH
     return DVP_OK;
@@ -2397,18 +2394,21 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
     const uint32_t nb = cdiv(nk, SCAN_BLK);
     // (the caller's stream only: the side-stream flavour keeps the sort's own scan, padding and maximum)
     uint32_t* off0 = side_stream ? nullptr : off;
-    hipLaunchKernelGGL(k_mscan_local, dim3(nb), dim3(SCAN_TPB), 0, bk, cnt, nk, ra_plan, rp, bsum2);
-    hipLaunchKernelGGL(k_mscan_bsums, dim3(ra_plan), dim3(SCAN_TPB), 0, bk, bsum2, nb, nk, rp, off0, off0 ? d_max : (uint32_t*)nullptr);
+    DVP_LAUNCH(k_mscan_local, dim3(nb), dim3(SCAN_TPB), 0, bk, cnt, nk, ra_plan, rp, bsum2);
+    DVP_LAUNCH(k_mscan_bsums, dim3(ra_plan), dim3(SCAN_TPB), 0, bk, bsum2, nb, nk, rp, off0, off0 ? d_max : (uint32_t*)nullptr);
     if (off0) DVP_TRY(read_max());  // the largest bucket is on its way to the host before the descriptors and the last scatter run
-    hipLaunchKernelGGL(k_mscan_add, dim3(nb), dim3(SCAN_TPB), 0, bk, rp, bsum2, nk, ra_plan, (const uint32_t*)cnt, off0, items);
+    DVP_LAUNCH(k_mscan_add, dim3(nb), dim3(SCAN_TPB), 0, bk, rp, bsum2, nk, ra_plan, (const uint32_t*)cnt, off0, items);
     DescPlan plan;
     for (int q = 0; q < 40; ++q) plan.at[q] = q < ra_plan ? desc_at[q] : 0;
     const size_t per_key = (e_est >> 2) / nk;  // round 1's outputs per bucket
     const int lpk = per_key >= 48 ? 64 : per_key >= 8 ? 16 : 4;
-    auto desc_all = lpk == 64 ? (dense ? k_round_desc_all<64, true> : k_round_desc_all<64, false>)
-                  : lpk == 16 ? (dense ? k_round_desc_all<16, true> : k_round_desc_all<16, false>)
-                              : (dense ? k_round_desc_all<4, true> : k_round_desc_all<4, false>);
-    hipLaunchKernelGGL(desc_all, dim3(cdiv((size_t)nk * lpk, 1024)), dim3(1024), 0, bk, rp, nk, ra_plan, plan, gdesc);
+#define DVP_DESC_ALL(LPK)                                                                                                                   \
+  do {                                                                                                                                     \
+    if (dense) DVP_LAUNCH((k_round_desc_all<LPK, true>), dim3(cdiv((size_t)nk * LPK, 1024)), dim3(1024), 0, bk, rp, nk, ra_plan, plan, gdesc); \
+    else DVP_LAUNCH((k_round_desc_all<LPK, false>), dim3(cdiv((size_t)nk * LPK, 1024)), dim3(1024), 0, bk, rp, nk, ra_plan, plan, gdesc);      \
+  } while (0)
+    if (lpk == 64) DVP_DESC_ALL(64); else if (lpk == 16) DVP_DESC_ALL(16); else DVP_DESC_ALL(4);
+#undef DVP_DESC_ALL
     if (side_stream) DVP_HIP(hipEventRecord(g_ws.ev_side[0], g_ws.side));
     DVP_HIP(hipGetLastError());
     prepared = ra_plan;
@@ -2427,66 +2427,64 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
   if (fused1)
     ;  // no entry words in HBM: both level-1 kernels recompute them
   else if (fx && fx->signed_digits)
-    hipLaunchKernelGGL(k_recode_signed, dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf, (uint32_t)n,
+    DVP_LAUNCH(k_recode_signed, dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf, (uint32_t)n,
                        p.c, p.W, p.n_narrow, digits32, err);
   else if (fx)
-    hipLaunchKernelGGL((k_recode<uint32_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf,
+    DVP_LAUNCH((k_recode<uint32_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf,
                        (uint32_t)n, p.c, p.W, p.n_narrow, digits32, err);
   else
-    hipLaunchKernelGGL((k_recode<uint16_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf,
+    DVP_LAUNCH((k_recode<uint16_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf,
                        (uint32_t)n, p.c, p.W, p.n_narrow, digits, err);
   if (fx) {
     const uint32_t gmax = fx_nblk + FX_NP;  // upper bound on the number of level-2 chunks
     if (fused1)
-      hipLaunchKernelGGL(k_part_hist_signed, dim3(fx_nblk), dim3(SORT_TPB), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf, (uint32_t)n,
+      DVP_LAUNCH(k_part_hist_signed, dim3(fx_nblk), dim3(SORT_TPB), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf, (uint32_t)n,
                          p.c, p.W, p.n_narrow, fx_S, fb, phist, err);
     else
-      hipLaunchKernelGGL(k_part_hist, dim3(fx_nblk), dim3(SORT_TPB), 0, st, digits32, p.e_max, fb, phist);
-    hipLaunchKernelGGL(k_part_scan_chunks, dim3(fx_nch), dim3(256), 0, st, phist, fx_nblk, fb, pbase, ctot, fx_nch);
-    hipLaunchKernelGGL(k_part_scan_totals, dim3(cdiv((size_t)FX_NP * 64, 256)), dim3(256), 0, st, ctot, fx_nch, fb, pcount);
-    hipLaunchKernelGGL(k_part_starts, dim3(1), dim3(FX_NP_MAX), 0, st, pcount, fb, pstart, cstart);
+      DVP_LAUNCH(k_part_hist, dim3(fx_nblk), dim3(SORT_TPB), 0, st, digits32, p.e_max, fb, phist);
+    DVP_LAUNCH(k_part_scan_chunks, dim3(fx_nch), dim3(256), 0, st, phist, fx_nblk, fb, pbase, ctot, fx_nch);
+    DVP_LAUNCH(k_part_scan_totals, dim3(cdiv((size_t)FX_NP * 64, 256)), dim3(256), 0, st, ctot, fx_nch, fb, pcount);
+    DVP_LAUNCH(k_part_starts, dim3(1), dim3(FX_NP_MAX), 0, st, pcount, fb, pstart, cstart);
     const bool staged1 = FX_NP >= 64;           // few partitions: direct stores already coalesce
     const bool staged2 = fb.lo <= 10;           // one bin per thread in the block scan
     if (fused1 && staged1)
-      hipLaunchKernelGGL(k_part_scatter_signed<true>, dim3(fx_nblk), dim3(SORT_TPB), FX_STAGE1_LDS, st, (const uint32_t*)d_scalars,
+      DVP_LAUNCH(k_part_scatter_signed<true>, dim3(fx_nblk), dim3(SORT_TPB), FX_STAGE1_LDS, st, (const uint32_t*)d_scalars,
                          (const uint8_t*)d_inf, (uint32_t)n, p.c, p.W, p.n_narrow, fx_S, fx->n_total, i0, fb, phist, pbase, ctot, fx_nch, pstart, plo, pid);
     else if (fused1)
-      hipLaunchKernelGGL(k_part_scatter_signed<false>, dim3(fx_nblk), dim3(SORT_TPB), (2 * FX_NP_MAX + SORT_TPB) * 4, st, (const uint32_t*)d_scalars,
+      DVP_LAUNCH(k_part_scatter_signed<false>, dim3(fx_nblk), dim3(SORT_TPB), (2 * FX_NP_MAX + SORT_TPB) * 4, st, (const uint32_t*)d_scalars,
                          (const uint8_t*)d_inf, (uint32_t)n, p.c, p.W, p.n_narrow, fx_S, fx->n_total, i0, fb, phist, pbase, ctot, fx_nch, pstart, plo, pid);
     else if (staged1)
-      hipLaunchKernelGGL(k_part_scatter_staged, dim3(fx_nblk), dim3(SORT_TPB), FX_STAGE1_LDS, st, digits32, p.e_max, (uint32_t)n,
+      DVP_LAUNCH(k_part_scatter_staged, dim3(fx_nblk), dim3(SORT_TPB), FX_STAGE1_LDS, st, digits32, p.e_max, (uint32_t)n,
                          fx->n_total, i0, fb, phist, pbase, ctot, fx_nch, pstart, plo, pid);
     else
-      hipLaunchKernelGGL(k_part_scatter, dim3(fx_nblk), dim3(SORT_TPB), 0, st, digits32, p.e_max, (uint32_t)n, fx->n_total, i0, fb, pbase,
+      DVP_LAUNCH(k_part_scatter, dim3(fx_nblk), dim3(SORT_TPB), 0, st, digits32, p.e_max, (uint32_t)n, fx->n_total, i0, fb, pbase,
                          ctot, fx_nch, pstart, plo, pid);
-    hipLaunchKernelGGL(k_hist_local2, dim3(gmax), dim3(SORT_TPB), (1u << fb.lo) * 2, st, plo, pstart, cstart, fb, hist16);
-    hipLaunchKernelGGL(k_hist_scan2, dim3(cdiv(nk, 256)), dim3(256), 0, st, hist16, cstart, fb, chunk_off, cnt);
+    DVP_LAUNCH(k_hist_local2, dim3(gmax), dim3(SORT_TPB), (1u << fb.lo) * 2, st, plo, pstart, cstart, fb, hist16);
+    DVP_LAUNCH(k_hist_scan2, dim3(cdiv(nk, 256)), dim3(256), 0, st, hist16, cstart, fb, chunk_off, cnt);
     DVP_TRY(prepare_rounds());  // needs the counts only
-    if (!sort_done_by_mscan) DVP_TRY(scan_exclusive(cnt, off, nk, bsum, st, /*pad2=*/true));
+    if (!sort_done_by_mscan) DVP_TRY(scan_exclusive_pad2(cnt, off, nk, bsum, st));
     if (staged2)
-      hipLaunchKernelGGL(k_scatter_local2_staged, dim3(gmax), dim3(SORT_TPB), FX_STAGE2_LDS, st, plo, pid, pstart, cstart, fb, off,
+      DVP_LAUNCH(k_scatter_local2_staged, dim3(gmax), dim3(SORT_TPB), FX_STAGE2_LDS, st, plo, pid, pstart, cstart, fb, off,
                          chunk_off, hist16, items);
     else
-      hipLaunchKernelGGL(k_scatter_local2, dim3(gmax), dim3(SORT_TPB), (1u << fb.lo) * 4, st, plo, pid, pstart, cstart, fb, off, chunk_off, items);
+      DVP_LAUNCH(k_scatter_local2, dim3(gmax), dim3(SORT_TPB), (1u << fb.lo) * 4, st, plo, pid, pstart, cstart, fb, off, chunk_off, items);
   } else {
     const uint32_t nchunks = cdiv(n, SORT_CHUNK), nb = 1u << p.c;
-    hipLaunchKernelGGL(k_hist_local, dim3(nchunks, p.W), dim3(SORT_TPB), (nb >> 1) * 4, st, digits, (uint32_t)n, p.c, hist16);
-    hipLaunchKernelGGL(k_hist_scan, dim3(cdiv(nk, 256)), dim3(256), 0, st, hist16, nchunks, p.c, p.W, chunk_off, cnt);
+    DVP_LAUNCH(k_hist_local, dim3(nchunks, p.W), dim3(SORT_TPB), (nb >> 1) * 4, st, digits, (uint32_t)n, p.c, hist16);
+    DVP_LAUNCH(k_hist_scan, dim3(cdiv(nk, 256)), dim3(256), 0, st, hist16, nchunks, p.c, p.W, chunk_off, cnt);
     DVP_TRY(prepare_rounds());  // needs the counts only
-    if (!sort_done_by_mscan) DVP_TRY(scan_exclusive(cnt, off, nk, bsum, st, /*pad2=*/true));
-    hipLaunchKernelGGL(k_scatter_local, dim3(nchunks, p.W), dim3(SORT_TPB), nb * 4, st, digits, (uint32_t)n, p.c, off, chunk_off, items);
+    if (!sort_done_by_mscan) DVP_TRY(scan_exclusive_pad2(cnt, off, nk, bsum, st));
+    DVP_LAUNCH(k_scatter_local, dim3(nchunks, p.W), dim3(SORT_TPB), nb * 4, st, digits, (uint32_t)n, p.c, off, chunk_off, items);
   }
   ps_sort.stop();
   // ---- bucket accumulation: batched-affine pair rounds while a round still carries >= aff_min additions,
   // then the projective fan-in-K reducer on what is left (it has a short critical path and balances skew)
   uint32_t* pc[3] = {cnt, ntask, cnt2};
   uint32_t* po[3] = {off, toff, off2};
-  bool r0_offsets_ready = false;
   if (!sort_done_by_mscan) {
-    // odd buckets' NONE, the first round's counts / offsets (into the ring's next pair, where k_round0_offsets would put them) and the
+    // odd buckets' NONE, the first round's counts / offsets (into the ring's next pair, where run_round(0) expects them) and the
     // largest bucket in one launch (d_max: zeroed by the previous MSM's tail kernel)
-    hipLaunchKernelGGL(k_post_sort, dim3(cdiv(nk + 1, 256)), dim3(256), 0, st, items, cnt, off, nk, pc[1], po[1], d_max);
-    r0_offsets_ready = true;
+    DVP_LAUNCH(k_post_sort, dim3(cdiv(nk + 1, 256)), dim3(256), 0, st, items, cnt, off, nk, pc[1], po[1], d_max);
     DVP_TRY(read_max());
   }
   int cur = 0;  // index of the live (cnt, off) pair
@@ -2527,17 +2525,17 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
       ProfScope ps0(r == 0 ? PROF_MSM_ACCUM_AFFINE : -1, st, (uint64_t)n);
       WaveTrace wt{wt_buf, wt_cap, g_wave_trace_tag.fetch_add(wt_on ? 1u : 0u)};
       if (r == 0 && wt.buf)
-        hipLaunchKernelGGL((k_affine_round<true, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, sign_mask, wt);
+        DVP_LAUNCH((k_affine_round<true, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, sign_mask, wt);
       else if (r == 0)
-        hipLaunchKernelGGL((k_affine_round<true, false>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, sign_mask, wt);
+        DVP_LAUNCH((k_affine_round<true, false>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, sign_mask, wt);
       else if (dense && wt.buf)
-        hipLaunchKernelGGL((k_affine_round<false, true, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
+        DVP_LAUNCH((k_affine_round<false, true, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
       else if (dense)
-        hipLaunchKernelGGL((k_affine_round<false, false, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
+        DVP_LAUNCH((k_affine_round<false, false, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
       else if (wt.buf)
-        hipLaunchKernelGGL((k_affine_round<false, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
+        DVP_LAUNCH((k_affine_round<false, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
       else
-        hipLaunchKernelGGL((k_affine_round<false, false>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
+        DVP_LAUNCH((k_affine_round<false, false>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
       ps0.stop();
       if (r > 0) count_later_round(dense);
     }
@@ -2552,11 +2550,9 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
       return DVP_OK;
     }
     const int nxt = (cur + 1) % 3;
-    if (r == 0) {
-      if (!(r0_offsets_ready && cur == 0))
-        hipLaunchKernelGGL(k_round0_offsets, dim3(cdiv(nk + 1, 256)), dim3(256), 0, st, pc[cur], po[cur], nk, pc[nxt], po[nxt]);
-    } else
-      DVP_TRY(bookkeep(r, pc[cur], po[cur], pc[nxt], po[nxt], gdesc, st, bsum));
+    // (r == 0: cur == 0 and k_post_sort has left the first round's counts / offsets in pc[1] / po[1] -- an MSM that is not pipelined
+    // always runs it)
+    if (r > 0) DVP_TRY(bookkeep(r, pc[cur], po[cur], pc[nxt], po[nxt], gdesc, st, bsum));
     DVP_TRY(launch_round(r, po[nxt] + nk, r == 0 ? (const uint2*)items : (const uint2*)(const void*)gdesc));
     cur = nxt;
     return DVP_OK;
@@ -2619,13 +2615,13 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
   uint64_t rem_max = ((uint64_t)max_cnt + ((uint64_t)1 << ra) - 1) >> ra;  // largest bucket after the affine rounds
   if (rem_max <= 1) {
     if (ra == 0)
-      hipLaunchKernelGGL(k_bucket_gather_items, dim3(cdiv(nk, 256)), dim3(256), 0, st, bases0, items, cnt, off, nk, bkt, sign_mask);
+      DVP_LAUNCH(k_bucket_gather_items, dim3(cdiv(nk, 256)), dim3(256), 0, st, bases0, items, cnt, off, nk, bkt, sign_mask);
     else
-      hipLaunchKernelGGL(k_bucket_gather_aff, dim3(cdiv(nk, 256)), dim3(256), 0, st, pts_in, pc[cur], po[cur], nk, bkt);
+      DVP_LAUNCH(k_bucket_gather_aff, dim3(cdiv(nk, 256)), dim3(256), 0, st, pts_in, pc[cur], po[cur], nk, bkt);
   } else if (ra > 0 && rem_max <= (uint64_t)(tn.msm_bucket_pairs_max >= 0 ? tn.msm_bucket_pairs_max : 0)) {
     // a handful of points per bucket left: one thread per bucket; buckets that meet an exceptional pair are redone from a list
-    hipLaunchKernelGGL(k_bucket_pairs, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, pc[cur], po[cur], nk, bkt, rest_n, rest_list);
-    hipLaunchKernelGGL(k_bucket_rest, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, pc[cur], po[cur], rest_n, rest_list, bkt);
+    DVP_LAUNCH(k_bucket_pairs, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, pc[cur], po[cur], nk, bkt, rest_n, rest_list);
+    DVP_LAUNCH(k_bucket_rest, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, pc[cur], po[cur], rest_n, rest_list, bkt);
   } else {
     // level 1: mixed additions from affine inputs
     int nxt = (cur + 1) % 3;
@@ -2634,25 +2630,25 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
     const size_t accum_quad_max = tn.msm_accum_quad_max > 0 ? (size_t)tn.msm_accum_quad_max : ACCUM_QUAD_MAX;
     const size_t accum_hex_max = tn.msm_accum_hex_max >= 0 ? (size_t)tn.msm_accum_hex_max : ACCUM_HEX_MAX;
     // tmax is an upper bound on the tasks (the real count sits on the device); quads when even the bound fits one chip-full
-    // (the rest list holds task numbers: tmax of them at most; the bucket-pair list's room is nk entries and tmax can exceed it, so
-    // the fast flavour runs only where the list is sure to fit.  Tune::msm_accum_fast = 0: the general kernel of rounds 1-5)
+    // (the rest list holds task numbers: tmax of them at most, and rest_cap is sized from tmax at its largest, so the list always fits;
+    // the comparison stays as the bound's witness.  Tune::msm_accum_fast = 0: the general kernel of rounds 1-5)
     const bool accum_fast = tn.msm_accum_fast != 0 && tmax <= rest_cap;
 #define DVP_ACCUM_AFFINE(IND)                                                                                                                  \
   do {                                                                                                                                         \
     if (accum_fast) {                                                                                                                          \
       if (tmax <= accum_quad_max)                                                                                                              \
-        hipLaunchKernelGGL((k_accum_affine_fast<IND, true>), dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, pts_in, items, pc[cur], \
+        DVP_LAUNCH((k_accum_affine_fast<IND, true>), dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, pts_in, items, pc[cur], \
                            po[cur], po[nxt], nk, p.K, bufA, sign_mask, rest_n, rest_list);                                                    \
       else                                                                                                                                     \
-        hipLaunchKernelGGL((k_accum_affine_fast<IND, false>), dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, items, pc[cur],      \
+        DVP_LAUNCH((k_accum_affine_fast<IND, false>), dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, items, pc[cur],      \
                            po[cur], po[nxt], nk, p.K, bufA, sign_mask, rest_n, rest_list);                                                    \
-      hipLaunchKernelGGL((k_accum_affine_rest<IND>), dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, items, pc[cur], po[cur],       \
+      DVP_LAUNCH((k_accum_affine_rest<IND>), dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, items, pc[cur], po[cur],       \
                          po[nxt], nk, p.K, bufA, sign_mask, rest_n, rest_list);                                                                \
     } else if (tmax <= accum_quad_max)                                                                                                         \
-      hipLaunchKernelGGL((k_accum_affine<IND, true>), dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, pts_in, items, pc[cur], po[cur], \
+      DVP_LAUNCH((k_accum_affine<IND, true>), dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, pts_in, items, pc[cur], po[cur], \
                          po[nxt], nk, p.K, bufA, sign_mask);                                                                                   \
     else                                                                                                                                       \
-      hipLaunchKernelGGL((k_accum_affine<IND, false>), dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, items, pc[cur], po[cur],     \
+      DVP_LAUNCH((k_accum_affine<IND, false>), dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, items, pc[cur], po[cur],     \
                          po[nxt], nk, p.K, bufA, sign_mask);                                                                                   \
   } while (0)
     if (ra == 0) {
@@ -2672,16 +2668,16 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
       // the LAST level of a small MSM (every bucket ends with one task of at most K partial sums, typically one or two): rows of 16
       // lanes when the tasks fit ACCUM_HEX_MAX (measured at 2^16 points, round 6)
       if (left <= p.K && tmax <= accum_hex_max)
-        hipLaunchKernelGGL(k_accum_proj<16>, dim3(cdiv(16 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
+        DVP_LAUNCH(k_accum_proj<16>, dim3(cdiv(16 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
       else if (tmax <= accum_quad_max)
-        hipLaunchKernelGGL(k_accum_proj<4>, dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
+        DVP_LAUNCH(k_accum_proj<4>, dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
       else
-        hipLaunchKernelGGL(k_accum_proj<1>, dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
+        DVP_LAUNCH(k_accum_proj<1>, dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
       cap = tmax;
       cur = nxt;
       Ld* t = in; in = outb; outb = t;
     }
-    hipLaunchKernelGGL(k_bucket_gather, dim3(cdiv(nk, 256)), dim3(256), 0, st, in, pc[cur], po[cur], nk, bkt);
+    DVP_LAUNCH(k_bucket_gather, dim3(cdiv(nk, 256)), dim3(256), 0, st, in, pc[cur], po[cur], nk, bkt);
   }
   ProfScope ps_tail(PROF_MSM_TAIL, st);  // merge tree, Frobenius tail, final add tree
   const int merge_levels = fx ? fx->key_bits() : p.c;
@@ -2692,7 +2688,7 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
     uint32_t total = (nk >> (j + 1)) * (uint32_t)(j + 1);
     const uint32_t quad_max = tn.msm_quad_max > 0 ? (uint32_t)tn.msm_quad_max : MERGE_QUAD_MAX;
     const uint32_t hex_max = tn.msm_hex_max >= 0 ? (uint32_t)tn.msm_hex_max : MERGE_HEX_MAX;
-#define DVP_MERGE(G, F, LDSB) hipLaunchKernelGGL((k_merge<G, F>), dim3(cdiv((size_t)G * total, EC_TPB)), dim3(EC_TPB), LDSB, st, bkt, j, total, save0)
+#define DVP_MERGE(G, F, LDSB) DVP_LAUNCH((k_merge<G, F>), dim3(cdiv((size_t)G * total, EC_TPB)), dim3(EC_TPB), LDSB, st, bkt, j, total, save0)
     if (total <= hex_max) { if (j == 0) DVP_MERGE(16, true, EC_LDS_Q); else DVP_MERGE(16, false, EC_LDS_Q); }
     else if (total <= quad_max) { if (j == 0) DVP_MERGE(4, true, EC_LDS_Q); else DVP_MERGE(4, false, EC_LDS_Q); }
     else { if (j == 0) DVP_MERGE(1, true, EC_LDS); else DVP_MERGE(1, false, EC_LDS); }
@@ -2702,17 +2698,17 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
   uint32_t cntT = (uint32_t)(w_tail * p.c);
   Ld* ta = tail;  // 2 * cntT entries: the two halves of k_tail's ping-pong
   if (sign_mask && tn.msm_hex_max != 0)  // c points: one row of 16 lanes each
-    hipLaunchKernelGGL(k_tail<true>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, bkt, p.c, w_tail, -3, Tsq, ta, (uint32_t*)d_out_xy, (uint32_t*)d_out_inf,
+    DVP_LAUNCH(k_tail<true>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, bkt, p.c, w_tail, -3, Tsq, ta, (uint32_t*)d_out_xy, (uint32_t*)d_out_inf,
                        (uint8_t*)d_out_enc, d_out_enc ? dvp_codec_get_rule() : 0, err, d_err_defer);
   else if (!sign_mask && cntT > 32 && tn.msm_tail_groups != 0) {
     // many points (the one-shot MSM's W x c): group sums on cdiv(cntT, 16) workgroups first, then the single-workgroup tail on those
     Ld* part = tail + 2 * (size_t)cntT + 1;
     const int nparts = (int)cdiv(cntT, 16);
-    hipLaunchKernelGGL(k_tail_groups, dim3(nparts), dim3(EC_TPB), EC_LDS_Q, st, bkt, p.c, w_tail, fx ? 0 : p.n_narrow, Tsq, ta, part);
-    hipLaunchKernelGGL(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, bkt, nparts, 1, -4, Tsq, part, (uint32_t*)d_out_xy,
+    DVP_LAUNCH(k_tail_groups, dim3(nparts), dim3(EC_TPB), EC_LDS_Q, st, bkt, p.c, w_tail, fx ? 0 : p.n_narrow, Tsq, ta, part);
+    DVP_LAUNCH(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, bkt, nparts, 1, -4, Tsq, part, (uint32_t*)d_out_xy,
                        (uint32_t*)d_out_inf, (uint8_t*)d_out_enc, d_out_enc ? dvp_codec_get_rule() : 0, err, d_err_defer);
   } else
-    hipLaunchKernelGGL(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, bkt, p.c, w_tail, sign_mask ? -3 : (fx ? 0 : p.n_narrow), Tsq, ta, (uint32_t*)d_out_xy,
+    DVP_LAUNCH(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, bkt, p.c, w_tail, sign_mask ? -3 : (fx ? 0 : p.n_narrow), Tsq, ta, (uint32_t*)d_out_xy,
                        (uint32_t*)d_out_inf, (uint8_t*)d_out_enc, d_out_enc ? dvp_codec_get_rule() : 0, err, d_err_defer);
   ps_tail.stop();
   ps_total.stop();
@@ -2745,7 +2741,7 @@ int msm_sum_points_dev(const void* d_pts, uint32_t pt_stride_bytes, const void* 
                        void* d_out_inf, hipStream_t st) {
   GfSqrTables Tsq;
   DVP_TRY(gf_sqr_tables(&Tsq, st));
-  hipLaunchKernelGGL(k_sum_points, dim3(1), dim3(64), GF_LDS_BYTES_PER_WAVE, st, (const char*)d_pts, pt_stride_bytes, (const uint32_t*)d_inf32, n,
+  DVP_LAUNCH(k_sum_points, dim3(1), dim3(64), GF_LDS_BYTES_PER_WAVE, st, (const char*)d_pts, pt_stride_bytes, (const uint32_t*)d_inf32, n,
                      inf_stride, Tsq, (uint32_t*)d_out_xy, (uint32_t*)d_out_inf);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
@@ -2758,7 +2754,7 @@ int msm_join_points_dev(const void* d_a_xy, const void* d_a_inf, const unsigned 
                         unsigned long long* d_err_out, hipStream_t st) {
   GfSqrTables Tsq;
   DVP_TRY(gf_sqr_tables(&Tsq, st));
-  hipLaunchKernelGGL(k_join_points, dim3(1), dim3(64), GF_LDS_BYTES_PER_WAVE, st, (const Aff*)d_a_xy, (const uint32_t*)d_a_inf, d_a_err, (const Aff*)d_b_xy,
+  DVP_LAUNCH(k_join_points, dim3(1), dim3(64), GF_LDS_BYTES_PER_WAVE, st, (const Aff*)d_a_xy, (const uint32_t*)d_a_inf, d_a_err, (const Aff*)d_b_xy,
                      (const uint32_t*)d_b_inf, d_b_err, covered, Tsq, (uint32_t*)d_out_xy, (uint32_t*)d_out_inf, (uint8_t*)d_out_enc,
                      d_out_enc ? dvp_codec_get_rule() : 0, d_err_out);
   DVP_HIP(hipGetLastError());
@@ -2839,14 +2835,14 @@ static int msm_fixed_build(const Aff* d_bases, uint32_t n_total, size_t range_hi
       const size_t per = (size_t)(c->W > 1 ? c->W - 1 : 1) * n_total;
       if (e == hipSuccess) e = hipMalloc((void**)&scratch, 2 * per * sizeof(Gf));
       if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_dbl_table, dim3(cdiv(n_total, 256)), dim3(256), EC_LDS, 0, d_bases, n_total, c->c, c->W, c->n_narrow, Tsq, c->table,
+        DVP_LAUNCH(k_dbl_table, dim3(cdiv(n_total, 256)), dim3(256), EC_LDS, 0, d_bases, n_total, c->c, c->W, c->n_narrow, Tsq, c->table,
                            scratch, scratch + per);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipDeviceSynchronize();
       }
       if (scratch) (void)hipFree(scratch);
     } else
-      hipLaunchKernelGGL(k_frob_table, dim3(cdiv(n_total, 256)), dim3(256), 0, 0, d_bases, n_total, c->c, c->W, c->n_narrow, c->table);
+      DVP_LAUNCH(k_frob_table, dim3(cdiv(n_total, 256)), dim3(256), 0, 0, d_bases, n_total, c->c, c->W, c->n_narrow, c->table);
     if (e == hipSuccess) e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -2981,7 +2977,7 @@ extern "C" int dvp_ubench_gf_mul(int reps, double* products_per_s) {
   float best = 1e30f;
   for (int it = 0; it < 3; ++it) {
     DVP_HIP(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(k_ubench_mul, dim3(blocks), dim3(EC_TPB), EC_LDS, 0, out.as<Gf>(), reps);
+    DVP_LAUNCH(k_ubench_mul, dim3(blocks), dim3(EC_TPB), EC_LDS, 0, out.as<Gf>(), reps);
     DVP_HIP(hipEventRecord(e1, 0));
     DVP_HIP(hipEventSynchronize(e1));
     float ms = 0;
@@ -3033,10 +3029,10 @@ extern "C" int dvp_ubench_gather(const void* d_table, size_t table_bytes, int re
   hipEvent_t e0, e1;
   DVP_HIP(hipEventCreate(&e0));
   DVP_HIP(hipEventCreate(&e1));
-  hipLaunchKernelGGL(k_ubench_gather, dim3(blocks), dim3(256), 0, 0, (const uint4*)d_table, nlines, per, 1u, out.as<uint32_t>());
+  DVP_LAUNCH(k_ubench_gather, dim3(blocks), dim3(256), 0, 0, (const uint4*)d_table, nlines, per, 1u, out.as<uint32_t>());
   DVP_HIP(hipEventRecord(e0, 0));
   for (int r = 0; r < reps; ++r)
-    hipLaunchKernelGGL(k_ubench_gather, dim3(blocks), dim3(256), 0, 0, (const uint4*)d_table, nlines, per, 2u + (uint32_t)r, out.as<uint32_t>());
+    DVP_LAUNCH(k_ubench_gather, dim3(blocks), dim3(256), 0, 0, (const uint4*)d_table, nlines, per, 2u + (uint32_t)r, out.as<uint32_t>());
   DVP_HIP(hipEventRecord(e1, 0));
   DVP_HIP(hipEventSynchronize(e1));
   float ms = 0;
@@ -3051,6 +3047,28 @@ extern "C" int dvp_ubench_gather(const void* d_table, size_t table_bytes, int re
 
 // the signed aligned windows (k_recode_signed): out_words[w * n + i] = 0 (digit 0) or 0x80000000 | 0x10000000 if the digit is
 // negative | w << 20 | |digit| (|digit| = 2^(c-1) stored as key 0); *windows = ceil(234 / c)
+// entries the device put on the rest list (k_bucket_pairs' buckets, k_accum_affine_fast's tasks) during the calling thread's last MSM:
+// the tail kernel keeps the control word before it clears it for the next MSM
+extern "C" int dvp_debug_msm_rest_len(uint32_t* n) {
+  using namespace dvp;
+  if (!n) return DVP_EINVAL;
+  const LastMsm lm = g_last_msm;
+  if (lm.dev < 0) return DVP_EINVAL;  // this thread has run no MSM
+  MsmWorkspace& ws = g_ws_dev[lm.dev][lm.slot];
+  std::lock_guard<std::mutex> g(ws.mu);
+  if (!ws.p || ws.device != lm.dev) return DVP_EINVAL;
+  int prev = 0;
+  DVP_HIP(hipGetDevice(&prev));
+  if (prev != lm.dev) DVP_HIP(hipSetDevice(lm.dev));
+  hipError_t e = hipStreamSynchronize(lm.st);
+  uint32_t w[2] = {0, 0};  // (d_max, rest_n)
+  if (e == hipSuccess) e = hipMemcpy(w, (const char*)ws.p + 24, 8, hipMemcpyDeviceToHost);
+  if (prev != lm.dev) (void)hipSetDevice(prev);
+  DVP_HIP(e);
+  *n = w[1];
+  return DVP_OK;
+}
+
 extern "C" int dvp_debug_recode_signed(const uint64_t* scalars, size_t n, int c, uint32_t* out_words, int* windows) {
   if (!windows || c < 8 || c > FX_C_MAX + 1 || n > (1u << 24)) return DVP_EINVAL;
   MsmFixedCtx plan;
@@ -3065,7 +3083,7 @@ extern "C" int dvp_debug_recode_signed(const uint64_t* scalars, size_t n, int c,
   DVP_TRY(de.alloc(8));
   DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
   DVP_HIP(hipMemset(de.p, 0xff, 8));
-  hipLaunchKernelGGL(k_recode_signed, dim3(cdiv(n, 256)), dim3(256), 0, 0, ds.as<uint32_t>(), (const uint8_t*)nullptr, (uint32_t)n, c, *windows, plan.n_narrow,
+  DVP_LAUNCH(k_recode_signed, dim3(cdiv(n, 256)), dim3(256), 0, 0, ds.as<uint32_t>(), (const uint8_t*)nullptr, (uint32_t)n, c, *windows, plan.n_narrow,
                      dw.as<uint32_t>(), de.as<unsigned long long>());
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(out_words, dw.p, (size_t)*windows * n * 4, hipMemcpyDeviceToHost));

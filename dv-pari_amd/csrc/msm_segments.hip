@@ -216,7 +216,7 @@ static void seg_launch(const SegLayout& w, char* work, int level, uint32_t n_seg
   const uint32_t* off_out = off_in + (n_seg + 1);  // not read by the last level
   const Ld* in = level ? (const Ld*)(work + w.buf[(level - 1) & 1]) : nullptr;
   Ld* out = (Ld*)(work + w.buf[level & 1]);
-  hipLaunchKernelGGL((k_seg_reduce<AFF, FINAL>), dim3(cdiv(n_tasks, SEG_TPB)), dim3(SEG_TPB), SEG_LDS, st, (const Aff*)(work + w.prod),
+  DVP_LAUNCH((k_seg_reduce<AFF, FINAL>), dim3(cdiv(n_tasks, SEG_TPB)), dim3(SEG_TPB), SEG_LDS, st, (const Aff*)(work + w.prod),
                      (const uint8_t*)(work + w.flags), in, off_in, off_out, n_seg, n_tasks, P, T, out, (Aff*)d_out_xy, (uint8_t*)d_out_inf);
 }
 

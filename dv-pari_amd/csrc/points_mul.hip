@@ -287,7 +287,7 @@ template <int W>
 static void pm_launch(const void* d_scalars, uint32_t stride, const void* d_xy, const void* d_inf, size_t n, const GfSqrTables& T, void* d_out_xy,
                       void* d_out_inf, void* d_summary, hipStream_t st) {
   static_assert(PmShape<W>::LDS_BYTES <= 64 * 1024, "dynamic LDS of one workgroup");
-  hipLaunchKernelGGL(k_points_mul<W>, dim3(cdiv(n, 64)), dim3(64), PmShape<W>::LDS_BYTES, st, (const uint32_t*)d_scalars, stride, (const Aff*)d_xy,
+  DVP_LAUNCH(k_points_mul<W>, dim3(cdiv(n, 64)), dim3(64), PmShape<W>::LDS_BYTES, st, (const uint32_t*)d_scalars, stride, (const Aff*)d_xy,
                      (const uint8_t*)d_inf, n, T, (Aff*)d_out_xy, (uint8_t*)d_out_inf, (unsigned long long*)d_summary);
 }
 
@@ -405,9 +405,9 @@ extern "C" int dvp_debug_recode_tnaf(const uint64_t* scalars, size_t n, int w, i
   DVP_TRY(dd.alloc(n * (size_t)nd));
   DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
   const dim3 grid(cdiv(n, 256)), block(256);
-  if (w == 3) hipLaunchKernelGGL(k_recode_tnaf<3>, grid, block, 0, 0, ds.as<uint32_t>(), n, dd.as<int8_t>());
-  else if (w == 4) hipLaunchKernelGGL(k_recode_tnaf<4>, grid, block, 0, 0, ds.as<uint32_t>(), n, dd.as<int8_t>());
-  else hipLaunchKernelGGL(k_recode_tnaf<5>, grid, block, 0, 0, ds.as<uint32_t>(), n, dd.as<int8_t>());
+  if (w == 3) DVP_LAUNCH(k_recode_tnaf<3>, grid, block, 0, 0, ds.as<uint32_t>(), n, dd.as<int8_t>());
+  else if (w == 4) DVP_LAUNCH(k_recode_tnaf<4>, grid, block, 0, 0, ds.as<uint32_t>(), n, dd.as<int8_t>());
+  else DVP_LAUNCH(k_recode_tnaf<5>, grid, block, 0, 0, ds.as<uint32_t>(), n, dd.as<int8_t>());
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(digits, dd.p, n * (size_t)nd, hipMemcpyDeviceToHost));
   return DVP_OK;

@@ -594,9 +594,9 @@ static int prover_init(dvp_prover* p, uint32_t log2_m, uint32_t n_public, uint32
   DVP_HIP(hipMemset(p->inf_k, 0, 4 * m));
   dvp_ecfft* t = p->tree;
   int kk = (int)log2_m;
-  hipLaunchKernelGGL(k_split_domains, dim3(cdiv(m, PT)), dim3(PT), 0, 0, t->layer(0), (uint32_t)m, p->dD, p->dD2);
+  DVP_LAUNCH(k_split_domains, dim3(cdiv(m, PT)), dim3(PT), 0, 0, t->layer(0), (uint32_t)m, p->dD, p->dD2);
   // bar weights of D and 1/Z_D on D'
-  hipLaunchKernelGGL(k_domain_tables, dim3(cdiv(m, PT)), dim3(PT), 0, 0, t->layer(0), (uint32_t)m, t->d_x0, t->d_t, kk,
+  DVP_LAUNCH(k_domain_tables, dim3(cdiv(m, PT)), dim3(PT), 0, 0, t->layer(0), (uint32_t)m, t->d_x0, t->d_t, kk,
                      t->layer(kk), 0, p->barw, p->z2inv);
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipMemcpy(p->ctop_host, t->layer(kk), 2 * sizeof(Fr), hipMemcpyDeviceToHost));
@@ -636,7 +636,7 @@ extern "C" int dvp_prover_set_coeffs(dvp_prover* p, const uint64_t* coeffs, uint
   DevBuf tmp;
   DVP_TRY(tmp.alloc((size_t)n * sizeof(Fr)));
   DVP_HIP(hipMemcpy(tmp.p, coeffs, (size_t)n * sizeof(Fr), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_to_mont_vec, dim3(cdiv(n, PT)), dim3(PT), 0, 0, tmp.as<Fr>(), p->coeffs_m, (size_t)n);
+  DVP_LAUNCH(k_to_mont_vec, dim3(cdiv(n, PT)), dim3(PT), 0, 0, tmp.as<Fr>(), p->coeffs_m, (size_t)n);
   DVP_HIP(hipDeviceSynchronize());
   p->n_coeffs = n;
   return DVP_OK;
@@ -847,9 +847,9 @@ extern "C" int dvp_prover_debug_transcript_dev(dvp_prover* p, const uint8_t comm
   DVP_HIP(hipMemcpy(in.p, head, 64, hipMemcpyHostToDevice));
   if (n_public) DVP_HIP(hipMemcpy((char*)in.p + 64, public_inputs, (size_t)n_public * sizeof(Fr), hipMemcpyHostToDevice));
   Fr* o = out.as<Fr>();
-  hipLaunchKernelGGL(k_transcript, dim3(1), dim3(64), 0, 0, (const uint32_t*)in.p, (const Fr*)((char*)in.p + 64), n_public, p->h_ct, o, o + 1);
-  hipLaunchKernelGGL(k_zalpha, dim3(1), dim3(64), 0, 0, o + 1, p->tree->d_x0, p->tree->d_t, (int)p->log_m, p->tree->layer((int)p->log_m), o + 2);
-  hipLaunchKernelGGL(k_from_mont_vec, dim3(1), dim3(PT), 0, 0, o + 2, o + 3, (size_t)1);
+  DVP_LAUNCH(k_transcript, dim3(1), dim3(64), 0, 0, (const uint32_t*)in.p, (const Fr*)((char*)in.p + 64), n_public, p->h_ct, o, o + 1);
+  DVP_LAUNCH(k_zalpha, dim3(1), dim3(64), 0, 0, o + 1, p->tree->d_x0, p->tree->d_t, (int)p->log_m, p->tree->layer((int)p->log_m), o + 2);
+  DVP_LAUNCH(k_from_mont_vec, dim3(1), dim3(PT), 0, 0, o + 2, o + 3, (size_t)1);
   DVP_HIP(hipGetLastError());
   DVP_HIP(hipDeviceSynchronize());
   DVP_HIP(hipMemcpy(out_alpha, o, sizeof(Fr), hipMemcpyDeviceToHost));
@@ -925,7 +925,7 @@ static int prove_begin_impl(dvp_prover* p, const void* d_assignment, int need_ex
   Csr B{p->mat[1].row_ptr, p->mat[1].wire, p->mat[1].coeff, p->mat[1].n_rows};
   Csr C{p->mat[2].row_ptr, p->mat[2].wire, p->mat[2].coeff, p->mat[2].n_rows};
   dim3 gm(cdiv(m, PT)), bt(PT);
-  hipLaunchKernelGGL(k_r1cs_eval, gm, bt, 0, st, A, B, C, p->coeffs_m, p->SA, p->dD, p->n_pub, m, p->E, p->flags);
+  DVP_LAUNCH(k_r1cs_eval, gm, bt, 0, st, A, B, C, p->coeffs_m, p->SA, p->dD, p->n_pub, m, p->E, p->flags);
   DVP_HIP(hipGetLastError());
   if (need_extend) {
     DVP_TRY(dvp_prove_extend_vectors(p, (1u << prover_n_ext(p)) - 1, stream));
@@ -986,9 +986,9 @@ extern "C" int dvp_prove_quotient(dvp_prover* p, void* stream) {
   if (p->ext_filled != (1u << prover_n_ext(p)) - 1) return DVP_EINVAL;  // a missed broadcast would otherwise give a silently wrong q2
   dim3 gm(cdiv(m, PT)), bt(PT);
   if (prover_n_ext(p) == 3)
-    hipLaunchKernelGGL(k_quotient<true>, gm, bt, 0, st, p->E2, p->z2inv, m, p->SA, p->dD2, p->n_pub, p->r2, p->SA + nw);
+    DVP_LAUNCH(k_quotient<true>, gm, bt, 0, st, p->E2, p->z2inv, m, p->SA, p->dD2, p->n_pub, p->r2, p->SA + nw);
   else
-    hipLaunchKernelGGL(k_quotient<false>, gm, bt, 0, st, p->E2, p->z2inv, m, p->SA, p->dD2, p->n_pub, p->r2, p->SA + nw);
+    DVP_LAUNCH(k_quotient<false>, gm, bt, 0, st, p->E2, p->z2inv, m, p->SA, p->dD2, p->n_pub, p->r2, p->SA + nw);
   DVP_HIP(hipGetLastError());
   p->last_begin_extended = true;
   return DVP_OK;
@@ -1345,24 +1345,24 @@ extern "C" size_t dvp_prover_msm_size(const dvp_prover* p, int which) {
 static int challenge_vector_stages(dvp_prover* p, hipStream_t st, bool z_on_side_stream) {
   const uint32_t m = p->m;
   dim3 gm(cdiv(m, PT)), bt(PT);
-  hipLaunchKernelGGL(k_alpha_denoms, gm, bt, 0, st, p->dD, p->dD2, p->chal_dev, m, p->den, p->den2, p->flags + 1);
+  DVP_LAUNCH(k_alpha_denoms, gm, bt, 0, st, p->dD, p->dD2, p->chal_dev, m, p->den, p->den2, p->flags + 1);
   DVP_TRY(batch_inverse_dev(p->den, 2 * (size_t)m, st));  // den2 = den + m
   uint32_t nb = cdiv(m, PT);
   if (nb > 1024) nb = 1024;
-  hipLaunchKernelGGL(k_bary3_partial, dim3(nb), bt, 0, st, p->E, p->barw, p->den, m, p->partial);
+  DVP_LAUNCH(k_bary3_partial, dim3(nb), bt, 0, st, p->E, p->barw, p->den, m, p->partial);
   if (z_on_side_stream) DVP_HIP(hipStreamWaitEvent(st, p->ev_negz, 0));
-  hipLaunchKernelGGL(k_bary3_final, dim3(1), bt, 0, st, p->partial, nb, p->chal_dev + 1, p->abir0);
-  hipLaunchKernelGGL(k_kscalars, gm, bt, 0, st, p->E, p->r2, p->den, p->den2, p->abir0, m, p->SK);
+  DVP_LAUNCH(k_bary3_final, dim3(1), bt, 0, st, p->partial, nb, p->chal_dev + 1, p->abir0);
+  DVP_LAUNCH(k_kscalars, gm, bt, 0, st, p->E, p->r2, p->den, p->den2, p->abir0, m, p->SK);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
 // the same phase with the transcript on the device: commit_p's 30 bytes are where the commitment MSM's tail kernel wrote them
 // (p->enc), the public inputs in the witness vector; no host round trip
 static int challenge_dev(dvp_prover* p, hipStream_t st) {
-  hipLaunchKernelGGL(k_transcript, dim3(1), dim3(64), 0, st, (const uint32_t*)p->enc, p->SA + 1, p->n_pub, p->h_ct, p->alpha_dev, p->chal_dev);
+  DVP_LAUNCH(k_transcript, dim3(1), dim3(64), 0, st, (const uint32_t*)p->enc, p->SA + 1, p->n_pub, p->h_ct, p->alpha_dev, p->chal_dev);
   DVP_HIP(hipEventRecord(p->ev_alpha, st));
   DVP_HIP(hipStreamWaitEvent(p->side, p->ev_alpha, 0));
-  hipLaunchKernelGGL(k_zalpha, dim3(1), dim3(64), 0, p->side, p->chal_dev, p->tree->d_x0, p->tree->d_t, (int)p->log_m, p->tree->layer((int)p->log_m),
+  DVP_LAUNCH(k_zalpha, dim3(1), dim3(64), 0, p->side, p->chal_dev, p->tree->d_x0, p->tree->d_t, (int)p->log_m, p->tree->layer((int)p->log_m),
                      p->chal_dev + 1);
   DVP_HIP(hipEventRecord(p->ev_negz, p->side));
   return challenge_vector_stages(p, st, /*z_on_side_stream=*/true);
@@ -1450,21 +1450,21 @@ extern "C" int dvp_prove_challenge_partial(dvp_prover* p, const void* d_commit_x
   }
   for (auto& x : merged) {
     const uint32_t cnt = (uint32_t)(x.second - x.first);
-    hipLaunchKernelGGL(k_alpha_denoms_range, dim3(cdiv(cnt, PT)), bt, 0, st, p->dD, alpha_m, (uint32_t)x.first, (uint32_t)x.second, p->den, p->flags + 1);
+    DVP_LAUNCH(k_alpha_denoms_range, dim3(cdiv(cnt, PT)), bt, 0, st, p->dD, alpha_m, (uint32_t)x.first, (uint32_t)x.second, p->den, p->flags + 1);
     DVP_TRY(batch_inverse_dev(p->den + x.first, cnt, st));
   }
   if (kri.first < kri.second) {
     const uint32_t cnt = (uint32_t)(kri.second - kri.first);
-    hipLaunchKernelGGL(k_alpha_denoms_range, dim3(cdiv(cnt, PT)), bt, 0, st, p->dD2, alpha_m, (uint32_t)kri.first, (uint32_t)kri.second, p->den2, p->flags + 1);
+    DVP_LAUNCH(k_alpha_denoms_range, dim3(cdiv(cnt, PT)), bt, 0, st, p->dD2, alpha_m, (uint32_t)kri.first, (uint32_t)kri.second, p->den2, p->flags + 1);
     DVP_TRY(batch_inverse_dev(p->den2 + kri.first, cnt, st));
   }
   uint32_t nb = 0;
   if (d_lo < d_hi) {
     nb = cdiv((uint32_t)(d_hi - d_lo), PT);
     if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(k_bary3_partial_range, dim3(nb), bt, 0, st, p->E, p->barw, p->den, m, (uint32_t)d_lo, (uint32_t)d_hi, p->partial);
+    DVP_LAUNCH(k_bary3_partial_range, dim3(nb), bt, 0, st, p->E, p->barw, p->den, m, (uint32_t)d_lo, (uint32_t)d_hi, p->partial);
   }
-  hipLaunchKernelGGL(k_bary3_record, dim3(1), bt, 0, st, p->partial, nb, p->flags + 1, (Fr*)d_record_out);
+  DVP_LAUNCH(k_bary3_record, dim3(1), bt, 0, st, p->partial, nb, p->flags + 1, (Fr*)d_record_out);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
@@ -1473,9 +1473,9 @@ extern "C" int dvp_prove_challenge_finish(dvp_prover* p, const void* d_records, 
   const uint32_t m = p->m;
   if (k_lo > k_hi || k_hi > 4 * (size_t)m) return DVP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_bary3_from_records, dim3(1), dim3(64), 0, st, (const Fr*)d_records, n_records, p->neg_z_alpha_m, p->abir0, p->flags + 1);
+  DVP_LAUNCH(k_bary3_from_records, dim3(1), dim3(64), 0, st, (const Fr*)d_records, n_records, p->neg_z_alpha_m, p->abir0, p->flags + 1);
   if (k_lo < k_hi)
-    hipLaunchKernelGGL(k_kscalars_range, dim3(cdiv(k_hi - k_lo, PT)), dim3(PT), 0, st, p->E, p->r2, p->den, p->den2, p->abir0, m, k_lo, k_hi, p->SK);
+    DVP_LAUNCH(k_kscalars_range, dim3(cdiv(k_hi - k_lo, PT)), dim3(PT), 0, st, p->E, p->r2, p->den, p->den2, p->abir0, m, k_lo, k_hi, p->SK);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
@@ -1638,7 +1638,7 @@ extern "C" int dvp_prover_debug_read(dvp_prover* p, const char* name, uint64_t* 
   if (mont) {
     DevBuf tmp;
     DVP_TRY(tmp.alloc(n * sizeof(Fr)));
-    hipLaunchKernelGGL(k_from_mont_vec, dim3(cdiv(n, PT)), dim3(PT), 0, 0, src, tmp.as<Fr>(), n);
+    DVP_LAUNCH(k_from_mont_vec, dim3(cdiv(n, PT)), dim3(PT), 0, 0, src, tmp.as<Fr>(), n);
     DVP_HIP(hipMemcpy(out, tmp.p, n * sizeof(Fr), hipMemcpyDeviceToHost));
   } else {
     DVP_HIP(hipMemcpy(out, src, n * sizeof(Fr), hipMemcpyDeviceToHost));
@@ -1654,10 +1654,10 @@ int ecfft_domain_tables_dev(dvp_ecfft* t, int which, Fr* d_bar_weights, Fr* d_zi
   const size_t m = t->n_leaves / 2;
   const int kk = t->log_n - 1;
   DVP_TRY(ecfft_device_consts(t));
-  hipLaunchKernelGGL(k_domain_tables, dim3(cdiv(m, PT)), dim3(PT), 0, st, t->layer(0), (uint32_t)m, t->d_x0, t->d_t, kk, t->layer(kk),
+  DVP_LAUNCH(k_domain_tables, dim3(cdiv(m, PT)), dim3(PT), 0, st, t->layer(0), (uint32_t)m, t->d_x0, t->d_t, kk, t->layer(kk),
                      which, d_bar_weights, d_zinv_other);
-  hipLaunchKernelGGL(k_from_mont_vec, dim3(cdiv(m, PT)), dim3(PT), 0, st, d_bar_weights, d_bar_weights, m);
-  hipLaunchKernelGGL(k_from_mont_vec, dim3(cdiv(m, PT)), dim3(PT), 0, st, d_zinv_other, d_zinv_other, m);
+  DVP_LAUNCH(k_from_mont_vec, dim3(cdiv(m, PT)), dim3(PT), 0, st, d_bar_weights, d_bar_weights, m);
+  DVP_LAUNCH(k_from_mont_vec, dim3(cdiv(m, PT)), dim3(PT), 0, st, d_zinv_other, d_zinv_other, m);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }

@@ -252,7 +252,7 @@ int setup_scalars_core(const SetupCircuit& cc, const uint64_t tau[4], const Fr& 
   Fr* s_k1 = s_k0 + m;
   Fr* s_k2 = s_k1 + m;
   const dim3 gm(cdiv(m, TPB)), bt(TPB);
-  hipLaunchKernelGGL(ks_domains, gm, bt, 0, st, tree->layer(0), (uint32_t)m, d.as<Fr>(), d2.as<Fr>());
+  DVP_LAUNCH(ks_domains, gm, bt, 0, st, tree->layer(0), (uint32_t)m, d.as<Fr>(), d2.as<Fr>());
   DVP_TRY(ecfft_domain_tables_dev(tree, 0, bar.as<Fr>(), z2inv.as<Fr>(), st));    // 1/Z_D'(D_i),  1/Z_D(D'_i)
   DVP_TRY(ecfft_domain_tables_dev(tree, 1, bard.as<Fr>(), z2dinv.as<Fr>(), st));  // 1/Z_D''(D'_i), 1/Z_D'(D_i)
   uint64_t zt[4], zdt[4];
@@ -263,30 +263,30 @@ int setup_scalars_core(const SetupCircuit& cc, const uint64_t tau[4], const Fr& 
   const Fr z_tau_m = fr_to_mont(z_tau), zd_tau_m = fr_to_mont(zd_tau), delta_m = fr_to_mont(delta_c), eps_m = fr_to_mont(eps_c);
   const Fr delta2_m = fr_to_mont(fr_mul(delta_m, delta_c));  // fr_mul(Montgomery, canonical) = canonical product
   // L_i(tau), L'_i(tau)
-  hipLaunchKernelGGL(ks_scalar_sub, gm, bt, 0, st, tau_c, d.as<Fr>(), t1.as<Fr>(), m);
+  DVP_LAUNCH(ks_scalar_sub, gm, bt, 0, st, tau_c, d.as<Fr>(), t1.as<Fr>(), m);
   DVP_TRY(batch_inverse_dev(t1.as<Fr>(), m, st));
-  hipLaunchKernelGGL(ks_mul_scale, gm, bt, 0, st, t1.as<Fr>(), bar.as<Fr>(), z_tau_m, l_tau.as<Fr>(), m);
-  hipLaunchKernelGGL(ks_scalar_sub, gm, bt, 0, st, tau_c, d2.as<Fr>(), t1.as<Fr>(), m);
+  DVP_LAUNCH(ks_mul_scale, gm, bt, 0, st, t1.as<Fr>(), bar.as<Fr>(), z_tau_m, l_tau.as<Fr>(), m);
+  DVP_LAUNCH(ks_scalar_sub, gm, bt, 0, st, tau_c, d2.as<Fr>(), t1.as<Fr>(), m);
   DVP_TRY(batch_inverse_dev(t1.as<Fr>(), m, st));
-  hipLaunchKernelGGL(ks_mul_scale, gm, bt, 0, st, t1.as<Fr>(), bard.as<Fr>(), zd_tau_m, l_taud.as<Fr>(), m);
+  DVP_LAUNCH(ks_mul_scale, gm, bt, 0, st, t1.as<Fr>(), bard.as<Fr>(), zd_tau_m, l_taud.as<Fr>(), m);
   // g_k_0 = L(tau), g_k_1 = delta L(tau), g_k_2 = delta^2 x the unified-domain values, interleaved [D_i, D'_i] (src/ec_fft.rs:445-448)
   DVP_HIP(hipMemcpyAsync(s_k0, l_tau.p, m * sizeof(Fr), hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(ks_scale, gm, bt, 0, st, l_tau.as<Fr>(), delta_m, s_k1, m);
+  DVP_LAUNCH(ks_scale, gm, bt, 0, st, l_tau.as<Fr>(), delta_m, s_k1, m);
   const Fr zd_d2_m = fr_to_mont(fr_mul(delta2_m, zd_tau)), z_d2_m = fr_to_mont(fr_mul(delta2_m, z_tau));
-  hipLaunchKernelGGL(ks_mul_scale_strided, gm, bt, 0, st, l_tau.as<Fr>(), z2dinv.as<Fr>(), zd_d2_m, s_k2, m, 2u, 0u);
-  hipLaunchKernelGGL(ks_mul_scale_strided, gm, bt, 0, st, l_taud.as<Fr>(), z2inv.as<Fr>(), z_d2_m, s_k2, m, 2u, 1u);
+  DVP_LAUNCH(ks_mul_scale_strided, gm, bt, 0, st, l_tau.as<Fr>(), z2dinv.as<Fr>(), zd_d2_m, s_k2, m, 2u, 0u);
+  DVP_LAUNCH(ks_mul_scale_strided, gm, bt, 0, st, l_taud.as<Fr>(), z2inv.as<Fr>(), z_d2_m, s_k2, m, 2u, 1u);
   // g_q = eps Z_D(tau) delta^2 L'(tau)
   const Fr gq_m = fr_to_mont(fr_mul(eps_m, fr_mul(delta2_m, z_tau)));
-  hipLaunchKernelGGL(ks_scale, gm, bt, 0, st, l_taud.as<Fr>(), gq_m, s_gq, m);
+  DVP_LAUNCH(ks_scale, gm, bt, 0, st, l_taud.as<Fr>(), gq_m, s_gq, m);
   // g_m = eps m(tau, delta): gather per wire over the transposed matrices
   {
     DevBuf coeffs_m;
     DVP_TRY(coeffs_m.alloc((size_t)(n_coeffs ? n_coeffs : 1) * sizeof(Fr)));
-    if (n_coeffs) hipLaunchKernelGGL(ks_to_mont, dim3(cdiv(n_coeffs, TPB)), bt, 0, st, d_coeffs.as<Fr>(), coeffs_m.as<Fr>(), (size_t)n_coeffs);
+    if (n_coeffs) DVP_LAUNCH(ks_to_mont, dim3(cdiv(n_coeffs, TPB)), bt, 0, st, d_coeffs.as<Fr>(), coeffs_m.as<Fr>(), (size_t)n_coeffs);
     CsrT A{tptr[0].as<uint32_t>(), trow[0].as<uint32_t>(), tcid[0].as<uint32_t>()};
     CsrT B{tptr[1].as<uint32_t>(), trow[1].as<uint32_t>(), tcid[1].as<uint32_t>()};
     CsrT Cm{tptr[2].as<uint32_t>(), trow[2].as<uint32_t>(), tcid[2].as<uint32_t>()};
-    hipLaunchKernelGGL(ks_m_values, dim3(cdiv(n_wires, TPB)), bt, 0, st, A, B, Cm, coeffs_m.as<Fr>(), l_tau.as<Fr>(), delta_m, delta2_m, eps_m,
+    DVP_LAUNCH(ks_m_values, dim3(cdiv(n_wires, TPB)), bt, 0, st, A, B, Cm, coeffs_m.as<Fr>(), l_tau.as<Fr>(), delta_m, delta2_m, eps_m,
                        n_wires, s_gm);
     DVP_HIP(hipGetLastError());
     DVP_HIP(hipStreamSynchronize(st));
@@ -297,14 +297,14 @@ int setup_scalars_core(const SetupCircuit& cc, const uint64_t tau[4], const Fr& 
     const uint32_t nb = std::min<uint32_t>(cdiv(m, TPB), 1024u);
     DVP_TRY(pw.alloc(m * sizeof(Fr)));
     DVP_TRY(part.alloc((size_t)nb * sizeof(Fr)));
-    hipLaunchKernelGGL(ks_fill_one, gm, bt, 0, st, pw.as<Fr>(), m);
+    DVP_LAUNCH(ks_fill_one, gm, bt, 0, st, pw.as<Fr>(), m);
     const Fr ed2_m = fr_to_mont(fr_mul(eps_m, fr_mul(delta2_m, fr_one_canon())));  // eps delta^2
     // per public input: block partials of <d^j, L(tau)>, then ONE block folds them and subtracts eps delta^2 x the sum from the wire's
     // scalar in place -- no copy to the host and no wait inside the loop (the first version took two host round trips per input)
     for (uint32_t j = 0; j < n_public; ++j) {
-      hipLaunchKernelGGL(ks_dot_partial, dim3(nb), bt, 0, st, pw.as<Fr>(), l_tau.as<Fr>(), m, part.as<Fr>());
-      hipLaunchKernelGGL(ks_fold_apply, dim3(1), bt, 0, st, part.as<Fr>(), nb, ed2_m, s_gm + 1 + j);
-      if (j + 1 < n_public) hipLaunchKernelGGL(ks_mul, gm, bt, 0, st, pw.as<Fr>(), d.as<Fr>(), pw.as<Fr>(), m);
+      DVP_LAUNCH(ks_dot_partial, dim3(nb), bt, 0, st, pw.as<Fr>(), l_tau.as<Fr>(), m, part.as<Fr>());
+      DVP_LAUNCH(ks_fold_apply, dim3(1), bt, 0, st, part.as<Fr>(), nb, ed2_m, s_gm + 1 + j);
+      if (j + 1 < n_public) DVP_LAUNCH(ks_mul, gm, bt, 0, st, pw.as<Fr>(), d.as<Fr>(), pw.as<Fr>(), m);
     }
     DVP_HIP(hipGetLastError());
     DVP_HIP(hipStreamSynchronize(st));  // pw / part go out of scope
@@ -453,10 +453,10 @@ extern "C" int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delt
       // compute_vanishing_polynomial (src/ec_fft.rs:241-282): Z_S on the 2m leaves (0 on S, 1 / zinv on the other half) -> exit
       DVP_HIP(hipMemcpyAsync(t1.p, z, m * sizeof(Fr), hipMemcpyDeviceToDevice, st));
       DVP_TRY(batch_inverse_dev(t1.as<Fr>(), m, st));
-      hipLaunchKernelGGL(ks_vanish_evals, gm, bt, 0, st, t1.as<Fr>(), (uint32_t)m, which, ev.as<Fr>());
+      DVP_LAUNCH(ks_vanish_evals, gm, bt, 0, st, t1.as<Fr>(), (uint32_t)m, which, ev.as<Fr>());
       DVP_TRY(dvp_ecfft_exit_dev(tree, ev.p, co.p, st));
       DVP_HIP(hipMemsetAsync(flag.p, 0, 4, st));
-      hipLaunchKernelGGL(ks_check_monic, gm, bt, 0, st, co.as<Fr>(), (uint32_t)m, flag.as<unsigned int>());
+      DVP_LAUNCH(ks_check_monic, gm, bt, 0, st, co.as<Fr>(), (uint32_t)m, flag.as<unsigned int>());
       unsigned int bad = 0;
       DVP_HIP(hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, st));
       DVP_HIP(hipMemcpyAsync(host.data(), co.p, (m + 1) * sizeof(Fr), hipMemcpyDeviceToHost, st));
@@ -639,8 +639,8 @@ extern "C" int dvp_prover_prepares_precomputes(const char* cache_dir, int valida
       return DVP_EINVAL;
     }
     const Fr cinv_m = fr_inv(fr_to_mont(c));  // Montgomery: ks_scale(canonical, Montgomery) -> canonical
-    hipLaunchKernelGGL(ks_scale, gm, bt, 0, st, bar.as<Fr>(), cinv_m, bar.as<Fr>(), m);
-    hipLaunchKernelGGL(ks_scale, gm, bt, 0, st, zinv.as<Fr>(), cinv_m, zinv.as<Fr>(), m);
+    DVP_LAUNCH(ks_scale, gm, bt, 0, st, bar.as<Fr>(), cinv_m, bar.as<Fr>(), m);
+    DVP_LAUNCH(ks_scale, gm, bt, 0, st, zinv.as<Fr>(), cinv_m, zinv.as<Fr>(), m);
     DVP_HIP(hipGetLastError());
   }
   std::vector<uint64_t> host(m * 4), found(m * 4);
@@ -687,7 +687,7 @@ extern "C" int dvp_prover_prepares_precomputes(const char* cache_dir, int valida
     DVP_HIP(hipMemcpyAsync(co.p, zpoly.data(), nz * sizeof(Fr), hipMemcpyHostToDevice, st));
     DVP_TRY(dvp_ecfft_enter_dev(tree, co.p, ev.p, st));
     DVP_HIP(hipMemsetAsync(flag.p, 0xff, 4, st));
-    hipLaunchKernelGGL(ks_first_nonzero_even, gm, bt, 0, st, ev.as<Fr>(), (uint32_t)m, flag.as<unsigned int>());
+    DVP_LAUNCH(ks_first_nonzero_even, gm, bt, 0, st, ev.as<Fr>(), (uint32_t)m, flag.as<unsigned int>());
     unsigned int first_bad = 0;
     DVP_HIP(hipMemcpyAsync(&first_bad, flag.p, 4, hipMemcpyDeviceToHost, st));
     DVP_HIP(hipStreamSynchronize(st));

@@ -525,7 +525,7 @@ static int verify_enqueue(const VerifyConsts& c, const void* d_pub, uint32_t npu
   DVP_TRY(gen_table(&tab, st));
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
-  hipLaunchKernelGGL(k_verify<false>, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
+  DVP_LAUNCH(k_verify<false>, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
                      (const Fr*)d_pub, npub, c, tab, T, codec_rule_now(), (uint8_t*)d_verdicts, (const uint32_t*)nullptr);
   DVP_HIP(hipGetLastError());
   return DVP_OK;
@@ -657,17 +657,17 @@ static int rlc_enqueue(const VerifyConsts& c, const uint8_t key[32], const void*
   const int rule = codec_rule_now();
   uint8_t* verdicts = (uint8_t*)d_verdicts;
   h.enqueued = true;
-  hipLaunchKernelGGL(k_verify_rlc_prep, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
+  DVP_LAUNCH(k_verify_rlc_prep, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
                      (const Fr*)d_pub, npub, c, kw, T, rule, sc, bases, inf, ur, verdicts);
   const uint32_t nparts = std::min<uint32_t>(cdiv(n, RLC_SUM_TPB), RLC_SUM_BLOCKS);
-  hipLaunchKernelGGL(k_rlc_sum_blocks, dim3(nparts), dim3(RLC_SUM_TPB), 0, st, (const Fr*)ur, (const uint8_t*)verdicts, n, part, part_w);
-  hipLaunchKernelGGL(k_rlc_sum_final, dim3(1), dim3(RLC_SUM_TPB), 0, st, (const Fr*)part, (const uint32_t*)part_w, nparts, tab, sc + 2 * n,
+  DVP_LAUNCH(k_rlc_sum_blocks, dim3(nparts), dim3(RLC_SUM_TPB), 0, st, (const Fr*)ur, (const uint8_t*)verdicts, n, part, part_w);
+  DVP_LAUNCH(k_rlc_sum_final, dim3(1), dim3(RLC_SUM_TPB), 0, st, (const Fr*)part, (const uint32_t*)part_w, nparts, tab, sc + 2 * n,
                      bases + 2 * n, inf + 2 * n, n_w);
   DVP_HIP(hipGetLastError());
   DVP_TRY(msm_affine_dev_enc(sc, bases, inf, 2 * n + 1, out_xy, out_inf, nullptr, nullptr, nullptr, 0, st, err));
-  hipLaunchKernelGGL(k_rlc_check, dim3(1), dim3(64), 0, st, (const uint32_t*)out_inf, (const unsigned long long*)err, (const uint32_t*)n_w, gate,
+  DVP_LAUNCH(k_rlc_check, dim3(1), dim3(64), 0, st, (const uint32_t*)out_inf, (const unsigned long long*)err, (const uint32_t*)n_w, gate,
                      report, (uint32_t*)d_report);
-  hipLaunchKernelGGL(k_verify<true>, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
+  DVP_LAUNCH(k_verify<true>, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,
                      (const Fr*)d_pub, npub, c, tab, T, rule, verdicts, (const uint32_t*)gate);
   DVP_HIP(hipGetLastError());
   return DVP_OK;

@@ -32,6 +32,18 @@ void dvp_tune_reset(void);
 void dvp_profile_enable(int on);
 void dvp_profile_reset(void);
 int dvp_profile_read(const char* name, double* total_ms, uint64_t* launches);
+/* The launch census: every kernel launch of the library is counted per variant, always (one relaxed host increment per launch).  A
+ * variant is one kernel with its instantiated template arguments, named "<file>:<kernel><args>" as the compiler spells the
+ * instantiation, without blanks and with every argument written out: "msm.hip:k_merge<16,false>", "msm.hip:k_affine_round<false,false,true>",
+ * "ecfft.hip:k_leaf_matmul8".  dvp_debug_launch_names writes the newline-separated list of all names (every variant host code can
+ * launch, known when the library is loaded) into buf (truncated to cap, NUL-terminated) and returns the bytes needed; it touches no
+ * device.  dvp_profile_read("launch:<name>", &ms, &n) gives n = launches of that variant since the last dvp_profile_reset and ms = 0;
+ * an unknown name is DVP_EINVAL. */
+int dvp_debug_launch_names(char* buf, size_t cap);
+/* the length the device wrote into the rest list (k_bucket_pairs' buckets / k_accum_affine_fast's tasks that met an exceptional pair)
+ * during the calling thread's last MSM, read from its workspace after waiting for that MSM's stream.  DVP_EINVAL before the first MSM. */
+int dvp_debug_msm_rest_len(uint32_t* n);
+
 /* "msm_affine_round0" split by launch shape: entry k = (pairs of the MSM, summed ms, launches) for every distinct MSM size
  * since the last reset; returns the number of shapes (fills at most `cap`), < 0 on error */
 int dvp_profile_round0_shapes(uint64_t* pairs, double* total_ms, uint64_t* launches, int cap);

@@ -11,6 +11,8 @@ import pytest
 import c_oracle as co
 import pyref as o
 from util import to_limbs, from_limbs, rand_fr_np
+import ecfft_cases as ec
+import msm_cases as mc
 
 pytestmark = pytest.mark.gpu
 VEC = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "oracle_vectors.json")))
@@ -133,7 +135,8 @@ def test_extend_pass_groupings_agree(dvp, nat, log_m):
     0), and the oracle's, element for element, up to m = 2^14; extreme inputs (0, p - 1) ride along: the lazy 30-bit-limb
     values inside an extend (fr.cuh) are only reduced by its last pass.  Round 5: DVP_ECFFT_RADIX4 = 3 (the default) runs 4..9 top
     layers in ONE LDS-tiled launch (k_extend_top): log_m = 15..19 are its tile shapes with 128 .. 8 columns (the prover's own 2^20
-    has 4: test_extend_2_20_and_enter_2_16_vs_oracle), log_m = 21 the case with a grouped pass above the tiled ones."""
+    has 4: test_extend_2_20_and_enter_2_16_vs_oracle), log_m = 21 the case with a grouped pass above the tiled ones.  The launch
+    census (ecfft_cases.extend_variants) shows after every extend that the kernels of that grouping ran and no others."""
     m = 1 << log_m
     t = dvp.ec_fft.FFTree(2 * m)
     ot = co.FFTree(log_m + 1) if log_m <= 14 else None
@@ -143,8 +146,12 @@ def test_extend_pass_groupings_agree(dvp, nat, log_m):
         ev[batch - 1, m // 2:] = to_limbs([o.P - 1] * (m // 2))
         outs = []
         for radix in (3, 2, 1, 0):
+            dvp.lib.dvp_profile_reset()
             with nat.tune(DVP_ECFFT_RADIX4=radix):
                 outs.append(t.extend(ev))
+            # the launch census: the grouping this radix stands for ran, in this batch's instantiation, and no other pass kernel did
+            ran, idle = ec.extend_variants(log_m, radix, batch)
+            mc.assert_census(dvp, ran, idle, (log_m, radix, batch))
         assert all(np.array_equal(outs[0], x) for x in outs[1:]), batch
         if ot is not None and batch in (1, 3):
             for b in range(batch):
@@ -338,25 +345,41 @@ def test_enter_exit_roundtrip_2_20(dvp):
         assert from_limbs(ev[idx][None])[0] == (a * pow(L, j, o.P) + b * pow(L, k, o.P)) % o.P
 
 
+def _assert_paths(dvp, paths, where):
+    """launch census: these variants ran since the last reset, those did not, and these ran exactly so often"""
+    ran, idle, counts = paths
+    mc.assert_census(dvp, ran, idle, where)
+    for nm, cnt in counts.items():
+        assert mc.launches(dvp, nm) == cnt, (nm, where, mc.launches(dvp, nm), cnt)
+
+
 @pytest.mark.parametrize("log_n", [1, 2, 3, 6, 10, 11, 12, 13, 15])
 def test_enter_exit_folded_stages_vs_oracle_and_unfolded(dvp, nat, log_n):
     """Round 6: enter / exit fold their pointwise stages (k_exit_pre / _mid / _mulc / _post, the h1 -> h0 copy, k_enter_combine for
     sub-vectors up to 1024) into the first / last pass of their extends (ExtIo in ecfft.hip).  Every level shape is crossed here:
     h = 1 (never folded), single-launch extends (h <= 2048), and extends with k_extend_top in front and behind (h >= 4096, incl. the
     short-vector tile walk); folded and unfolded (DVP_ECFFT_FOLD=0) must both equal the oracle element for element, on enter
-    images and on evaluations that are no enter image."""
+    images and on evaluations that are no enter image.  Once the tables stand, the launch census (ecfft_cases.enter_exit_variants) shows
+    that the folded kernels ran and the pointwise ones did not at the levels ext_io_ok admits, and the reverse unfolded."""
     n = 1 << log_n
     t = dvp.ec_fft.FFTree(n)
     ot = co.FFTree(log_n)
     c = rand_fr_np(n, 600 + log_n)
     ev = rand_fr_np(n, 700 + log_n)
     want_e, want_x = ot.enter(c), ot.exit(ev)
-    for fold in (1, 0, 1):
+    for turn, fold in enumerate((1, 0, 1)):
+        enter_paths, exit_paths = ec.enter_exit_variants(log_n, fold)
         with nat.tune(DVP_ECFFT_FOLD=fold):
+            dvp.lib.dvp_profile_reset()
             e = t.enter(c)
             assert np.array_equal(e, want_e), fold
+            if turn:  # (the first call builds the tables, with enters and extends of its own)
+                _assert_paths(dvp, enter_paths, ("enter", log_n, fold))
             assert np.array_equal(t.exit(e), c), fold
+            dvp.lib.dvp_profile_reset()
             assert np.array_equal(t.exit(ev), want_x), fold
+            if turn:
+                _assert_paths(dvp, exit_paths, ("exit", log_n, fold))
     ot.close()
     t.close()
 
@@ -385,6 +408,71 @@ def test_exit_enter_2_20_folded_equals_unfolded(dvp, nat):
     t.exit_dev(d_c.data_ptr(), d_c.data_ptr(), st)
     assert torch.equal(d_c, d_in)
     t.close()
+
+
+def test_enter_exit_2_21_two_column_tile(dvp, nat, big_tree):
+    """enter / exit on 2^21 leaves: the top level's extends are 2^20 values long, nine tiled top layers (tl = TOP_MAX = 9), so
+    k_extend_top<false,3> (enter's folded combine) and <false,1> / <false,2> (exit's folded stages) run with two columns per tile row
+    (lc = FUSE_LOG - tl - 1 = 1) -- 2^21 is the smallest tree that reaches the shape.  On device tensors: folded == unfolded,
+    exit(enter(c)) == c, in place == out of place; against Python integers: enter of a X^j + b X^k is a L^j + b L^k on leaves 0, 1,
+    n - 1 and 61 random ones, j and k in the top half of the degrees (so that the 2^20-wide level carries them); and the launch census
+    shows the folded launches ran under DVP_ECFFT_FOLD = 1 with k_enter_combine left to the one level ext_io_ok refuses (h = 2048)
+    and no k_exit_pre / _post at all, and the reverse under DVP_ECFFT_FOLD = 0."""
+    import torch
+
+    log_n = 21
+    n = 1 << log_n
+    t = big_tree
+    st = torch.cuda.current_stream().cuda_stream
+    d_in = torch.from_numpy(rand_fr_np(n, 2121).view(np.int64)).cuda()
+    rnd = random.Random(21)
+    j, k = rnd.randrange(n // 2, n), rnd.randrange(n // 2, n)
+    a, b = rnd.randrange(o.P), rnd.randrange(o.P)
+    sp = np.zeros((n, 4), dtype=np.uint64)
+    sp[j], sp[k] = to_limbs([a])[0], to_limbs([b])[0]
+    d_sp = torch.from_numpy(sp.view(np.int64)).cuda()
+    outs = {}
+    for fold in (0, 1, 0, 1):  # the first turn of either flavour builds its tables; the census is read on the second
+        enter_paths, exit_paths = ec.enter_exit_variants(log_n, fold)
+        with nat.tune(DVP_ECFFT_FOLD=fold):
+            d_x, d_e, d_m = torch.empty_like(d_in), torch.empty_like(d_in), torch.empty_like(d_in)
+            dvp.lib.dvp_profile_reset()
+            t.enter_dev(d_in.data_ptr(), d_e.data_ptr(), st)
+            t.enter_dev(d_sp.data_ptr(), d_m.data_ptr(), st)
+            torch.cuda.synchronize()
+            if fold in outs:
+                ran, idle, counts = enter_paths
+                mc.assert_census(dvp, ran, idle, ("enter", fold))
+                assert {nm: mc.launches(dvp, nm) for nm in counts} == {nm: 2 * c for nm, c in counts.items()}, fold  # two enters
+                top, combine = mc.launches(dvp, ec.E + "k_extend_top<false,3>"), mc.launches(dvp, ec.E + "k_enter_combine")
+                assert (top, combine) == ((2 * 9, 2 * 1) if fold else (0, 2 * 21)), (fold, top, combine)  # levels h = 2^20 .. 2^12 fold in a top launch
+            dvp.lib.dvp_profile_reset()
+            t.exit_dev(d_in.data_ptr(), d_x.data_ptr(), st)
+            torch.cuda.synchronize()
+            if fold in outs:
+                _assert_paths(dvp, exit_paths, ("exit", fold))
+                sm1, pre, post = (mc.launches(dvp, ec.E + nm) for nm in ("k_extend_top<false,1>", "k_exit_pre", "k_exit_post"))
+                assert (sm1, pre, post) == ((2 * 9, 0, 0) if fold else (0, 2 * 21, 21)), (fold, sm1, pre, post)
+            outs[fold] = (d_x, d_e, d_m)
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]) and torch.equal(outs[0][2], outs[1][2])
+    for fold in (0, 1):
+        with nat.tune(DVP_ECFFT_FOLD=fold):
+            d_c = d_in.clone()
+            t.enter_dev(d_c.data_ptr(), d_c.data_ptr(), st)  # in place (d_out == d_in)
+            assert torch.equal(d_c, outs[fold][1]), fold
+            t.exit_dev(d_c.data_ptr(), d_c.data_ptr(), st)
+            assert torch.equal(d_c, d_in), fold  # exit(enter(c)) == c
+            d_r = torch.empty_like(d_in)
+            t.exit_dev(outs[fold][1].data_ptr(), d_r.data_ptr(), st)  # and out of place
+            assert torch.equal(d_r, d_in), fold
+            d_c = d_in.clone()
+            t.exit_dev(d_c.data_ptr(), d_c.data_ptr(), st)
+            assert torch.equal(d_c, outs[fold][0]), fold
+    leaves = t.leaves()
+    ev = outs[1][2].cpu().numpy().view(np.uint64)
+    for idx in [0, 1, n - 1] + [rnd.randrange(n) for _ in range(61)]:
+        L = from_limbs(leaves[idx][None])[0]
+        assert from_limbs(ev[idx][None])[0] == (a * pow(L, j, o.P) + b * pow(L, k, o.P)) % o.P, idx
 
 
 def test_extend_consistent_with_enter(dvp):

@@ -12,6 +12,7 @@ import pytest
 import pyref as o
 import c_oracle as co
 from util import to_limbs, from_limbs, pts_to_np, np_to_pt, rand_fr_np, np_dot_mod, np_dot_mod_fast, tau_adversarial_scalars
+from msm_cases import exceptional_pairs_input, assert_census, rest_len
 
 pytestmark = pytest.mark.gpu
 OSSL = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "k233_openssl.json")))["vectors"]
@@ -231,48 +232,98 @@ def test_msm_heavy_skew_2_18(dvp):
     assert np_to_pt(xy, is_inf) == co.k233_mulgen(np_dot_mod(s, k))
 
 
-def exceptional_pairs_input(n=4096):
-    """bases drawn from eight points and their negatives, scalars from five values: (bases, scalars, the scalars and the bases'
-    discrete logs as integers, the expected sum)"""
-    rnd = random.Random(777)
-    k8 = [rnd.randrange(1, o.P) for _ in range(8)]
-    p8 = [co.k233_mulgen(x) for x in k8]
-    vals = [rnd.randrange(o.P) for _ in range(4)] + [1]
-    pts, ks, sv = [], [], []
-    for i in range(n):
-        j, neg = rnd.randrange(8), rnd.random() < 0.5
-        pts.append(o.k233_neg(p8[j]) if neg else p8[j])
-        ks.append(o.P - k8[j] if neg else k8[j])
-        sv.append(rnd.choice(vals))
-    return pts_to_np(pts), to_limbs(sv), sv, ks, co.k233_mulgen(sum(a * b for a, b in zip(sv, ks)) % o.P)
+M = "msm.hip:"
+FAST_TABLE = [M + "k_accum_affine_fast<true,true>", M + "k_accum_affine_fast<true,false>", M + "k_accum_affine_rest<true>"]
+FAST_ROUNDS = [M + "k_accum_affine_fast<false,true>", M + "k_accum_affine_fast<false,false>", M + "k_accum_affine_rest<false>"]
+GENERAL = [M + "k_accum_affine<true,true>", M + "k_accum_affine<true,false>", M + "k_accum_affine<false,true>", M + "k_accum_affine<false,false>"]
+PAIRS = [M + "k_bucket_pairs", M + "k_bucket_rest"]
+GATHERS = [M + "k_bucket_gather_items", M + "k_bucket_gather_aff"]
+ROUNDS = [M + "k_affine_round<true,false,false>", M + "k_affine_round<false,false,false>", M + "k_affine_round<false,false,true>"]
+
+
+def reducer_route(dvp, n, windows, aff_min, pairs_max, fast=1):
+    """the launch census of one MSM of the exceptional-pairs input against the route msm_core takes for it; returns whether that
+    route keeps a rest list that this input must fill.  e = n x windows entries; rounds planned: ra_plan with (e >> ra_plan) >= aff_min
+    > (e >> (ra_plan + 1)).  The input's buckets hold hundreds of points, so every planned round runs and:
+      no round   -> the reducer reads table entries: k_accum_affine_fast<true,*> + k_accum_affine_rest<true> (DVP_MSM_BUCKET_PAIRS_MAX
+                    only applies behind a round), the general k_accum_affine<true,*> with DVP_MSM_ACCUM_FAST = 0;
+      1 .. 4     -> more than 12 points per bucket are left: k_bucket_pairs + k_bucket_rest with DVP_MSM_BUCKET_PAIRS_MAX = 100000,
+                    else the reducer on the rounds' output, k_accum_affine_fast<false,*> + _rest<false> / k_accum_affine<false,*>;
+      more       -> (DVP_MSM_AFF_MIN = 32, 512) how many points the last round leaves is the device's business: one per bucket goes
+                    through k_bucket_gather_aff; the census still shows that the knob kept the other family out.
+    The rest list is non-empty where the route keeps one and at most one round ran: the buckets are full of equal and opposite
+    points then.  (Measured on this input: four rounds have used the exceptional pairs up, the list is empty from there on.)"""
+    e, ra_plan = n * windows, 0
+    while (e >> (ra_plan + 1)) >= aff_min:
+        ra_plan += 1
+    where = (n, windows, aff_min, pairs_max, fast, ra_plan)
+    first = (FAST_TABLE if fast else GENERAL[:2]) if ra_plan == 0 else (FAST_ROUNDS if fast else GENERAL[2:])
+    others = [x for x in FAST_TABLE + FAST_ROUNDS + GENERAL if x not in first]
+    if ra_plan == 0:
+        assert_census(dvp, [first[0][:first[0].index("<")] + "*"], others + PAIRS + GATHERS + ROUNDS, where)
+        if fast:
+            assert_census(dvp, [first[-1]], [], where)
+    elif ra_plan <= 4:
+        assert_census(dvp, [ROUNDS[0]], [GATHERS[0]], where)
+        if pairs_max >= 100000:
+            assert_census(dvp, PAIRS, FAST_TABLE + FAST_ROUNDS + GENERAL + GATHERS + [M + "k_bucket_gather"], where)
+        else:
+            assert_census(dvp, [first[0][:first[0].index("<")] + "*", M + "k_bucket_gather"], others + PAIRS + GATHERS, where)
+            if fast:
+                assert_census(dvp, [first[-1]], [], where)
+    else:
+        assert_census(dvp, ROUNDS[:1], [GATHERS[0]] + FAST_TABLE + GENERAL[:2] + (PAIRS if pairs_max == 0 else []) +
+                      (FAST_ROUNDS + GENERAL[2:] + [M + "k_bucket_gather"] if pairs_max >= 100000 else []) + (FAST_ROUNDS if not fast else GENERAL[2:]), where)
+    keeps_list = ra_plan <= 1 and (fast or (ra_plan == 1 and pairs_max >= 100000))
+    if keeps_list:
+        assert rest_len(dvp) > 0, where
+    return keeps_list
 
 
 def test_bucket_reduction_exceptional_pairs(dvp):
     """what the pair rounds leave (k_bucket_pairs / k_bucket_rest): bases drawn from eight points and their negatives,
     scalars from five values, so that the buckets the rounds hand over hold equal points (P + P), opposite points
     (P - P) and the infinity markers earlier rounds made of them -- the pairs the fast formulas refuse and the list
-    redoes.  Fixed-base and one-shot, the rounds stopped at several depths, against the fan-in-K reducer route
-    (DVP_MSM_BUCKET_PAIRS_MAX=0) and the oracle."""
+    redoes.  Fixed-base and one-shot, the rounds stopped at several depths (after none and after one as well: DVP_MSM_AFF_MIN =
+    2^19 / 2^15, where the reducer's own exception-free first level and its rest list take the table entries / the first round's
+    output), against the fan-in-K reducer route (DVP_MSM_BUCKET_PAIRS_MAX=0) and the oracle.  Beside every oracle comparison the
+    launch census shows the route that ran (reducer_route), and the rest list's length that it was used."""
     bases, s, sv, ks, exp = exceptional_pairs_input()
     lo, hi = 100, 3000
     exp_part = co.k233_mulgen(sum(a * b for a, b in zip(sv[lo:hi], ks[lo:hi])) % o.P)
+    listed = 0
     for c in (8, 11):
         with dvp.tune(DVP_MSM_FIXED_C=c):
             fb = dvp.curve.FixedBaseMsm(bases)
-        for aff_min in (32, 512, 4096):
+        w_fx, w_os = fb.plan()[1], (234 + c - 1) // c  # entries per point that really exist (the overflow windows stay empty)
+        for aff_min in (32, 512, 4096, 1 << 15, 1 << 19):
             for pairs_max in (0, 12, 100000):
                 with dvp.tune(DVP_MSM_AFF_MIN=aff_min, DVP_MSM_BUCKET_PAIRS_MAX=pairs_max, DVP_MSM_C=c, DVP_MSM_ROUND_PIPELINE=int(aff_min != 512)):
+                    dvp.lib.dvp_profile_reset()
                     assert np_to_pt(*fb.run(s)) == exp, (c, aff_min, pairs_max)
+                    listed += reducer_route(dvp, len(sv), w_fx, aff_min, pairs_max)
+                    dvp.lib.dvp_profile_reset()
                     assert np_to_pt(*fb.run(s[lo:hi], lo, hi)) == exp_part, (c, aff_min, pairs_max)
+                    listed += reducer_route(dvp, hi - lo, w_fx, aff_min, pairs_max)
+                    dvp.lib.dvp_profile_reset()
                     assert gpu_msm(dvp, s, bases) == exp, (c, aff_min, pairs_max)
+                    listed += reducer_route(dvp, len(sv), w_os, aff_min, pairs_max)
                 if pairs_max == 0:
                     # round 6: the reducer's first level without exceptional branches + its rest list (k_accum_affine_fast / _rest), its last
                     # level on rows of 16 lanes, ld_add_nodbl's doubling from a copy, the one-shot tail's group sums -- each switched off in turn
                     for knob in ("DVP_MSM_ACCUM_FAST", "DVP_MSM_ACCUM_HEX_MAX", "DVP_MSM_TAIL_GROUPS"):
+                        off = {"DVP_MSM_ACCUM_FAST": FAST_TABLE + FAST_ROUNDS, "DVP_MSM_ACCUM_HEX_MAX": [M + "k_accum_proj<16>"], "DVP_MSM_TAIL_GROUPS": [M + "k_tail_groups"]}[knob]
                         with dvp.tune(DVP_MSM_AFF_MIN=aff_min, DVP_MSM_BUCKET_PAIRS_MAX=0, DVP_MSM_C=c, **{knob: 0}):
+                            dvp.lib.dvp_profile_reset()
                             assert np_to_pt(*fb.run(s)) == exp, (c, aff_min, knob)
+                            reducer_route(dvp, len(sv), w_fx, aff_min, 0, fast=int(knob != "DVP_MSM_ACCUM_FAST"))
+                            assert_census(dvp, [], off, (c, aff_min, knob))
+                            dvp.lib.dvp_profile_reset()
                             assert gpu_msm(dvp, s, bases) == exp, (c, aff_min, knob)
+                            reducer_route(dvp, len(sv), w_os, aff_min, 0, fast=int(knob != "DVP_MSM_ACCUM_FAST"))
+                            assert_census(dvp, [M + "k_tail<false>"], off, (c, aff_min, knob))
         fb.close()
+    assert listed >= 2 * 2 * 3 * 2  # both windows, AFF_MIN 2^15 and 2^19, every DVP_MSM_BUCKET_PAIRS_MAX, fixed-base and one-shot at the least
 
 
 def test_msm_multiplier_form_knobs(dvp):
@@ -289,7 +340,9 @@ def test_msm_multiplier_form_knobs(dvp):
       DVP_MSM_AFF_TPB 64 / 128, DVP_MSM_AFF_BMIN 1 / 136 (= DVP_MSM_AFF_BMAX, the most it accepts) -- the pair rounds, which
         DVP_MSM_AFF_MIN=32 makes run at this size;
       DVP_FX_HI at both ends of what msm_fixed_settle accepts (0 <= h <= 10, 1 <= key bits - h <= 15): 0 / 9 for c = 11 (10 key bits),
-        2 / 10 for c = 18 (17 key bits); read when the context is created."""
+        2 / 10 for c = 18 (17 key bits); read when the context is created.
+    Beside each oracle comparison of a setting the launch census shows the variants the setting names ran and their complement under
+    that knob did not (paths, below)."""
     big = 1 << 30
     xb, xs, _, _, xexp = exceptional_pairs_input()
     n = 3000
@@ -311,14 +364,56 @@ def test_msm_multiplier_form_knobs(dvp):
     ]
     for knob in ("DVP_GF_INV_TABS", "DVP_MSM_HEX_MAX", "DVP_MSM_QUAD_MAX", "DVP_MSM_ACCUM_QUAD_MAX", "DVP_MSM_AFF_TPB", "DVP_MSM_AFF_BMIN"):
         assert any(knob in st for st in settings)
+    merges = {g: [f"{M}k_merge<{g},true>", f"{M}k_merge<{g},false>"] for g in (1, 4, 16)}
+    proj = {g: f"{M}k_accum_proj<{g}>" for g in (1, 4, 16)}
+
+    def paths(st, one_shot, random_points):
+        """(variants that ran, variants that did not) under the setting `st`, from the launch census: what the knob selects where
+        msm_core reads it, and its complement.  c = 11: 1 024 buckets fixed-base, 23 x 2 048 one-shot; every merge level has at least
+        ten additions, so DVP_MSM_QUAD_MAX = 1 leaves none to the quads."""
+        ran, idle = [], []
+        if st.get("DVP_MSM_AFF_MIN", 1 << 19) == 32:  # the pair rounds run (one-word descriptors: DVP_MSM_ROUND_DENSE is 0)
+            ran += ROUNDS[:2]
+            idle += ROUNDS[2:] + FAST_TABLE + GENERAL[:2]
+        elif "DVP_MSM_AFF_MIN" not in st:
+            idle += ROUNDS
+        if st.get("DVP_MSM_HEX_MAX") == 0:
+            idle += merges[16] + [M + "k_tail<true>"]
+            ran += [M + "k_tail<false>"]
+            if st.get("DVP_MSM_QUAD_MAX") == big:
+                ran, idle = ran + merges[4], idle + merges[1]
+            elif st.get("DVP_MSM_QUAD_MAX") == 1:
+                ran, idle = ran + merges[1], idle + merges[4]
+        if "DVP_MSM_ACCUM_QUAD_MAX" in st:  # the fan-in reducer, forced; its last level never on rows of 16
+            quad = st["DVP_MSM_ACCUM_QUAD_MAX"] == big
+            q, nq = ("true", "false") if quad else ("false", "true")
+            idle += PAIRS + [proj[16], proj[1] if quad else proj[4]]
+            behind_rounds = st.get("DVP_MSM_AFF_MIN") == 4096
+            ind, nind = ("false", "true") if behind_rounds else ("true", "false")
+            fast = st.get("DVP_MSM_ACCUM_FAST", 1)
+            name = "k_accum_affine_fast" if fast else "k_accum_affine"
+            mine = [f"{M}{name}<{ind},{q}>"] + ([f"{M}k_accum_affine_rest<{ind}>"] if fast else [])
+            idle += [x for x in FAST_TABLE + FAST_ROUNDS + GENERAL if x not in mine]
+            # (3 000 random points one-shot: ~1.4 points per bucket, the largest holds a handful: four planned rounds leave one point
+            # per bucket and k_bucket_gather_aff takes them -- no reducer level runs, whatever the knob; everywhere else the named one does)
+            if not (behind_rounds and one_shot and random_points):
+                ran += mine + [M + "k_bucket_gather"]
+            if behind_rounds:
+                ran += ROUNDS[:1]
+        return ran, idle
+
     for bases, sc, exp in inputs:
         with dvp.tune(DVP_MSM_FIXED_C=11):
             fb = dvp.curve.FixedBaseMsm(bases)
         assert np_to_pt(*fb.run(sc)) == exp and gpu_msm(dvp, sc, bases) == exp  # the defaults
         for st in settings:
             with dvp.tune(DVP_MSM_C=11, **st):
+                dvp.lib.dvp_profile_reset()
                 assert np_to_pt(*fb.run(sc)) == exp, st
+                assert_census(dvp, *paths(st, False, bases is rb), (st, "fixed-base"))
+                dvp.lib.dvp_profile_reset()
                 assert gpu_msm(dvp, sc, bases) == exp, st
+                assert_census(dvp, *paths(st, True, bases is rb), (st, "one-shot"))
         fb.close()
         for c, his in ((11, (0, 9)), (18, (2, 10))):
             for h in his:

@@ -15,6 +15,7 @@ import pytest
 import pyref as o
 import c_oracle as co
 from util import to_limbs, from_limbs, pts_to_np, np_to_pt, rand_fr_np, np_dot_mod
+from msm_cases import exceptional_pairs_input
 
 pytestmark = pytest.mark.gpu
 
@@ -109,25 +110,10 @@ def test_degenerate_leftover_patterns(dvp, c):
             fb.close()
 
 
-def exceptional_pairs_input(n=4096):
-    """the input of test_gpu_msm.test_bucket_reduction_exceptional_pairs: bases drawn from eight points and their negatives, scalars
-    from five values -- (bases, scalars, expected sum)"""
-    rnd = random.Random(777)
-    k8 = [rnd.randrange(1, o.P) for _ in range(8)]
-    p8 = [co.k233_mulgen(x) for x in k8]
-    vals = [rnd.randrange(o.P) for _ in range(4)] + [1]
-    pts, ks, sv = [], [], []
-    for i in range(n):
-        j, neg = rnd.randrange(8), rnd.random() < 0.5
-        pts.append(o.k233_neg(p8[j]) if neg else p8[j])
-        ks.append(o.P - k8[j] if neg else k8[j])
-        sv.append(rnd.choice(vals))
-    return pts_to_np(pts), to_limbs(sv), co.k233_mulgen(sum(a * b for a, b in zip(sv, ks)) % o.P)
-
-
 @pytest.fixture(scope="module")
 def exceptional_input():
-    return exceptional_pairs_input()
+    bases, s, _, _, exp = exceptional_pairs_input()  # the input of test_gpu_msm.test_bucket_reduction_exceptional_pairs
+    return bases, s, exp
 
 
 @pytest.mark.parametrize("c", [8, 11])
