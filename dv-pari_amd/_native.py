@@ -67,6 +67,11 @@ _SIGS = {
     "dvp_fr_vec_axpy": (C.c_int, [u64p, u64p, u64p, sz, u64p]),
     "dvp_fr_vec_dot": (C.c_int, [u64p, u64p, sz, u64p]),
     "dvp_fr_spmv": (C.c_int, [vp, vp, vp, u32, u64p, u32, u64p, u32, u64p]),
+    "dvp_fr_from_be32": (C.c_int, [u8p, sz, u64p]),
+    "dvp_fr_from_be32_dev": (C.c_int, [vp, sz, vp, vp]),
+    "dvp_debug_fr_from_be32_host": (C.c_int, [u8p, sz, u64p]),
+    "dvp_prove_be32": (C.c_int, [vp, u8p, sz, u8p]),
+    "dvp_prove_cache_dir_witness_file": (C.c_int, [C.c_char_p, u32, C.c_char_p, u8p, u64p]),
     "dvp_debug_fr_op": (C.c_int, [C.c_int, C.POINTER(vp), sz, C.c_int, C.POINTER(vp)]),
     "dvp_debug_gf_op": (C.c_int, [C.c_int, C.c_int, C.POINTER(vp), sz, C.c_uint64, C.POINTER(vp)]),
     "dvp_barycentric_eval": (C.c_int, [u64p, u64p, u64p, u64p, sz, u64p, u64p]),

@@ -31,6 +31,11 @@
 
 #include "../../include/dvpari.h"
 #include "../../include/dvpari_internal.h"  // dvp_tune_get (DVP_CACHE_REPLICAS)
+#include "fr_wire.cuh"                      // fr_from_be32_words: element 0 and the public inputs of a witness file
+
+namespace dvp {
+extern thread_local int64_t g_last_error_index;  // capi.cpp (dvp_last_error_index)
+}
 
 namespace {
 
@@ -442,9 +447,10 @@ extern "C" int dvp_prover_open_cache_dir(const char* cache_dir, uint32_t n_publi
   return DVP_OK;
 }
 
-extern "C" int dvp_prove_cache_dir(const char* cache_dir, const uint64_t* public_inputs, uint32_t n_public,
-                                   const uint64_t* private_inputs, uint32_t n_private, uint8_t proof[118]) {
-  if (!cache_dir || !proof) return DVP_EINVAL;
+// one proof on the entry of (cache_dir, n_public): takes a prover of the entry (waiting its turn), brings its binding up to date, runs
+// prove(prover), gives the prover back.  Shared by the limb flavour and the witness-file flavour of Proof::prove(cache_dir, ..).
+template <class F>
+static int prove_on_entry(const char* cache_dir, uint32_t n_public, F prove) {
   std::shared_ptr<OpenEntry> e;
   int rc = open_entry(cache_dir, n_public, &e);
   if (rc) return rc;
@@ -496,13 +502,51 @@ extern "C" int dvp_prove_cache_dir(const char* cache_dir, const uint64_t* public
       if (rc == DVP_OK) e->applied_gen[slot] = gen;
     }
   }
-  if (rc == DVP_OK) rc = dvp_prove(pv, public_inputs, n_public, private_inputs, n_private, proof);
+  if (rc == DVP_OK) rc = prove(pv);
   {
     std::lock_guard<std::mutex> g(e->slot_mu);
     e->busy[slot] = false;
     if (rc == DVP_OK) ++e->proofs_done;
   }
   e->slot_cv.notify_one();
+  return rc;
+}
+
+extern "C" int dvp_prove_cache_dir(const char* cache_dir, const uint64_t* public_inputs, uint32_t n_public,
+                                   const uint64_t* private_inputs, uint32_t n_private, uint8_t proof[118]) {
+  if (!cache_dir || !proof) return DVP_EINVAL;
+  return prove_on_entry(cache_dir, n_public,
+                        [&](dvp_prover* pv) { return dvp_prove(pv, public_inputs, n_public, private_inputs, n_private, proof); });
+}
+
+// load_witness_from_file + Proof::prove in one call (src/gnark_r1cs.rs:188-211, src/dvsnark_test.rs:189-229): the file is mapped and its
+// payload handed to dvp_prove_be32 as it is -- the elements are reduced mod p on the device.  Everything that can be said about the file
+// without a device (header, count against the length, element 0 == 1) is said BEFORE the cache_dir entry is opened.
+extern "C" int dvp_prove_cache_dir_witness_file(const char* cache_dir, uint32_t n_public, const char* witness_path, uint8_t proof[118],
+                                                uint64_t* public_inputs_out) {
+  if (!cache_dir || !proof) return DVP_EINVAL;
+  const std::string path = witness_path ? std::string(witness_path) : join(cache_dir, "witness_to_dvsnark");  // src/artifacts.rs
+  Mapped f;
+  int rc = f.open_ro(path.c_str());
+  if (rc) return rc;
+  if (f.len < 4) return DVP_EIO;
+  const uint32_t cnt = ((uint32_t)f.p[0] << 24) | ((uint32_t)f.p[1] << 16) | ((uint32_t)f.p[2] << 8) | f.p[3];
+  if ((f.len - 4) / 32 < cnt) return DVP_EIO;
+  if (cnt < 1 + (uint64_t)n_public) return DVP_EINVAL;  // [1, public.., private..]
+  const uint8_t* payload = f.p + 4;
+  auto reduce = [&](size_t i, uint64_t out[4]) {
+    uint32_t be[8], r[8];
+    memcpy(be, payload + 32 * i, 32);
+    dvp::fr_from_be32_words(be, r);
+    memcpy(out, r, 32);
+  };
+  if (!dvp::fr_be32_is_one(payload)) {  // the constant wire (src/proving.rs:449-452)
+    dvp::g_last_error_index = 0;
+    return DVP_EINVAL;
+  }
+  rc = prove_on_entry(cache_dir, n_public, [&](dvp_prover* pv) { return dvp_prove_be32(pv, payload, cnt, proof); });
+  if (rc == DVP_OK && public_inputs_out)
+    for (uint32_t i = 0; i < n_public; ++i) reduce(1 + (size_t)i, public_inputs_out + 4 * (size_t)i);
   return rc;
 }
 

@@ -27,6 +27,7 @@
 #include "blake3_dev.cuh"
 #include "common.h"
 #include "ecfft_internal.h"
+#include "fr_wire.cuh"
 #include "k233.cuh"
 
 extern "C" int dvp_ecfft_create(uint32_t log_n, int shifted, uint32_t base_log, dvp_ecfft** out);
@@ -1607,6 +1608,24 @@ extern "C" int dvp_prove(dvp_prover* p, const uint64_t* public_inputs, uint32_t 
   if (n_public) DVP_HIP(hipMemcpyAsync(p->w + 1, public_inputs, (size_t)n_public * 32, hipMemcpyHostToDevice, p->own_stream));
   if (n_private) DVP_HIP(hipMemcpyAsync(p->w + 1 + n_public, private_inputs, (size_t)n_private * 32, hipMemcpyHostToDevice, p->own_stream));
   DVP_HIP(hipStreamSynchronize(p->own_stream));  // `one` lives on this stack frame, and the caller's buffers are free again on return anyway
+  return dvp_prove_dev(p, p->w, proof, p->own_stream);
+}
+
+// The same from the witness as the file holds it (load_witness_from_file's payload, src/gnark_r1cs.rs:188-211 -> Proof::prove,
+// src/dvsnark_test.rs:189-229): n >= n_wires elements of 32 bytes big-endian, unreduced.  dvp_prove step for step, except that the raw
+// bytes go into p->w and k_fr_from_be32 (fr_wire.hip) reduces them there, in place: no staging buffer.  The kernel is enqueued behind
+// the wait for the copy, so it runs while the host enqueues the proof.  The host looks at element 0 only (it must be the constant 1).
+extern "C" int dvp_prove_be32(dvp_prover* p, const uint8_t* witness_be32, size_t n, uint8_t proof[118]) {
+  if (!p || !proof || !witness_be32 || n < p->n_wires) return DVP_EINVAL;
+  if (!fr_be32_is_one(witness_be32)) {
+    g_last_error_index = 0;
+    return DVP_EINVAL;
+  }
+  if (!prover_ready(p)) return DVP_EINVAL;
+  if (!p->own_stream) DVP_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
+  DVP_HIP(hipMemcpyAsync(p->w, witness_be32, (size_t)p->n_wires * 32, hipMemcpyHostToDevice, p->own_stream));
+  DVP_HIP(hipStreamSynchronize(p->own_stream));  // the caller's buffer is free again on return
+  DVP_TRY(dvp_fr_from_be32_dev(p->w, p->n_wires, p->w, p->own_stream));
   return dvp_prove_dev(p, p->w, proof, p->own_stream);
 }
 

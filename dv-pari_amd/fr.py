@@ -76,6 +76,41 @@ def batch_inverse(a):
     return a
 
 
+def _be32_arg(raw) -> np.ndarray:
+    """n x 32 big-endian bytes (bytes-like, or a uint8 array of shape [n, 32] / [32 n]) as a contiguous uint8 [n, 32]"""
+    a = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else np.asarray(raw)
+    if a.dtype != np.uint8:
+        raise ValueError(f"from_be32: expected bytes or a uint8 array, got {a.dtype}")
+    if a.ndim == 2 and a.shape[1] != 32 or a.ndim > 2 or a.size % 32:
+        raise ValueError(f"from_be32: expected n x 32 bytes, got shape {a.shape}")
+    return np.ascontiguousarray(a).reshape(-1, 32)
+
+
+def from_be32(raw) -> np.ndarray:
+    """gnark_element_to_fr over a vector (src/gnark_r1cs.rs:58-77): n x 32 big-endian bytes, any value below 2^256, -> uint64 [n, 4]
+    canonical, reduced mod p on the GPU (dvp_fr_from_be32)"""
+    a = _be32_arg(raw)
+    out = np.zeros((a.shape[0], 4), dtype=np.uint64)
+    if a.shape[0]:
+        check(lib.dvp_fr_from_be32(ptr(a), a.shape[0], ptr(out)), "dvp_fr_from_be32")
+    return out
+
+
+def from_be32_host(raw) -> np.ndarray:
+    """the host build of the same function (dvp_debug_fr_from_be32_host): no GPU needed; for tests"""
+    a = _be32_arg(raw)
+    out = np.zeros((a.shape[0], 4), dtype=np.uint64)
+    if a.shape[0]:
+        check(lib.dvp_debug_fr_from_be32_host(ptr(a), a.shape[0], ptr(out)), "dvp_debug_fr_from_be32_host")
+    return out
+
+
+def from_be32_dev(d_be32: int, n: int, d_out: int = None, stream: int = 0):
+    """dvp_fr_from_be32_dev: n elements at the device address d_be32 -> d_out (None = in place), both 16-byte aligned; only enqueues
+    on `stream`"""
+    check(lib.dvp_fr_from_be32_dev(d_be32 or None, n, (d_be32 if d_out is None else d_out) or None, stream or None), "dvp_fr_from_be32_dev")
+
+
 # enum dvp_fr_op (include/dvpari_internal.h): name -> (number, inputs, outputs)
 DEBUG_OPS = {name: (k, n_in, n_out) for k, (name, n_in, n_out) in enumerate([
     ("add", 2, 1), ("sub", 2, 1), ("neg", 1, 1), ("dbl", 1, 1), ("cond_sub_p", 1, 1), ("is_canonical", 1, 1), ("mul", 2, 1),

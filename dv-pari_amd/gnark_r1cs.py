@@ -133,6 +133,23 @@ def load_witness_from_file(path) -> np.ndarray:
     return out
 
 
+def read_witness_raw(path) -> np.ndarray:
+    """the payload of a witness file as it is: uint8 [n, 32], big-endian and NOT reduced, a read-only view of the mapped file (no
+    copy).  Feed it to Prover.prove_be32 or fr.from_be32; the header is checked as dvp_file_witness_read checks it."""
+    import mmap
+    import os
+
+    with open(os.fspath(path), "rb") as f:
+        size = os.fstat(f.fileno()).st_size
+        if size < 4:
+            raise ValueError(f"{path}: too short for the count")
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    (n,) = struct.unpack_from(">I", mm, 0)
+    if (size - 4) // 32 < n:
+        raise ValueError(f"{path}: the count {n} exceeds the {size - 4} bytes that follow")
+    return np.frombuffer(mm, dtype=np.uint8, count=32 * n, offset=4).reshape(n, 32)
+
+
 def write_witness_to_file(path, values):
     """the writer side of the witness format (the reference only reads it; used by the synthetic generators)"""
     import os

@@ -53,6 +53,20 @@ class Proof:
               "dvp_prove_cache_dir")
         return Proof.from_bytes(out.tobytes())
 
+    @staticmethod
+    def prove_witness_file(cache_dir, num_public_inputs: int, witness_path=None):
+        """load_witness_from_file + Proof::prove in one call (dvp_prove_cache_dir_witness_file): the witness file (None =
+        cache_dir/witness_to_dvsnark) is mapped and its elements are reduced mod p on the GPU.  Returns (Proof, public_inputs as
+        uint64 [num_public_inputs, 4])."""
+        import os
+
+        out = np.zeros(118, dtype=np.uint8)
+        pub = np.zeros((max(num_public_inputs, 1), 4), dtype=np.uint64)
+        wp = None if witness_path is None else os.fspath(witness_path).encode()
+        check(lib.dvp_prove_cache_dir_witness_file(os.fspath(cache_dir).encode(), num_public_inputs, wp, ptr(out), ptr(pub)),
+              "dvp_prove_cache_dir_witness_file")
+        return Proof.from_bytes(out.tobytes()), pub[:num_public_inputs]
+
     def a0_fr(self):
         v = int.from_bytes(self.a0, "little")
         return (v, True) if v < P else (0, False)  # FrBits::to_fr, src/curve.rs:43-59
@@ -243,6 +257,14 @@ class Prover:
         pub, prv = _fr_arg(public_inputs), _fr_arg(private_inputs)
         out = np.zeros(118, dtype=np.uint8)
         check(lib.dvp_prove(self._h, ptr(pub), pub.shape[0], ptr(prv), prv.shape[0], ptr(out)), "dvp_prove")
+        return Proof.from_bytes(out.tobytes())
+
+    def prove_be32(self, raw) -> Proof:
+        """the same from the witness as its file holds it (gnark_r1cs.read_witness_raw): at least n_wires elements of
+        [1, public.., private..], 32 big-endian bytes each, reduced mod p on the GPU (dvp_prove_be32)"""
+        a = fr._be32_arg(raw)
+        out = np.zeros(118, dtype=np.uint8)
+        check(lib.dvp_prove_be32(self._h, ptr(a) if a.shape[0] else None, a.shape[0], ptr(out)), "dvp_prove_be32")
         return Proof.from_bytes(out.tobytes())
 
     def debug(self, name: str, n: int = None):

@@ -3,6 +3,13 @@
 // (src/proving.rs:426) from files alone:
 //
 //   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3] [--table-budget <bytes>] [--bind-srs] [--circuit-hash <hex>]
+//                 [--host-witness] [--repeat N --threads T]
+//
+// The witness goes from the file to the proof in one call, dvp_prove_cache_dir_witness_file: the library maps
+// <cache_dir>/witness_to_dvsnark and reduces its elements mod p on the GPU.  --host-witness keeps the two-step path a host used before
+// that entry existed: dvp_file_witness_read (reduction on one host thread) + dvp_prover_open_cache_dir + dvp_prove.  Same bytes.
+// --repeat N --threads T: N more proofs through dvp_prove_cache_dir with the witness as limbs in host memory, whichever way the first
+// proof went; the witness is read and reduced on the host only for this leg or under --host-witness.
 //
 // --bind-srs: bind the proof's challenge to the SRS (dvp_prover_srs_hash + dvp_prover_set_transcript_binding); the SRS hash used goes
 // to stderr -- the verifier needs it (dvp_verify_cli --srs-hash).  --circuit-hash <64 hex digits>: the circuit half of the binding
@@ -48,7 +55,7 @@ static bool parse_hash(const char* s, uint8_t out[32]) {
 
 int main(int argc, char** argv) {
   std::vector<int> devices;
-  bool bind_srs = false, have_circuit = false;
+  bool bind_srs = false, have_circuit = false, host_witness = false;
   uint8_t srs_hash[32] = {0}, circuit_hash[32] = {0};
   int repeat = 0, threads = 1;  // --repeat N --threads T: N more proofs through dvp_prove_cache_dir from T host threads
   std::vector<char*> pos;
@@ -66,6 +73,8 @@ int main(int argc, char** argv) {
       have_budget = true;
     } else if (std::string(argv[i]) == "--bind-srs") {
       bind_srs = true;
+    } else if (std::string(argv[i]) == "--host-witness") {
+      host_witness = true;
     } else if (std::string(argv[i]) == "--circuit-hash" && i + 1 < argc) {
       if (!parse_hash(argv[++i], circuit_hash)) {
         fprintf(stderr, "--circuit-hash: expected 64 hex digits, got '%s'\n", argv[i]);
@@ -97,7 +106,7 @@ int main(int argc, char** argv) {
     }
   }
   if (pos.size() < 2) {
-    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--circuit-hash HEX] [--repeat N --threads T]\n", argv[0]);
+    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--circuit-hash HEX] [--host-witness] [--repeat N --threads T]\n", argv[0]);
     return 2;
   }
   argc = (int)pos.size() + 1;
@@ -117,74 +126,139 @@ int main(int argc, char** argv) {
     }
   }
   const std::string wpath = dir + "/witness_to_dvsnark";
-  size_t n = 0;
-  int rc = dvp_file_witness_read(wpath.c_str(), nullptr, 0, &n);
-  if (rc != DVP_OK) {
-    fprintf(stderr, "%s: %s\n", wpath.c_str(), dvp_strerror(rc));
-    return 1;
-  }
-  std::vector<uint64_t> w(4 * n);
-  rc = dvp_file_witness_read(wpath.c_str(), w.data(), n, &n);
-  if (rc != DVP_OK || n < 1 + (size_t)n_public) {
-    fprintf(stderr, "witness: %s (n = %zu)\n", dvp_strerror(rc), n);
-    return 1;
-  }
-  if (w[0] != 1 || w[1] || w[2] || w[3]) {
-    fprintf(stderr, "witness[0] must be the constant 1 (src/proving.rs:449-452)\n");
-    return 1;
-  }
   uint8_t proof[118];
-  // The dump knows wires only up to the highest one used; the library takes the witness length from |g_m|, so hand over
-  // exactly that many private inputs (a longer witness file is truncated by the reference's zip as well).
-  dvp_prover* p = nullptr;
-  rc = dvp_prover_open_cache_dir(dir.c_str(), n_public, &p);
-  if (rc != DVP_OK) {
-    fprintf(stderr, "open %s: %s (index %lld)\n", dir.c_str(), dvp_strerror(rc), (long long)dvp_last_error_index());
-    return 1;
+  std::vector<uint64_t> w;  // the witness as canonical limbs, read and reduced on the host: --host-witness and --repeat only
+  size_t n = 0, n_wires = 0;
+  int rc = DVP_OK;
+  if (host_witness || repeat > 0) {
+    rc = dvp_file_witness_read(wpath.c_str(), nullptr, 0, &n);
+    if (rc != DVP_OK) {
+      fprintf(stderr, "%s: %s\n", wpath.c_str(), dvp_strerror(rc));
+      return 1;
+    }
+    w.resize(4 * n);
+    rc = dvp_file_witness_read(wpath.c_str(), w.data(), n, &n);
+    if (rc != DVP_OK || n < 1 + (size_t)n_public) {
+      fprintf(stderr, "witness: %s (n = %zu)\n", dvp_strerror(rc), n);
+      return 1;
+    }
+    if (w[0] != 1 || w[1] || w[2] || w[3]) {
+      fprintf(stderr, "witness[0] must be the constant 1 (src/proving.rs:449-452)\n");
+      return 1;
+    }
   }
-  // |[w | q2]| = n_wires + m and |[k_a | k_b | k_r]| = 4m
-  const size_t n_wires = dvp_prover_msm_size(p, 0) - dvp_prover_msm_size(p, 1) / 4;
-  if (n_wires < 1 + (size_t)n_public || n_wires > n) {
-    fprintf(stderr, "witness has %zu entries, the commitment key wants %zu\n", n, n_wires);
+  if (!host_witness) {
+    // load_witness_from_file + Proof::prove as ONE call: the library maps the file and reduces its elements mod p on the GPU.  The
+    // prover is the one the library keeps for this directory, so the budget and the binding go to that one.
+    dvp_prover* cp = nullptr;
+    if (have_budget || bind_srs) {
+      rc = dvp_cache_dir_prover(dir.c_str(), n_public, &cp);
+      if (rc != DVP_OK) {
+        fprintf(stderr, "open %s: %s (index %lld)\n", dir.c_str(), dvp_strerror(rc), (long long)dvp_last_error_index());
+        return 1;
+      }
+    }
+    if (have_budget) {
+      rc = dvp_prover_set_table_budget(cp, budget);
+      if (rc != DVP_OK) {
+        fprintf(stderr, "--table-budget: %s\n", dvp_strerror(rc));
+        return 1;
+      }
+    }
+    if (bind_srs || have_circuit) {
+      rc = bind_srs ? dvp_prover_srs_hash(cp, srs_hash) : DVP_OK;
+      if (rc == DVP_OK) rc = dvp_cache_dir_set_binding(dir.c_str(), n_public, bind_srs ? srs_hash : nullptr, have_circuit ? circuit_hash : nullptr, 0);
+      if (rc != DVP_OK) {
+        fprintf(stderr, "--bind-srs / --circuit-hash: %s\n", dvp_strerror(rc));
+        return 1;
+      }
+      if (bind_srs) {
+        fprintf(stderr, "srs hash: ");
+        for (int i = 0; i < 32; ++i) fprintf(stderr, "%02x", srs_hash[i]);
+        fprintf(stderr, "\n");
+      }
+    }
+    rc = dvp_prove_cache_dir_witness_file(dir.c_str(), n_public, nullptr, proof, nullptr);
+    if (rc != DVP_OK) {
+      fprintf(stderr, "prove from %s: %s (index %lld)\n", wpath.c_str(), dvp_strerror(rc), (long long)dvp_last_error_index());
+      return 1;
+    }
+    if (have_budget)
+      for (int which = 1; which >= 0; --which) {
+        size_t covered = 0, total = 0;
+        int reason = 0;
+        if (dvp_prover_msm_coverage(cp, which, &covered, &total, &reason) == DVP_OK)
+          fprintf(stderr, "MSM %d: %zu of %zu bases from tables (%llu bytes)%s\n", which, covered, total,
+                  (unsigned long long)dvp_prover_msm_table_bytes(cp, which, nullptr),
+                  reason == 1 ? ", limited by the budget" : reason == 2 ? ", table refused by the runtime" : "");
+      }
+    if (repeat > 0) {  // the repeat leg hands limbs to dvp_prove_cache_dir: it needs the commitment key's length, as below
+      if (!cp) rc = dvp_cache_dir_prover(dir.c_str(), n_public, &cp);
+      if (rc != DVP_OK) {
+        fprintf(stderr, "open %s: %s\n", dir.c_str(), dvp_strerror(rc));
+        return 1;
+      }
+      n_wires = dvp_prover_msm_size(cp, 0) - dvp_prover_msm_size(cp, 1) / 4;
+      if (n_wires < 1 + (size_t)n_public || n_wires > n) {
+        fprintf(stderr, "witness has %zu entries, the commitment key wants %zu\n", n, n_wires);
+        return 1;
+      }
+    } else {
+      dvp_cache_dir_release(nullptr);
+    }
+  } else {
+    // The dump knows wires only up to the highest one used; the library takes the witness length from |g_m|, so hand over
+    // exactly that many private inputs (a longer witness file is truncated by the reference's zip as well).
+    dvp_prover* p = nullptr;
+    rc = dvp_prover_open_cache_dir(dir.c_str(), n_public, &p);
+    if (rc != DVP_OK) {
+      fprintf(stderr, "open %s: %s (index %lld)\n", dir.c_str(), dvp_strerror(rc), (long long)dvp_last_error_index());
+      return 1;
+    }
+    // |[w | q2]| = n_wires + m and |[k_a | k_b | k_r]| = 4m
+    n_wires = dvp_prover_msm_size(p, 0) - dvp_prover_msm_size(p, 1) / 4;
+    if (n_wires < 1 + (size_t)n_public || n_wires > n) {
+      fprintf(stderr, "witness has %zu entries, the commitment key wants %zu\n", n, n_wires);
+      dvp_prover_destroy(p);
+      return 1;
+    }
+    if (have_budget) {
+      rc = dvp_prover_set_table_budget(p, budget);
+      if (rc != DVP_OK) {
+        fprintf(stderr, "--table-budget: %s\n", dvp_strerror(rc));
+        dvp_prover_destroy(p);
+        return 1;
+      }
+    }
+    if (bind_srs || have_circuit) {
+      rc = bind_srs ? dvp_prover_srs_hash(p, srs_hash) : DVP_OK;
+      if (rc == DVP_OK) rc = dvp_prover_set_transcript_binding(p, bind_srs ? srs_hash : nullptr, have_circuit ? circuit_hash : nullptr);
+      if (rc != DVP_OK) {
+        fprintf(stderr, "--bind-srs / --circuit-hash: %s\n", dvp_strerror(rc));
+        dvp_prover_destroy(p);
+        return 1;
+      }
+      if (bind_srs) {
+        fprintf(stderr, "srs hash: ");
+        for (int i = 0; i < 32; ++i) fprintf(stderr, "%02x", srs_hash[i]);
+        fprintf(stderr, "\n");
+      }
+    }
+    rc = dvp_prove(p, w.data() + 4, n_public, w.data() + 4 * (1 + (size_t)n_public), (uint32_t)(n_wires - 1 - n_public), proof);
+    if (have_budget && rc == DVP_OK)
+      for (int which = 1; which >= 0; --which) {
+        size_t covered = 0, total = 0;
+        int reason = 0;
+        if (dvp_prover_msm_coverage(p, which, &covered, &total, &reason) == DVP_OK)
+          fprintf(stderr, "MSM %d: %zu of %zu bases from tables (%llu bytes)%s\n", which, covered, total,
+                  (unsigned long long)dvp_prover_msm_table_bytes(p, which, nullptr),
+                  reason == 1 ? ", limited by the budget" : reason == 2 ? ", table refused by the runtime" : "");
+      }
     dvp_prover_destroy(p);
-    return 1;
-  }
-  if (have_budget) {
-    rc = dvp_prover_set_table_budget(p, budget);
     if (rc != DVP_OK) {
-      fprintf(stderr, "--table-budget: %s\n", dvp_strerror(rc));
-      dvp_prover_destroy(p);
+      fprintf(stderr, "prove: %s (index %lld)\n", dvp_strerror(rc), (long long)dvp_last_error_index());
       return 1;
     }
-  }
-  if (bind_srs || have_circuit) {
-    rc = bind_srs ? dvp_prover_srs_hash(p, srs_hash) : DVP_OK;
-    if (rc == DVP_OK) rc = dvp_prover_set_transcript_binding(p, bind_srs ? srs_hash : nullptr, have_circuit ? circuit_hash : nullptr);
-    if (rc != DVP_OK) {
-      fprintf(stderr, "--bind-srs / --circuit-hash: %s\n", dvp_strerror(rc));
-      dvp_prover_destroy(p);
-      return 1;
-    }
-    if (bind_srs) {
-      fprintf(stderr, "srs hash: ");
-      for (int i = 0; i < 32; ++i) fprintf(stderr, "%02x", srs_hash[i]);
-      fprintf(stderr, "\n");
-    }
-  }
-  rc = dvp_prove(p, w.data() + 4, n_public, w.data() + 4 * (1 + (size_t)n_public), (uint32_t)(n_wires - 1 - n_public), proof);
-  if (have_budget && rc == DVP_OK)
-    for (int which = 1; which >= 0; --which) {
-      size_t covered = 0, total = 0;
-      int reason = 0;
-      if (dvp_prover_msm_coverage(p, which, &covered, &total, &reason) == DVP_OK)
-        fprintf(stderr, "MSM %d: %zu of %zu bases from tables (%llu bytes)%s\n", which, covered, total,
-                (unsigned long long)dvp_prover_msm_table_bytes(p, which, nullptr),
-                reason == 1 ? ", limited by the budget" : reason == 2 ? ", table refused by the runtime" : "");
-    }
-  dvp_prover_destroy(p);
-  if (rc != DVP_OK) {
-    fprintf(stderr, "prove: %s (index %lld)\n", dvp_strerror(rc), (long long)dvp_last_error_index());
-    return 1;
   }
   for (int i = 0; i < 118; ++i) printf("%02x", proof[i]);
   printf("\n");

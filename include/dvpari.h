@@ -115,6 +115,13 @@ int dvp_fr_spmv(const uint32_t* row_ptr, const uint32_t* col, const uint32_t* co
                 const uint64_t* coeffs, uint32_t n_coeffs, const uint64_t* x, uint32_t n_cols, uint64_t* out);
 int dvp_barycentric_eval(const uint64_t* domain, const uint64_t* bar_weights, const uint64_t z_at_alpha[4],
                          const uint64_t* evals, size_t n, const uint64_t alpha[4], uint64_t out[4]);
+/* gnark_element_to_fr over a vector (src/gnark_r1cs.rs:58-77,188-211): n x 32 bytes big-endian, any value below 2^256, -> n x 4
+ * canonical limbs, exactly Fr::from_be_bytes_mod_order, one lane per element on the device.  n = 0 is DVP_OK and touches nothing.  The
+ * host flavour takes be32 at any alignment (a witness file's payload starts at byte 4).  The _dev flavour only enqueues on `stream`;
+ * d_out may equal d_be32 (in place: a lane reads and writes only its own 32 bytes); DVP_EINVAL before any device call for a NULL
+ * pointer with n > 0, for a pointer that is not 16-byte aligned and for n > 2^32 - 256 (one launch; the file format counts in 32 bits). */
+int dvp_fr_from_be32(const uint8_t* be32, size_t n, uint64_t* out /* n x 4 */);
+int dvp_fr_from_be32_dev(const void* d_be32, size_t n, void* d_out /* may equal d_be32 */, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* sect233k1 / xsk233 group                                                                     */
@@ -296,6 +303,13 @@ int dvp_prove(dvp_prover* p, const uint64_t* public_inputs, uint32_t n_public, c
               uint32_t n_private, uint8_t proof[118]);
 /* the same with the assignment [1, public.., private..] (n_wires canonical Fr) already in HBM */
 int dvp_prove_dev(dvp_prover* p, const void* d_assignment, uint8_t proof[118], void* stream);
+/* load_witness_from_file's payload -> Proof::prove (src/gnark_r1cs.rs:188-211, src/dvsnark_test.rs:189-229): the first n_wires
+ * elements of [1, public.., private..] as the witness file holds them, 32 bytes big-endian each and NOT reduced -- the bytes are
+ * copied into the prover's witness buffer and reduced mod p there, on the device (dvp_fr_from_be32_dev, in place); everything else
+ * is dvp_prove (device lists, transcript flavours, table budgets, bindings, error order).  n < n_wires is DVP_EINVAL; n > n_wires
+ * reads the first n_wires elements only (the reference's zip truncates the same way).  Element 0 must reduce to 1 (1 + p is
+ * accepted), else DVP_EINVAL with dvp_last_error_index() = 0, before any device work; no other element is looked at on the host. */
+int dvp_prove_be32(dvp_prover* p, const uint8_t* witness_be32, size_t n, uint8_t proof[118]);
 /* prove in phases, so that the two MSMs -- the only stages that shard across GPUs -- can be split by
  * index range and their partial sums combined by the caller (all-gather + local add):
  *   begin -> msm_partial(0, lo, hi) -> challenge(commit point) -> msm_partial(1, lo, hi) -> finish */
@@ -535,6 +549,14 @@ int dvp_prover_open_cache_dir(const char* cache_dir, uint32_t n_public, dvp_prov
  * rule are supported until that rule is pinned against xs233 (tools/pin_xsk233.py). */
 int dvp_prove_cache_dir(const char* cache_dir, const uint64_t* public_inputs, uint32_t n_public, const uint64_t* private_inputs,
                         uint32_t n_private, uint8_t proof[118]);
+/* load_witness_from_file + Proof::prove in one call (src/gnark_r1cs.rs:188-211 -> src/proving.rs:426): the witness file
+ * (witness_path == NULL reads <cache_dir>/witness_to_dvsnark) is mapped and proved through dvp_prove_be32 on the entry's prover, under
+ * the locking and replica rules of dvp_prove_cache_dir; its elements are reduced on the device.  The header is checked by the rules
+ * of dvp_file_witness_read (DVP_EIO for a missing or short file), the count must reach 1 + n_public and element 0 must be 1
+ * (DVP_EINVAL, index 0) -- all of it before cache_dir is opened, so these answers need no device.  A file longer than the commitment
+ * key is truncated, a shorter one is DVP_EINVAL.  public_inputs_out (optional, n_public x 4): elements 1 .. n_public, canonical. */
+int dvp_prove_cache_dir_witness_file(const char* cache_dir, uint32_t n_public, const char* witness_path, uint8_t proof[118],
+                                     uint64_t* public_inputs_out);
 void dvp_cache_dir_release(const char* cache_dir);
 /* dvp_prover_set_transcript_binding for the prover(s) dvp_prove_cache_dir keeps for (cache_dir, n_public), opened if need be:
  * bind_srs != 0 with srs_hash == NULL computes dvp_prover_srs_hash of the opened prover and binds that; a second prover

@@ -3,6 +3,8 @@
 //   * dvp_fftr_sections / dvp_fftr_read_fr on damaged FFTR tree files (src/tree_io.rs:217-350), incl. nested subtrees
 //   * dvp_file_fr_vec_read / dvp_file_point_vec_read / dvp_file_witness_read on damaged vector files (src/io_utils.rs:42-239)
 //   * dvp_prover_open_cache_dir on a directory of damaged files (stops at the first GPU entry: tools/asan/stubs.cpp)
+//   * dvp_prove_cache_dir_witness_file on damaged witness files, by explicit path and by the cache_dir's own (header, count and
+//     element 0 are judged on the host; a file that passes stops at the first stand-in behind the opening of cache_dir)
 // Every call must return a status; the sanitizers abort on any out-of-bounds access, overflowing index computation or leak.
 #include <sys/stat.h>
 #include <unistd.h>
@@ -154,6 +156,43 @@ static void fuzz_cache_dir(const std::string& dir, int iters) {
   if (!rcs[4]) FAIL();
 }
 
+// dvp_prove_cache_dir_witness_file: the witness file's header, count and element 0 are judged before cache_dir is opened; a file that
+// passes reaches the stand-in of the first device entry behind a well-formed cache_dir (DVP_EHIP), never DVP_OK
+static void fuzz_witness_entry(const std::string& dir, int iters) {
+  const std::string cd = dir + "/wdir";
+  if (mkdir(cd.c_str(), 0700) != 0) FAIL();
+  write_file(cd + "/r1cs_to_dvsnark", good_dump(6, 8));
+  static const char* const names[5] = {"g_m", "g_q", "g_k_0", "g_k_1", "g_k_2"};
+  for (int i = 0; i < 5; ++i) {
+    const size_t n = i == 0 ? 50 : i == 4 ? 16 : 8;
+    std::vector<uint8_t> p;
+    put64(p, n);
+    for (size_t k = 0; k < n * 30; ++k) p.push_back((uint8_t)rnd());
+    write_file(cd + "/" + names[i], p);
+  }
+  std::vector<uint8_t> good = {0, 0, 0, 50};
+  for (int i = 0; i < 50 * 32; ++i) good.push_back(i < 32 ? (uint8_t)(i == 31) : (uint8_t)rnd());  // element 0 = 1, the rest unreduced
+  const std::string wf = cd + "/witness_to_dvsnark", other = dir + "/witness_elsewhere";
+  int rcs[8] = {0}, idx0 = 0;
+  for (int it = 0; it < iters; ++it) {
+    const bool by_path = it % 2;
+    write_file(by_path ? other : wf, it < 2 ? good : damage(good, it));
+    uint8_t proof[118];
+    uint64_t pub[8];
+    const int rc = dvp_prove_cache_dir_witness_file(cd.c_str(), 2, by_path ? other.c_str() : nullptr, proof, it % 3 ? pub : nullptr);
+    if (rc == DVP_OK) FAIL();
+    if (it < 2 && rc != DVP_EHIP) FAIL();  // the good file gets as far as the device entry
+    if (rc == DVP_EINVAL && dvp_last_error_index() == 0) ++idx0;
+    ++rcs[(-rc) & 7];
+  }
+  if (dvp_prove_cache_dir_witness_file(cd.c_str(), 2, (dir + "/no_such_file").c_str(), nullptr, nullptr) != DVP_EINVAL) FAIL();
+  uint8_t proof[118];
+  if (dvp_prove_cache_dir_witness_file(cd.c_str(), 2, (dir + "/no_such_file").c_str(), proof, nullptr) != DVP_EIO) FAIL();
+  dvp_cache_dir_release(nullptr);
+  printf("witness file entry: %d cases; statuses EINVAL %d (element 0: %d) EHIP(reached the device entry) %d EIO %d\n", iters, rcs[1], idx0, rcs[4], rcs[6]);
+  if (!rcs[1] || !rcs[4] || !rcs[6] || !idx0) FAIL();
+}
+
 int main(int argc, char** argv) {
   const int iters = argc > 1 ? atoi(argv[1]) : 20000;
   char tmpl[] = "/tmp/dvp_asan_XXXXXX";
@@ -164,6 +203,7 @@ int main(int argc, char** argv) {
   fuzz_fftr(dir, iters / 4);
   fuzz_vec_files(dir, iters / 2);
   fuzz_cache_dir(dir, iters / 20);
+  fuzz_witness_entry(dir, iters / 20);
   std::string cmd = "rm -rf " + dir;
   (void)!system(cmd.c_str());
   printf("asan fuzz: clean\n");

@@ -5,7 +5,12 @@
 #include "../../include/dvpari.h"
 #include "../../include/dvpari_internal.h"
 
+namespace dvp {
+thread_local int64_t g_last_error_index = -1;  // capi.cpp's in the product
+}
+
 extern "C" {
+int64_t dvp_last_error_index(void) { return dvp::g_last_error_index; }
 int dvp_prover_create(uint32_t, uint32_t, uint32_t, dvp_prover**) { return DVP_EHIP; }
 void dvp_prover_destroy(dvp_prover*) {}
 int dvp_prover_set_coeffs(dvp_prover*, const uint64_t*, uint32_t) { return DVP_EHIP; }
@@ -14,6 +19,7 @@ int dvp_prover_set_srs_encoded(dvp_prover*, int, const uint8_t*, size_t) { retur
 int dvp_prover_srs_hash(dvp_prover*, uint8_t*) { return DVP_EHIP; }
 int dvp_prover_set_transcript_binding(dvp_prover*, const uint8_t*, const uint8_t*) { return DVP_EHIP; }
 int dvp_prove(dvp_prover*, const uint64_t*, uint32_t, const uint64_t*, uint32_t, uint8_t*) { return DVP_EHIP; }
+int dvp_prove_be32(dvp_prover*, const uint8_t*, size_t, uint8_t*) { return DVP_EHIP; }
 int dvp_tune_get(const char*, long long* v) { if (v) *v = 1; return DVP_OK; }
 hipError_t hipGetDevice(int* d) { if (d) *d = 0; return hipSuccess; }
 hipError_t hipMemGetInfo(size_t* f, size_t* t) { if (f) *f = 0; if (t) *t = 0; return hipSuccess; }
