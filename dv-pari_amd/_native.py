@@ -167,6 +167,8 @@ _SIGS = {
     "dvp_debug_blake3_leaves_dev": (C.c_int, [vp, sz, C.c_uint64, vp, vp]),
     "dvp_debug_blake3_reduce_dev": (C.c_int, [vp, sz, vp, vp, vp]),
     "dvp_prover_srs_hash": (C.c_int, [vp, u8p]),
+    "dvp_prover_circuit_hash": (C.c_int, [vp, u8p]),
+    "dvp_circuit_hash_cache_dir": (C.c_int, [C.c_char_p, u32, u8p]),
     "dvp_prover_set_transcript_binding": (C.c_int, [vp, u8p, u8p]),
     "dvp_transcript_challenge_bound": (C.c_int, [u8p, u64p, u32, u8p, u8p, u64p]),
     "dvp_verify_set_binding": (C.c_int, [u8p, u8p]),

@@ -16,6 +16,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -580,6 +581,69 @@ extern "C" int dvp_cache_dir_set_binding(const char* cache_dir, uint32_t n_publi
   }
   ++e->bind_gen;
   return DVP_OK;
+}
+
+// dvp_prover_circuit_hash from the R1CS dump of cache_dir alone (Transcript::circuit_info_hash, src/proving.rs:111-134, on the instance
+// update_to_include_vandermode_matrix_d leaves, src/gnark_r1cs.rs:333-386) -- the verifier's way to the value: it ran the setup from
+// the same dump.  The prover dvp_prove_cache_dir keeps for (cache_dir, n_public) on this device is used when it is open (taking its
+// turn like a proof); otherwise a prover without SRS is built from the dump and destroyed: no SRS file is read.
+extern "C" int dvp_circuit_hash_cache_dir(const char* cache_dir, uint32_t n_public, uint8_t out[32]) {
+  if (!cache_dir || !out) return DVP_EINVAL;
+  std::shared_ptr<OpenEntry> e;
+  {
+    std::lock_guard<std::mutex> g(g_open_mu);
+    auto it = g_open.find(OpenKey(std::string(cache_dir), n_public, current_device()));
+    if (it != g_open.end() && it->second->opened.load(std::memory_order_acquire) && it->second->rc == DVP_OK) e = it->second;
+  }
+  if (e) {
+    {
+      std::unique_lock<std::mutex> g(e->slot_mu);
+      e->slot_cv.wait(g, [&] { return !e->busy[0]; });
+      e->busy[0] = true;
+    }
+    const int rc = dvp_prover_circuit_hash(e->p, out);
+    {
+      std::lock_guard<std::mutex> g(e->slot_mu);
+      e->busy[0] = false;
+    }
+    e->slot_cv.notify_all();
+    return rc;
+  }
+  Mapped dump;
+  int rc = dump.open_ro(join(cache_dir, "r1cs_to_dvsnark").c_str());  // R1CS_CONSTRAINTS_FILE, src/artifacts.rs:76
+  if (rc) return rc;
+  DumpView v;
+  rc = dump_scan(dump.p, dump.len, &v);  // what dvp_r1cs_dump_sizes reports: n_wires = highest wire id used + 1
+  if (rc) return rc == DVP_EINVAL ? DVP_EIO : rc;  // a coefficient id outside the table: malformed
+  if (v.n_rows == 0 || v.n_coeffs == 0) return DVP_EIO;
+  for (int k = 0; k < 3; ++k)
+    if (v.nnz[k] > 0xffffffffull) return DVP_EINVAL;
+  uint32_t log_m = 0;
+  while ((1ull << log_m) < v.n_rows) ++log_m;  // next_power_of_two, src/gnark_r1cs.rs:291
+  if (log_m < 1) log_m = 1;
+  std::vector<uint64_t> coeffs((size_t)4 * v.n_coeffs);
+  std::vector<uint32_t> rp[3], wi[3], ci[3];
+  uint32_t *rpp[3], *wip[3], *cip[3];
+  for (int k = 0; k < 3; ++k) {
+    rp[k].resize((size_t)v.n_rows + 1);
+    wi[k].resize(v.nnz[k] ? v.nnz[k] : 1);
+    ci[k].resize(v.nnz[k] ? v.nnz[k] : 1);
+    rpp[k] = rp[k].data();
+    wip[k] = wi[k].data();
+    cip[k] = ci[k].data();
+  }
+  dump_fill(v, coeffs.data(), rpp, wip, cip);
+  // the hash reads no wire: the prover only has to admit the ids the dump uses and [1, public..]
+  const uint64_t n_wires = std::max<uint64_t>(v.n_wires, 1 + (uint64_t)n_public);
+  if (n_wires > 0xffffffffull) return DVP_EINVAL;
+  dvp_prover* p = nullptr;
+  rc = dvp_prover_create(log_m, n_public, (uint32_t)n_wires, &p);
+  if (rc) return rc;
+  rc = dvp_prover_set_coeffs(p, coeffs.data(), v.n_coeffs);
+  for (int k = 0; k < 3 && !rc; ++k) rc = dvp_prover_set_matrix(p, k, v.n_rows, rpp[k], wip[k], cip[k]);
+  if (!rc) rc = dvp_prover_circuit_hash(p, out);
+  dvp_prover_destroy(p);
+  return rc;
 }
 
 // the prover dvp_prove_cache_dir uses for (cache_dir, n_public) on the current device, opened if need be: BORROWED --

@@ -139,6 +139,7 @@ static void tune_from_env(Tune& t) {
   t.msm_aligned_signed = geti("DVP_MSM_ALIGNED_SIGNED", t.msm_aligned_signed);
   t.points_mul_w = geti("DVP_POINTS_MUL_W", t.points_mul_w);
   t.msm_seg_piece = geti("DVP_MSM_SEG_PIECE", t.msm_seg_piece);
+  t.circuit_hash_window = geti("DVP_CIRCUIT_HASH_WINDOW", t.circuit_hash_window);
   t.prove_host_transcript = geti("DVP_PROVE_HOST_TRANSCRIPT", t.prove_host_transcript);
   t.msm_table_refuse = geti("DVP_MSM_TABLE_REFUSE", t.msm_table_refuse);
   if (const char* e = getenv("DVP_TABLE_BUDGET_BYTES")) {  // the full u64 range: UINT64_MAX and anything above LLONG_MAX read as "no limit"
@@ -166,7 +167,8 @@ static long long* tune_slot(const char* name) {
       {"DVP_MSM_QUAD_MAX", &t.msm_quad_max}, {"DVP_MSM_ACCUM_QUAD_MAX", &t.msm_accum_quad_max}, {"DVP_MSM_FIXED_MIN", &t.msm_fixed_min}, {"DVP_HORNER_MAX_PUB", &t.horner_max_pub}, {"DVP_FR_BI_SHAPE", &t.fr_bi_shape},
       {"DVP_MSM_ALIGNED_SIGNED", &t.msm_aligned_signed}, {"DVP_PROVE_HOST_TRANSCRIPT", &t.prove_host_transcript},
       {"DVP_TABLE_BUDGET_BYTES", &t.table_budget_bytes}, {"DVP_MSM_TABLE_REFUSE", &t.msm_table_refuse},
-      {"DVP_POINTS_MUL_W", &t.points_mul_w}, {"DVP_MSM_SEG_PIECE", &t.msm_seg_piece}};
+      {"DVP_POINTS_MUL_W", &t.points_mul_w}, {"DVP_MSM_SEG_PIECE", &t.msm_seg_piece},
+      {"DVP_CIRCUIT_HASH_WINDOW", &t.circuit_hash_window}};
   for (auto& e : tab)
     if (!strcmp(name, e.n)) return e.v;
   return nullptr;

@@ -47,6 +47,13 @@ int b3_leaves_dev(const uint8_t* d_data, size_t len, uint64_t chunk_base, uint32
 int b3_single_chunk_dev(const uint8_t* d_data, size_t len, uint32_t* d_out32, hipStream_t st);
 size_t b3_reduce_tmp_bytes(size_t n);
 int b3_reduce_dev(uint32_t* d_cvs, size_t n, uint32_t* d_tmp, uint32_t* d_out32, hipStream_t st);
+struct ChCsr {  // circuit_hash.hip: row pointers and coefficient ids of the three matrices
+  const uint32_t* rp[3];
+  const uint32_t* cid[3];
+  uint32_t n_rows[3];
+};
+int circuit_hash_dev(const ChCsr& mats, const uint64_t nnz[3], const Fr* coeffs_m, uint32_t n0, const Fr* dom_m, uint32_t m, uint32_t k,
+                     long long window_chunks, uint8_t out[32], hipStream_t st);
 struct MsmFixedCtx;
 int msm_fixed_create(const Aff* d_bases, uint32_t n_total, size_t range_hint, MsmFixedCtx** out);
 int msm_sum_points_dev(const void* d_pts, uint32_t pt_stride_bytes, const void* d_inf32, uint32_t n, uint32_t inf_stride, void* d_out_xy,
@@ -832,6 +839,24 @@ extern "C" int dvp_prover_srs_hash(dvp_prover* p, uint8_t out[32]) {
   DVP_HIP(hipMemcpyAsync(out, dout.p, 32, hipMemcpyDeviceToHost, st));
   DVP_HIP(hipStreamSynchronize(st));
   return DVP_OK;
+}
+
+// BLAKE3 of the stream the commented-out body of Transcript::circuit_info_hash would build (src/proving.rs:111-134) on the instance after
+// update_to_include_vandermode_matrix_d (src/gnark_r1cs.rs:333-386): generated from mat[], coeffs_m and dD by circuit_hash.hip, which
+// states the stream.  Needs no SRS; the matrix conditions are prover_ready's.
+extern "C" int dvp_prover_circuit_hash(dvp_prover* p, uint8_t out[32]) {
+  if (!p || !out) return DVP_EINVAL;
+  if (!(p->coeffs_m && p->mat[0].row_ptr && p->mat[1].row_ptr && p->mat[2].row_ptr)) return DVP_EINVAL;
+  ChCsr mats;
+  uint64_t nnz[3];
+  for (int k = 0; k < 3; ++k) {
+    if (p->mat[k].nnz && p->mat[k].max_coeff_id >= p->n_coeffs) return DVP_EINVAL;
+    mats.rp[k] = p->mat[k].row_ptr;
+    mats.cid[k] = p->mat[k].coeff;
+    mats.n_rows[k] = p->mat[k].n_rows;
+    nnz[k] = p->mat[k].nnz;
+  }
+  return circuit_hash_dev(mats, nnz, p->coeffs_m, p->n_coeffs, p->dD, p->m, p->n_pub, tune().circuit_hash_window, out, nullptr);
 }
 
 // parity-test access to the DEVICE flavour of the transcript (k_transcript, k_zalpha) on caller-supplied inputs: alpha (canonical) and

@@ -166,6 +166,17 @@ def set_cache_dir_binding(cache_dir, num_public_inputs: int, srs_hash=None, circ
     check(lib.dvp_cache_dir_set_binding(os.fspath(cache_dir).encode(), num_public_inputs, s, c, int(bool(bind_srs))), "dvp_cache_dir_set_binding")
 
 
+def circuit_hash_cache_dir(cache_dir, num_public_inputs: int) -> bytes:
+    """dvp_circuit_hash_cache_dir: Prover.circuit_hash() from <cache_dir>/r1cs_to_dvsnark alone -- the verifier's way to the value.
+    The prover Proof.prove(cache_dir, ..) keeps for the directory is used when it is open; otherwise one without SRS is built from
+    the dump and destroyed"""
+    import os
+
+    out = np.zeros(32, dtype=np.uint8)
+    check(lib.dvp_circuit_hash_cache_dir(os.fspath(cache_dir).encode(), num_public_inputs, ptr(out)), "dvp_circuit_hash_cache_dir")
+    return out.tobytes()
+
+
 class Prover:
     """The artefacts Proof::prove reads from cache_dir (R1CS dump, SRS point vectors, TREE_2N and the
     prover precomputes, src/proving.rs:435-511,562-565,666-672), loaded once and kept in HBM."""
@@ -220,6 +231,15 @@ class Prover:
         src/proving.rs:91-101), encoded and hashed on the device; depends on the codec rule in force (dvp_prover_srs_hash)"""
         out = np.zeros(32, dtype=np.uint8)
         check(lib.dvp_prover_srs_hash(self._h, ptr(out)), "dvp_prover_srs_hash")
+        return out.tobytes()
+
+    def circuit_hash(self) -> bytes:
+        """BLAKE3 of the stream Transcript::circuit_info_hash would hash (src/proving.rs:111-134) on the instance with the Vandermonde
+        terms (src/gnark_r1cs.rs:333-386): per row the coeff_ids of A, B, C and the Vandermonde ids as u32 LE (no wire ids), then
+        the updated coefficient table as a count and 29-byte entries; generated and hashed on the device (dvp_prover_circuit_hash).
+        Needs the coefficients and the matrices, no SRS"""
+        out = np.zeros(32, dtype=np.uint8)
+        check(lib.dvp_prover_circuit_hash(self._h, ptr(out)), "dvp_prover_circuit_hash")
         return out.tobytes()
 
     def set_transcript_binding(self, srs_hash=None, circuit_hash=None):

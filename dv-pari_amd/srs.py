@@ -216,7 +216,8 @@ def _public_array(public_inputs, n: int) -> np.ndarray:
 
 def set_verify_binding(srs_hash=None, circuit_hash=None):
     """dvp_verify_set_binding: the (srs_hash, circuit_hash) pair every verify entry of this process checks proofs against from now on;
-    None = BLAKE3(""), (None, None) = the reference's unbound transcript"""
+    None = BLAKE3(""), (None, None) = the reference's unbound transcript.  A verifier that ran the setup from cache_dir gets the
+    circuit half with proving.circuit_hash_cache_dir(cache_dir, num_public_inputs), which reads the R1CS dump alone"""
     from ._native import lib, check
     from .proving import _hash_arg
 

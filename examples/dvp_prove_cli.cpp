@@ -2,7 +2,7 @@
 // against.  It mirrors the reference's `Proof::prove(cache_dir, public_inputs, private_inputs)` call
 // (src/proving.rs:426) from files alone:
 //
-//   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3] [--table-budget <bytes>] [--bind-srs] [--circuit-hash <hex>]
+//   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3] [--table-budget <bytes>] [--bind-srs] [--bind-circuit | --circuit-hash <hex>]
 //                 [--host-witness] [--repeat N --threads T]
 //
 // The witness goes from the file to the proof in one call, dvp_prove_cache_dir_witness_file: the library maps
@@ -13,7 +13,10 @@
 //
 // --bind-srs: bind the proof's challenge to the SRS (dvp_prover_srs_hash + dvp_prover_set_transcript_binding); the SRS hash used goes
 // to stderr -- the verifier needs it (dvp_verify_cli --srs-hash).  --circuit-hash <64 hex digits>: the circuit half of the binding
-// (whatever the host defines it to be).  Without either the transcript is the reference's, which binds neither.
+// (whatever the host defines it to be).  --bind-circuit: the circuit half is dvp_prover_circuit_hash of the prover, the hash of the
+// stream Transcript::circuit_info_hash would build (coeff_ids per row and the coefficient table, Vandermonde terms included); it goes to
+// stderr as well (dvp_verify_cli --circuit-hash; a verifier computes the same value with dvp_circuit_hash_cache_dir).  It excludes
+// --circuit-hash.  Without any of them the transcript is the reference's, which binds neither.
 //
 // --table-budget <bytes>: the most HBM per device the prover's fixed-base tables may hold (dvp_prover_set_table_budget; 0 = no
 // tables).  What does not fit runs through the one-shot MSM; the proof bytes do not depend on it.  The coverage goes to stderr.
@@ -55,7 +58,7 @@ static bool parse_hash(const char* s, uint8_t out[32]) {
 
 int main(int argc, char** argv) {
   std::vector<int> devices;
-  bool bind_srs = false, have_circuit = false, host_witness = false;
+  bool bind_srs = false, bind_circuit = false, have_circuit = false, host_witness = false;
   uint8_t srs_hash[32] = {0}, circuit_hash[32] = {0};
   int repeat = 0, threads = 1;  // --repeat N --threads T: N more proofs through dvp_prove_cache_dir from T host threads
   std::vector<char*> pos;
@@ -73,6 +76,8 @@ int main(int argc, char** argv) {
       have_budget = true;
     } else if (std::string(argv[i]) == "--bind-srs") {
       bind_srs = true;
+    } else if (std::string(argv[i]) == "--bind-circuit") {
+      bind_circuit = true;
     } else if (std::string(argv[i]) == "--host-witness") {
       host_witness = true;
     } else if (std::string(argv[i]) == "--circuit-hash" && i + 1 < argc) {
@@ -105,8 +110,9 @@ int main(int argc, char** argv) {
       pos.push_back(argv[i]);
     }
   }
-  if (pos.size() < 2) {
-    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--circuit-hash HEX] [--host-witness] [--repeat N --threads T]\n", argv[0]);
+  if (bind_circuit && have_circuit) fprintf(stderr, "--bind-circuit and --circuit-hash exclude each other\n");
+  if (pos.size() < 2 || (bind_circuit && have_circuit)) {
+    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--bind-circuit | --circuit-hash HEX] [--host-witness] [--repeat N --threads T]\n", argv[0]);
     return 2;
   }
   argc = (int)pos.size() + 1;
@@ -151,7 +157,7 @@ int main(int argc, char** argv) {
     // load_witness_from_file + Proof::prove as ONE call: the library maps the file and reduces its elements mod p on the GPU.  The
     // prover is the one the library keeps for this directory, so the budget and the binding go to that one.
     dvp_prover* cp = nullptr;
-    if (have_budget || bind_srs) {
+    if (have_budget || bind_srs || bind_circuit) {
       rc = dvp_cache_dir_prover(dir.c_str(), n_public, &cp);
       if (rc != DVP_OK) {
         fprintf(stderr, "open %s: %s (index %lld)\n", dir.c_str(), dvp_strerror(rc), (long long)dvp_last_error_index());
@@ -165,16 +171,25 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
-    if (bind_srs || have_circuit) {
+    if (bind_srs || have_circuit || bind_circuit) {
       rc = bind_srs ? dvp_prover_srs_hash(cp, srs_hash) : DVP_OK;
+      if (rc == DVP_OK && bind_circuit) {
+        rc = dvp_prover_circuit_hash(cp, circuit_hash);
+        have_circuit = rc == DVP_OK;
+      }
       if (rc == DVP_OK) rc = dvp_cache_dir_set_binding(dir.c_str(), n_public, bind_srs ? srs_hash : nullptr, have_circuit ? circuit_hash : nullptr, 0);
       if (rc != DVP_OK) {
-        fprintf(stderr, "--bind-srs / --circuit-hash: %s\n", dvp_strerror(rc));
+        fprintf(stderr, "--bind-srs / --bind-circuit / --circuit-hash: %s\n", dvp_strerror(rc));
         return 1;
       }
       if (bind_srs) {
         fprintf(stderr, "srs hash: ");
         for (int i = 0; i < 32; ++i) fprintf(stderr, "%02x", srs_hash[i]);
+        fprintf(stderr, "\n");
+      }
+      if (bind_circuit) {
+        fprintf(stderr, "circuit hash: ");
+        for (int i = 0; i < 32; ++i) fprintf(stderr, "%02x", circuit_hash[i]);
         fprintf(stderr, "\n");
       }
     }
@@ -230,17 +245,26 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
-    if (bind_srs || have_circuit) {
+    if (bind_srs || have_circuit || bind_circuit) {
       rc = bind_srs ? dvp_prover_srs_hash(p, srs_hash) : DVP_OK;
+      if (rc == DVP_OK && bind_circuit) {
+        rc = dvp_prover_circuit_hash(p, circuit_hash);
+        have_circuit = rc == DVP_OK;
+      }
       if (rc == DVP_OK) rc = dvp_prover_set_transcript_binding(p, bind_srs ? srs_hash : nullptr, have_circuit ? circuit_hash : nullptr);
       if (rc != DVP_OK) {
-        fprintf(stderr, "--bind-srs / --circuit-hash: %s\n", dvp_strerror(rc));
+        fprintf(stderr, "--bind-srs / --bind-circuit / --circuit-hash: %s\n", dvp_strerror(rc));
         dvp_prover_destroy(p);
         return 1;
       }
       if (bind_srs) {
         fprintf(stderr, "srs hash: ");
         for (int i = 0; i < 32; ++i) fprintf(stderr, "%02x", srs_hash[i]);
+        fprintf(stderr, "\n");
+      }
+      if (bind_circuit) {
+        fprintf(stderr, "circuit hash: ");
+        for (int i = 0; i < 32; ++i) fprintf(stderr, "%02x", circuit_hash[i]);
         fprintf(stderr, "\n");
       }
     }

@@ -396,9 +396,24 @@ int dvp_blake3_dev(const void* d_data, size_t len, void* d_out32, void* stream);
  * dvp_set_devices the home device's copies are hashed (they stay complete), so the device list does not change the result.  Waits
  * for the result; call it between proofs.
  * dvp_prover_set_transcript_binding: may be called between proofs; every path that derives alpha follows it (dvp_prove, dvp_prove_dev
- * with the device or the host transcript, device lists, dvp_prove_challenge, dvp_prove_challenge_partial).  The circuit hash is the
- * caller's: the reference has not settled what it is (:110); dvp_blake3 / dvp_blake3_dev hash whatever a host decides on.
- * dvp_transcript_challenge_bound: dvp_transcript_challenge under a binding (host only). */
+ * with the device or the host transcript, device lists, dvp_prove_challenge, dvp_prove_challenge_partial).  The circuit hash may be
+ * dvp_prover_circuit_hash (below) or any 32 bytes a host defines: dvp_blake3 / dvp_blake3_dev hash whatever a host decides on.
+ * dvp_transcript_challenge_bound: dvp_transcript_challenge under a binding (host only).
+ *
+ * dvp_prover_circuit_hash: BLAKE3 of the stream the commented-out body of Transcript::circuit_info_hash would build
+ * (src/proving.rs:111-134) on the instance Proof::prove hands it, i.e. after update_to_include_vandermode_matrix_d
+ * (src/gnark_r1cs.rs:333-386).  With m constraints, k public inputs, the coefficient table c[0, n0) and d_i the i-th element of D:
+ * i1 = the first index with c[i1] == p - 1, or n0 with p - 1 appended when there is none (for k = 0 as well); n1 = the table's length
+ * then; the updated table is c[0, n1) followed by -(d_i^j) mod p at index n1 + i (k - 1) + (j - 1) for i in [0, m), j in [1, k): N
+ * entries.  The stream is, for i = 0 .. m - 1, the coeff_ids of row i of A, of B and of C, then (k >= 1) i1, then the ids
+ * n1 + i (k - 1) + (j - 1) for j = 1 .. k - 1, each a u32 little-endian (:130 hashes the rows first); then the table as
+ * Vec<Fr>::serialize_uncompressed: N as u64 little-endian and every entry as 29 bytes little-endian canonical, the payload layout of
+ * the Fr vector files.  WIRE IDS ARE NOT PART OF IT, because the reference wrote only the coeff_ids; the SRS hash depends on the
+ * wiring through g_m.  Generated and hashed on the device through a bounded staging window (DVP_CIRCUIT_HASH_WINDOW); nothing of the
+ * stream reaches the host.  Needs the coefficients and all three matrices (DVP_EINVAL otherwise, and when a stored coefficient id lies
+ * outside the table, as dvp_prove would answer) and no SRS; N > 2^32 is DVP_EINVAL (the reference's `as u32` would wrap silently).
+ * Waits for the result; call it between proofs, not beside a proof on the same handle. */
+int dvp_prover_circuit_hash(dvp_prover* p, uint8_t out[32]);
 int dvp_prover_srs_hash(dvp_prover* p, uint8_t out[32]);
 int dvp_prover_set_transcript_binding(dvp_prover* p, const uint8_t srs_hash[32], const uint8_t circuit_hash[32]);
 int dvp_transcript_challenge_bound(const uint8_t commit_p[30], const uint64_t* public_inputs, uint32_t n_public,
@@ -563,6 +578,12 @@ void dvp_cache_dir_release(const char* cache_dir);
  * (DVP_CACHE_REPLICAS=2) inherits the binding.  Waits for a proof in flight on the entry's first prover when it has to compute the hash;
  * takes effect with the next proof that starts; a release of the entry drops it. */
 int dvp_cache_dir_set_binding(const char* cache_dir, uint32_t n_public, const uint8_t* srs_hash, const uint8_t* circuit_hash, int bind_srs);
+/* dvp_prover_circuit_hash (Transcript::circuit_info_hash, src/proving.rs:111-134, on the instance src/gnark_r1cs.rs:333-386 leaves) from
+ * <cache_dir>/r1cs_to_dvsnark alone -- the verifier's way to the value, since it ran the setup from the same dump.  No other file of
+ * the directory is read.  When dvp_prove_cache_dir's prover of (cache_dir, n_public) is open on the current device it is used (the
+ * call takes its turn like a proof); otherwise a prover without SRS is built from the dump (log2 m by next_power_of_two of the row
+ * count, n_wires as dvp_r1cs_dump_sizes reports it) and destroyed.  DVP_EIO for a missing or malformed dump. */
+int dvp_circuit_hash_cache_dir(const char* cache_dir, uint32_t n_public, uint8_t out[32]);
 /* the cached prover of (cache_dir, n_public), opened if need be -- borrowed, for inspection only (debug reads, plans) */
 int dvp_cache_dir_prover(const char* cache_dir, uint32_t n_public, dvp_prover** out);
 

@@ -3,6 +3,7 @@
 //   * dvp_fftr_sections / dvp_fftr_read_fr on damaged FFTR tree files (src/tree_io.rs:217-350), incl. nested subtrees
 //   * dvp_file_fr_vec_read / dvp_file_point_vec_read / dvp_file_witness_read on damaged vector files (src/io_utils.rs:42-239)
 //   * dvp_prover_open_cache_dir on a directory of damaged files (stops at the first GPU entry: tools/asan/stubs.cpp)
+//   * dvp_circuit_hash_cache_dir on the same directories (reads the dump alone; an intact one stops at the stand-in of dvp_prover_create)
 //   * dvp_prove_cache_dir_witness_file on damaged witness files, by explicit path and by the cache_dir's own (header, count and
 //     element 0 are judged on the host; a file that passes stops at the first stand-in behind the opening of cache_dir)
 // Every call must return a status; the sanitizers abort on any out-of-bounds access, overflowing index computation or leak.
@@ -151,6 +152,9 @@ static void fuzz_cache_dir(const std::string& dir, int iters) {
     int rc = dvp_prover_open_cache_dir(dir.c_str(), 2, &h);
     if (rc == DVP_OK || h) FAIL();  // no GPU here: the best case ends at the first device entry (DVP_EHIP)
     ++rcs[(-rc) & 7];
+    uint8_t ch[32];
+    const int rc2 = dvp_circuit_hash_cache_dir(dir.c_str(), 2, ch);  // the dump alone: a damaged SRS file does not matter to it
+    if (rc2 == DVP_OK || (it % 2 == 0 && rc2 != DVP_EHIP)) FAIL();
   }
   printf("open_cache_dir: %d cases; statuses EINVAL %d EHIP(reached the device entry) %d EIO %d\n", iters, rcs[1], rcs[4], rcs[6]);
   if (!rcs[4]) FAIL();

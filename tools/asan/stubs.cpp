@@ -17,6 +17,7 @@ int dvp_prover_set_coeffs(dvp_prover*, const uint64_t*, uint32_t) { return DVP_E
 int dvp_prover_set_matrix(dvp_prover*, int, uint32_t, const uint32_t*, const uint32_t*, const uint32_t*) { return DVP_EHIP; }
 int dvp_prover_set_srs_encoded(dvp_prover*, int, const uint8_t*, size_t) { return DVP_EHIP; }
 int dvp_prover_srs_hash(dvp_prover*, uint8_t*) { return DVP_EHIP; }
+int dvp_prover_circuit_hash(dvp_prover*, uint8_t*) { return DVP_EHIP; }
 int dvp_prover_set_transcript_binding(dvp_prover*, const uint8_t*, const uint8_t*) { return DVP_EHIP; }
 int dvp_prove(dvp_prover*, const uint64_t*, uint32_t, const uint64_t*, uint32_t, uint8_t*) { return DVP_EHIP; }
 int dvp_prove_be32(dvp_prover*, const uint8_t*, size_t, uint8_t*) { return DVP_EHIP; }
