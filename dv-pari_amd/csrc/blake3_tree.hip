@@ -10,6 +10,7 @@
 
 #include "blake3_dev.cuh"
 #include "common.h"
+#include "host_api.h"
 
 namespace dvp {
 

@@ -33,10 +33,7 @@
 #include "../../include/dvpari.h"
 #include "../../include/dvpari_internal.h"  // dvp_tune_get (DVP_CACHE_REPLICAS)
 #include "fr_wire.cuh"                      // fr_from_be32_words: element 0 and the public inputs of a witness file
-
-namespace dvp {
-extern thread_local int64_t g_last_error_index;  // capi.cpp (dvp_last_error_index)
-}
+#include "host_api.h"
 
 namespace {
 

@@ -19,20 +19,9 @@
 
 #include "common.h"
 #include "fr.cuh"
+#include "host_api.h"
 
 namespace dvp {
-
-int b3_leaves_dev(const uint8_t* d_data, size_t len, uint64_t chunk_base, uint32_t* d_cvs, hipStream_t st);  // blake3_tree.hip
-int b3_single_chunk_dev(const uint8_t* d_data, size_t len, uint32_t* d_out32, hipStream_t st);
-size_t b3_reduce_tmp_bytes(size_t n);
-int b3_reduce_dev(uint32_t* d_cvs, size_t n, uint32_t* d_tmp, uint32_t* d_out32, hipStream_t st);
-
-// what the generator reads of the three matrices: row pointers and coefficient ids (never the wire ids)
-struct ChCsr {
-  const uint32_t* rp[3];
-  const uint32_t* cid[3];
-  uint32_t n_rows[3];
-};
 
 static constexpr int CH_TPB = 256;
 static constexpr uint32_t CH_ROW_TABLE = 128;                       // row offsets a workgroup of k_ch_rows keeps in LDS

@@ -22,12 +22,9 @@
 #include "k233.cuh"
 #include "tau.cuh"
 #include "codec.cuh"
+#include "host_api.h"
 
 namespace dvp {
-
-int msm_affine_dev(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, void* d_out_xy,
-                   void* d_out_inf, hipStream_t st);
-int gf_sqr_tables(GfSqrTables* out, hipStream_t st);
 
 // NIST K-233 base point
 __constant__ uint32_t K233_GX[8] = {0xefad6126u, 0x0a4c9d6eu, 0x19c26bf5u, 0x149563a4u,
@@ -516,10 +513,6 @@ extern "C" int dvp_ubench_points_check(const void* d_xy, const void* d_inf, cons
 
 // dvp_points_mul_dev (its two 8-byte fills and k_points_mul at the width in force) and k_mulgen alone on the same scalars and count, device
 // events, median of `reps` after one warm-up each (tools/points_mul.py)
-namespace dvp {
-int points_mul_dev(const void* d_scalars, size_t n_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf,
-                   void* d_summary, hipStream_t st);
-}
 extern "C" int dvp_ubench_points_mul(const void* d_scalars, const void* d_xy, size_t n, void* d_scratch, int reps, double* mul_ms, double* mulgen_ms) {
   if (!d_scalars || !d_xy || !d_scratch || !n || reps < 1 || reps > 99 || !(reps & 1) || !mul_ms || !mulgen_ms) return DVP_EINVAL;
   GfSqrTables T;
@@ -574,7 +567,7 @@ extern "C" int dvp_msm_xsk233(const uint8_t* scalars, const uint8_t* bases_enc, 
     DVP_HIP(hipMemcpy(de.p, bases_enc, n * 30, hipMemcpyHostToDevice));
     DVP_TRY(decode_dev(de.as<uint8_t>(), n, dp.as<Aff>(), di.as<uint8_t>(), 0));
   }
-  DVP_TRY(msm_affine_dev(ds.p, dp.p, di.p, n, dout.p, (char*)dout.p + 64, 0));
+  DVP_TRY(msm_affine_dev(ds.p, dp.p, di.p, n, MsmOut{dout.p, (char*)dout.p + 64}, 0));
   // the infinity flag of the result is a u32; k_encode wants a byte mask
   uint32_t inf32;
   DVP_HIP(hipMemcpy(&inf32, (char*)dout.p + 64, 4, hipMemcpyDeviceToHost));

@@ -9,10 +9,10 @@
 #include <vector>
 
 #include "../../include/dvpari_internal.h"
+#include "host_api.h"
 
 namespace dvp {
 
-extern thread_local int64_t g_last_error_index;
 extern thread_local hipError_t g_last_hip_error;
 
 inline int hip_fail(hipError_t e, const char* what, const char* file, int line) {

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "host_api.h"
 #include "fr.cuh"
 
 namespace dvp {
@@ -929,7 +930,6 @@ static int get_xnn(dvp_ecfft* c, int sl, Fr** out, hipStream_t st) {
 
 // ---- C ABI ---------------------------------------------------------------------------------------
 static int ecfft_init(dvp_ecfft* c, uint32_t log_n, int shifted, uint32_t base_log);
-extern "C" void dvp_ecfft_destroy(dvp_ecfft* c);
 
 extern "C" int dvp_ecfft_create(uint32_t log_n, int shifted, uint32_t base_log, dvp_ecfft** out) {
   if (!out || log_n < 1 || log_n > (uint32_t)ECFFT_LOG_ORDER) return DVP_EINVAL;

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "host_api.h"
 #include "fr.cuh"
 
 namespace dvp {

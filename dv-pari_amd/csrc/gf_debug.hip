@@ -12,10 +12,9 @@
 
 #include "common.h"
 #include "k233.cuh"
+#include "host_api.h"
 
 namespace dvp {
-
-int gf_sqr_tables(GfSqrTables* out, hipStream_t st);  // msm.hip
 
 // values an op reads / writes (index = enum dvp_gf_op); a flag goes to out[3] on top of the values
 constexpr int GFOP_N_IN[DVP_GFOP_COUNT] = {2, 2, 3, 1, 1, 2, 2, 1, 1, 1, 1, 1, 1, 1, 3, 5, 5, 4, 6, 6, 3, 3, 3, 6, 3, 3};

@@ -35,6 +35,7 @@
 #include "k233.cuh"
 #include "tau.cuh"
 #include "codec.cuh"
+#include "host_api.h"
 
 namespace dvp {
 
@@ -2051,7 +2052,14 @@ struct MsmPlan {
 };
 
 static MsmPlan msm_plan(size_t n, const struct MsmFixedCtx* fx);
-// Windows of the fixed-base mode.  tau-adic expansions of reduced scalars are at most 234 digits long (measured: 229-233
+// The window split every flavour shares: the 234 real digits go into ceil(234 / c) windows (the return value) whose widths differ by
+// at most one, the *n_narrow LOW windows being c - 1 digits wide.  What a flavour adds above them (overflow windows) is its own.
+static int window_split(int c, int* n_narrow) {
+  const int w_main = (234 + c - 1) / c;
+  *n_narrow = w_main * c - 234;
+  return w_main;
+}
+// Windows of the fixed-base mode. tau-adic expansions of reduced scalars are at most 234 digits long (measured: 229-233
 // typical) and their top 3-4 digits are mostly zero.  A uniform split leaves a short top window (234 mod c digits) whose
 // entries pile into a few hundred buckets of the shared set -- n/2^7 entries per bucket for c = 16 -- and the reducer
 // then runs 15-long serial chains.  So the 234 digits are split into W_main = ceil(234/c) windows whose widths differ by
@@ -2063,9 +2071,7 @@ struct MsmFixedCtx {
   int c = FX_C_MAX, W = TAU_DIGITS / FX_C_MAX, n_narrow = 0;
   void set_c(int cc) {
     c = cc;
-    int w_main = (234 + cc - 1) / cc;
-    n_narrow = w_main * cc - 234;
-    W = w_main + 1;
+    W = window_split(cc, &n_narrow) + 1;
   }
   bool signed_digits = false;    // aligned windows with digits in [-2^(c-1), 2^(c-1)] over the scalar's BINARY digits (k_recode_signed,
                                  // table rows 2^(o_w) P from k_dbl_table): 2^(c-1) buckets.  false = the tau-adic aligned windows
@@ -2075,8 +2081,7 @@ struct MsmFixedCtx {
   // narrow is the next smaller c.
   void set_c_signed(int cc) {
     for (;; --cc) {
-      W = (234 + cc - 1) / cc;
-      n_narrow = W * cc - 234;
+      W = window_split(cc, &n_narrow);
       if (n_narrow < W || cc <= 2) break;
     }
     c = cc;
@@ -2095,11 +2100,7 @@ static MsmPlan msm_plan(size_t n, const MsmFixedCtx* fx) {
   // (see MsmFixedCtx): the 234 real digits go into ceil(234/c) windows of c or c-1 digits (narrow ones first), the
   // digits above them (never seen beyond 236) into overflow windows.  A uniform 240/c split left a short top window
   // whose entries all fell into a few dozen buckets and serialised the reducer.
-  auto windows = [](int c, int* n_narrow) {
-    int w_main = (234 + c - 1) / c;
-    *n_narrow = w_main * c - 234;
-    return w_main + (TAU_DIGITS - 234 + c - 1) / c;
-  };
+  auto windows = [](int c, int* n_narrow) { return window_split(c, n_narrow) + (TAU_DIGITS - 234 + c - 1) / c; };
   double best = 1e300;
   p.c = 4;
   int nn;
@@ -2146,216 +2147,208 @@ static MsmPlan msm_plan(size_t n, const MsmFixedCtx* fx) {
 }
 
 static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+// dynamic-LDS limits are a per-device property of a kernel: set them once on every device that runs an MSM
+static int msm_set_lds_limits(int dev) {
+  static std::mutex attr_mu;
+  static bool attr_done[MSM_MAX_DEVICES] = {false};
+  std::lock_guard<std::mutex> ga(attr_mu);
+  if (attr_done[dev]) return DVP_OK;
+  const struct { const void* f; int bytes; } sort_lim[] = {
+      {(const void*)k_scatter_local, 131072}, {(const void*)k_hist_local, 65536}, {(const void*)k_scatter_local2, 131072},
+      {(const void*)k_hist_local2, 65536}, {(const void*)k_part_scatter_staged, (int)FX_STAGE1_LDS},
+      {(const void*)k_part_scatter_signed<true>, (int)FX_STAGE1_LDS}, {(const void*)k_scatter_local2_staged, (int)FX_STAGE2_LDS}};
+  const void* ec[] = {(const void*)k_accum_affine<true, false>, (const void*)k_accum_affine<false, false>, (const void*)k_accum_affine<true, true>,
+                      (const void*)k_accum_affine<false, true>, (const void*)k_accum_proj<1>, (const void*)k_accum_proj<4>, (const void*)k_accum_proj<16>,
+                      (const void*)k_accum_affine_fast<true, false>, (const void*)k_accum_affine_fast<false, false>, (const void*)k_accum_affine_fast<true, true>,
+                      (const void*)k_accum_affine_fast<false, true>, (const void*)k_accum_affine_rest<true>, (const void*)k_accum_affine_rest<false>,
+                      (const void*)k_tail_groups, (const void*)k_merge<1, false>, (const void*)k_merge<4, false>, (const void*)k_merge<16, false>, (const void*)k_merge<1, true>, (const void*)k_merge<4, true>, (const void*)k_merge<16, true>,
+                      (const void*)k_affine_round<true, false>, (const void*)k_affine_round<false, false>, (const void*)k_affine_round<true, true>,
+                      (const void*)k_affine_round<false, true>, (const void*)k_affine_round<false, false, true>, (const void*)k_affine_round<false, true, true>,
+                      (const void*)k_sum_points, (const void*)k_tail<false>, (const void*)k_tail<true>,
+                      (const void*)k_bucket_pairs, (const void*)k_bucket_rest};
+  for (const auto& l : sort_lim) DVP_HIP(hipFuncSetAttribute(l.f, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes));
+  for (const void* f : ec) DVP_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, EC_LDS_Q));
+  attr_done[dev] = true;
+  return DVP_OK;
+}
 
-// fx == nullptr: one-shot MSM over (d_scalars, d_bases).  fx != nullptr: fixed-base mode, the scalars
-// d_scalars[0..n) belong to bases i0 .. i0+n of the pre-rotated table and d_inf is already offset by i0.
-static int msm_core(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, const MsmFixedCtx* fx, uint32_t i0,
-                    void* d_out_xy, void* d_out_inf, hipStream_t st, void* d_out_enc = nullptr /* + the result's 30-byte encoding */,
-                    void* h_copy = nullptr, const void* d_copy = nullptr, size_t copy_bytes = 0 /* a device block the caller wants on the
-                    host (pinned) when this call returns: it rides on the MSM's own final synchronisation */,
-                    unsigned long long* d_err_defer = nullptr /* DEFERRED completion: the call returns once everything is enqueued -- no final
-                    synchronisation, no h_copy; the scalar-range word (~0 = fine, else the index of the first scalar >= p) is written to
-                    this device word by the tail kernel and the caller reads it with whatever it synchronises on later */) {
-  if (n == 0 && d_err_defer) {
-    DVP_HIP(hipMemsetAsync(d_out_xy, 0, 64, st));
-    if (d_out_enc) DVP_HIP(hipMemsetAsync(d_out_enc, 0, 30, st));
-    DVP_HIP(hipMemsetAsync(d_out_inf, 0, 4, st));
-    DVP_HIP(hipMemsetAsync(d_out_inf, 1, 1, st));  // little-endian u32 1
-    DVP_HIP(hipMemsetAsync(d_err_defer, 0xff, 8, st));
-    return DVP_OK;
-  }
-  if (n == 0) {
-    DVP_HIP(hipMemsetAsync(d_out_xy, 0, 64, st));
-    if (d_out_enc) DVP_HIP(hipMemsetAsync(d_out_enc, 0, 30, st));
-    if (h_copy) DVP_HIP(hipMemcpyAsync(h_copy, d_copy, copy_bytes, hipMemcpyDeviceToHost, st));
-    uint32_t one = 1;
-    DVP_HIP(hipMemcpyAsync(d_out_inf, &one, 4, hipMemcpyHostToDevice, st));
-    DVP_HIP(hipStreamSynchronize(st));
-    return DVP_OK;
-  }
-  if (n > (1u << 27)) return DVP_EINVAL;
-  const uint32_t sign_mask = (fx && fx->signed_digits) ? ITEM_NEG : 0u;  // signed flavours keep the sign in bit 31 of an item
-  {  // entry positions and pre-rotated table indices are 32-bit (0xffffffff = "no partner" in a slot descriptor)
-    const MsmPlan pl = msm_plan(n, fx);
-    const uint64_t tab = fx ? (uint64_t)fx->rows() * fx->n_total : (uint64_t)n;
-    if ((uint64_t)pl.e_max >= 0xfffffff0ull || tab >= (sign_mask ? 0x7ffffff0ull : 0xfffffff0ull)) return DVP_EINVAL;
-  }
-  int cur_dev = 0;
-  DVP_HIP(hipGetDevice(&cur_dev));
-  if (cur_dev < 0 || cur_dev >= MSM_MAX_DEVICES) return DVP_EINVAL;
-  {  // dynamic-LDS limits are a per-device property of a kernel: set them once on every device that runs an MSM
-    static std::mutex attr_mu;
-    static bool attr_done[MSM_MAX_DEVICES] = {false};
-    std::lock_guard<std::mutex> ga(attr_mu);
-    if (!attr_done[cur_dev]) {
-      hipError_t attr_err = hipFuncSetAttribute((const void*)k_scatter_local, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-      if (attr_err == hipSuccess)
-        attr_err = hipFuncSetAttribute((const void*)k_hist_local, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-      if (attr_err == hipSuccess)
-        attr_err = hipFuncSetAttribute((const void*)k_scatter_local2, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-      if (attr_err == hipSuccess)
-        attr_err = hipFuncSetAttribute((const void*)k_hist_local2, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-      if (attr_err == hipSuccess)
-        attr_err = hipFuncSetAttribute((const void*)k_part_scatter_staged, hipFuncAttributeMaxDynamicSharedMemorySize, FX_STAGE1_LDS);
-      if (attr_err == hipSuccess)
-        attr_err = hipFuncSetAttribute((const void*)k_part_scatter_signed<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_STAGE1_LDS);
-      if (attr_err == hipSuccess)
-        attr_err = hipFuncSetAttribute((const void*)k_scatter_local2_staged, hipFuncAttributeMaxDynamicSharedMemorySize, FX_STAGE2_LDS);
-      const void* ec[] = {(const void*)k_accum_affine<true, false>, (const void*)k_accum_affine<false, false>, (const void*)k_accum_affine<true, true>,
-                          (const void*)k_accum_affine<false, true>, (const void*)k_accum_proj<1>, (const void*)k_accum_proj<4>, (const void*)k_accum_proj<16>,
-                          (const void*)k_accum_affine_fast<true, false>, (const void*)k_accum_affine_fast<false, false>, (const void*)k_accum_affine_fast<true, true>,
-                          (const void*)k_accum_affine_fast<false, true>, (const void*)k_accum_affine_rest<true>, (const void*)k_accum_affine_rest<false>,
-                          (const void*)k_tail_groups, (const void*)k_merge<1, false>, (const void*)k_merge<4, false>, (const void*)k_merge<16, false>, (const void*)k_merge<1, true>, (const void*)k_merge<4, true>, (const void*)k_merge<16, true>,
-                          (const void*)k_affine_round<true, false>, (const void*)k_affine_round<false, false>, (const void*)k_affine_round<true, true>,
-                          (const void*)k_affine_round<false, true>, (const void*)k_affine_round<false, false, true>, (const void*)k_affine_round<false, true, true>,
-                          (const void*)k_sum_points, (const void*)k_tail<false>, (const void*)k_tail<true>,
-                          (const void*)k_bucket_pairs, (const void*)k_bucket_rest};
-      for (const void* f : ec)
-        if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, EC_LDS_Q);
-      DVP_HIP(attr_err);
-      attr_done[cur_dev] = true;
-    }
-  }
-  MsmPlan p = msm_plan(n, fx);
-  const FxBits fb = fx ? fx->bits() : FxBits{0, 0};
-  const uint32_t FX_NP = fb.np();
-  std::unique_lock<std::mutex> g;
-  int ws_slot = 0;
-  const int ws_slots = tune().msm_ws_slots >= 1 && tune().msm_ws_slots <= MSM_WS_SLOTS ? (int)tune().msm_ws_slots : 1;
-  // first choice: a workspace nobody holds AND whose last deferred MSM (if any) is finished or sits on this very stream
-  for (int pass = 0; pass < 2 && !g.owns_lock(); ++pass)
-    for (int sl = 0; sl < ws_slots && !g.owns_lock(); ++sl) {
-      g = std::unique_lock<std::mutex>(g_ws_dev[cur_dev][sl].mu, std::try_to_lock);
-      if (g.owns_lock() && pass == 0 && g_ws_dev[cur_dev][sl].busy_for(st)) g.unlock();
-      if (g.owns_lock()) ws_slot = sl;
-    }
-  if (!g.owns_lock()) g = std::unique_lock<std::mutex>(g_ws_dev[cur_dev][0].mu);
-  MsmWorkspace& g_ws = g_ws_dev[cur_dev][ws_slot];
-  g_last_msm = LastMsm{cur_dev, ws_slot, st};
-  if (g_ws.busy_valid) {  // kernels of a deferred MSM may still be using this workspace
-    if (g_ws.busy_stream != st) DVP_HIP(hipStreamWaitEvent(st, g_ws.ev_busy, 0));
-    g_ws.busy_valid = false;
-  }
-  // carve the workspace
-  size_t o = 0;
-  auto carve = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes); return r; };
-  size_t o_err = carve(32);  // err (u64) | d_max, rest_n (u32 each) | err_out (u64): the tail kernel's copy of err for the host | the tail kernel's copy of (d_max, rest_n)
-  size_t o_digits = carve(fx ? 16 : (size_t)p.W * n * 2);
-  // signed flavour: level 1 of the sort reads the scalars themselves (k_part_hist_signed), a block per fx_S scalars
-  const bool fused1 = fx && fx->signed_digits && tune().msm_sort_fused != 0;
-  const uint32_t fx_S = fused1 ? (FX_CHUNK / (uint32_t)p.W > 0 ? FX_CHUNK / (uint32_t)p.W : 1u) : 0u;
-  const uint32_t fx_nblk = fused1 ? cdiv(n, fx_S) : cdiv(p.e_max, FX_CHUNK);
-  size_t o_digits32 = carve(fx && !fused1 ? p.e_max * 4 : 16);
-  size_t o_plo = carve(fx ? p.e_max * 2 : 16);
-  size_t o_pid = carve(fx ? p.e_max * 4 : 16);
-  size_t o_phist = carve(fx ? (size_t)fx_nblk * FX_NP * 4 : 16);
-  size_t o_pbase = carve(fx ? (size_t)fx_nblk * FX_NP * 4 : 16);
-  const uint32_t fx_nch = cdiv(fx_nblk, FX_SCAN_CB);  // chunks of the level-1 scan (k_part_scan_chunks)
-  size_t o_ctot = carve(fx ? (size_t)FX_NP * fx_nch * 4 : 16);
-  size_t o_pstart = carve((FX_NP_MAX + 1) * 4 * 3);
-  size_t o_cnt = carve(((size_t)p.nkeys + 1) * 4);
-  size_t o_off = carve(((size_t)p.nkeys + 1) * 4);
-  size_t o_ntask = carve(((size_t)p.nkeys + 1) * 4);
-  size_t o_toff = carve(((size_t)p.nkeys + 1) * 4);
-  size_t o_cnt2 = carve(((size_t)p.nkeys + 1) * 4);
-  size_t o_off2 = carve(((size_t)p.nkeys + 1) * 4);
-  size_t o_bsum = carve(((size_t)p.nkeys / SCAN_BLK + 8) * 4);
-  size_t o_items = carve((p.e_max + (size_t)p.nkeys + 2) * 4);  // odd buckets are padded to even (k_post_sort)
-  const size_t sort_cells = fx ? ((size_t)(fx_nblk + FX_NP + 1) << fb.lo) : ((size_t)p.W * cdiv(n, SORT_CHUNK) << p.c);
-  size_t o_hist16 = carve(sort_cells * 2);
-  size_t o_choff = carve(sort_cells * 4);
-  size_t o_bufA = carve(p.t1_max * sizeof(Ld));
-  size_t o_bufB = carve(p.t2_max * sizeof(Ld));
-  const Tune tn = tune();
-  const bool affine_mode = !tn.msm_proj;
-  const size_t affA_n = p.e_max / 2 + p.nkeys + 1, affB_n = p.e_max / 4 + p.nkeys + 1;
-  size_t o_affA = carve(affine_mode ? affA_n * sizeof(Aff) : 16);
-  size_t o_affB = carve(affine_mode ? affB_n * sizeof(Aff) : 16);
-  size_t o_prefix = carve(affine_mode ? (affA_n + 256) * sizeof(Gf) : 16);  // one prefix product per output slot (+ the B - 1 <= 254 slots the last thread's rows may overhang)
-  // pair rounds the SIZE rule allows (the largest bucket, which only the device knows, may stop them sooner): rounds run while a
-  // round still carries >= aff_min additions
-  const size_t aff_min = (size_t)(tn.msm_aff_min > 0 ? tn.msm_aff_min : 1);
-  // entries that really exist: the overflow windows are empty in practice
-  const size_t e_est = (size_t)n * (size_t)((fx && fx->signed_digits) ? p.W : (234 + p.c - 1) / p.c);
-  int ra_plan = 0;
-  while (affine_mode && ra_plan < 40 && (e_est >> (ra_plan + 1)) >= aff_min) ++ra_plan;
-  // bookkeeping of ALL later rounds behind the first one (side stream, see below): every round keeps its own counts / offsets /
-  // descriptors, so nothing the side stream writes is ever read by a round still in flight
-  const bool pipelined = affine_mode && tn.msm_round_pipeline != 0 && ra_plan >= 2 && e_est >= 4 * (size_t)p.nkeys;
-  const bool side_stream = pipelined && tn.msm_round_pipeline == 1;
-  // the all-rounds bookkeeping lays a round out densely (additions first, leftovers behind them), two descriptor words per slot
-  const bool dense = pipelined && tn.msm_round_dense != 0;
-  std::vector<size_t> desc_at((size_t)ra_plan + 1, 0);  // round r's descriptors start at gdesc + desc_at[r] (r >= 1; even: uint2 on the dense path)
-  size_t desc_n = affA_n + 64;
-  if (pipelined) {
-    size_t cap_r = p.e_max + p.nkeys, at = 0;
-    for (int r = 0; r < ra_plan; ++r) {
-      const size_t out_max = cap_r / 2 + p.nkeys + 1;
-      if (r >= 1) { desc_at[r] = at; at += (dense ? 2 : 1) * (out_max + 64); }
-      cap_r = out_max;
-    }
-    if (at > desc_n) desc_n = at;
-  }
-  size_t o_gdesc = carve(affine_mode ? desc_n * sizeof(uint32_t) : 16);  // one descriptor word per output slot (dense: two)
-  size_t o_rp = carve(pipelined ? (size_t)ra_plan * 2 * ((size_t)p.nkeys + 1) * 4 : 16);  // (counts, offsets) of rounds 1 .. ra_plan
-  size_t o_bsum2 = carve(((size_t)((ra_plan > 0 ? ra_plan : 1) + 1) * ((size_t)p.nkeys / SCAN_BLK + 1) + 8) * 4);  // scan scratch of the side stream: a row of block sums per round
-  size_t o_bkt = carve((size_t)p.nkeys * sizeof(Ld));
+// a run-time flag or value as a template argument: f receives std::true_type / std::false_type, or the lanes per bucket of a
+// descriptor kernel (by the average bucket size of the round) as a std::integral_constant
+template <class F> static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_lpk(size_t per_key, F&& f) {
+  if (per_key >= 48) f(std::integral_constant<int, 64>{});
+  else if (per_key >= 8) f(std::integral_constant<int, 16>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
+// ---- the workspace of one MSM, described once ------------------------------------------------------------------------------
+// MsmLayout = every decision that shapes the workspace, from (n, plan, context, knobs) alone: no HIP call.  MsmBuffers = its regions,
+// typed; msm_carve is the ONE place that gives a region its size, its position and its pointer (256-byte aligned, in this order).
+struct MsmLayout {
+  FxBits fb;                // the fixed-base sort's split of the key bits ({0, 0} for a one-shot MSM)
+  bool fused1;              // signed flavour: level 1 of the sort reads the scalars themselves (k_part_hist_signed), a block per fx_S scalars
+  uint32_t fx_S, fx_nblk, fx_nch;  // fx_nch: chunks of the level-1 scan (k_part_scan_chunks)
+  size_t sort_cells, affA_n, affB_n;
+  bool affine_mode;
+  // pair rounds the SIZE rule allows (ra_plan; the largest bucket, which only the device knows, may stop them sooner): rounds run while
+  // a round still carries >= aff_min additions of the e_est entries that really exist (the overflow windows are empty in practice)
+  size_t aff_min, e_est;
+  int ra_plan;
+  // bookkeeping of ALL later rounds behind the sort (prepare_rounds): every round keeps its own counts / offsets / descriptors,
+  // so nothing the bookkeeping writes is ever read by a round still in flight
+  bool pipelined, side_stream;
+  bool dense;               // that bookkeeping lays a round out densely (additions first, leftovers behind them), two descriptor words per slot
+  size_t desc_at[41], desc_n;  // round r's descriptors start at gdesc + desc_at[r] (r >= 1; even: uint2 on the dense path)
   // k_bucket_pairs' list of buckets that met an exceptional pair (<= nkeys), or k_accum_affine_fast's list of such TASKS (chunks of K entries)
   // (sized by the reducer's own bound on its first-level tasks at its largest, no pair round run: (e_max + nkeys) / K + nkeys + 1)
-  const size_t rest_cap = (size_t)p.nkeys + 2 + (p.e_max + (size_t)p.nkeys) / (size_t)(p.K > 0 ? p.K : 1);
-  size_t o_rest = carve(rest_cap * 4);
-  const uint32_t tail_groups = ((uint32_t)(p.W * p.c) + 15u) / 16u;  // k_tail_groups: workgroups of 16 points
-  size_t o_tail = carve(((size_t)2 * p.W * p.c + 1 + 2 * (size_t)tail_groups) * sizeof(Ld));
-  DVP_TRY(g_ws.ensure(o, g_ws_need[cur_dev]));
-  char* base = (char*)g_ws.p;
-  auto* err = (unsigned long long*)(base + o_err);
-  auto* digits = (uint16_t*)(base + o_digits);
-  auto* digits32 = (uint32_t*)(base + o_digits32);
-  auto* plo = (uint16_t*)(base + o_plo);
-  auto* pid = (uint32_t*)(base + o_pid);
-  auto* phist = (uint32_t*)(base + o_phist);
-  auto* pbase = (uint32_t*)(base + o_pbase);
-  auto* ctot = (uint32_t*)(base + o_ctot);
-  auto* pstart = (uint32_t*)(base + o_pstart);
-  auto* cstart = pstart + FX_NP_MAX + 1;
-  auto* pcount = cstart + FX_NP_MAX + 1;
-  auto* cnt = (uint32_t*)(base + o_cnt);
-  auto* off = (uint32_t*)(base + o_off);
-  auto* ntask = (uint32_t*)(base + o_ntask);
-  auto* toff = (uint32_t*)(base + o_toff);
-  auto* cnt2 = (uint32_t*)(base + o_cnt2);
-  auto* off2 = (uint32_t*)(base + o_off2);
-  auto* bsum = (uint32_t*)(base + o_bsum);
-  auto* items = (uint32_t*)(base + o_items);
-  auto* hist16 = (uint16_t*)(base + o_hist16);
-  auto* chunk_off = (uint32_t*)(base + o_choff);
-  Ld* bufA = (Ld*)(base + o_bufA);
-  Ld* bufB = (Ld*)(base + o_bufB);
-  Ld* bkt = (Ld*)(base + o_bkt);
-  Aff* affA = (Aff*)(base + o_affA);
-  Aff* affB = (Aff*)(base + o_affB);
-  Gf* prefix = (Gf*)(base + o_prefix);
-  uint32_t* gdesc = (uint32_t*)(base + o_gdesc);  // one word per output slot (rounds after the first)
-  auto* rp = (uint32_t*)(base + o_rp);
-  auto* bsum2 = (uint32_t*)(base + o_bsum2);
-  Ld* tail = (Ld*)(base + o_tail);
-  auto* rest_list = (uint32_t*)(base + o_rest);
-  const uint32_t nk = p.nkeys;
+  size_t rest_cap;
+  uint32_t tail_groups;     // k_tail_groups: workgroups of 16 points
+  size_t bytes;             // the whole workspace
+  // pipelined bookkeeping on the caller's stream: the scan of all rounds also yields the item offsets, the odd buckets' padding and the
+  // largest bucket (k_mscan_add)
+  bool sort_done_by_mscan() const { return pipelined && !side_stream; }
+};
+struct MsmBuffers {
+  unsigned long long* err;  // err (u64) | d_max, rest_n (u32 each) | err_out (u64): the tail kernel's copy of err for the host | the tail kernel's copy of (d_max, rest_n)
+  uint32_t *d_max, *rest_n;  // the largest bucket; entries of the rest list
+  uint16_t *digits, *plo, *hist16;
+  uint32_t *digits32, *pid, *phist, *pbase, *ctot, *pstart, *cstart, *pcount, *chunk_off;
+  uint32_t *cnt, *off, *ntask, *toff, *cnt2, *off2, *bsum, *items, *rest_list;
+  Ld *bufA, *bufB, *bkt, *tail;
+  Aff *affA, *affB;
+  Gf* prefix;
+  uint32_t* gdesc;  // one word per output slot (rounds after the first; dense: two)
+  uint32_t* rp;     // (counts, offsets) of rounds 1 .. ra_plan
+  uint32_t* bsum2;  // scan scratch of the all-rounds bookkeeping: a row of block sums per round
+};
+struct Carver {
+  uintptr_t base;
+  size_t o = 0;
+  template <class T> T* take(size_t bytes) { T* r = (T*)(base + o); o = align_up(o + bytes); return r; }
+};
+// the regions over `base`, and their total (with base = 0 the only thing of use)
+static MsmBuffers msm_carve(size_t n, const MsmPlan& p, const MsmFixedCtx* fx, const MsmLayout& L, void* base, size_t* bytes = nullptr) {
+  Carver c{(uintptr_t)base};
+  MsmBuffers b;
+  const uint32_t FX_NP = L.fb.np();
+  const size_t keys4 = ((size_t)p.nkeys + 1) * 4;
+  b.err = c.take<unsigned long long>(32);
+  b.d_max = (uint32_t*)(b.err + 1);
+  b.rest_n = b.d_max + 1;
+  b.digits = c.take<uint16_t>(fx ? 16 : (size_t)p.W * n * 2);
+  b.digits32 = c.take<uint32_t>(fx && !L.fused1 ? p.e_max * 4 : 16);
+  b.plo = c.take<uint16_t>(fx ? p.e_max * 2 : 16);
+  b.pid = c.take<uint32_t>(fx ? p.e_max * 4 : 16);
+  for (uint32_t** r : {&b.phist, &b.pbase}) *r = c.take<uint32_t>(fx ? (size_t)L.fx_nblk * FX_NP * 4 : 16);
+  b.ctot = c.take<uint32_t>(fx ? (size_t)FX_NP * L.fx_nch * 4 : 16);
+  b.pstart = c.take<uint32_t>((FX_NP_MAX + 1) * 4 * 3);
+  b.cstart = b.pstart + FX_NP_MAX + 1;
+  b.pcount = b.cstart + FX_NP_MAX + 1;
+  for (uint32_t** r : {&b.cnt, &b.off, &b.ntask, &b.toff, &b.cnt2, &b.off2}) *r = c.take<uint32_t>(keys4);
+  b.bsum = c.take<uint32_t>(((size_t)p.nkeys / SCAN_BLK + 8) * 4);
+  b.items = c.take<uint32_t>((p.e_max + (size_t)p.nkeys + 2) * 4);  // odd buckets are padded to even (k_post_sort)
+  b.hist16 = c.take<uint16_t>(L.sort_cells * 2);
+  b.chunk_off = c.take<uint32_t>(L.sort_cells * 4);
+  b.bufA = c.take<Ld>(p.t1_max * sizeof(Ld));
+  b.bufB = c.take<Ld>(p.t2_max * sizeof(Ld));
+  b.affA = c.take<Aff>(L.affine_mode ? L.affA_n * sizeof(Aff) : 16);
+  b.affB = c.take<Aff>(L.affine_mode ? L.affB_n * sizeof(Aff) : 16);
+  b.prefix = c.take<Gf>(L.affine_mode ? (L.affA_n + 256) * sizeof(Gf) : 16);  // one prefix product per output slot (+ the B - 1 <= 254 slots the last thread's rows may overhang)
+  b.gdesc = c.take<uint32_t>(L.affine_mode ? L.desc_n * sizeof(uint32_t) : 16);
+  b.rp = c.take<uint32_t>(L.pipelined ? (size_t)L.ra_plan * 2 * keys4 : 16);
+  b.bsum2 = c.take<uint32_t>(((size_t)((L.ra_plan > 0 ? L.ra_plan : 1) + 1) * ((size_t)p.nkeys / SCAN_BLK + 1) + 8) * 4);
+  b.bkt = c.take<Ld>((size_t)p.nkeys * sizeof(Ld));
+  b.rest_list = c.take<uint32_t>(L.rest_cap * 4);
+  b.tail = c.take<Ld>(((size_t)2 * p.W * p.c + 1 + 2 * (size_t)L.tail_groups) * sizeof(Ld));
+  if (bytes) *bytes = c.o;
+  return b;
+}
+static MsmLayout msm_layout(size_t n, const MsmPlan& p, const MsmFixedCtx* fx, const Tune& tn) {
+  MsmLayout L{};
+  L.fb = fx ? fx->bits() : FxBits{0, 0};
+  L.fused1 = fx && fx->signed_digits && tn.msm_sort_fused != 0;
+  L.fx_S = L.fused1 ? (FX_CHUNK / (uint32_t)p.W > 0 ? FX_CHUNK / (uint32_t)p.W : 1u) : 0u;
+  L.fx_nblk = L.fused1 ? cdiv(n, L.fx_S) : cdiv(p.e_max, FX_CHUNK);
+  L.fx_nch = cdiv(L.fx_nblk, FX_SCAN_CB);
+  L.sort_cells = fx ? ((size_t)(L.fx_nblk + L.fb.np() + 1) << L.fb.lo) : ((size_t)p.W * cdiv(n, SORT_CHUNK) << p.c);
+  L.affine_mode = !tn.msm_proj;
+  L.affA_n = p.e_max / 2 + p.nkeys + 1;
+  L.affB_n = p.e_max / 4 + p.nkeys + 1;
+  L.aff_min = (size_t)(tn.msm_aff_min > 0 ? tn.msm_aff_min : 1);
+  L.e_est = (size_t)n * (size_t)((fx && fx->signed_digits) ? p.W : (234 + p.c - 1) / p.c);
+  while (L.affine_mode && L.ra_plan < 40 && (L.e_est >> (L.ra_plan + 1)) >= L.aff_min) ++L.ra_plan;
+  L.pipelined = L.affine_mode && tn.msm_round_pipeline != 0 && L.ra_plan >= 2 && L.e_est >= 4 * (size_t)p.nkeys;
+  L.side_stream = L.pipelined && tn.msm_round_pipeline == 1;
+  L.dense = L.pipelined && tn.msm_round_dense != 0;
+  L.desc_n = L.affA_n + 64;
+  if (L.pipelined) {
+    size_t cap_r = p.e_max + p.nkeys, at = 0;
+    for (int r = 0; r < L.ra_plan; ++r) {
+      const size_t out_max = cap_r / 2 + p.nkeys + 1;
+      if (r >= 1) { L.desc_at[r] = at; at += (L.dense ? 2 : 1) * (out_max + 64); }
+      cap_r = out_max;
+    }
+    if (at > L.desc_n) L.desc_n = at;
+  }
+  L.rest_cap = (size_t)p.nkeys + 2 + (p.e_max + (size_t)p.nkeys) / (size_t)(p.K > 0 ? p.K : 1);
+  L.tail_groups = ((uint32_t)(p.W * p.c) + 15u) / 16u;
+  (void)msm_carve(n, p, fx, L, nullptr, &L.bytes);
+  return L;
+}
 
-  // counts / offsets of round r's outputs (r >= 1) from those of its inputs, and its slot descriptors, on stream s
-  auto bookkeep = [&](int r, const uint32_t* ic, const uint32_t* io, uint32_t* oc, uint32_t* oo, uint32_t* dsc, hipStream_t s, uint32_t* bs) -> int {
-    DVP_TRY(scan_exclusive_div(ic, 2u, oc, oo, nk, bs, s));
-    // descriptors: lanes per bucket by the average bucket size of this round
-    const size_t per_key = (e_est >> (r + 1)) / nk;
-#define DVP_DESC_LAUNCH(LPK) DVP_LAUNCH((k_round_desc<LPK>), dim3(cdiv((size_t)nk * LPK, 256)), dim3(256), 0, s, ic, io, oo, nk, dsc)
-    if (per_key >= 48) DVP_DESC_LAUNCH(64); else if (per_key >= 8) DVP_DESC_LAUNCH(16); else DVP_DESC_LAUNCH(4);
-#undef DVP_DESC_LAUNCH
+// the workspace this call runs in, held through `g` until the call returns: a slot nobody holds AND whose last deferred MSM (if any)
+// is finished or sits on this very stream, else any free slot, else a wait for slot 0; then large enough for `bytes`
+static int msm_acquire_workspace(int dev, hipStream_t st, int ws_slots, size_t bytes, std::unique_lock<std::mutex>& g, MsmWorkspace** out) {
+  int ws_slot = 0;
+  for (int pass = 0; pass < 2 && !g.owns_lock(); ++pass)
+    for (int sl = 0; sl < ws_slots && !g.owns_lock(); ++sl) {
+      g = std::unique_lock<std::mutex>(g_ws_dev[dev][sl].mu, std::try_to_lock);
+      if (g.owns_lock() && pass == 0 && g_ws_dev[dev][sl].busy_for(st)) g.unlock();
+      if (g.owns_lock()) ws_slot = sl;
+    }
+  if (!g.owns_lock()) g = std::unique_lock<std::mutex>(g_ws_dev[dev][0].mu);
+  MsmWorkspace& ws = g_ws_dev[dev][ws_slot];
+  g_last_msm = LastMsm{dev, ws_slot, st};
+  if (ws.busy_valid) {  // kernels of a deferred MSM may still be using this workspace
+    if (ws.busy_stream != st) DVP_HIP(hipStreamWaitEvent(st, ws.ev_busy, 0));
+    ws.busy_valid = false;
+  }
+  DVP_TRY(ws.ensure(bytes, g_ws_need[dev]));
+  *out = &ws;
+  return DVP_OK;
+}
+
+// One MSM: the call, its plan and layout, the workspace it holds -- what every stage reads -- and the stages, in the order msm_core
+// runs them.  A stage only enqueues; what one stage hands to the next lives in the workspace (b) or in PairRounds.
+struct PairRounds;
+struct MsmRun {
+  const uint32_t* scalars;
+  const uint8_t* inf;
+  const Aff* bases0;  // the one-shot MSM's bases, or the context's pre-rotated table
+  size_t n;
+  const MsmFixedCtx* fx;
+  uint32_t i0, sign_mask;  // sign_mask: signed flavours keep the sign in bit 31 of an item
+  hipStream_t st;
+  int dev, ws_slots;
+  Tune tn;
+  MsmPlan p;
+  MsmLayout L;
+  MsmBuffers b;
+  MsmWorkspace* ws;
+  GfSqrTables Tsq;
+  int reduce_leftovers(const PairRounds& pr) const;
+  // the largest bucket goes to the host on the aux stream while the caller's stream carries on
+  int read_max() const {
+    DVP_TRY(ws->ensure_aux());
+    DVP_HIP(hipEventRecord(ws->ev, st));
+    DVP_HIP(hipStreamWaitEvent(ws->aux, ws->ev, 0));
+    DVP_HIP(hipMemcpyAsync(ws->pinned, b.d_max, 4, hipMemcpyDeviceToHost, ws->aux));
     return DVP_OK;
-  };
-  // Round bookkeeping in one piece (round 4).  A pair round's counts, offsets and slot descriptors depend on the bucket COUNTS only,
-  // never on the points, so all rounds are prepared at once -- arrays per round, four launches (k_mscan_*, k_round_desc_all) -- as
-  // soon as the sort has its counts, and the rounds then follow each other back to back (three 5 us scan launches and a descriptor
-  // kernel per round used to sit between them).  Where the four launches run (Tune::msm_round_pipeline):
+  }
+  // Round bookkeeping in one piece.  A pair round's counts, offsets and slot descriptors depend on the bucket COUNTS only, never on the
+  // points, so all rounds are prepared at once -- arrays per round, four launches (k_mscan_*, k_round_desc_all) -- as soon as the sort
+  // has its counts (cnt final on the caller's stream), and the rounds then follow each other back to back (three 5 us scan launches and a
+  // descriptor kernel per round sit between them otherwise).  Where the four launches run (Tune::msm_round_pipeline):
   //   2 (default)  on the caller's stream, before the sort's last scatter;
   //   1            on a side stream beside that scatter (HBM-bound).  One proof at a time the two are equal within noise (bench.py's
   //                configuration: 21.0-21.2 ms either way; only with every proof on the NULL stream did the side stream measure
@@ -2363,377 +2356,443 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
   //                its workgroups land in the OTHER proof's pair rounds.  NEVER beside this MSM's own first round: a round is an
   //                exact number of chip-fulls, and a few foreign workgroups holding wave slots when it is dispatched push some of
   //                its workgroups into an extra pass (measured: +0.4 ms per MSM).
-  // (rc(r), ro(r)) = counts / offsets of round r's INPUT; round 0's are the sort's.
-  auto rc = [&](int r) -> uint32_t* { return r == 0 ? cnt : rp + (size_t)(2 * (r - 1)) * ((size_t)nk + 1); };
-  auto ro = [&](int r) -> uint32_t* { return r == 0 ? off : rp + (size_t)(2 * (r - 1) + 1) * ((size_t)nk + 1); };
-  int prepared = 0;  // pipelined: the bookkeeping of rounds < prepared is enqueued on the side stream (ev_side[0] = all of it is done)
-  uint32_t* d_max = (uint32_t*)(err + 1);
-  uint32_t* rest_n = d_max + 1;  // entries of k_bucket_pairs' list
-  // the largest bucket goes to the host on the aux stream while the caller's stream carries on
-  auto read_max = [&]() -> int {
-    DVP_TRY(g_ws.ensure_aux());
-    DVP_HIP(hipEventRecord(g_ws.ev, st));
-    DVP_HIP(hipStreamWaitEvent(g_ws.aux, g_ws.ev, 0));
-    DVP_HIP(hipMemcpyAsync(g_ws.pinned, d_max, 4, hipMemcpyDeviceToHost, g_ws.aux));
-    return DVP_OK;
-  };
-  // pipelined bookkeeping on the caller's stream: the scan of all rounds also yields the item offsets, the odd buckets' padding and the
-  // largest bucket (k_mscan_add)
-  const bool sort_done_by_mscan = pipelined && !side_stream;
-  auto prepare_rounds = [&]() -> int {  // call once the sort's counts (cnt) are final on `st`
-    if (!pipelined) return DVP_OK;
-    hipStream_t bk = st;  // Tune::msm_round_pipeline == 2: the same four launches on the caller's stream
-    if (side_stream) {
-      DVP_TRY(g_ws.ensure_side(1));
-      DVP_HIP(hipEventRecord(g_ws.ev_pre, st));
-      DVP_HIP(hipStreamWaitEvent(g_ws.side, g_ws.ev_pre, 0));
-      bk = g_ws.side;
+  int prepare_rounds() const {
+    if (!L.pipelined) return DVP_OK;
+    const uint32_t nk = p.nkeys;
+    hipStream_t bk = st;
+    if (L.side_stream) {
+      DVP_TRY(ws->ensure_side(1));
+      DVP_HIP(hipEventRecord(ws->ev_pre, st));
+      DVP_HIP(hipStreamWaitEvent(ws->side, ws->ev_pre, 0));
+      bk = ws->side;
     }
     // (c_r, o_r), r = 1 .. ra_plan, in one three-launch scan (round 0's outputs included: its even-aligned buckets make the sorted
     // item list the descriptor array, and the scan of ceil(c_0 / 2) is that list's offsets halved), then every round's descriptors
     const uint32_t nb = cdiv(nk, SCAN_BLK);
     // (the caller's stream only: the side-stream flavour keeps the sort's own scan, padding and maximum)
-    uint32_t* off0 = side_stream ? nullptr : off;
-    DVP_LAUNCH(k_mscan_local, dim3(nb), dim3(SCAN_TPB), 0, bk, cnt, nk, ra_plan, rp, bsum2);
-    DVP_LAUNCH(k_mscan_bsums, dim3(ra_plan), dim3(SCAN_TPB), 0, bk, bsum2, nb, nk, rp, off0, off0 ? d_max : (uint32_t*)nullptr);
+    uint32_t* off0 = L.side_stream ? nullptr : b.off;
+    DVP_LAUNCH(k_mscan_local, dim3(nb), dim3(SCAN_TPB), 0, bk, b.cnt, nk, L.ra_plan, b.rp, b.bsum2);
+    DVP_LAUNCH(k_mscan_bsums, dim3(L.ra_plan), dim3(SCAN_TPB), 0, bk, b.bsum2, nb, nk, b.rp, off0, off0 ? b.d_max : (uint32_t*)nullptr);
     if (off0) DVP_TRY(read_max());  // the largest bucket is on its way to the host before the descriptors and the last scatter run
-    DVP_LAUNCH(k_mscan_add, dim3(nb), dim3(SCAN_TPB), 0, bk, rp, bsum2, nk, ra_plan, (const uint32_t*)cnt, off0, items);
+    DVP_LAUNCH(k_mscan_add, dim3(nb), dim3(SCAN_TPB), 0, bk, b.rp, b.bsum2, nk, L.ra_plan, (const uint32_t*)b.cnt, off0, b.items);
     DescPlan plan;
-    for (int q = 0; q < 40; ++q) plan.at[q] = q < ra_plan ? desc_at[q] : 0;
-    const size_t per_key = (e_est >> 2) / nk;  // round 1's outputs per bucket
-    const int lpk = per_key >= 48 ? 64 : per_key >= 8 ? 16 : 4;
-#define DVP_DESC_ALL(LPK)                                                                                                                   \
-  do {                                                                                                                                     \
-    if (dense) DVP_LAUNCH((k_round_desc_all<LPK, true>), dim3(cdiv((size_t)nk * LPK, 1024)), dim3(1024), 0, bk, rp, nk, ra_plan, plan, gdesc); \
-    else DVP_LAUNCH((k_round_desc_all<LPK, false>), dim3(cdiv((size_t)nk * LPK, 1024)), dim3(1024), 0, bk, rp, nk, ra_plan, plan, gdesc);      \
-  } while (0)
-    if (lpk == 64) DVP_DESC_ALL(64); else if (lpk == 16) DVP_DESC_ALL(16); else DVP_DESC_ALL(4);
-#undef DVP_DESC_ALL
-    if (side_stream) DVP_HIP(hipEventRecord(g_ws.ev_side[0], g_ws.side));
+    for (int q = 0; q < 40; ++q) plan.at[q] = q < L.ra_plan ? L.desc_at[q] : 0;
+    with_lpk((L.e_est >> 2) / nk /* round 1's outputs per bucket */, [&](auto lpk) {
+      with_bool(L.dense, [&](auto dense) {
+        constexpr int LPK = decltype(lpk)::value;
+        DVP_LAUNCH((k_round_desc_all<LPK, decltype(dense)::value>), dim3(cdiv((size_t)nk * LPK, 1024)), dim3(1024), 0, bk, b.rp, nk, L.ra_plan, plan, b.gdesc);
+      });
+    });
+    if (L.side_stream) DVP_HIP(hipEventRecord(ws->ev_side[0], ws->side));
     DVP_HIP(hipGetLastError());
-    prepared = ra_plan;
     return DVP_OK;
-  };
-  ProfScope ps_total(PROF_MSM_TOTAL, st);
-  ProfScope ps_sort(PROF_MSM_SORT, st);  // recode + counting sort
-  // the control words [err | d_max, rest_n | err_out]: every MSM's tail kernel leaves err = ~0 and d_max = rest_n = 0 behind for the
-  // next one (two memset nodes per MSM, ~6 us each plus their dispatch gaps, sat on the critical path); a fresh allocation, or a call
-  // that returned before its tail kernel was enqueued, resets them here
-  if (!g_ws.ctrl_clean) {
-    DVP_HIP(hipMemsetAsync(err, 0xff, 8, st));
-    DVP_HIP(hipMemsetAsync(err + 1, 0, 8, st));
   }
-  g_ws.ctrl_clean = false;
-  if (fused1)
-    ;  // no entry words in HBM: both level-1 kernels recompute them
-  else if (fx && fx->signed_digits)
-    DVP_LAUNCH(k_recode_signed, dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf, (uint32_t)n,
-                       p.c, p.W, p.n_narrow, digits32, err);
-  else if (fx)
-    DVP_LAUNCH((k_recode<uint32_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf,
-                       (uint32_t)n, p.c, p.W, p.n_narrow, digits32, err);
-  else
-    DVP_LAUNCH((k_recode<uint16_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf,
-                       (uint32_t)n, p.c, p.W, p.n_narrow, digits, err);
-  if (fx) {
-    const uint32_t gmax = fx_nblk + FX_NP;  // upper bound on the number of level-2 chunks
-    if (fused1)
-      DVP_LAUNCH(k_part_hist_signed, dim3(fx_nblk), dim3(SORT_TPB), 0, st, (const uint32_t*)d_scalars, (const uint8_t*)d_inf, (uint32_t)n,
-                         p.c, p.W, p.n_narrow, fx_S, fb, phist, err);
+  // control words, recode, counting sort: the items of every bucket side by side (b.items, b.cnt, b.off) and the largest bucket on its
+  // way to the host.  The all-rounds bookkeeping is enqueued as soon as the counts exist, before the last scatter.
+  int sort() const {
+    const FxBits fb = L.fb;
+    const uint32_t nk = p.nkeys;
+    ProfScope ps_sort(PROF_MSM_SORT, st);  // recode + counting sort
+    // the control words [err | d_max, rest_n | err_out]: every MSM's tail kernel leaves err = ~0 and d_max = rest_n = 0 behind for the
+    // next one (two memset nodes per MSM, ~6 us each plus their dispatch gaps, sat on the critical path); a fresh allocation, or a call
+    // that returned before its tail kernel was enqueued, resets them here
+    if (!ws->ctrl_clean) {
+      DVP_HIP(hipMemsetAsync(b.err, 0xff, 8, st));
+      DVP_HIP(hipMemsetAsync(b.err + 1, 0, 8, st));
+    }
+    ws->ctrl_clean = false;
+    if (L.fused1)
+      ;  // no entry words in HBM: both level-1 kernels recompute them
+    else if (fx && fx->signed_digits)
+      DVP_LAUNCH(k_recode_signed, dim3(cdiv(n, 256)), dim3(256), 0, st, scalars, inf, n, p.c, p.W, p.n_narrow, b.digits32, b.err);
+    else if (fx)
+      DVP_LAUNCH((k_recode<uint32_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, scalars, inf, n, p.c, p.W, p.n_narrow, b.digits32, b.err);
     else
-      DVP_LAUNCH(k_part_hist, dim3(fx_nblk), dim3(SORT_TPB), 0, st, digits32, p.e_max, fb, phist);
-    DVP_LAUNCH(k_part_scan_chunks, dim3(fx_nch), dim3(256), 0, st, phist, fx_nblk, fb, pbase, ctot, fx_nch);
-    DVP_LAUNCH(k_part_scan_totals, dim3(cdiv((size_t)FX_NP * 64, 256)), dim3(256), 0, st, ctot, fx_nch, fb, pcount);
-    DVP_LAUNCH(k_part_starts, dim3(1), dim3(FX_NP_MAX), 0, st, pcount, fb, pstart, cstart);
-    const bool staged1 = FX_NP >= 64;           // few partitions: direct stores already coalesce
-    const bool staged2 = fb.lo <= 10;           // one bin per thread in the block scan
-    if (fused1 && staged1)
-      DVP_LAUNCH(k_part_scatter_signed<true>, dim3(fx_nblk), dim3(SORT_TPB), FX_STAGE1_LDS, st, (const uint32_t*)d_scalars,
-                         (const uint8_t*)d_inf, (uint32_t)n, p.c, p.W, p.n_narrow, fx_S, fx->n_total, i0, fb, phist, pbase, ctot, fx_nch, pstart, plo, pid);
-    else if (fused1)
-      DVP_LAUNCH(k_part_scatter_signed<false>, dim3(fx_nblk), dim3(SORT_TPB), (2 * FX_NP_MAX + SORT_TPB) * 4, st, (const uint32_t*)d_scalars,
-                         (const uint8_t*)d_inf, (uint32_t)n, p.c, p.W, p.n_narrow, fx_S, fx->n_total, i0, fb, phist, pbase, ctot, fx_nch, pstart, plo, pid);
-    else if (staged1)
-      DVP_LAUNCH(k_part_scatter_staged, dim3(fx_nblk), dim3(SORT_TPB), FX_STAGE1_LDS, st, digits32, p.e_max, (uint32_t)n,
-                         fx->n_total, i0, fb, phist, pbase, ctot, fx_nch, pstart, plo, pid);
-    else
-      DVP_LAUNCH(k_part_scatter, dim3(fx_nblk), dim3(SORT_TPB), 0, st, digits32, p.e_max, (uint32_t)n, fx->n_total, i0, fb, pbase,
-                         ctot, fx_nch, pstart, plo, pid);
-    DVP_LAUNCH(k_hist_local2, dim3(gmax), dim3(SORT_TPB), (1u << fb.lo) * 2, st, plo, pstart, cstart, fb, hist16);
-    DVP_LAUNCH(k_hist_scan2, dim3(cdiv(nk, 256)), dim3(256), 0, st, hist16, cstart, fb, chunk_off, cnt);
-    DVP_TRY(prepare_rounds());  // needs the counts only
-    if (!sort_done_by_mscan) DVP_TRY(scan_exclusive_pad2(cnt, off, nk, bsum, st));
-    if (staged2)
-      DVP_LAUNCH(k_scatter_local2_staged, dim3(gmax), dim3(SORT_TPB), FX_STAGE2_LDS, st, plo, pid, pstart, cstart, fb, off,
-                         chunk_off, hist16, items);
-    else
-      DVP_LAUNCH(k_scatter_local2, dim3(gmax), dim3(SORT_TPB), (1u << fb.lo) * 4, st, plo, pid, pstart, cstart, fb, off, chunk_off, items);
-  } else {
-    const uint32_t nchunks = cdiv(n, SORT_CHUNK), nb = 1u << p.c;
-    DVP_LAUNCH(k_hist_local, dim3(nchunks, p.W), dim3(SORT_TPB), (nb >> 1) * 4, st, digits, (uint32_t)n, p.c, hist16);
-    DVP_LAUNCH(k_hist_scan, dim3(cdiv(nk, 256)), dim3(256), 0, st, hist16, nchunks, p.c, p.W, chunk_off, cnt);
-    DVP_TRY(prepare_rounds());  // needs the counts only
-    if (!sort_done_by_mscan) DVP_TRY(scan_exclusive_pad2(cnt, off, nk, bsum, st));
-    DVP_LAUNCH(k_scatter_local, dim3(nchunks, p.W), dim3(SORT_TPB), nb * 4, st, digits, (uint32_t)n, p.c, off, chunk_off, items);
+      DVP_LAUNCH((k_recode<uint16_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, scalars, inf, n, p.c, p.W, p.n_narrow, b.digits, b.err);
+    if (fx) {
+      const uint32_t FX_NP = fb.np(), fx_nblk = L.fx_nblk, fx_nch = L.fx_nch;
+      const uint32_t gmax = fx_nblk + FX_NP;  // upper bound on the number of level-2 chunks
+      if (L.fused1)
+        DVP_LAUNCH(k_part_hist_signed, dim3(fx_nblk), dim3(SORT_TPB), 0, st, scalars, inf, n, p.c, p.W, p.n_narrow, L.fx_S, fb, b.phist, b.err);
+      else
+        DVP_LAUNCH(k_part_hist, dim3(fx_nblk), dim3(SORT_TPB), 0, st, b.digits32, p.e_max, fb, b.phist);
+      DVP_LAUNCH(k_part_scan_chunks, dim3(fx_nch), dim3(256), 0, st, b.phist, fx_nblk, fb, b.pbase, b.ctot, fx_nch);
+      DVP_LAUNCH(k_part_scan_totals, dim3(cdiv((size_t)FX_NP * 64, 256)), dim3(256), 0, st, b.ctot, fx_nch, fb, b.pcount);
+      DVP_LAUNCH(k_part_starts, dim3(1), dim3(FX_NP_MAX), 0, st, b.pcount, fb, b.pstart, b.cstart);
+      const bool staged1 = FX_NP >= 64;           // few partitions: direct stores already coalesce
+      const bool staged2 = fb.lo <= 10;           // one bin per thread in the block scan
+      if (L.fused1 && staged1)
+        DVP_LAUNCH(k_part_scatter_signed<true>, dim3(fx_nblk), dim3(SORT_TPB), FX_STAGE1_LDS, st, scalars, inf, n, p.c, p.W, p.n_narrow, L.fx_S,
+                   fx->n_total, i0, fb, b.phist, b.pbase, b.ctot, fx_nch, b.pstart, b.plo, b.pid);
+      else if (L.fused1)
+        DVP_LAUNCH(k_part_scatter_signed<false>, dim3(fx_nblk), dim3(SORT_TPB), (2 * FX_NP_MAX + SORT_TPB) * 4, st, scalars, inf, n, p.c, p.W,
+                   p.n_narrow, L.fx_S, fx->n_total, i0, fb, b.phist, b.pbase, b.ctot, fx_nch, b.pstart, b.plo, b.pid);
+      else if (staged1)
+        DVP_LAUNCH(k_part_scatter_staged, dim3(fx_nblk), dim3(SORT_TPB), FX_STAGE1_LDS, st, b.digits32, p.e_max, n, fx->n_total, i0, fb, b.phist,
+                   b.pbase, b.ctot, fx_nch, b.pstart, b.plo, b.pid);
+      else
+        DVP_LAUNCH(k_part_scatter, dim3(fx_nblk), dim3(SORT_TPB), 0, st, b.digits32, p.e_max, n, fx->n_total, i0, fb, b.pbase, b.ctot, fx_nch,
+                   b.pstart, b.plo, b.pid);
+      DVP_LAUNCH(k_hist_local2, dim3(gmax), dim3(SORT_TPB), (1u << fb.lo) * 2, st, b.plo, b.pstart, b.cstart, fb, b.hist16);
+      DVP_LAUNCH(k_hist_scan2, dim3(cdiv(nk, 256)), dim3(256), 0, st, b.hist16, b.cstart, fb, b.chunk_off, b.cnt);
+      DVP_TRY(prepare_rounds());  // needs the counts only
+      if (!L.sort_done_by_mscan()) DVP_TRY(scan_exclusive_pad2(b.cnt, b.off, nk, b.bsum, st));
+      if (staged2)
+        DVP_LAUNCH(k_scatter_local2_staged, dim3(gmax), dim3(SORT_TPB), FX_STAGE2_LDS, st, b.plo, b.pid, b.pstart, b.cstart, fb, b.off, b.chunk_off,
+                   b.hist16, b.items);
+      else
+        DVP_LAUNCH(k_scatter_local2, dim3(gmax), dim3(SORT_TPB), (1u << fb.lo) * 4, st, b.plo, b.pid, b.pstart, b.cstart, fb, b.off, b.chunk_off, b.items);
+    } else {
+      const uint32_t nchunks = cdiv(n, SORT_CHUNK), nb = 1u << p.c;
+      DVP_LAUNCH(k_hist_local, dim3(nchunks, p.W), dim3(SORT_TPB), (nb >> 1) * 4, st, b.digits, n, p.c, b.hist16);
+      DVP_LAUNCH(k_hist_scan, dim3(cdiv(nk, 256)), dim3(256), 0, st, b.hist16, nchunks, p.c, p.W, b.chunk_off, b.cnt);
+      DVP_TRY(prepare_rounds());  // needs the counts only
+      if (!L.sort_done_by_mscan()) DVP_TRY(scan_exclusive_pad2(b.cnt, b.off, nk, b.bsum, st));
+      DVP_LAUNCH(k_scatter_local, dim3(nchunks, p.W), dim3(SORT_TPB), nb * 4, st, b.digits, n, p.c, b.off, b.chunk_off, b.items);
+    }
+    ps_sort.stop();
+    if (!L.sort_done_by_mscan()) {
+      // odd buckets' NONE, the first round's counts / offsets (into the ring's next pair, where PairRounds::run(0) expects them) and the
+      // largest bucket in one launch (d_max: zeroed by the previous MSM's tail kernel)
+      DVP_LAUNCH(k_post_sort, dim3(cdiv(nk + 1, 256)), dim3(256), 0, st, b.items, b.cnt, b.off, nk, b.ntask, b.toff, b.d_max);
+      DVP_TRY(read_max());
+    }
+    return DVP_OK;
   }
-  ps_sort.stop();
-  // ---- bucket accumulation: batched-affine pair rounds while a round still carries >= aff_min additions,
-  // then the projective fan-in-K reducer on what is left (it has a short critical path and balances skew)
-  uint32_t* pc[3] = {cnt, ntask, cnt2};
-  uint32_t* po[3] = {off, toff, off2};
-  if (!sort_done_by_mscan) {
-    // odd buckets' NONE, the first round's counts / offsets (into the ring's next pair, where run_round(0) expects them) and the
-    // largest bucket in one launch (d_max: zeroed by the previous MSM's tail kernel)
-    DVP_LAUNCH(k_post_sort, dim3(cdiv(nk + 1, 256)), dim3(256), 0, st, items, cnt, off, nk, pc[1], po[1], d_max);
-    DVP_TRY(read_max());
+  // one level of the merge tree with G lanes per addition
+  template <int G> void launch_merge(int j, uint32_t total, size_t lds, Ld* save0) const {
+    with_bool(j == 0, [&](auto first) {
+      DVP_LAUNCH((k_merge<G, decltype(first)::value>), dim3(cdiv((size_t)G * total, EC_TPB)), dim3(EC_TPB), lds, st, b.bkt, j, total, save0);
+    });
   }
-  int cur = 0;  // index of the live (cnt, off) pair
-  const Aff* bases0 = fx ? fx->table : (const Aff*)d_bases;
-  const Aff* pts_in = bases0;
-  size_t cap = p.e_max + nk;  // upper bound on the entries of the live array (incl. the even padding of the buckets)
-  GfSqrTables Tsq;
-  DVP_TRY(gf_sqr_tables(&Tsq, st));
-  // resident threads of k_affine_round on this device (3 blocks of 256 per CU on MI355X: 196 608)
-  int n_cu = 256, blk_per_cu = 3;
-  DVP_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, cur_dev));
-  // workgroup size of the pair rounds (Tune::msm_aff_tpb): the kernel has no block-level synchronisation (LDS tables are per wave),
-  // so smaller workgroups only change how soon a finished wave's slot is handed to the next workgroup
-  const uint32_t aff_tpb = (tn.msm_aff_tpb == 64 || tn.msm_aff_tpb == 128 || tn.msm_aff_tpb == 256) ? (uint32_t)tn.msm_aff_tpb : (uint32_t)EC_TPB;
-  const uint32_t aff_lds = (aff_tpb / 64) * GF_LDSK_BYTES_PER_WAVE;
-  // (asked of one instantiation for all of them: amdgpu_waves_per_eu(3, 3) pins every flavour -- first, later, dense, traced -- to three waves per SIMD)
-  DVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blk_per_cu, (const void*)k_affine_round<false, false>, (int)aff_tpb, aff_lds));
-  if (blk_per_cu < 1) blk_per_cu = 1;
-  const uint32_t aff_cap = (uint32_t)n_cu * (uint32_t)blk_per_cu * aff_tpb;
-  const uint32_t aff_bmax_only = tn.msm_aff_bmax >= 1 && tn.msm_aff_bmax <= 255 ? (uint32_t)tn.msm_aff_bmax : AFF_BMAX;
-  const uint32_t aff_bmin = tn.msm_aff_bmin >= 1 && (uint32_t)tn.msm_aff_bmin <= aff_bmax_only ? (uint32_t)tn.msm_aff_bmin : 1u;
-  const uint32_t aff_bmax = aff_bmax_only | (aff_bmin << 8);
-  unsigned long long* wt_buf = nullptr;
-  uint32_t wt_cap = 0;
-  wave_trace_snapshot(&wt_buf, &wt_cap);  // one snapshot per MSM: every round of it traces into the same buffer or none does
-  const bool wt_on = wt_buf != nullptr;
-  // the round itself: d_total = the scanned output count (ooff[nkeys]), dsc = one (a, b) descriptor per output slot
-  auto launch_round = [&](int r, const uint32_t* d_total, const uint2* dsc) -> int {
-    size_t out_max = cap / 2 + nk + 1;
-    Aff* outp = (r & 1) ? affB : affA;
+  // merge tree, Frobenius tail, final add tree: the result (and the control words for the next MSM) from the buckets
+  void merge_and_tail(const MsmOut& out) const {
+    ProfScope ps_tail(PROF_MSM_TAIL, st);
+    const int merge_levels = fx ? fx->key_bits() : p.c;
+    // bucket 0 (digits of magnitude 2^(c-1)) is kept aside by the first merge level, before it turns slot 0 into the total: k_tail weighs
+    // it by 2^(c-1) (a 96-byte device-to-device copy node of its own cost 14 us per MSM)
+    Ld* save0 = sign_mask ? b.tail + 2 * (size_t)p.c : nullptr;
+    const uint32_t quad_max = tn.msm_quad_max > 0 ? (uint32_t)tn.msm_quad_max : MERGE_QUAD_MAX;
+    const uint32_t hex_max = tn.msm_hex_max >= 0 ? (uint32_t)tn.msm_hex_max : MERGE_HEX_MAX;
+    for (int j = 0; j < merge_levels; ++j) {
+      const uint32_t total = (p.nkeys >> (j + 1)) * (uint32_t)(j + 1);
+      if (total <= hex_max) launch_merge<16>(j, total, EC_LDS_Q, save0);
+      else if (total <= quad_max) launch_merge<4>(j, total, EC_LDS_Q, save0);
+      else launch_merge<1>(j, total, EC_LDS, save0);
+    }
+    const int w_tail = fx ? 1 : p.W;  // fixed-base mode has a single bucket set
+    const uint32_t cntT = (uint32_t)(w_tail * p.c);
+    Ld* ta = b.tail;  // 2 * cntT entries: the two halves of k_tail's ping-pong
+    uint32_t *o_xy = (uint32_t*)out.d_out_xy, *o_inf = (uint32_t*)out.d_out_inf;
+    uint8_t* o_enc = (uint8_t*)out.d_out_enc;
+    const int rule = o_enc ? dvp_codec_get_rule() : 0;
+    if (sign_mask && tn.msm_hex_max != 0)  // c points: one row of 16 lanes each
+      DVP_LAUNCH(k_tail<true>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, b.bkt, p.c, w_tail, -3, Tsq, ta, o_xy, o_inf, o_enc, rule, b.err, out.d_err_defer);
+    else if (!sign_mask && cntT > 32 && tn.msm_tail_groups != 0) {
+      // many points (the one-shot MSM's W x c): group sums on cdiv(cntT, 16) workgroups first, then the single-workgroup tail on those
+      Ld* part = b.tail + 2 * (size_t)cntT + 1;
+      const int nparts = (int)cdiv(cntT, 16);
+      DVP_LAUNCH(k_tail_groups, dim3(nparts), dim3(EC_TPB), EC_LDS_Q, st, b.bkt, p.c, w_tail, fx ? 0 : p.n_narrow, Tsq, ta, part);
+      DVP_LAUNCH(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, b.bkt, nparts, 1, -4, Tsq, part, o_xy, o_inf, o_enc, rule, b.err, out.d_err_defer);
+    } else
+      DVP_LAUNCH(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, b.bkt, p.c, w_tail, sign_mask ? -3 : (fx ? 0 : p.n_narrow), Tsq, ta, o_xy, o_inf,
+                 o_enc, rule, b.err, out.d_err_defer);
+    ps_tail.stop();
+  }
+  // deferred completion: the workspace stays in use until this point of the stream; nothing here touches the host
+  int complete_deferred() const {
+    DVP_HIP(hipEventRecord(ws->ev_busy, st));
+    ws->busy_stream = st;
+    ws->busy_valid = true;
+    return DVP_OK;
+  }
+  // the scalar-range flag is the only thing that needs the host: into the workspace's pinned words (a pageable destination makes the
+  // runtime stage the copy and take a host round trip of its own between the two copies: 60 us per MSM)
+  int complete(const MsmOut& out) const {
+    volatile unsigned long long* h_err = (volatile unsigned long long*)(ws->pinned + 2);
+    if (out.h_copy) DVP_HIP(hipMemcpyAsync(out.h_copy, out.d_copy, out.copy_bytes, hipMemcpyDeviceToHost, st));
+    DVP_HIP(hipMemcpyAsync((void*)h_err, b.err + 2, 8, hipMemcpyDeviceToHost, st));  // err_out
+    DVP_HIP(hipStreamSynchronize(st));
+    count_host_wait(0);
+    const unsigned long long e = *h_err;
+    if (e != ~0ull) {
+      g_last_error_index = (int64_t)(e & 0xffffffffull);
+      return DVP_EINVAL;
+    }
+    return DVP_OK;
+  }
+};
+
+// ---- bucket accumulation: batched-affine pair rounds while a round still carries >= aff_min additions, then the projective
+// fan-in-K reducer on what is left (it has a short critical path and balances skew)
+struct PairRounds {
+  const MsmRun& m;
+  uint32_t *pc[3], *po[3];  // ring of (counts, offsets): the sort's, then each stage's outputs
+  int cur = 0;         // index of the live (cnt, off) pair
+  const Aff* pts_in;   // the live points
+  size_t cap;          // upper bound on the entries of the live array (incl. the even padding of the buckets)
+  int launched = 0, ra = 0;  // rounds enqueued ahead of the largest-bucket read; rounds in all
+  uint32_t max_cnt = 0;      // the largest bucket, as the sort left it
+  uint32_t aff_tpb = 0, aff_lds = 0, aff_cap = 0, aff_bmax_only = 0, aff_bmax = 0, wt_cap = 0;
+  unsigned long long* wt_buf = nullptr;  // the wave trace's buffer (wt_cap records), if one is set
+  std::unique_lock<std::mutex> heavy;  // HeavyGate: held from the first pair round's enqueue to the last one's (released on every return)
+  explicit PairRounds(const MsmRun& m_)
+      : m(m_), pc{m_.b.cnt, m_.b.ntask, m_.b.cnt2}, po{m_.b.off, m_.b.toff, m_.b.off2}, pts_in(m_.bases0), cap(m_.p.e_max + m_.p.nkeys) {}
+  // (rc(r), ro(r)) = counts / offsets of round r's INPUT under the all-rounds bookkeeping; round 0's are the sort's
+  uint32_t* rc(int r) const { return r == 0 ? m.b.cnt : m.b.rp + (size_t)(2 * (r - 1)) * ((size_t)m.p.nkeys + 1); }
+  uint32_t* ro(int r) const { return r == 0 ? m.b.off : m.b.rp + (size_t)(2 * (r - 1) + 1) * ((size_t)m.p.nkeys + 1); }
+  int init() {
+    const Tune& tn = m.tn;
+    // resident threads of k_affine_round on this device (3 blocks of 256 per CU on MI355X: 196 608)
+    int n_cu = 256, blk_per_cu = 3;
+    DVP_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, m.dev));
+    // workgroup size of the pair rounds (Tune::msm_aff_tpb): the kernel has no block-level synchronisation (LDS tables are per wave),
+    // so smaller workgroups only change how soon a finished wave's slot is handed to the next workgroup
+    aff_tpb = (tn.msm_aff_tpb == 64 || tn.msm_aff_tpb == 128 || tn.msm_aff_tpb == 256) ? (uint32_t)tn.msm_aff_tpb : (uint32_t)EC_TPB;
+    aff_lds = (aff_tpb / 64) * GF_LDSK_BYTES_PER_WAVE;
+    // (asked of one instantiation for all of them: amdgpu_waves_per_eu(3, 3) pins every flavour -- first, later, dense, traced -- to three waves per SIMD)
+    DVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blk_per_cu, (const void*)k_affine_round<false, false>, (int)aff_tpb, aff_lds));
+    if (blk_per_cu < 1) blk_per_cu = 1;
+    aff_cap = (uint32_t)n_cu * (uint32_t)blk_per_cu * aff_tpb;
+    aff_bmax_only = tn.msm_aff_bmax >= 1 && tn.msm_aff_bmax <= 255 ? (uint32_t)tn.msm_aff_bmax : AFF_BMAX;
+    const uint32_t aff_bmin = tn.msm_aff_bmin >= 1 && (uint32_t)tn.msm_aff_bmin <= aff_bmax_only ? (uint32_t)tn.msm_aff_bmin : 1u;
+    aff_bmax = aff_bmax_only | (aff_bmin << 8);
+    wave_trace_snapshot(&wt_buf, &wt_cap);  // one snapshot per MSM: every round of it traces into the same buffer or none does
+    return DVP_OK;
+  }
+  // round r: its bookkeeping where that is per round, then the round itself over d_total = the scanned output count (ooff[nkeys]) and
+  // dsc = one (a, b) descriptor per output slot
+  int run(int r) {
+    const MsmLayout& L = m.L;
+    const MsmBuffers& b = m.b;
+    const uint32_t nk = m.p.nkeys;
+    hipStream_t st = m.st;
+    const int nxt = (cur + 1) % 3;
+    const uint32_t *d_total, *dsc = r == 0 ? b.items : b.gdesc;
+    if (L.pipelined) {  // r < ra_plan always (ra <= ra_plan); everything a round needs was prepared behind the sort
+      if (r == 0 && L.side_stream) DVP_HIP(hipStreamWaitEvent(st, m.ws->ev_side[0], 0));
+      d_total = ro(r + 1) + nk;
+      if (r > 0) dsc = b.gdesc + L.desc_at[r];
+    } else {
+      // (r == 0: cur == 0 and k_post_sort has left the first round's counts / offsets in pc[1] / po[1] -- an MSM that is not pipelined
+      // always runs it.)  r > 0: counts / offsets of the round's outputs from those of its inputs, and its slot descriptors
+      if (r > 0) {
+        DVP_TRY(scan_exclusive_div(pc[cur], 2u, pc[nxt], po[nxt], nk, b.bsum, st));
+        with_lpk((L.e_est >> (r + 1)) / nk, [&](auto lpk) {
+          constexpr int LPK = decltype(lpk)::value;
+          DVP_LAUNCH((k_round_desc<LPK>), dim3(cdiv((size_t)nk * LPK, 256)), dim3(256), 0, st, pc[cur], po[cur], po[nxt], nk, b.gdesc);
+        });
+      }
+      d_total = po[nxt] + nk;
+    }
+    const size_t out_max = cap / 2 + nk + 1;
+    Aff* outp = (r & 1) ? b.affB : b.affA;
     // grid: upper bound on the threads the device-side choice of B can ask for (R chip-fulls, see k_affine_round)
     const uint32_t r_max = cdiv(cdiv(out_max, aff_cap), aff_bmax_only);
     const uint32_t grid = r_max * (aff_cap / aff_tpb) + 1;
-    {
-      // r == 0 is the dominant kernel (it gathers the bases) and is timed launch by launch; the later rounds share ONE scope (ps_rest,
-      // below): an event pair around every round put ~10 us of packet processing between two rounds that otherwise follow each
-      // other back to back (kernel trace: 10-13 us gaps after every round, none between the merge levels)
-      ProfScope ps0(r == 0 ? PROF_MSM_ACCUM_AFFINE : -1, st, (uint64_t)n);
-      WaveTrace wt{wt_buf, wt_cap, g_wave_trace_tag.fetch_add(wt_on ? 1u : 0u)};
-      if (r == 0 && wt.buf)
-        DVP_LAUNCH((k_affine_round<true, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, sign_mask, wt);
-      else if (r == 0)
-        DVP_LAUNCH((k_affine_round<true, false>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, sign_mask, wt);
-      else if (dense && wt.buf)
-        DVP_LAUNCH((k_affine_round<false, true, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
-      else if (dense)
-        DVP_LAUNCH((k_affine_round<false, false, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
-      else if (wt.buf)
-        DVP_LAUNCH((k_affine_round<false, true>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
-      else
-        DVP_LAUNCH((k_affine_round<false, false>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, dsc, d_total, aff_cap, aff_bmax, Tsq, prefix, outp, 0u, wt);
-      ps0.stop();
-      if (r > 0) count_later_round(dense);
-    }
+    // r == 0 is the dominant kernel (it gathers the bases) and is timed launch by launch; the later rounds share ONE scope (finish()):
+    // an event pair around every round put ~10 us of packet processing between two rounds that otherwise follow each other back to
+    // back (kernel trace: 10-13 us gaps after every round, none between the merge levels)
+    ProfScope ps0(r == 0 ? PROF_MSM_ACCUM_AFFINE : -1, st, (uint64_t)m.n);
+    WaveTrace wt{wt_buf, wt_cap, g_wave_trace_tag.fetch_add(wt_buf ? 1u : 0u)};
+    with_bool(r == 0, [&](auto first) {
+      with_bool(wt.buf != nullptr, [&](auto trace) {
+        with_bool(r > 0 && L.dense, [&](auto dense) {
+          constexpr bool FIRST = decltype(first)::value, TRACE = decltype(trace)::value, DENSE = decltype(dense)::value;
+          if constexpr (!(FIRST && DENSE))  // a first round is never dense: no such kernel
+            DVP_LAUNCH((k_affine_round<FIRST, TRACE, DENSE>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, (const uint2*)(const void*)dsc, d_total,
+                       aff_cap, aff_bmax, m.Tsq, b.prefix, outp, FIRST ? m.sign_mask : 0u, wt);
+        });
+      });
+    });
+    ps0.stop();
+    if (r > 0) count_later_round(L.dense);
     pts_in = outp;
     cap = out_max;
+    if (!L.pipelined) cur = nxt;
     return DVP_OK;
-  };
-  auto run_round = [&](int r) -> int {
-    if (pipelined) {  // r < ra_plan always (ra <= ra_plan); everything a round needs was prepared behind the sort
-      if (r == 0 && side_stream) DVP_HIP(hipStreamWaitEvent(st, g_ws.ev_side[0], 0));
-      DVP_TRY(launch_round(r, ro(r + 1) + nk, r == 0 ? (const uint2*)items : (const uint2*)(const void*)(gdesc + desc_at[r])));
-      return DVP_OK;
-    }
-    const int nxt = (cur + 1) % 3;
-    // (r == 0: cur == 0 and k_post_sort has left the first round's counts / offsets in pc[1] / po[1] -- an MSM that is not pipelined
-    // always runs it)
-    if (r > 0) DVP_TRY(bookkeep(r, pc[cur], po[cur], pc[nxt], po[nxt], gdesc, st, bsum));
-    DVP_TRY(launch_round(r, po[nxt] + nk, r == 0 ? (const uint2*)items : (const uint2*)(const void*)gdesc));
-    cur = nxt;
-    return DVP_OK;
-  };
+  }
   // The number of rounds depends on the largest bucket, which only the device knows.  When the average bucket already
   // holds >= 4 entries the first round is certain to be needed, so it is enqueued BEFORE the host waits for that number:
   // the round trip (and the launch ramp after it) hides behind ~5 ms of round 0 instead of idling the GPU mid-MSM.
-  int launched = 0;
-  std::unique_lock<std::mutex> heavy;  // held from the first pair round's enqueue to the last one's (released on every return)
-  if (ws_slots > 1 && affine_mode) {
-    heavy = std::unique_lock<std::mutex>(g_heavy[cur_dev].mu);
-    if (g_heavy[cur_dev].last && g_heavy[cur_dev].last != g_ws.ev_heavy) DVP_HIP(hipStreamWaitEvent(st, g_heavy[cur_dev].last, 0));
-  }
-  if (affine_mode && (e_est >> 1) >= aff_min && e_est >= 4 * (size_t)nk) {
-    DVP_TRY(run_round(0));
-    launched = 1;
-  }
-  DVP_HIP(hipStreamSynchronize(g_ws.aux));  // the caller's stream keeps running round 0 meanwhile
-  count_host_wait(launched ? 1 : 0);
-  const uint32_t max_cnt = *g_ws.pinned;
-  int ra = 0;
-  if (affine_mode)
-    while (((uint64_t)1 << ra) < max_cnt && (e_est >> (ra + 1)) >= aff_min) ++ra;
-  if (ra < launched) ra = launched;  // a first round over single-entry buckets only passes them through
-  // the gate's event goes after the last round that still fills the chip several times over (>= Tune::msm_gate_min additions):
-  // the late rounds are latency-bound and are exactly what the next MSM's first round should overlap
-  int r_evt = -1;
-  if (heavy.owns_lock() && ra > 0) {
-    const size_t gate_min = tn.msm_gate_min > 0 ? (size_t)tn.msm_gate_min : 1;
-    r_evt = 0;
-    while (r_evt + 1 < ra && (e_est >> (r_evt + 2)) >= gate_min) ++r_evt;
-  }
-  auto gate_event = [&]() -> int {
-    DVP_HIP(hipEventRecord(g_ws.ev_heavy, st));
-    g_heavy[cur_dev].last = g_ws.ev_heavy;
+  int begin() {
+    const MsmLayout& L = m.L;
+    if (m.ws_slots > 1 && L.affine_mode) {
+      HeavyGate& hg = g_heavy[m.dev];
+      heavy = std::unique_lock<std::mutex>(hg.mu);
+      if (hg.last && hg.last != m.ws->ev_heavy) DVP_HIP(hipStreamWaitEvent(m.st, hg.last, 0));
+    }
+    if (L.affine_mode && (L.e_est >> 1) >= L.aff_min && L.e_est >= 4 * (size_t)m.p.nkeys) {
+      DVP_TRY(run(0));
+      launched = 1;
+    }
+    DVP_HIP(hipStreamSynchronize(m.ws->aux));  // the caller's stream keeps running round 0 meanwhile
+    count_host_wait(launched ? 1 : 0);
+    max_cnt = *m.ws->pinned;
+    if (L.affine_mode)
+      while (((uint64_t)1 << ra) < max_cnt && (L.e_est >> (ra + 1)) >= L.aff_min) ++ra;
+    if (ra < launched) ra = launched;  // a first round over single-entry buckets only passes them through
     return DVP_OK;
-  };
-  if (r_evt >= 0 && r_evt < launched) DVP_TRY(gate_event());
-  {
+  }
+  int gate_event() {
+    DVP_HIP(hipEventRecord(m.ws->ev_heavy, m.st));
+    g_heavy[m.dev].last = m.ws->ev_heavy;
+    return DVP_OK;
+  }
+  // the rounds begin() did not enqueue; afterwards (pc[cur], po[cur], pts_in, cap) describe what the rounds left
+  int finish() {
+    // the gate's event goes after the last round that still fills the chip several times over (>= Tune::msm_gate_min additions):
+    // the late rounds are latency-bound and are exactly what the next MSM's first round should overlap
+    int r_evt = -1;
+    if (heavy.owns_lock() && ra > 0) {
+      const size_t gate_min = m.tn.msm_gate_min > 0 ? (size_t)m.tn.msm_gate_min : 1;
+      r_evt = 0;
+      while (r_evt + 1 < ra && (m.L.e_est >> (r_evt + 2)) >= gate_min) ++r_evt;
+    }
+    if (r_evt >= 0 && r_evt < launched) DVP_TRY(gate_event());
     int r = launched;
     if (r == 0 && ra > 0) {  // (small MSMs: the first round was not enqueued ahead of the largest-bucket read)
-      DVP_TRY(run_round(0));
+      DVP_TRY(run(0));
       if (r_evt == 0) DVP_TRY(gate_event());
       r = 1;
     }
-    ProfScope ps_rest(ra > r ? PROF_MSM_AFFINE_REST : -1, st, (uint64_t)(ra > r ? ra - r : 0));
+    ProfScope ps_rest(ra > r ? PROF_MSM_AFFINE_REST : -1, m.st, (uint64_t)(ra > r ? ra - r : 0));
     for (; r < ra; ++r) {
-      DVP_TRY(run_round(r));
+      DVP_TRY(run(r));
       if (r == r_evt) DVP_TRY(gate_event());
     }
     ps_rest.stop();
-  }
-  if (pipelined && prepared) {
-    // what the rounds left is described by the arrays of round `ra`: they head the ring of three the reducer works in
-    if (!launched && side_stream) DVP_HIP(hipStreamWaitEvent(st, g_ws.ev_side[0], 0));  // (not reached: a pipelined MSM always starts its first round early)
-    pc[0] = rc(ra); po[0] = ro(ra);
-    cur = 0;
-  }
-  if (heavy.owns_lock()) heavy.unlock();
-  uint64_t rem_max = ((uint64_t)max_cnt + ((uint64_t)1 << ra) - 1) >> ra;  // largest bucket after the affine rounds
-  if (rem_max <= 1) {
-    if (ra == 0)
-      DVP_LAUNCH(k_bucket_gather_items, dim3(cdiv(nk, 256)), dim3(256), 0, st, bases0, items, cnt, off, nk, bkt, sign_mask);
-    else
-      DVP_LAUNCH(k_bucket_gather_aff, dim3(cdiv(nk, 256)), dim3(256), 0, st, pts_in, pc[cur], po[cur], nk, bkt);
-  } else if (ra > 0 && rem_max <= (uint64_t)(tn.msm_bucket_pairs_max >= 0 ? tn.msm_bucket_pairs_max : 0)) {
-    // a handful of points per bucket left: one thread per bucket; buckets that meet an exceptional pair are redone from a list
-    DVP_LAUNCH(k_bucket_pairs, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, pc[cur], po[cur], nk, bkt, rest_n, rest_list);
-    DVP_LAUNCH(k_bucket_rest, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, pc[cur], po[cur], rest_n, rest_list, bkt);
-  } else {
-    // level 1: mixed additions from affine inputs
-    int nxt = (cur + 1) % 3;
-    DVP_TRY(scan_exclusive_div(pc[cur], p.K, pc[nxt], po[nxt], nk, bsum, st));
-    size_t tmax = cap / p.K + nk + 1;
-    const size_t accum_quad_max = tn.msm_accum_quad_max > 0 ? (size_t)tn.msm_accum_quad_max : ACCUM_QUAD_MAX;
-    const size_t accum_hex_max = tn.msm_accum_hex_max >= 0 ? (size_t)tn.msm_accum_hex_max : ACCUM_HEX_MAX;
-    // tmax is an upper bound on the tasks (the real count sits on the device); quads when even the bound fits one chip-full
-    // (the rest list holds task numbers: tmax of them at most, and rest_cap is sized from tmax at its largest, so the list always fits;
-    // the comparison stays as the bound's witness.  Tune::msm_accum_fast = 0: the general kernel of rounds 1-5)
-    const bool accum_fast = tn.msm_accum_fast != 0 && tmax <= rest_cap;
-#define DVP_ACCUM_AFFINE(IND)                                                                                                                  \
-  do {                                                                                                                                         \
-    if (accum_fast) {                                                                                                                          \
-      if (tmax <= accum_quad_max)                                                                                                              \
-        DVP_LAUNCH((k_accum_affine_fast<IND, true>), dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, pts_in, items, pc[cur], \
-                           po[cur], po[nxt], nk, p.K, bufA, sign_mask, rest_n, rest_list);                                                    \
-      else                                                                                                                                     \
-        DVP_LAUNCH((k_accum_affine_fast<IND, false>), dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, items, pc[cur],      \
-                           po[cur], po[nxt], nk, p.K, bufA, sign_mask, rest_n, rest_list);                                                    \
-      DVP_LAUNCH((k_accum_affine_rest<IND>), dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, items, pc[cur], po[cur],       \
-                         po[nxt], nk, p.K, bufA, sign_mask, rest_n, rest_list);                                                                \
-    } else if (tmax <= accum_quad_max)                                                                                                         \
-      DVP_LAUNCH((k_accum_affine<IND, true>), dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, pts_in, items, pc[cur], po[cur], \
-                         po[nxt], nk, p.K, bufA, sign_mask);                                                                                   \
-    else                                                                                                                                       \
-      DVP_LAUNCH((k_accum_affine<IND, false>), dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pts_in, items, pc[cur], po[cur],     \
-                         po[nxt], nk, p.K, bufA, sign_mask);                                                                                   \
-  } while (0)
-    if (ra == 0) {
-      ProfScope ps0(PROF_MSM_ACCUM_AFFINE, st);  // small inputs: no pair rounds, this is the dominant kernel
-      DVP_ACCUM_AFFINE(true);
-      ps0.stop();
-    } else
-      DVP_ACCUM_AFFINE(false);
-#undef DVP_ACCUM_AFFINE
-    cur = nxt;
-    cap = tmax;
-    Ld *in = bufA, *outb = bufB;
-    for (uint64_t left = (rem_max + p.K - 1) / p.K; left > 1; left = (left + p.K - 1) / p.K) {
-      nxt = (cur + 1) % 3;
-      DVP_TRY(scan_exclusive_div(pc[cur], p.K, pc[nxt], po[nxt], nk, bsum, st));
-      tmax = cap / p.K + nk + 1;
-      // the LAST level of a small MSM (every bucket ends with one task of at most K partial sums, typically one or two): rows of 16
-      // lanes when the tasks fit ACCUM_HEX_MAX (measured at 2^16 points, round 6)
-      if (left <= p.K && tmax <= accum_hex_max)
-        DVP_LAUNCH(k_accum_proj<16>, dim3(cdiv(16 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
-      else if (tmax <= accum_quad_max)
-        DVP_LAUNCH(k_accum_proj<4>, dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
-      else
-        DVP_LAUNCH(k_accum_proj<1>, dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
-      cap = tmax;
-      cur = nxt;
-      Ld* t = in; in = outb; outb = t;
+    if (m.L.pipelined) {
+      // what the rounds left is described by the arrays of round `ra`: they head the ring of three the reducer works in
+      // (a pipelined MSM always starts its first round early, so the side stream's bookkeeping has been waited for)
+      pc[0] = rc(ra);
+      po[0] = ro(ra);
+      cur = 0;
     }
-    DVP_LAUNCH(k_bucket_gather, dim3(cdiv(nk, 256)), dim3(256), 0, st, in, pc[cur], po[cur], nk, bkt);
-  }
-  ProfScope ps_tail(PROF_MSM_TAIL, st);  // merge tree, Frobenius tail, final add tree
-  const int merge_levels = fx ? fx->key_bits() : p.c;
-  // bucket 0 (digits of magnitude 2^(c-1)) is kept aside by the first merge level, before it turns slot 0 into the total: k_tail weighs
-  // it by 2^(c-1) (a 96-byte device-to-device copy node of its own cost 14 us per MSM)
-  Ld* save0 = sign_mask ? tail + 2 * (size_t)p.c : nullptr;
-  for (int j = 0; j < merge_levels; ++j) {
-    uint32_t total = (nk >> (j + 1)) * (uint32_t)(j + 1);
-    const uint32_t quad_max = tn.msm_quad_max > 0 ? (uint32_t)tn.msm_quad_max : MERGE_QUAD_MAX;
-    const uint32_t hex_max = tn.msm_hex_max >= 0 ? (uint32_t)tn.msm_hex_max : MERGE_HEX_MAX;
-#define DVP_MERGE(G, F, LDSB) DVP_LAUNCH((k_merge<G, F>), dim3(cdiv((size_t)G * total, EC_TPB)), dim3(EC_TPB), LDSB, st, bkt, j, total, save0)
-    if (total <= hex_max) { if (j == 0) DVP_MERGE(16, true, EC_LDS_Q); else DVP_MERGE(16, false, EC_LDS_Q); }
-    else if (total <= quad_max) { if (j == 0) DVP_MERGE(4, true, EC_LDS_Q); else DVP_MERGE(4, false, EC_LDS_Q); }
-    else { if (j == 0) DVP_MERGE(1, true, EC_LDS); else DVP_MERGE(1, false, EC_LDS); }
-#undef DVP_MERGE
-  }
-  const int w_tail = fx ? 1 : p.W;  // fixed-base mode has a single bucket set
-  uint32_t cntT = (uint32_t)(w_tail * p.c);
-  Ld* ta = tail;  // 2 * cntT entries: the two halves of k_tail's ping-pong
-  if (sign_mask && tn.msm_hex_max != 0)  // c points: one row of 16 lanes each
-    DVP_LAUNCH(k_tail<true>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, bkt, p.c, w_tail, -3, Tsq, ta, (uint32_t*)d_out_xy, (uint32_t*)d_out_inf,
-                       (uint8_t*)d_out_enc, d_out_enc ? dvp_codec_get_rule() : 0, err, d_err_defer);
-  else if (!sign_mask && cntT > 32 && tn.msm_tail_groups != 0) {
-    // many points (the one-shot MSM's W x c): group sums on cdiv(cntT, 16) workgroups first, then the single-workgroup tail on those
-    Ld* part = tail + 2 * (size_t)cntT + 1;
-    const int nparts = (int)cdiv(cntT, 16);
-    DVP_LAUNCH(k_tail_groups, dim3(nparts), dim3(EC_TPB), EC_LDS_Q, st, bkt, p.c, w_tail, fx ? 0 : p.n_narrow, Tsq, ta, part);
-    DVP_LAUNCH(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, bkt, nparts, 1, -4, Tsq, part, (uint32_t*)d_out_xy,
-                       (uint32_t*)d_out_inf, (uint8_t*)d_out_enc, d_out_enc ? dvp_codec_get_rule() : 0, err, d_err_defer);
-  } else
-    DVP_LAUNCH(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, bkt, p.c, w_tail, sign_mask ? -3 : (fx ? 0 : p.n_narrow), Tsq, ta, (uint32_t*)d_out_xy,
-                       (uint32_t*)d_out_inf, (uint8_t*)d_out_enc, d_out_enc ? dvp_codec_get_rule() : 0, err, d_err_defer);
-  ps_tail.stop();
-  ps_total.stop();
-  DVP_HIP(hipGetLastError());
-  g_ws.ctrl_clean = true;  // the tail kernel is enqueued: it resets the control words
-  // the scalar-range flag is the only thing that needs the host
-  // into the workspace's pinned words (a pageable destination makes the runtime stage the copy and take a host round trip of its own
-  // between the two copies: 60 us per MSM)
-  if (d_err_defer) {  // deferred: the workspace stays in use until this point of the stream
-    DVP_HIP(hipEventRecord(g_ws.ev_busy, st));
-    g_ws.busy_stream = st;
-    g_ws.busy_valid = true;
+    if (heavy.owns_lock()) heavy.unlock();
     return DVP_OK;
   }
-  volatile unsigned long long* h_err = (volatile unsigned long long*)(g_ws.pinned + 2);
-  if (h_copy) DVP_HIP(hipMemcpyAsync(h_copy, d_copy, copy_bytes, hipMemcpyDeviceToHost, st));
-  DVP_HIP(hipMemcpyAsync((void*)h_err, err + 2, 8, hipMemcpyDeviceToHost, st));  // err_out
-  DVP_HIP(hipStreamSynchronize(st));
-  count_host_wait(0);
-  const unsigned long long e = *h_err;
-  if (e != ~0ull) {
-    g_last_error_index = (int64_t)(e & 0xffffffffull);
-    return DVP_EINVAL;
+};
+
+// what the pair rounds left, down to one point per bucket (b.bkt), by one of three routes
+int MsmRun::reduce_leftovers(const PairRounds& pr) const {
+  const uint32_t nk = p.nkeys;
+  uint32_t *const *pc = pr.pc, *const *po = pr.po;
+  int cur = pr.cur;
+  const uint64_t rem_max = ((uint64_t)pr.max_cnt + ((uint64_t)1 << pr.ra) - 1) >> pr.ra;  // largest bucket after the affine rounds
+  if (rem_max <= 1) {
+    if (pr.ra == 0)
+      DVP_LAUNCH(k_bucket_gather_items, dim3(cdiv(nk, 256)), dim3(256), 0, st, bases0, b.items, b.cnt, b.off, nk, b.bkt, sign_mask);
+    else
+      DVP_LAUNCH(k_bucket_gather_aff, dim3(cdiv(nk, 256)), dim3(256), 0, st, pr.pts_in, pc[cur], po[cur], nk, b.bkt);
+    return DVP_OK;
   }
+  if (pr.ra > 0 && rem_max <= (uint64_t)(tn.msm_bucket_pairs_max >= 0 ? tn.msm_bucket_pairs_max : 0)) {
+    // a handful of points per bucket left: one thread per bucket; buckets that meet an exceptional pair are redone from a list
+    DVP_LAUNCH(k_bucket_pairs, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pr.pts_in, pc[cur], po[cur], nk, b.bkt, b.rest_n, b.rest_list);
+    DVP_LAUNCH(k_bucket_rest, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pr.pts_in, pc[cur], po[cur], b.rest_n, b.rest_list, b.bkt);
+    return DVP_OK;
+  }
+  // the fan-in-K reducer.  Level 1: mixed additions from affine inputs (IND: the items index the bases; else the pair rounds' outputs)
+  int nxt = (cur + 1) % 3;
+  DVP_TRY(scan_exclusive_div(pc[cur], p.K, pc[nxt], po[nxt], nk, b.bsum, st));
+  size_t tmax = pr.cap / p.K + nk + 1;
+  const size_t accum_quad_max = tn.msm_accum_quad_max > 0 ? (size_t)tn.msm_accum_quad_max : ACCUM_QUAD_MAX;
+  const size_t accum_hex_max = tn.msm_accum_hex_max >= 0 ? (size_t)tn.msm_accum_hex_max : ACCUM_HEX_MAX;
+  // tmax is an upper bound on the tasks (the real count sits on the device); quads when even the bound fits one chip-full
+  // (the rest list holds task numbers: tmax of them at most, and rest_cap is sized from tmax at its largest, so the list always fits;
+  // the comparison stays as the bound's witness.  Tune::msm_accum_fast = 0: the general kernel)
+  const bool accum_fast = tn.msm_accum_fast != 0 && tmax <= L.rest_cap;
+  ProfScope ps0(pr.ra == 0 ? PROF_MSM_ACCUM_AFFINE : -1, st);  // small inputs: no pair rounds, this is the dominant kernel
+  with_bool(pr.ra == 0, [&](auto ind) {
+    with_bool(tmax <= accum_quad_max, [&](auto quad) {
+      constexpr bool IND = decltype(ind)::value, QUAD = decltype(quad)::value;
+      const dim3 grid(cdiv((QUAD ? 4 : 1) * tmax, EC_TPB)), grid1(cdiv(tmax, EC_TPB));
+      const size_t lds = QUAD ? EC_LDS_Q : EC_LDS;
+      if (accum_fast) {
+        DVP_LAUNCH((k_accum_affine_fast<IND, QUAD>), grid, dim3(EC_TPB), lds, st, pr.pts_in, b.items, pc[cur], po[cur], po[nxt], nk, p.K, b.bufA,
+                   sign_mask, b.rest_n, b.rest_list);
+        DVP_LAUNCH((k_accum_affine_rest<IND>), grid1, dim3(EC_TPB), EC_LDS, st, pr.pts_in, b.items, pc[cur], po[cur], po[nxt], nk, p.K, b.bufA,
+                   sign_mask, b.rest_n, b.rest_list);
+      } else
+        DVP_LAUNCH((k_accum_affine<IND, QUAD>), grid, dim3(EC_TPB), lds, st, pr.pts_in, b.items, pc[cur], po[cur], po[nxt], nk, p.K, b.bufA, sign_mask);
+    });
+  });
+  ps0.stop();
+  cur = nxt;
+  size_t cap = tmax;
+  Ld *in = b.bufA, *outb = b.bufB;
+  for (uint64_t left = (rem_max + p.K - 1) / p.K; left > 1; left = (left + p.K - 1) / p.K) {
+    nxt = (cur + 1) % 3;
+    DVP_TRY(scan_exclusive_div(pc[cur], p.K, pc[nxt], po[nxt], nk, b.bsum, st));
+    tmax = cap / p.K + nk + 1;
+    // the LAST level of a small MSM (every bucket ends with one task of at most K partial sums, typically one or two): rows of 16
+    // lanes when the tasks fit ACCUM_HEX_MAX (measured at 2^16 points)
+    if (left <= p.K && tmax <= accum_hex_max)
+      DVP_LAUNCH(k_accum_proj<16>, dim3(cdiv(16 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
+    else if (tmax <= accum_quad_max)
+      DVP_LAUNCH(k_accum_proj<4>, dim3(cdiv(4 * tmax, EC_TPB)), dim3(EC_TPB), EC_LDS_Q, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
+    else
+      DVP_LAUNCH(k_accum_proj<1>, dim3(cdiv(tmax, EC_TPB)), dim3(EC_TPB), EC_LDS, st, in, pc[cur], po[cur], po[nxt], nk, p.K, outb);
+    cap = tmax;
+    cur = nxt;
+    std::swap(in, outb);
+  }
+  DVP_LAUNCH(k_bucket_gather, dim3(cdiv(nk, 256)), dim3(256), 0, st, in, pc[cur], po[cur], nk, b.bkt);
   return DVP_OK;
+}
+
+// n == 0: the point at infinity.  The two flavours differ on purpose: the deferred one must not touch the host.
+static int msm_empty(const MsmOut& out, hipStream_t st) {
+  DVP_HIP(hipMemsetAsync(out.d_out_xy, 0, 64, st));
+  if (out.d_out_enc) DVP_HIP(hipMemsetAsync(out.d_out_enc, 0, 30, st));
+  if (out.d_err_defer) {
+    DVP_HIP(hipMemsetAsync(out.d_out_inf, 0, 4, st));
+    DVP_HIP(hipMemsetAsync(out.d_out_inf, 1, 1, st));  // little-endian u32 1
+    DVP_HIP(hipMemsetAsync(out.d_err_defer, 0xff, 8, st));
+    return DVP_OK;
+  }
+  if (out.h_copy) DVP_HIP(hipMemcpyAsync(out.h_copy, out.d_copy, out.copy_bytes, hipMemcpyDeviceToHost, st));
+  uint32_t one = 1;
+  DVP_HIP(hipMemcpyAsync(out.d_out_inf, &one, 4, hipMemcpyHostToDevice, st));
+  DVP_HIP(hipStreamSynchronize(st));
+  return DVP_OK;
+}
+
+// fx == nullptr: one-shot MSM over (d_scalars, d_bases).  fx != nullptr: fixed-base mode, the scalars
+// d_scalars[0..n) belong to bases i0 .. i0+n of the pre-rotated table and d_inf is already offset by i0.
+static int msm_core(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, const MsmFixedCtx* fx, uint32_t i0, const MsmOut& out,
+                    hipStream_t st) {
+  if (n == 0) return msm_empty(out, st);
+  if (n > (1u << 27)) return DVP_EINVAL;
+  MsmRun m{(const uint32_t*)d_scalars, (const uint8_t*)d_inf, fx ? fx->table : (const Aff*)d_bases, n, fx, i0, (fx && fx->signed_digits) ? ITEM_NEG : 0u, st};
+  m.p = msm_plan(n, fx);
+  {  // entry positions and pre-rotated table indices are 32-bit (0xffffffff = "no partner" in a slot descriptor)
+    const uint64_t tab = fx ? (uint64_t)fx->rows() * fx->n_total : (uint64_t)n;
+    if ((uint64_t)m.p.e_max >= 0xfffffff0ull || tab >= (m.sign_mask ? 0x7ffffff0ull : 0xfffffff0ull)) return DVP_EINVAL;
+  }
+  DVP_HIP(hipGetDevice(&m.dev));
+  if (m.dev < 0 || m.dev >= MSM_MAX_DEVICES) return DVP_EINVAL;
+  DVP_TRY(msm_set_lds_limits(m.dev));
+  m.tn = tune();
+  m.ws_slots = m.tn.msm_ws_slots >= 1 && m.tn.msm_ws_slots <= MSM_WS_SLOTS ? (int)m.tn.msm_ws_slots : 1;
+  m.L = msm_layout(n, m.p, fx, m.tn);
+  std::unique_lock<std::mutex> g;  // the workspace is this call's until it returns
+  DVP_TRY(msm_acquire_workspace(m.dev, st, m.ws_slots, m.L.bytes, g, &m.ws));
+  m.b = msm_carve(n, m.p, fx, m.L, m.ws->p);
+  ProfScope ps_total(PROF_MSM_TOTAL, st);
+  DVP_TRY(m.sort());
+  DVP_TRY(gf_sqr_tables(&m.Tsq, st));
+  PairRounds pr(m);
+  DVP_TRY(pr.init());
+  DVP_TRY(pr.begin());   // the first round where it is certain, then the host learns the largest bucket and settles the number of rounds
+  DVP_TRY(pr.finish());  // the other rounds
+  DVP_TRY(m.reduce_leftovers(pr));
+  m.merge_and_tail(out);
+  ps_total.stop();
+  DVP_HIP(hipGetLastError());
+  m.ws->ctrl_clean = true;  // the tail kernel is enqueued: it resets the control words
+  return out.d_err_defer ? m.complete_deferred() : m.complete(out);
 }
 
 // d_pts: n affine points `pt_stride_bytes` apart (>= 64, a multiple of 16), d_inf32: n flags (u32, `inf_stride` words apart) -> their sum
@@ -2761,22 +2820,17 @@ int msm_join_points_dev(const void* d_a_xy, const void* d_a_inf, const unsigned 
   return DVP_OK;
 }
 
-int msm_affine_dev(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, void* d_out_xy,
-                   void* d_out_inf, hipStream_t st) {
-  return msm_core(d_scalars, d_bases, d_inf, n, nullptr, 0, d_out_xy, d_out_inf, st);
+int msm_affine_dev(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, const MsmOut& out, hipStream_t st) {
+  return msm_core(d_scalars, d_bases, d_inf, n, nullptr, 0, out, st);
 }
 
 // ---- fixed-base contexts (the prover's SRS vectors) -----------------------------------------------
 // range_hint = number of bases a typical call will cover (the per-GPU shard): the shared window size c
 // minimises an empirical cost in field multiplications (pair additions + a per-bucket term, see below)
-void msm_fixed_destroy(MsmFixedCtx* c);
 // Table flavours: the default is aligned windows of SIGNED binary digits over W rows 2^(o_w) P (768 B per base at W = 12: 4.8 GB for
 // both SRS vectors of a 2^20-constraint prover); DVP_MSM_ALIGNED_SIGNED = 0 selects round 1-2's aligned tau-adic windows over rows
 // tau^(o_w) P instead (one window and twice the buckets more: 24.6 against 23.5 ms per proof in round 3) -- kept because it shares
-// its recode, merge and Frobenius tail with the one-shot MSM and is the independent cross-check of the signed flavour in the
-// tests.  (Rounds 2-3 also carried two SLIDING-window flavours over a multiple of every base for every digit position, 94-97 GB
-// of tables at 2^20; the signed aligned windows matched their speed at a twentieth of the memory -- 23.54 against 23.57 / 23.98 ms
-// -- and they were removed in round 4 together with their recoders, table builders and test matrix.)
+// its recode, merge and Frobenius tail with the one-shot MSM and is the independent cross-check of the signed flavour in the tests.
 // window size, window count and sort split of a context that typically serves `range_hint` bases per call -- everything about a
 // context that does not need the device (the table-budget planner reads the row count from here)
 static void msm_fixed_settle(MsmFixedCtx* c, size_t range_hint) {
@@ -2787,27 +2841,20 @@ static void msm_fixed_settle(MsmFixedCtx* c, size_t range_hint) {
   // constraints: 2^18 buckets beat 2^16, 2^17, 2^19 and 2^20 for every shard from 0.26 M to 4.2 M pairs of the tau-adic aligned
   // windows (2^20 wins from ~8 M pairs); the signed windows run the same model over their own entry and bucket counts
   // (ceil(234 / c) entries, 2^(c-1) buckets)
-  if (signed_aligned) {
-    for (int cc = 8; cc <= FX_C_MAX + 1; ++cc) {
-      MsmFixedCtx probe;
-      probe.set_c_signed(cc);
-      if (probe.c != cc) continue;  // all windows narrow: the same plan as cc - 1
-      const int kb = cc - 1;
-      const double per_scalar = (double)probe.W;
-      double cost = per_scalar * (double)range_hint * 5.6 + 10.0 * (double)(1u << kb) + (kb > 18 ? 25.0 * (double)((1u << kb) - (1u << 18)) : 0.0);
-      if (cost < best) { best = cost; best_c = cc; }
-    }
-    if (tune().msm_fixed_c >= 8 && tune().msm_fixed_c <= FX_C_MAX + 1) best_c = (int)tune().msm_fixed_c;
-    c->set_c_signed(best_c);
-  } else {
-    for (int cc = 8; cc <= FX_C_MAX; ++cc) {
-      const double per_scalar = (double)((234 + cc - 1) / cc);
-      double cost = per_scalar * (double)range_hint * 5.6 + 10.0 * (double)(1u << cc) + (cc > 18 ? 25.0 * (double)((1u << cc) - (1u << 18)) : 0.0);
-      if (cost < best) { best = cost; best_c = cc; }
-    }
-    if (tune().msm_fixed_c >= 8 && tune().msm_fixed_c <= FX_C_MAX) best_c = (int)tune().msm_fixed_c;
-    c->set_c(best_c);
+  // entries per scalar (windows that carry digits) and key bits -> cost
+  auto cost_of = [range_hint](int windows, int kb) {
+    return (double)windows * (double)range_hint * 5.6 + 10.0 * (double)(1u << kb) + (kb > 18 ? 25.0 * (double)((1u << kb) - (1u << 18)) : 0.0);
+  };
+  const int c_top = signed_aligned ? FX_C_MAX + 1 : FX_C_MAX;
+  for (int cc = 8; cc <= c_top; ++cc) {
+    MsmFixedCtx probe;
+    if (signed_aligned) probe.set_c_signed(cc);
+    if (signed_aligned && probe.c != cc) continue;  // all windows narrow: the same plan as cc - 1
+    const double cost = signed_aligned ? cost_of(probe.W, cc - 1) : cost_of((234 + cc - 1) / cc, cc);
+    if (cost < best) { best = cost; best_c = cc; }
   }
+  if (tune().msm_fixed_c >= 8 && tune().msm_fixed_c <= c_top) best_c = (int)tune().msm_fixed_c;
+  if (signed_aligned) c->set_c_signed(best_c); else c->set_c(best_c);
   const int kb = c->key_bits();
   c->hi_bits = kb / 2;  // even split: both levels have <= 2^10 bins and use the LDS-staged scatters
   if (int h = (int)tune().fx_hi; h >= 0 && h <= 10 && kb - h <= 15 && kb - h >= 1) c->hi_bits = h;
@@ -2876,24 +2923,10 @@ void msm_fixed_destroy(MsmFixedCtx* c) {
   if (c->table) (void)hipFree(c->table);
   delete c;
 }
-// partial sum over bases [lo, hi) of the context; d_scalars / d_inf point at element lo
-int msm_fixed_dev(const MsmFixedCtx* c, const void* d_scalars, const void* d_inf, uint32_t lo, uint32_t hi, void* d_out_xy,
-                  void* d_out_inf, hipStream_t st) {
+// partial sum over bases [lo, hi) of the context; d_scalars / d_inf point at element lo (what `out` may ask for: host_api.h, MsmOut)
+int msm_fixed_dev(const MsmFixedCtx* c, const void* d_scalars, const void* d_inf, uint32_t lo, uint32_t hi, const MsmOut& out, hipStream_t st) {
   if (!c || lo > hi || hi > c->n_total) return DVP_EINVAL;
-  return msm_core(d_scalars, nullptr, d_inf, hi - lo, c, lo, d_out_xy, d_out_inf, st);
-}
-// the same with the result's 30-byte encoding written to d_out_enc by the tail kernel itself
-// (h_copy, d_copy, copy_bytes): a device block copied to pinned host memory before the call's own final synchronisation
-// d_err_defer != nullptr: deferred completion (see msm_core) -- returns once everything is enqueued
-int msm_fixed_dev_enc(const MsmFixedCtx* c, const void* d_scalars, const void* d_inf, uint32_t lo, uint32_t hi, void* d_out_xy,
-                      void* d_out_inf, void* d_out_enc, void* h_copy, const void* d_copy, size_t copy_bytes, hipStream_t st,
-                      unsigned long long* d_err_defer) {
-  if (!c || lo > hi || hi > c->n_total) return DVP_EINVAL;
-  return msm_core(d_scalars, nullptr, d_inf, hi - lo, c, lo, d_out_xy, d_out_inf, st, d_out_enc, h_copy, d_copy, copy_bytes, d_err_defer);
-}
-int msm_affine_dev_enc(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf,
-                       void* d_out_enc, void* h_copy, const void* d_copy, size_t copy_bytes, hipStream_t st, unsigned long long* d_err_defer) {
-  return msm_core(d_scalars, d_bases, d_inf, n, nullptr, 0, d_out_xy, d_out_inf, st, d_out_enc, h_copy, d_copy, copy_bytes, d_err_defer);
+  return msm_core(d_scalars, nullptr, d_inf, hi - lo, c, lo, out, st);
 }
 
 }  // namespace dvp
@@ -2935,7 +2968,7 @@ extern "C" int dvp_table_plan(size_t size0, size_t size1, uint64_t budget_bytes,
 extern "C" int dvp_msm_affine_dev(const void* d_scalars, const void* d_bases_xy, const void* d_bases_inf, size_t n,
                                   void* d_out_xy, void* d_out_inf, void* stream) {
   if ((n && (!d_scalars || !d_bases_xy)) || !d_out_xy || !d_out_inf) return DVP_EINVAL;
-  return msm_affine_dev(d_scalars, d_bases_xy, d_bases_inf, n, d_out_xy, d_out_inf, (hipStream_t)stream);
+  return msm_affine_dev(d_scalars, d_bases_xy, d_bases_inf, n, MsmOut{d_out_xy, d_out_inf}, (hipStream_t)stream);
 }
 
 // sum of n partial points laid out as n records of 80 bytes: x || y (64 B) + u32 infinity flag + pad -- the record a rank
@@ -3096,9 +3129,6 @@ extern "C" int dvp_debug_recode_signed(const uint64_t* scalars, size_t n, int c,
   return DVP_OK;
 }
 
-namespace dvp {
-int points_check_strict(const void* d_xy, const void* d_inf, size_t n, hipStream_t st);  // codec.hip: a no-op unless strict mode is on
-}
 extern "C" int dvp_msm_affine(const uint64_t* scalars, const uint64_t* bases_xy, const uint8_t* bases_inf, size_t n,
                               uint64_t out_xy[8], int* out_is_infinity) {
   if ((n && (!scalars || !bases_xy)) || !out_xy || !out_is_infinity) return DVP_EINVAL;
@@ -3115,7 +3145,7 @@ extern "C" int dvp_msm_affine(const uint64_t* scalars, const uint64_t* bases_xy,
     DVP_HIP(hipMemcpy(di.p, bases_inf, n, hipMemcpyHostToDevice));
   }
   DVP_TRY(points_check_strict(db.p, di.p, n, 0));
-  DVP_TRY(msm_affine_dev(ds.p, db.p, di.p, n, dout.p, (char*)dout.p + 64, 0));
+  DVP_TRY(msm_affine_dev(ds.p, db.p, di.p, n, MsmOut{dout.p, (char*)dout.p + 64}, 0));
   uint32_t inf;
   DVP_HIP(hipMemcpy(out_xy, dout.p, 64, hipMemcpyDeviceToHost));
   DVP_HIP(hipMemcpy(&inf, (char*)dout.p + 64, 4, hipMemcpyDeviceToHost));
@@ -3130,7 +3160,6 @@ struct dvp_msm_ctx {
   size_t n = 0;
 };
 
-extern "C" void dvp_msm_ctx_destroy(dvp_msm_ctx* c);
 extern "C" int dvp_msm_ctx_create(const uint64_t* bases_xy, const uint8_t* bases_inf, size_t n, size_t range_hint, dvp_msm_ctx** out) {
   if (!bases_xy || !out || !n || n >= ((size_t)1 << 27)) return DVP_EINVAL;
   if (!range_hint || range_hint > n) range_hint = n;
@@ -3164,7 +3193,7 @@ extern "C" uint64_t dvp_msm_ctx_table_bytes(const dvp_msm_ctx* c, int* signed_wi
 // sum_{i in [lo,hi)} scalars[i - lo] * base[i]; d_scalars holds hi - lo canonical scalars (device)
 extern "C" int dvp_msm_ctx_run_dev(dvp_msm_ctx* c, const void* d_scalars, size_t lo, size_t hi, void* d_out_xy, void* d_out_inf, void* stream) {
   if (!c || !d_scalars || !d_out_xy || !d_out_inf || lo > hi || hi > c->n) return DVP_EINVAL;
-  return msm_fixed_dev(c->fx, d_scalars, c->d_inf + lo, (uint32_t)lo, (uint32_t)hi, d_out_xy, d_out_inf, (hipStream_t)stream);
+  return msm_fixed_dev(c->fx, d_scalars, c->d_inf + lo, (uint32_t)lo, (uint32_t)hi, MsmOut{d_out_xy, d_out_inf}, (hipStream_t)stream);
 }
 extern "C" int dvp_msm_ctx_run(dvp_msm_ctx* c, const uint64_t* scalars, size_t lo, size_t hi, uint64_t out_xy[8], int* out_is_infinity) {
   if (!c || !scalars || !out_xy || !out_is_infinity || lo > hi || hi > c->n) return DVP_EINVAL;
@@ -3172,7 +3201,7 @@ extern "C" int dvp_msm_ctx_run(dvp_msm_ctx* c, const uint64_t* scalars, size_t l
   DVP_TRY(ds.alloc((hi - lo) * 32));
   DVP_TRY(dout.alloc(80));
   if (hi > lo) DVP_HIP(hipMemcpy(ds.p, scalars, (hi - lo) * 32, hipMemcpyHostToDevice));
-  DVP_TRY(msm_fixed_dev(c->fx, ds.p, c->d_inf + lo, (uint32_t)lo, (uint32_t)hi, dout.p, (char*)dout.p + 64, 0));
+  DVP_TRY(msm_fixed_dev(c->fx, ds.p, c->d_inf + lo, (uint32_t)lo, (uint32_t)hi, MsmOut{dout.p, (char*)dout.p + 64}, 0));
   uint32_t inf;
   DVP_HIP(hipMemcpy(out_xy, dout.p, 64, hipMemcpyDeviceToHost));
   DVP_HIP(hipMemcpy(&inf, (char*)dout.p + 64, 4, hipMemcpyDeviceToHost));

@@ -28,15 +28,10 @@
 
 #include "common.h"
 #include "k233.cuh"
+#include "host_api.h"
 
 namespace dvp {
 
-int gf_sqr_tables(GfSqrTables* out, hipStream_t st);
-int points_check_strict(const void* d_xy, const void* d_inf, size_t n, hipStream_t st);
-int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out, hipStream_t st);
-int decode_dev(const uint8_t* d_enc, size_t n, Aff* d_out, uint8_t* d_inf, hipStream_t st);
-int points_mul_dev(const void* d_scalars, size_t n_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf,
-                   void* d_summary, hipStream_t st);
 
 constexpr int SEG_TPB = 256;
 constexpr unsigned SEG_LDS = (SEG_TPB / 64) * GF_LDSK_BYTES_PER_WAVE;

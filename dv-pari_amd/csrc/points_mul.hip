@@ -22,13 +22,10 @@
 #include "common.h"
 #include "k233.cuh"
 #include "tau.cuh"
+#include "host_api.h"
 
 namespace dvp {
 
-int gf_sqr_tables(GfSqrTables* out, hipStream_t st);
-int points_check_strict(const void* d_xy, const void* d_inf, size_t n, hipStream_t st);
-int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out, hipStream_t st);
-int decode_dev(const uint8_t* d_enc, size_t n, Aff* d_out, uint8_t* d_inf, hipStream_t st);
 
 constexpr int PM_DEFAULT_W = 3;  // the fastest of the three at 2^20 pairs (tools/README.md)
 

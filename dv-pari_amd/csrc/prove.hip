@@ -28,51 +28,10 @@
 #include "common.h"
 #include "ecfft_internal.h"
 #include "fr_wire.cuh"
+#include "host_api.h"
 #include "k233.cuh"
 
-extern "C" int dvp_ecfft_create(uint32_t log_n, int shifted, uint32_t base_log, dvp_ecfft** out);
-extern "C" void dvp_ecfft_destroy(dvp_ecfft* c);
-int ecfft_device_consts(dvp_ecfft* c);
-
 namespace dvp {
-
-int msm_affine_dev(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, void* d_out_xy,
-                   void* d_out_inf, hipStream_t st);
-int decode_dev(const uint8_t* d_enc, size_t n, Aff* d_out, uint8_t* d_inf, hipStream_t st);
-int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out, hipStream_t st);
-int encode_point_dev(const Aff* d_pt, const uint32_t* d_inf32, uint8_t* d_out, hipStream_t st);
-int points_check_strict(const void* d_xy, const void* d_inf, size_t n, hipStream_t st);  // codec.hip: a no-op unless strict mode is on
-int batch_inverse_dev(Fr* d, size_t n, hipStream_t st);
-int b3_leaves_dev(const uint8_t* d_data, size_t len, uint64_t chunk_base, uint32_t* d_cvs, hipStream_t st);  // blake3_tree.hip
-int b3_single_chunk_dev(const uint8_t* d_data, size_t len, uint32_t* d_out32, hipStream_t st);
-size_t b3_reduce_tmp_bytes(size_t n);
-int b3_reduce_dev(uint32_t* d_cvs, size_t n, uint32_t* d_tmp, uint32_t* d_out32, hipStream_t st);
-struct ChCsr {  // circuit_hash.hip: row pointers and coefficient ids of the three matrices
-  const uint32_t* rp[3];
-  const uint32_t* cid[3];
-  uint32_t n_rows[3];
-};
-int circuit_hash_dev(const ChCsr& mats, const uint64_t nnz[3], const Fr* coeffs_m, uint32_t n0, const Fr* dom_m, uint32_t m, uint32_t k,
-                     long long window_chunks, uint8_t out[32], hipStream_t st);
-struct MsmFixedCtx;
-int msm_fixed_create(const Aff* d_bases, uint32_t n_total, size_t range_hint, MsmFixedCtx** out);
-int msm_sum_points_dev(const void* d_pts, uint32_t pt_stride_bytes, const void* d_inf32, uint32_t n, uint32_t inf_stride, void* d_out_xy,
-                       void* d_out_inf, hipStream_t st);
-void msm_fixed_destroy(MsmFixedCtx* c);
-int msm_fixed_info(const MsmFixedCtx* c, int* cbits, int* windows);
-uint64_t msm_fixed_table_bytes(const MsmFixedCtx* c, int* signed_flavour);
-const void* msm_fixed_table_ptr(const MsmFixedCtx* c);
-int msm_fixed_dev_enc(const MsmFixedCtx* c, const void* d_scalars, const void* d_inf, uint32_t lo, uint32_t hi, void* d_out_xy,
-                      void* d_out_inf, void* d_out_enc, void* h_copy, const void* d_copy, size_t copy_bytes, hipStream_t st,
-                      unsigned long long* d_err_defer);
-int msm_affine_dev_enc(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf,
-                       void* d_out_enc, void* h_copy, const void* d_copy, size_t copy_bytes, hipStream_t st, unsigned long long* d_err_defer);
-int msm_fixed_dev(const MsmFixedCtx* c, const void* d_scalars, const void* d_inf, uint32_t lo, uint32_t hi, void* d_out_xy,
-                  void* d_out_inf, hipStream_t st);
-int msm_fixed_rows_for(size_t count);
-int msm_join_points_dev(const void* d_a_xy, const void* d_a_inf, const unsigned long long* d_a_err, const void* d_b_xy, const void* d_b_inf,
-                        const unsigned long long* d_b_err, uint32_t covered, void* d_out_xy, void* d_out_inf, void* d_out_enc,
-                        unsigned long long* d_err_out, hipStream_t st);
 
 // ---- domain tables from the isogeny chain ---------------------------------------------------------
 // For S = even leaves (D) of the 2m-leaf tree, Z_S = U - c0 V with (U,V) the projective image under
@@ -533,7 +492,6 @@ static Fr host_vanish(const dvp_prover* p, int which, const Fr& x_m) {
 
 static int prover_init(dvp_prover* p, uint32_t log2_m, uint32_t n_public, uint32_t n_wires);
 static void shards_release(dvp_prover* p);
-extern "C" void dvp_prover_destroy(dvp_prover* p);
 
 extern "C" int dvp_prover_create(uint32_t log2_m, uint32_t n_public, uint32_t n_wires, dvp_prover** out) {
   // 2^24 constraints is the largest size the MSM index ranges cover (4m bases x 14 pre-rotated windows must stay below
@@ -905,8 +863,6 @@ static bool prover_ready(dvp_prover* p) {
 // phase 1 (src/proving.rs:434-508): assignment -> a,b,c',i -> extend -> q2; leaves SA = [w | q2].
 // d_assignment: n_wires canonical Fr = [1, public.., private..] already in HBM.
 static uint32_t prover_n_ext(const dvp_prover* p);
-extern "C" int dvp_prove_extend_vectors(dvp_prover* p, uint32_t mask, void* stream);
-extern "C" int dvp_prove_quotient(dvp_prover* p, void* stream);
 extern "C" int dvp_prove_begin(dvp_prover* p, const void* d_assignment, void* stream) {
   return dvp_prove_begin_partial(p, d_assignment, 1, stream);
 }
@@ -1045,6 +1001,7 @@ static int prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, vo
   const size_t fixed_min = (size_t)(tune().msm_fixed_min > 0 ? tune().msm_fixed_min : 1);
   hipStream_t st = (hipStream_t)stream;
   void* h_copy = d_out_enc && !d_err_defer ? p->fin_host : nullptr;
+  const MsmOut out{d_out_xy, d_out_inf, d_out_enc, h_copy, p->abir0, FIN_BYTES, d_err_defer};
   if (p->table_budget == UINT64_MAX) {
     if (hi - lo >= fixed_min && total < ((size_t)1 << 27) && !p->table_refused[which]) {
       if (p->fx[which] && (lo < p->fx_lo[which] || hi > p->fx_hi[which])) {
@@ -1060,12 +1017,11 @@ static int prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, vo
       }
       if (rc == DVP_OK) {
         const size_t o = p->fx_lo[which];
-        return msm_fixed_dev_enc(p->fx[which], sc + lo, inf + lo, (uint32_t)(lo - o), (uint32_t)(hi - o), d_out_xy, d_out_inf, d_out_enc, h_copy, p->abir0,
-                                 FIN_BYTES, st, d_err_defer);
+        return msm_fixed_dev(p->fx[which], sc + lo, inf + lo, (uint32_t)(lo - o), (uint32_t)(hi - o), out, st);
       }
       p->table_refused[which] = true;
     }
-    return msm_affine_dev_enc(sc + lo, bs + lo, inf + lo, hi - lo, d_out_xy, d_out_inf, d_out_enc, h_copy, p->abir0, FIN_BYTES, st, d_err_defer);
+    return msm_affine_dev(sc + lo, bs + lo, inf + lo, hi - lo, out, st);
   }
   // Under a budget the table is the planned prefix [0, cov) of the WHOLE vector, whatever range is asked for: [lo, min(hi, cov))
   // comes out of it, the rest of [lo, hi) out of the one-shot MSM, and k_join_points adds the two (a mixed MSM).
@@ -1092,8 +1048,7 @@ static int prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, vo
     if (rc == DVP_ENOMEM) {
       p->table_refused[which] = true;
     } else if (a == hi) {
-      return msm_fixed_dev_enc(p->fx[which], sc + lo, inf + lo, (uint32_t)lo, (uint32_t)hi, d_out_xy, d_out_inf, d_out_enc, h_copy, p->abir0, FIN_BYTES, st,
-                               d_err_defer);
+      return msm_fixed_dev(p->fx[which], sc + lo, inf + lo, (uint32_t)lo, (uint32_t)hi, out, st);
     } else {
       // both halves with deferred completion on the caller's stream (the second one queues behind the first in the same workspace),
       // then the join: it writes what a single MSM's tail kernel would have -- point, encoding, range word -- so the call ends as
@@ -1101,8 +1056,8 @@ static int prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, vo
       char* mx = p->mix;
       unsigned long long* e2 = (unsigned long long*)(mx + MIX_OFF_ERR);
       unsigned long long* e_out = d_err_defer ? d_err_defer : (unsigned long long*)(mx + MIX_OFF_ERR_OUT);
-      DVP_TRY(msm_fixed_dev_enc(p->fx[which], sc + lo, inf + lo, (uint32_t)lo, (uint32_t)a, mx, mx + MIX_OFF_INF, nullptr, nullptr, nullptr, 0, st, e2));
-      rc = msm_affine_dev_enc(sc + a, bs + a, inf + a, hi - a, mx + 64, mx + MIX_OFF_INF + 4, nullptr, nullptr, nullptr, 0, st, e2 + 1);
+      DVP_TRY(msm_fixed_dev(p->fx[which], sc + lo, inf + lo, (uint32_t)lo, (uint32_t)a, MsmOut{mx, mx + MIX_OFF_INF, nullptr, nullptr, nullptr, 0, e2}, st));
+      rc = msm_affine_dev(sc + a, bs + a, inf + a, hi - a, MsmOut{mx + 64, mx + MIX_OFF_INF + 4, nullptr, nullptr, nullptr, 0, e2 + 1}, st);
       if (rc == DVP_OK)
         rc = msm_join_points_dev(mx, mx + MIX_OFF_INF, e2, mx + 64, mx + MIX_OFF_INF + 4, e2 + 1, (uint32_t)(a - lo), d_out_xy, d_out_inf, d_out_enc, e_out, st);
       if (rc != DVP_OK) {
@@ -1123,7 +1078,7 @@ static int prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, vo
       return DVP_OK;
     }
   }
-  return msm_affine_dev_enc(sc + lo, bs + lo, inf + lo, hi - lo, d_out_xy, d_out_inf, d_out_enc, h_copy, p->abir0, FIN_BYTES, st, d_err_defer);
+  return msm_affine_dev(sc + lo, bs + lo, inf + lo, hi - lo, out, st);
 }
 extern "C" int dvp_prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, void* d_out_xy, void* d_out_inf, void* stream) {
   if (p && (which == 0 || which == 1) && d_out_xy == (void*)(p->pts + which)) p->enc_fused[which] = false;  // the point changes, its encoding does not follow
@@ -1247,9 +1202,9 @@ static int mgpu_msm(dvp_prover* p, int which, void* d_out_xy, void* d_out_inf, h
         uint32_t* out = sh.out + 20 * which;
         if (cnt) DVP_HIP(hipMemcpyPeerAsync(sh.sc[which], sh.device, sc + sh.lo[which], p->home_device, cnt * sizeof(Fr), sh.st));
         if (sh.fx[which])
-          DVP_TRY(msm_fixed_dev(sh.fx[which], sh.sc[which], sh.inf[which], 0, (uint32_t)cnt, out, out + 16, sh.st));
+          DVP_TRY(msm_fixed_dev(sh.fx[which], sh.sc[which], sh.inf[which], 0, (uint32_t)cnt, MsmOut{out, out + 16}, sh.st));
         else
-          DVP_TRY(msm_affine_dev(sh.sc[which], sh.bases[which], sh.inf[which], cnt, out, out + 16, sh.st));
+          DVP_TRY(msm_affine_dev(sh.sc[which], sh.bases[which], sh.inf[which], cnt, MsmOut{out, out + 16}, sh.st));
         DVP_HIP(hipMemcpyAsync(&recs[k], out, 68, hipMemcpyDeviceToHost, sh.st));
         DVP_HIP(hipStreamSynchronize(sh.st));
         return DVP_OK;

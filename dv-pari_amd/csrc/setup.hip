@@ -24,17 +24,10 @@
 
 #include "common.h"
 #include "ecfft_internal.h"
+#include "host_api.h"
 #include "k233.cuh"
 
-extern "C" int dvp_ecfft_create(uint32_t log_n, int shifted, uint32_t base_log, dvp_ecfft** out);
-extern "C" void dvp_ecfft_destroy(dvp_ecfft* c);
-extern "C" int dvp_ecfft_exit_dev(dvp_ecfft* c, const void* d_evals, void* d_out, void* stream);
-int ecfft_domain_tables_dev(dvp_ecfft* t, int which, Fr* d_bar_weights, Fr* d_zinv_other, hipStream_t st);
-
 namespace dvp {
-int batch_inverse_dev(Fr* d, size_t n, hipStream_t st);
-int mulgen_dev(const void* d_scalars, size_t n, Aff* d_out, uint8_t* d_inf, hipStream_t st);
-int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out, hipStream_t st);
 
 namespace {
 constexpr int TPB = 256;
@@ -474,9 +467,6 @@ extern "C" int dvp_setup_cache_dir(const uint64_t tau[4], const uint64_t delta[4
 }
 
 // ---- FFTR tree files from a regenerated tree, and prover_prepares_precomputes (src/proving.rs:225-325) ----------------------
-extern "C" int dvp_debug_ecfft_layer(const dvp_ecfft* c, uint32_t d, uint64_t* out);
-extern "C" int dvp_debug_ecfft_matrices(dvp_ecfft* c, int to_even, int which, uint64_t* out);
-extern "C" int dvp_ecfft_enter_dev(dvp_ecfft* c, const void* d_coeffs, void* d_out, void* stream);
 
 namespace {
 // Sections 0-2 of an FFTree as the reference holds them (what read_minimal_fftree_from_file loads, src/tree_io.rs:353-433):

@@ -32,16 +32,11 @@
 #include "codec.cuh"
 #include "common.h"
 #include "fr.cuh"
+#include "host_api.h"
 #include "k233.cuh"
 #include "tau.cuh"
 
 namespace dvp {
-
-int gen_table(const Aff** out, hipStream_t st);
-int gf_sqr_tables(GfSqrTables* out, hipStream_t st);
-int codec_rule_now();
-int msm_affine_dev_enc(const void* d_scalars, const void* d_bases, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf,
-                       void* d_out_enc, void* h_copy, const void* d_copy, size_t copy_bytes, hipStream_t st, unsigned long long* d_err_defer);
 
 constexpr uint32_t VERIFY_B3_LEVELS = 8;
 constexpr uint32_t VERIFY_MAX_PUBLIC = DVP_VERIFY_MAX_PUBLIC;
@@ -317,7 +312,7 @@ k_verify(const uint8_t* __restrict__ proofs, size_t n, const Fr* __restrict__ pu
 //   k_verify_rlc_prep   one lane per proof: the front half of k_verify, the coefficient, the bases, scalars and r_j u0_j
 //   k_rlc_sum_blocks    block partials of sum r_j u0_j (and of |W|)
 //   k_rlc_sum_final     one block: the G scalar, the G base (generator table, window 0, digit 1), |W|
-//   msm_affine_dev_enc  the one-shot MSM, deferred completion (its scalar-range word stays on the device)
+//   msm_affine_dev      the one-shot MSM, deferred completion (its scalar-range word stays on the device)
 //   k_rlc_check         report word and gate
 //   k_verify<true>      the per-lane check over the whole batch, unless the gate says the combination held
 
@@ -664,7 +659,7 @@ static int rlc_enqueue(const VerifyConsts& c, const uint8_t key[32], const void*
   DVP_LAUNCH(k_rlc_sum_final, dim3(1), dim3(RLC_SUM_TPB), 0, st, (const Fr*)part, (const uint32_t*)part_w, nparts, tab, sc + 2 * n,
                      bases + 2 * n, inf + 2 * n, n_w);
   DVP_HIP(hipGetLastError());
-  DVP_TRY(msm_affine_dev_enc(sc, bases, inf, 2 * n + 1, out_xy, out_inf, nullptr, nullptr, nullptr, 0, st, err));
+  DVP_TRY(msm_affine_dev(sc, bases, inf, 2 * n + 1, MsmOut{out_xy, out_inf, nullptr, nullptr, nullptr, 0, err}, st));
   DVP_LAUNCH(k_rlc_check, dim3(1), dim3(64), 0, st, (const uint32_t*)out_inf, (const unsigned long long*)err, (const uint32_t*)n_w, gate,
                      report, (uint32_t*)d_report);
   DVP_LAUNCH(k_verify<true>, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint8_t*)d_proofs, n,

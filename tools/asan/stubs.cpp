@@ -4,6 +4,7 @@
 
 #include "../../include/dvpari.h"
 #include "../../include/dvpari_internal.h"
+#include "../../dv-pari_amd/csrc/host_api.h"  // g_last_error_index is declared there; the other stand-ins are C ABI entries (dvpari.h)
 
 namespace dvp {
 thread_local int64_t g_last_error_index = -1;  // capi.cpp's in the product
