@@ -130,6 +130,7 @@ _SIGS = {
     "dvp_prover_set_table_budget": (C.c_int, [vp, C.c_uint64]),
     "dvp_prover_msm_coverage": (C.c_int, [vp, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "dvp_table_plan": (C.c_int, [sz, sz, C.c_uint64, C.POINTER(C.c_size_t * 2), C.POINTER(C.c_uint64 * 2)]),
+    "dvp_aff_share_plan": (C.c_int, [C.c_longlong, u32, C.c_uint64, C.c_uint64, C.c_uint64]),
     "dvp_prover_msm_partial": (C.c_int, [vp, C.c_int, sz, sz, vp, vp, vp]),
     "dvp_prove_challenge": (C.c_int, [vp, vp, vp, vp]),
     "dvp_prove_challenge_partial": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp]),

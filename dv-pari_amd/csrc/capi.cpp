@@ -57,6 +57,8 @@ static std::atomic<uint64_t> g_host_waits[2];
 void count_host_wait(int kind) { g_host_waits[kind & 1].fetch_add(1, std::memory_order_relaxed); }
 static std::atomic<uint64_t> g_later_rounds[2];
 void count_later_round(bool dense) { g_later_rounds[dense ? 1 : 0].fetch_add(1, std::memory_order_relaxed); }
+static std::atomic<uint64_t> g_rounds_inv[2];
+void count_round_inv(bool shared) { g_rounds_inv[shared ? 1 : 0].fetch_add(1, std::memory_order_relaxed); }
 
 // the launch census (common.h): name -> counter, filled while the library is loaded (the counters' own static initialisers call
 // census_register, so the registry is built on first use) and only read afterwards
@@ -121,6 +123,8 @@ static void tune_from_env(Tune& t) {
   t.msm_bucket_pairs_max = geti("DVP_MSM_BUCKET_PAIRS_MAX", t.msm_bucket_pairs_max);
   t.msm_aff_bmax = geti("DVP_MSM_AFF_BMAX", t.msm_aff_bmax);
   t.msm_aff_bmin = geti("DVP_MSM_AFF_BMIN", t.msm_aff_bmin);
+  t.msm_aff_share_inv = geti("DVP_MSM_AFF_SHARE_INV", t.msm_aff_share_inv);
+  t.msm_aff_share_min = geti("DVP_MSM_AFF_SHARE_MIN", t.msm_aff_share_min);
   t.ecfft_radix4 = geti("DVP_ECFFT_RADIX4", t.ecfft_radix4);
   t.ecfft_fold = geti("DVP_ECFFT_FOLD", t.ecfft_fold);
   t.msm_accum_fast = geti("DVP_MSM_ACCUM_FAST", t.msm_accum_fast);
@@ -163,7 +167,7 @@ static long long* tune_slot(const char* name) {
   dvp::Tune& t = dvp::tune();
   struct { const char* n; long long* v; } tab[] = {
       {"DVP_MSM_C", &t.msm_c}, {"DVP_MSM_K", &t.msm_k}, {"DVP_MSM_FIXED_C", &t.msm_fixed_c}, {"DVP_FX_HI", &t.fx_hi},
-      {"DVP_MSM_PROJ", &t.msm_proj}, {"DVP_MSM_AFF_MIN", &t.msm_aff_min}, {"DVP_MSM_HEX_MAX", &t.msm_hex_max}, {"DVP_MSM_ROUND_PIPELINE", &t.msm_round_pipeline}, {"DVP_MSM_ROUND_DENSE", &t.msm_round_dense}, {"DVP_MSM_SORT_FUSED", &t.msm_sort_fused}, {"DVP_MSM_BUCKET_PAIRS_MAX", &t.msm_bucket_pairs_max}, {"DVP_MSM_AFF_BMAX", &t.msm_aff_bmax}, {"DVP_MSM_AFF_BMIN", &t.msm_aff_bmin}, {"DVP_ECFFT_RADIX4", &t.ecfft_radix4}, {"DVP_ECFFT_FOLD", &t.ecfft_fold}, {"DVP_MSM_ACCUM_FAST", &t.msm_accum_fast}, {"DVP_MSM_TAIL_GROUPS", &t.msm_tail_groups}, {"DVP_MSM_ACCUM_HEX_MAX", &t.msm_accum_hex_max}, {"DVP_GF_INV_TABS", &t.gf_inv_tabs}, {"DVP_MSM_WS_SLOTS", &t.msm_ws_slots}, {"DVP_MSM_GATE_MIN", &t.msm_gate_min}, {"DVP_MSM_AFF_TPB", &t.msm_aff_tpb}, {"DVP_CACHE_REPLICAS", &t.cache_replicas},
+      {"DVP_MSM_PROJ", &t.msm_proj}, {"DVP_MSM_AFF_MIN", &t.msm_aff_min}, {"DVP_MSM_HEX_MAX", &t.msm_hex_max}, {"DVP_MSM_ROUND_PIPELINE", &t.msm_round_pipeline}, {"DVP_MSM_ROUND_DENSE", &t.msm_round_dense}, {"DVP_MSM_SORT_FUSED", &t.msm_sort_fused}, {"DVP_MSM_BUCKET_PAIRS_MAX", &t.msm_bucket_pairs_max}, {"DVP_MSM_AFF_BMAX", &t.msm_aff_bmax}, {"DVP_MSM_AFF_BMIN", &t.msm_aff_bmin}, {"DVP_MSM_AFF_SHARE_INV", &t.msm_aff_share_inv}, {"DVP_MSM_AFF_SHARE_MIN", &t.msm_aff_share_min}, {"DVP_ECFFT_RADIX4", &t.ecfft_radix4}, {"DVP_ECFFT_FOLD", &t.ecfft_fold}, {"DVP_MSM_ACCUM_FAST", &t.msm_accum_fast}, {"DVP_MSM_TAIL_GROUPS", &t.msm_tail_groups}, {"DVP_MSM_ACCUM_HEX_MAX", &t.msm_accum_hex_max}, {"DVP_GF_INV_TABS", &t.gf_inv_tabs}, {"DVP_MSM_WS_SLOTS", &t.msm_ws_slots}, {"DVP_MSM_GATE_MIN", &t.msm_gate_min}, {"DVP_MSM_AFF_TPB", &t.msm_aff_tpb}, {"DVP_CACHE_REPLICAS", &t.cache_replicas},
       {"DVP_MSM_QUAD_MAX", &t.msm_quad_max}, {"DVP_MSM_ACCUM_QUAD_MAX", &t.msm_accum_quad_max}, {"DVP_MSM_FIXED_MIN", &t.msm_fixed_min}, {"DVP_HORNER_MAX_PUB", &t.horner_max_pub}, {"DVP_FR_BI_SHAPE", &t.fr_bi_shape},
       {"DVP_MSM_ALIGNED_SIGNED", &t.msm_aligned_signed}, {"DVP_PROVE_HOST_TRANSCRIPT", &t.prove_host_transcript},
       {"DVP_TABLE_BUDGET_BYTES", &t.table_budget_bytes}, {"DVP_MSM_TABLE_REFUSE", &t.msm_table_refuse},
@@ -203,6 +207,8 @@ extern "C" void dvp_profile_reset(void) {
   dvp::g_host_waits[1] = 0;
   dvp::g_later_rounds[0] = 0;
   dvp::g_later_rounds[1] = 0;
+  dvp::g_rounds_inv[0] = 0;
+  dvp::g_rounds_inv[1] = 0;
   dvp::Census& c = dvp::census();
   std::lock_guard<std::mutex> gc(c.mu);
   for (auto& e : c.by_name) e.second->n.store(0, std::memory_order_relaxed);
@@ -242,6 +248,11 @@ extern "C" int dvp_profile_read(const char* name, double* total_ms, uint64_t* la
   if (!strcmp(name, "later_rounds_word") || !strcmp(name, "later_rounds_dense")) {  // launches since the last dvp_profile_reset
     *total_ms = 0;
     *launches = dvp::g_later_rounds[name[13] == 'd' ? 1 : 0].load();
+    return DVP_OK;
+  }
+  if (!strcmp(name, "rounds_inv_private") || !strcmp(name, "rounds_inv_shared")) {  // launches since the last dvp_profile_reset
+    *total_ms = 0;
+    *launches = dvp::g_rounds_inv[name[11] == 's' ? 1 : 0].load();
     return DVP_OK;
   }
   if (!strncmp(name, "launch:", 7)) {  // the launch census: launches of one variant since the last dvp_profile_reset

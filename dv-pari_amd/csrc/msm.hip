@@ -1334,11 +1334,43 @@ constexpr uint32_t AFF_BMAX = 136;
 // bmax_bmin: bits 0..7 = most slots per thread, bits 8..15 = fewest (a small round then runs on fewer threads, each sharing its
 // inversion among more additions: Tune::msm_aff_bmin)
 __device__ __forceinline__ uint32_t aff_slots_per_thread(uint32_t total, uint32_t cap, uint32_t bmax_bmin) {
-  const uint32_t bmax = bmax_bmin & 0xffu, bmin = (bmax_bmin >> 8) & 0xffu;
+  const uint32_t bmax = bmax_bmin & 0xffu, bmin = (bmax_bmin >> 8) & 0xffu;  // (bit 16: AFF_SHARE_INV, below)
   const uint32_t units = (total + cap - 1) / cap;  // slots per resident thread if the round were one chip-full
   const uint32_t R = (units + bmax - 1) / bmax;
   const uint32_t B = R ? (units + R - 1) / R : 1;
   return B < bmin ? bmin : B;
+}
+// ---- one inversion per WORKGROUP instead of one per wave (bit 16 of the kernel's bmax argument; Tune::msm_aff_share_inv) ----------
+// A SIMD pays an inversion per wave-instruction, not per lane: ~14 k of them per wave and launch, however few additions share them.
+// With the bit set the waves of a workgroup of 128 or 256 threads post their running products to an exchange area behind the table
+// regions, lane-wise products over the waves go up a tree (two waves form the pair products, one wave -- the INVERTING wave -- their
+// product), that wave alone runs the chain on the workgroup's product and sends the two half inverses back down, and every wave
+// recovers its own 1 / run with one more product: 3 + 2 + 4 wave-products and one chain per workgroup instead of four chains.  The
+// field inverse is exact, so the result is the same bits.  Everything between the barriers is workgroup-uniform control flow.
+// Exchange slots hold one Gf per lane of a wave as two rows of 64 x 16 B (conflict-free 128-bit accesses): slots 0 .. W-1 = the
+// waves' products; W = 4: slots 4, 5 = the pair products run0 run1 and run2 run3, then 1 / (run0 run1) and 1 / (run2 run3) in their
+// place; W = 2: slot 2 = the inverse of run0 run1.
+constexpr uint32_t AFF_SHARE_INV = 1u << 16;
+constexpr uint32_t AFF_X_SLOT_BYTES = 2048;
+constexpr uint32_t aff_exchange_bytes(uint32_t waves) { return waves == 4 ? 6 * AFF_X_SLOT_BYTES : waves == 2 ? 3 * AFF_X_SLOT_BYTES : 0; }
+// which wave inverts: co-resident workgroups should pick waves on DIFFERENT SIMDs, or their chains queue up on one.  The rule takes
+// consecutive waves for consecutive dispatch sweeps over the chip (one workgroup per CU: AFF_INV_SPREAD of them on an MI355X).  Any
+// value is correct; it only places the chains.  Measured (tools/wave_trace.py, "shared_inversion"): a wave's number does NOT name its
+// SIMD -- every wave number turns up on all four -- so the rule spreads the chains no better than chance: of the inverting waves that
+// overlap in time on one CU 27-33 % share a SIMD (docs/HISTORY.md; electing by the SIMD ids the waves could post is not built).
+constexpr uint32_t AFF_INV_SPREAD = 256;
+__device__ __forceinline__ void aff_x_put(uint32_t lane_addr, uint32_t slot, const Gf& v) {
+  const uint32_t a = lane_addr + slot * AFF_X_SLOT_BYTES;
+  gf_lds_st(a, (gf_u32x4){v.w[0], v.w[1], v.w[2], v.w[3]});
+  gf_lds_st(a + 1024, (gf_u32x4){v.w[4], v.w[5], v.w[6], v.w[7]});
+}
+__device__ __forceinline__ Gf aff_x_get(uint32_t lane_addr, uint32_t slot) {
+  const uint32_t a = lane_addr + slot * AFF_X_SLOT_BYTES;
+  const gf_u32x4 lo = gf_lds_ld(a), hi = gf_lds_ld(a + 1024);
+  Gf r;
+  r.w[0] = lo.x; r.w[1] = lo.y; r.w[2] = lo.z; r.w[3] = lo.w;
+  r.w[4] = hi.x; r.w[5] = hi.y; r.w[6] = hi.z; r.w[7] = hi.w;
+  return r;
 }
 // FIRST only names the launch: k_affine_round<true> is the first pair round of an MSM (random gathers out of the
 // pre-rotated table -- the dominant kernel bench.py's roofline block is about), <false> the later rounds (coalesced
@@ -1363,6 +1395,7 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
                uint32_t cap, uint32_t bmax, GfSqrTables T, Gf* __restrict__ prefix, Aff* __restrict__ out, uint32_t sign_mask, WaveTrace wt) {
   extern __shared__ char lds_raw[];
   unsigned long long tr_t0 = 0, tr_c0 = 0, tr_t1 = 0, tr_t2 = 0;
+  uint32_t tr_inverted = 0;  // bit 1: the launch shares its inversions, bit 0: this wave ran the chain
   if (TRACE) { tr_t0 = wall_clock64(); tr_c0 = clock64(); }
   GfLdsK L = gf_ldsk_init(lds_raw);
 #if AFF_PRIO
@@ -1381,14 +1414,18 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
   const int B = (int)aff_slots_per_thread(total, cap, bmax);
   const uint32_t nthr = (total + B - 1) / B;
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid >= nthr) return;
+  // shared inversion: barriers ahead, so only a workgroup WHOLLY beyond nthr leaves; in the last live one the threads at or beyond nthr
+  // stay with run = 1 and no slot (ld_desc), and a wave of such threads alone skips both passes
+  const bool share = (bmax & AFF_SHARE_INV) != 0 && blockDim.x > 64;
+  if (share ? blockIdx.x * blockDim.x >= nthr : tid >= nthr) return;
+  const bool wave_live = __builtin_amdgcn_readfirstlane(tid & ~63u) < nthr;
   const uint2 none = make_uint2(AFF_NONE, AFF_NONE);
   // (round 6: the load is unconditional from a clamped index and the VALUE is selected.  Returning `none` from the early exits made
   // hipcc select between two ADDRESSES -- &desc[sk] and a private copy of `none`: 16 B of scratch per lane and, worse, a FLAT load per
   // descriptor, which counts on lgkmcnt beside the multiplier's LDS reads)
   auto ld_desc = [&](int k) -> AffSlot {
     const uint32_t sk = (uint32_t)k * nthr + tid;
-    const bool ok = k >= 0 && k < B && sk < total;
+    const bool ok = k >= 0 && k < B && sk < total && tid < nthr;  // (tid >= nthr: sk would name another thread's slot)
     if (FIRST) {
       uint2 v = none;
       if (ok) v = desc[sk];
@@ -1405,7 +1442,7 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
   // A slot that adds nothing (no partner, an infinity, P - P) multiplies the product by one; a wave whose lanes all hold leftovers
   // -- the top rows of a DENSE round -- skips the product.  Only pairs park a prefix: pass 2 reads it for them alone.
   Gf run = one;
-  {
+  if (wave_live) {
     AffSlot d0 = ld_desc(0), d1 = ld_desc(1);
     Gf xa = gf_zero(), xb = gf_zero();
     if (d0.b != AFF_NONE) { xa = ldx(d0.a); xb = ldx(d0.b); }
@@ -1456,10 +1493,47 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
     }
   }
   if (TRACE) tr_t1 = wall_clock64();
-  Gf inv = gf_inv_fast(run, T, L);
+  // the inversion: of this wave's product, or (share) by one wave of the workgroup's.  ONE call site of the chain for both forms
+  // (a second chain for the inverting wave with unfenced table passes, gf_sqr_tab_wide or two words of lookups in flight, cost every
+  // instantiation 616-660 B of scratch per lane: the scheduler pulls the loads across the products around them)
+  const uint32_t W = blockDim.x >> 6, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t xa = L.lane_base + (W - w) * GF_LDSK_BYTES_PER_WAVE;  // this lane's entry of exchange slot 0, behind the W table regions
+  const uint32_t inverting = (blockIdx.x / AFF_INV_SPREAD) & (W - 1);
+  Gf inv = run;
+  if (share) {
+    if (TRACE) tr_inverted = w == inverting ? 3u : 2u;
+    aff_x_put(xa, w, run);
+    __syncthreads();
+    if (W == 4) {
+      if ((w & 1u) == 0) aff_x_put(xa, 4 + (w >> 1), gf_mul(run, aff_x_get(xa, w + 1), L));
+      __syncthreads();
+    }
+    if (w == inverting) {
+      // (its neighbours wait at the barrier and issue nothing: ahead of the other workgroups' passes on this SIMD)
+      __builtin_amdgcn_s_setprio(3);
+      inv = gf_mul(aff_x_get(xa, W == 4 ? 4 : 0), aff_x_get(xa, W == 4 ? 5 : 1), L);
+    }
+  }
+  if (!share || w == inverting) inv = gf_inv_fast(inv, T, L);
+  if (share) {
+    if (w == inverting) {
+      if (W == 4) {
+        // (the pair products are read back, not kept: nothing but the chain's own value is live across it)
+        Gf ia, ib;
+        gf_mul2(aff_x_get(xa, 5), aff_x_get(xa, 4), inv, L, ia, ib);  // 1 / (run0 run1) and 1 / (run2 run3)
+        aff_x_put(xa, 4, ia);
+        aff_x_put(xa, 5, ib);
+      } else {
+        aff_x_put(xa, 2, inv);
+      }
+      __builtin_amdgcn_s_setprio(0);  // (pass 2 resumes the rotation at its first slot)
+    }
+    __syncthreads();
+    inv = gf_mul(aff_x_get(xa, W == 4 ? 4 + (w >> 1) : 2), aff_x_get(xa, w ^ 1u), L);
+  }
   if (TRACE) tr_t2 = wall_clock64();
   // pass 2 (backwards): recover each inverse and finish the addition
-  {
+  if (wave_live) {
     AffSlot e0 = ld_desc(B - 1), e1 = ld_desc(B - 2);
     Gf px = gf_zero(), qx = gf_zero(), pre = one;
     if (e0.a != AFF_NONE) px = ldx(e0.a);
@@ -1563,7 +1637,8 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
         r[0] = tr_t0; r[1] = tr_t1; r[2] = tr_t2; r[3] = t3;
         r[4] = tr_c0; r[5] = c3;
         r[6] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);  // HW_ID | XCC_ID
-        r[7] = (unsigned long long)blockIdx.x | ((unsigned long long)wt.tag << 32) | ((unsigned long long)(uint32_t)B << 48);
+        r[7] = (unsigned long long)blockIdx.x | ((unsigned long long)wt.tag << 32) | ((unsigned long long)(uint32_t)B << 48) | ((unsigned long long)(threadIdx.x >> 6) << 56) |
+               ((unsigned long long)tr_inverted << 60);
       }
     }
   }
@@ -2167,6 +2242,8 @@ static int msm_set_lds_limits(int dev) {
                       (const void*)k_sum_points, (const void*)k_tail<false>, (const void*)k_tail<true>,
                       (const void*)k_bucket_pairs, (const void*)k_bucket_rest};
   for (const auto& l : sort_lim) DVP_HIP(hipFuncSetAttribute(l.f, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes));
+  // (the pair rounds ask for EC_LDS plus the exchange area of their shared inversion: inside the same limit)
+  static_assert(EC_LDS + aff_exchange_bytes(EC_TPB / 64) <= EC_LDS_Q, "k_affine_round's dynamic LDS exceeds the limit set here");
   for (const void* f : ec) DVP_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, EC_LDS_Q));
   attr_done[dev] = true;
   return DVP_OK;
@@ -2523,6 +2600,16 @@ struct MsmRun {
   }
 };
 
+// whether a pair round takes its inversion once per workgroup (a pure host function; dvp_aff_share_plan exposes it to the tests).
+// mode = Tune::msm_aff_share_inv, tpb = the rounds' workgroup size, planned = the additions the round plans (e_est >> (r + 1)),
+// share_min = Tune::msm_aff_share_min, chip_full = resident threads x fewest slots per thread: the threshold when share_min is 0
+static bool aff_share_plan(long long mode, uint32_t tpb, uint64_t planned, uint64_t share_min, uint64_t chip_full) {
+  if (tpb != 128 && tpb != 256) return false;  // one wave: nothing to share with
+  if (mode == 1) return true;
+  if (mode != 2) return false;
+  return planned >= (share_min ? share_min : chip_full);
+}
+
 // ---- bucket accumulation: batched-affine pair rounds while a round still carries >= aff_min additions, then the projective
 // fan-in-K reducer on what is left (it has a short critical path and balances skew)
 struct PairRounds {
@@ -2533,7 +2620,7 @@ struct PairRounds {
   size_t cap;          // upper bound on the entries of the live array (incl. the even padding of the buckets)
   int launched = 0, ra = 0;  // rounds enqueued ahead of the largest-bucket read; rounds in all
   uint32_t max_cnt = 0;      // the largest bucket, as the sort left it
-  uint32_t aff_tpb = 0, aff_lds = 0, aff_cap = 0, aff_bmax_only = 0, aff_bmax = 0, wt_cap = 0;
+  uint32_t aff_tpb = 0, aff_lds = 0, aff_cap = 0, aff_bmax_only = 0, aff_bmax = 0, aff_bmin = 0, wt_cap = 0;
   unsigned long long* wt_buf = nullptr;  // the wave trace's buffer (wt_cap records), if one is set
   std::unique_lock<std::mutex> heavy;  // HeavyGate: held from the first pair round's enqueue to the last one's (released on every return)
   explicit PairRounds(const MsmRun& m_)
@@ -2549,13 +2636,14 @@ struct PairRounds {
     // workgroup size of the pair rounds (Tune::msm_aff_tpb): the kernel has no block-level synchronisation (LDS tables are per wave),
     // so smaller workgroups only change how soon a finished wave's slot is handed to the next workgroup
     aff_tpb = (tn.msm_aff_tpb == 64 || tn.msm_aff_tpb == 128 || tn.msm_aff_tpb == 256) ? (uint32_t)tn.msm_aff_tpb : (uint32_t)EC_TPB;
-    aff_lds = (aff_tpb / 64) * GF_LDSK_BYTES_PER_WAVE;
+    // (with the exchange area of the shared inversion behind the table regions: 32 + 12 KB at 256 threads, still three workgroups per CU)
+    aff_lds = (aff_tpb / 64) * GF_LDSK_BYTES_PER_WAVE + aff_exchange_bytes(aff_tpb / 64);
     // (asked of one instantiation for all of them: amdgpu_waves_per_eu(3, 3) pins every flavour -- first, later, dense, traced -- to three waves per SIMD)
     DVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blk_per_cu, (const void*)k_affine_round<false, false>, (int)aff_tpb, aff_lds));
     if (blk_per_cu < 1) blk_per_cu = 1;
     aff_cap = (uint32_t)n_cu * (uint32_t)blk_per_cu * aff_tpb;
     aff_bmax_only = tn.msm_aff_bmax >= 1 && tn.msm_aff_bmax <= 255 ? (uint32_t)tn.msm_aff_bmax : AFF_BMAX;
-    const uint32_t aff_bmin = tn.msm_aff_bmin >= 1 && (uint32_t)tn.msm_aff_bmin <= aff_bmax_only ? (uint32_t)tn.msm_aff_bmin : 1u;
+    aff_bmin = tn.msm_aff_bmin >= 1 && (uint32_t)tn.msm_aff_bmin <= aff_bmax_only ? (uint32_t)tn.msm_aff_bmin : 1u;
     aff_bmax = aff_bmax_only | (aff_bmin << 8);
     wave_trace_snapshot(&wt_buf, &wt_cap);  // one snapshot per MSM: every round of it traces into the same buffer or none does
     return DVP_OK;
@@ -2593,6 +2681,9 @@ struct PairRounds {
     // r == 0 is the dominant kernel (it gathers the bases) and is timed launch by launch; the later rounds share ONE scope (finish()):
     // an event pair around every round put ~10 us of packet processing between two rounds that otherwise follow each other back to
     // back (kernel trace: 10-13 us gaps after every round, none between the merge levels)
+    const bool share = aff_share_plan(m.tn.msm_aff_share_inv, aff_tpb, (uint64_t)(L.e_est >> (r + 1)),
+                                      m.tn.msm_aff_share_min > 0 ? (uint64_t)m.tn.msm_aff_share_min : 0, (uint64_t)aff_cap * aff_bmin);
+    const uint32_t bmax_arg = aff_bmax | (share ? AFF_SHARE_INV : 0u);
     ProfScope ps0(r == 0 ? PROF_MSM_ACCUM_AFFINE : -1, st, (uint64_t)m.n);
     WaveTrace wt{wt_buf, wt_cap, g_wave_trace_tag.fetch_add(wt_buf ? 1u : 0u)};
     with_bool(r == 0, [&](auto first) {
@@ -2601,12 +2692,13 @@ struct PairRounds {
           constexpr bool FIRST = decltype(first)::value, TRACE = decltype(trace)::value, DENSE = decltype(dense)::value;
           if constexpr (!(FIRST && DENSE))  // a first round is never dense: no such kernel
             DVP_LAUNCH((k_affine_round<FIRST, TRACE, DENSE>), dim3(grid), dim3(aff_tpb), aff_lds, st, pts_in, (const uint2*)(const void*)dsc, d_total,
-                       aff_cap, aff_bmax, m.Tsq, b.prefix, outp, FIRST ? m.sign_mask : 0u, wt);
+                       aff_cap, bmax_arg, m.Tsq, b.prefix, outp, FIRST ? m.sign_mask : 0u, wt);
         });
       });
     });
     ps0.stop();
     if (r > 0) count_later_round(L.dense);
+    count_round_inv(share);
     pts_in = outp;
     cap = out_max;
     if (!L.pipelined) cur = nxt;
@@ -2932,6 +3024,11 @@ int msm_fixed_dev(const MsmFixedCtx* c, const void* d_scalars, const void* d_inf
 }  // namespace dvp
 
 using namespace dvp;
+
+// the pair rounds' choice between one inversion per workgroup and one per wave (include/dvpari_internal.h)
+extern "C" int dvp_aff_share_plan(long long mode, uint32_t tpb, uint64_t planned, uint64_t share_min, uint64_t chip_full) {
+  return aff_share_plan(mode, tpb, planned, share_min, chip_full) ? 1 : 0;
+}
 
 // ---- the table-budget planner (include/dvpari_internal.h: dvp_table_plan) ------------------------------------------------------
 // largest count <= total whose table -- rows x count x 64 bytes, rows as msm_fixed_build settles them for THAT count -- fits `budget`;

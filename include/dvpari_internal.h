@@ -67,7 +67,8 @@ int dvp_ubench_points_mul(const void* d_scalars, const void* d_xy, size_t n, voi
 /* Wave-level trace of the batched-affine pair rounds (dvp::k_affine_round, tools/wave_trace.py).  d_buf = device buffer of
  * 64 + 64 * n_records bytes zeroed by the caller, NULL = off.  While set, every pair round appends one 64-byte record per
  * wave (8 u64: s_memrealtime at wave start / after pass 1 / after the shared inversion / at the end; s_memtime at start / end;
- * HW_ID | XCC_ID << 32; blockIdx | launch tag << 32 | slots per thread << 48); word 0 of the buffer counts them. */
+ * HW_ID | XCC_ID << 32; blockIdx | launch tag << 32 | slots per thread << 48 | the wave's number in its workgroup << 56 | this wave
+ * ran the workgroup's inversion << 60 | the launch shares its inversions << 61); word 0 of the buffer counts them. */
 int dvp_debug_wave_trace(void* d_buf, uint32_t n_records);
 /* random 64-byte gathers per second (whole chip, two independent lines in flight per lane and step, as the first pair
  * round issues them) out of a device table of `table_bytes` bytes starting at d_table; d_table = NULL allocates a scratch
@@ -83,6 +84,13 @@ int dvp_prover_msm_table_ptr(const dvp_prover* p, int which, const void** d_tabl
  * (DVP_MSM_FIXED_C, DVP_MSM_ALIGNED_SIGNED and DVP_MSM_FIXED_MIN apply as they do to a prover).  bytes[0] + bytes[1] <= budget_bytes;
  * MSM 1 is served first and at most one of the two is partly covered. */
 int dvp_table_plan(size_t size0, size_t size1, uint64_t budget_bytes, size_t covered[2], uint64_t bytes[2]);
+
+/* Whether a batched-affine pair round takes its field inversion once per workgroup (1) or once per wave (0), as a pure host function
+ * (no device is touched): mode = DVP_MSM_AFF_SHARE_INV (0 never, 1 always, 2 by size), tpb = the rounds' workgroup size
+ * (DVP_MSM_AFF_TPB; 64 threads are one wave and never share), planned = the additions the round plans, share_min =
+ * DVP_MSM_AFF_SHARE_MIN, chip_full = resident pair-round threads x DVP_MSM_AFF_BMIN, the threshold that stands in for share_min = 0.
+ * dvp_profile_read("rounds_inv_shared" / "rounds_inv_private") counts the launches of either form. */
+int dvp_aff_share_plan(long long mode, uint32_t tpb, uint64_t planned, uint64_t share_min, uint64_t chip_full);
 
 /* parity-test access to the recode of the default fixed-base flavour alone (signed aligned windows): out_words[w * n + i] = 0 (digit 0) or 0x80000000 | 0x10000000 when the
  * digit is negative | w << 20 | |digit| (|digit| = 2^(c-1) is stored as key 0); *windows = ceil(234 / c_bits) */

@@ -9,6 +9,8 @@ and at its end, s_memtime (shader clock) at start and end, and the hardware slot
   * the same split into  ramp (until every CU has its 12 waves), steady, and drain (after the first slot goes idle for good)
   * gap statistics: time a (CU, SIMD, slot) stays empty between one wave's end and its successor's start
   * lifetime spread of the waves (p5 / p50 / p95 / max), per XCD medians, per phase medians (pass 1 / inversion / pass 2)
+  * shared inversions (one per workgroup): the SIMDs of the inverting waves, how often the inverting waves of workgroups that sit on
+    one CU at the same time share a SIMD, and the time from "after pass 1" to "after the inversion" of inverting and waiting waves
   * effective shader clock = d(s_memtime) / d(s_memrealtime) per wave (median, p5, p95) if s_memtime runs on the shader clock
 """
 import ctypes as C, faulthandler, importlib, json, os, signal, sys
@@ -45,7 +47,10 @@ hw = (rec[:, 6] & 0xffffffff).astype(np.int64)
 xcc = ((rec[:, 6] >> 32) & 0xf).astype(np.int64)
 blk = (rec[:, 7] & 0xffffffff).astype(np.int64)
 tag = ((rec[:, 7] >> 32) & 0xffff).astype(np.int64)
-Bs = ((rec[:, 7] >> 48) & 0xffff).astype(np.int64)
+Bs = ((rec[:, 7] >> 48) & 0xff).astype(np.int64)
+wave_no = ((rec[:, 7] >> 56) & 3).astype(np.int64)     # the wave's number in its workgroup
+inverted = ((rec[:, 7] >> 60) & 1).astype(bool)        # it ran the workgroup's inversion
+shared = ((rec[:, 7] >> 61) & 1).astype(bool)          # the launch takes one inversion per workgroup
 wave_id, simd, cu, sh, se = hw & 15, (hw >> 4) & 3, (hw >> 8) & 15, (hw >> 12) & 1, (hw >> 13) & 7
 cu_key = ((xcc * 8 + se) * 2 + sh) * 16 + cu
 slot_key = (cu_key * 4 + simd) * 16 + wave_id
@@ -109,6 +114,33 @@ for tg in sorted(set(tag.tolist())):
         "waves_by_xcd": {int(x): int((xs == x).sum()) for x in sorted(set(xs.tolist()))},
         "memtime_per_realtime_x100": {"p5": round(pct(clk, 5), 1), "p50": round(pct(clk, 50), 1), "p95": round(pct(clk, 95), 1)},
     }
+    if shared[m].any():
+        iv = m & inverted
+        simd_i, cu_i, b1_i, b2_i = simd[iv], cu_key[iv], t1[iv], t2[iv]
+        # inverting waves that overlap in time on one CU: pairs on the same SIMD queue their chains behind each other
+        same = other = 0
+        for c in np.unique(cu_i):
+            k = np.nonzero(cu_i == c)[0]
+            k = k[np.argsort(b1_i[k])]
+            for a in range(len(k)):
+                for b in range(a + 1, len(k)):
+                    if b1_i[k[b]] >= b2_i[k[a]]:
+                        break
+                    if simd_i[k[a]] == simd_i[k[b]]:
+                        same += 1
+                    else:
+                        other += 1
+        inv_t = (a2 - a1) * TICK
+        L["shared_inversion"] = {
+            "inverting_waves_by_simd": {int(x): int((simd_i == x).sum()) for x in range(4)},
+            "inverting_wave_no_by_simd": {int(x): sorted(set(wave_no[iv][simd_i == x].tolist())) for x in range(4)},
+            "overlapping_pairs_on_one_cu": {"same_simd": same, "different_simd": other},
+            "pass1_to_inverse_us": {"inverting_p50": round(pct(inv_t[inverted[m]], 50) * 1e3, 2), "inverting_p95": round(pct(inv_t[inverted[m]], 95) * 1e3, 2),
+                                    "waiting_p50": round(pct(inv_t[~inverted[m]], 50) * 1e3, 2), "waiting_p95": round(pct(inv_t[~inverted[m]], 95) * 1e3, 2)},
+        }
+    else:
+        inv_t = (a2 - a1) * TICK
+        L["private_inversion"] = {"pass1_to_inverse_us": {"p50": round(pct(inv_t, 50) * 1e3, 2), "p95": round(pct(inv_t, 95) * 1e3, 2)}}
     report["launches"].append(L)
     if L["waves"] > 2000:
         print(json.dumps(L), flush=True)
