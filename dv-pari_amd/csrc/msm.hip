@@ -2108,6 +2108,55 @@ struct LastMsm {
 };
 static thread_local LastMsm g_last_msm;
 static std::atomic<size_t> g_ws_need[MSM_MAX_DEVICES];
+
+// ---- stage capture (TEST ONLY: dvp_debug_msm_capture_arm / _fetch, include/dvpari_internal.h) -------------------------------------
+// A thread arms the capture for its NEXT MSM.  That MSM runs msm_core as it always does and, at the stage boundaries, enqueues
+// device-to-device copies of the arrays one stage hands to the next on its own stream: no kernel, no event, no wait.  The host does not
+// know the lengths the device settled on (off[nkeys], a round's total) when it enqueues, so every copy takes the region's upper bound
+// and the fetch, which waits for the stream, cuts the blob to the lengths the captured offsets name.  A copy that does not fit the
+// arena is not made and the fetch then fails as a whole.  An MSM of a thread that has not armed pays one null check per stage.
+constexpr uint32_t CAPTURE_MAGIC = 0x43505644u, CAPTURE_VERSION = 1, CAPTURE_HDR_WORDS = 104, CAPTURE_MAX_ROUNDS = 40;
+enum CaptureHdr {  // word indices of the blob's header
+  CH_MAGIC = 0, CH_VERSION, CH_HDR_WORDS, CH_FLAVOUR /* bit 0: fixed-base, bit 1: signed digits */, CH_C, CH_W, CH_N_NARROW, CH_NKEYS, CH_SIGN_MASK,
+  CH_N_TOTAL, CH_I0, CH_N, CH_RA, CH_RA_PLAN, CH_DENSE, CH_PIPELINE /* 0: per round, 1: side stream, 2: caller's stream */, CH_TPB, CH_AFF_CAP,
+  CH_BMAX, CH_BMIN, CH_ROUTE, CH_K, CH_MAX_CNT, CH_ITEMS_LEN, CH_SHARE /* [40] */, CH_TOTAL = CH_SHARE + CAPTURE_MAX_ROUNDS /* [40] */
+};
+static_assert(CH_TOTAL + CAPTURE_MAX_ROUNDS == CAPTURE_HDR_WORDS, "capture header layout");
+enum CaptureRoute { CR_GATHER_ITEMS = 0, CR_GATHER_AFF, CR_BUCKET_PAIRS, CR_REDUCER_FAST, CR_REDUCER_GENERAL };
+struct MsmCapture {
+  struct Sec { size_t at, bytes; };  // a region of the arena
+  struct Round { Sec ocnt, ooff, desc, pts; };
+  bool armed = false, taken = false;
+  int dev = -1;
+  hipStream_t st = nullptr;
+  char* arena = nullptr;
+  size_t cap = 0, used = 0, wanted = 0;  // wanted: what the MSM asked for, whether it fitted or not
+  hipError_t copy_err = hipSuccess;
+  uint32_t hdr[CAPTURE_HDR_WORDS] = {0};
+  Sec cnt = {0, 0}, off = {0, 0}, items = {0, 0}, bkt = {0, 0};
+  Round rounds[CAPTURE_MAX_ROUNDS] = {};
+  uint32_t nrounds = 0;
+  Sec grab(const void* src, size_t bytes, hipStream_t s) {
+    const size_t at = (wanted + 255) & ~(size_t)255;
+    wanted = at + bytes;
+    if (wanted > cap) return Sec{0, 0};  // (the fetch sees wanted > cap)
+    if (!bytes) return Sec{at, 0};
+    const hipError_t e = hipMemcpyAsync(arena + at, src, bytes, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess && copy_err == hipSuccess) copy_err = e;
+    used = wanted;
+    return Sec{at, bytes};
+  }
+  void release() {
+    if (arena) (void)hipFree(arena);
+    arena = nullptr;
+    cap = used = wanted = 0;
+    armed = taken = false;
+    nrounds = 0;
+    copy_err = hipSuccess;
+  }
+};
+static thread_local MsmCapture g_capture;
+
 // Two MSMs on one device overlap everything EXCEPT their pair rounds: those fill the chip on their own (two of them side by side
 // only contend: measured 4 % slower than taking turns), while everything around them -- sort, reducer, merge levels, tail, the
 // prover's Fr stages and host round trips -- leaves lanes idle.  So the pair rounds of the second MSM wait ON THE GPU
@@ -2413,7 +2462,16 @@ struct MsmRun {
   MsmBuffers b;
   MsmWorkspace* ws;
   GfSqrTables Tsq;
+  MsmCapture* cap;  // the calling thread's armed stage capture, else nullptr (every MSM but a test's)
   int reduce_leftovers(const PairRounds& pr) const;
+  // the end of reduce_leftovers, whichever route it took: the bucket array as the merge tree will read it
+  int leftovers_done(int route) const {
+    if (cap) {
+      cap->hdr[CH_ROUTE] = (uint32_t)route;
+      cap->bkt = cap->grab(b.bkt, (size_t)p.nkeys * sizeof(Ld), st);
+    }
+    return DVP_OK;
+  }
   // the largest bucket goes to the host on the aux stream while the caller's stream carries on
   int read_max() const {
     DVP_TRY(ws->ensure_aux());
@@ -2699,6 +2757,21 @@ struct PairRounds {
     ps0.stop();
     if (r > 0) count_later_round(L.dense);
     count_round_inv(share);
+    if (MsmCapture* c = m.cap; c && r < (int)CAPTURE_MAX_ROUNDS) {
+      // the round's output counts / offsets, its descriptors as the kernel read them (round 0: the item list, captured behind the sort)
+      // and its output points, before round r + 1 reuses the descriptors (per-round bookkeeping) and round r + 2 the points; each
+      // region at the bound the workspace gives it
+      const bool dense_r = r > 0 && L.dense;
+      const size_t pts_n = std::min(out_max, (r & 1) ? L.affB_n : L.affA_n);
+      const size_t desc_n = r == 0 ? 0 : (L.pipelined ? (dense_r ? 2 : 1) * (out_max + 64) : std::min(out_max, L.desc_n));
+      MsmCapture::Round& cr = c->rounds[r];
+      cr.ocnt = c->grab(L.pipelined ? rc(r + 1) : pc[nxt], (size_t)nk * 4, st);
+      cr.ooff = c->grab(L.pipelined ? ro(r + 1) : po[nxt], ((size_t)nk + 1) * 4, st);
+      cr.desc = c->grab(dsc, desc_n * 4, st);
+      cr.pts = c->grab(outp, pts_n * sizeof(Aff), st);
+      c->hdr[CH_SHARE + r] = share ? 1u : 0u;
+      c->nrounds = (uint32_t)r + 1;
+    }
     pts_in = outp;
     cap = out_max;
     if (!L.pipelined) cur = nxt;
@@ -2777,13 +2850,13 @@ int MsmRun::reduce_leftovers(const PairRounds& pr) const {
       DVP_LAUNCH(k_bucket_gather_items, dim3(cdiv(nk, 256)), dim3(256), 0, st, bases0, b.items, b.cnt, b.off, nk, b.bkt, sign_mask);
     else
       DVP_LAUNCH(k_bucket_gather_aff, dim3(cdiv(nk, 256)), dim3(256), 0, st, pr.pts_in, pc[cur], po[cur], nk, b.bkt);
-    return DVP_OK;
+    return leftovers_done(pr.ra == 0 ? CR_GATHER_ITEMS : CR_GATHER_AFF);
   }
   if (pr.ra > 0 && rem_max <= (uint64_t)(tn.msm_bucket_pairs_max >= 0 ? tn.msm_bucket_pairs_max : 0)) {
     // a handful of points per bucket left: one thread per bucket; buckets that meet an exceptional pair are redone from a list
     DVP_LAUNCH(k_bucket_pairs, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pr.pts_in, pc[cur], po[cur], nk, b.bkt, b.rest_n, b.rest_list);
     DVP_LAUNCH(k_bucket_rest, dim3(cdiv(nk, EC_TPB)), dim3(EC_TPB), EC_LDS, st, pr.pts_in, pc[cur], po[cur], b.rest_n, b.rest_list, b.bkt);
-    return DVP_OK;
+    return leftovers_done(CR_BUCKET_PAIRS);
   }
   // the fan-in-K reducer.  Level 1: mixed additions from affine inputs (IND: the items index the bases; else the pair rounds' outputs)
   int nxt = (cur + 1) % 3;
@@ -2831,7 +2904,7 @@ int MsmRun::reduce_leftovers(const PairRounds& pr) const {
     std::swap(in, outb);
   }
   DVP_LAUNCH(k_bucket_gather, dim3(cdiv(nk, 256)), dim3(256), 0, st, in, pc[cur], po[cur], nk, b.bkt);
-  return DVP_OK;
+  return leftovers_done(accum_fast ? CR_REDUCER_FAST : CR_REDUCER_GENERAL);
 }
 
 // n == 0: the point at infinity.  The two flavours differ on purpose: the deferred one must not touch the host.
@@ -2872,14 +2945,37 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
   std::unique_lock<std::mutex> g;  // the workspace is this call's until it returns
   DVP_TRY(msm_acquire_workspace(m.dev, st, m.ws_slots, m.L.bytes, g, &m.ws));
   m.b = msm_carve(n, m.p, fx, m.L, m.ws->p);
+  if (g_capture.armed) {  // a test armed this thread's stage capture: this MSM is the one it takes
+    m.cap = &g_capture;
+    m.cap->armed = false;
+    m.cap->dev = m.dev;
+    m.cap->st = st;
+  }
   ProfScope ps_total(PROF_MSM_TOTAL, st);
   DVP_TRY(m.sort());
+  if (MsmCapture* c = m.cap) {  // the sort's result; the rounds only read it (a first round the sort's stage did not wait for included)
+    c->cnt = c->grab(m.b.cnt, (size_t)m.p.nkeys * 4, st);
+    c->off = c->grab(m.b.off, ((size_t)m.p.nkeys + 1) * 4, st);
+    c->items = c->grab(m.b.items, (m.p.e_max + (size_t)m.p.nkeys + 2) * 4, st);
+  }
   DVP_TRY(gf_sqr_tables(&m.Tsq, st));
   PairRounds pr(m);
   DVP_TRY(pr.init());
   DVP_TRY(pr.begin());   // the first round where it is certain, then the host learns the largest bucket and settles the number of rounds
   DVP_TRY(pr.finish());  // the other rounds
   DVP_TRY(m.reduce_leftovers(pr));
+  if (MsmCapture* c = m.cap) {
+    uint32_t* h = c->hdr;
+    h[CH_MAGIC] = CAPTURE_MAGIC; h[CH_VERSION] = CAPTURE_VERSION; h[CH_HDR_WORDS] = CAPTURE_HDR_WORDS;
+    h[CH_FLAVOUR] = (fx ? 1u : 0u) | ((fx && fx->signed_digits) ? 2u : 0u);
+    h[CH_C] = (uint32_t)m.p.c; h[CH_W] = (uint32_t)m.p.W; h[CH_N_NARROW] = (uint32_t)m.p.n_narrow; h[CH_NKEYS] = m.p.nkeys;
+    h[CH_SIGN_MASK] = m.sign_mask; h[CH_N_TOTAL] = fx ? fx->n_total : (uint32_t)n; h[CH_I0] = i0; h[CH_N] = (uint32_t)n;
+    h[CH_RA] = (uint32_t)pr.ra; h[CH_RA_PLAN] = (uint32_t)m.L.ra_plan; h[CH_DENSE] = m.L.dense ? 1u : 0u;
+    h[CH_PIPELINE] = m.L.pipelined ? (m.L.side_stream ? 1u : 2u) : 0u;
+    h[CH_TPB] = pr.aff_tpb; h[CH_AFF_CAP] = pr.aff_cap; h[CH_BMAX] = pr.aff_bmax_only; h[CH_BMIN] = pr.aff_bmin;
+    h[CH_K] = m.p.K; h[CH_MAX_CNT] = pr.max_cnt;
+    c->taken = true;
+  }
   m.merge_and_tail(out);
   ps_total.stop();
   DVP_HIP(hipGetLastError());
@@ -3196,6 +3292,86 @@ extern "C" int dvp_debug_msm_rest_len(uint32_t* n) {
   if (prev != lm.dev) (void)hipSetDevice(prev);
   DVP_HIP(e);
   *n = w[1];
+  return DVP_OK;
+}
+
+// the stage capture (include/dvpari_internal.h; MsmCapture above)
+extern "C" int dvp_debug_msm_capture_arm(size_t arena_bytes) {
+  using namespace dvp;
+  MsmCapture& c = g_capture;
+  c.release();  // a capture nobody fetched, or an arming no MSM followed
+  if (!arena_bytes) return DVP_OK;  // disarm
+  DVP_HIP(hipMalloc((void**)&c.arena, arena_bytes));
+  c.cap = arena_bytes;
+  memset(c.hdr, 0, sizeof c.hdr);
+  c.cnt = c.off = c.items = c.bkt = MsmCapture::Sec{0, 0};
+  c.armed = true;
+  return DVP_OK;
+}
+extern "C" int dvp_debug_msm_capture_fetch(void* out, size_t cap_bytes, size_t* need) {
+  using namespace dvp;
+  MsmCapture& c = g_capture;
+  if (need) *need = 0;
+  if (!c.taken) return DVP_EINVAL;  // this thread's last armed MSM did not run, or failed before its buckets were reduced
+  int prev = 0;
+  DVP_HIP(hipGetDevice(&prev));
+  if (prev != c.dev) DVP_HIP(hipSetDevice(c.dev));
+  hipError_t e = hipStreamSynchronize(c.st);
+  std::vector<uint32_t> a;
+  const bool fits = c.wanted <= c.cap;
+  if (e == hipSuccess && c.copy_err != hipSuccess) e = c.copy_err;
+  if (e == hipSuccess && fits) {
+    a.resize((c.used + 3) / 4);
+    if (c.used) e = hipMemcpy(a.data(), c.arena, c.used, hipMemcpyDeviceToHost);
+  }
+  if (prev != c.dev) (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    c.release();
+    DVP_HIP(e);
+  }
+  if (!fits) {  // no partial blob: the arena the MSM wanted is reported instead
+    g_last_error_index = (int64_t)c.wanted;
+    c.release();
+    return DVP_EINVAL;
+  }
+  // the lengths the device settled on, read from the captured offsets
+  auto word = [&](const MsmCapture::Sec& s, size_t i) { return a[s.at / 4 + i]; };
+  const uint32_t nk = c.hdr[CH_NKEYS], ra = c.hdr[CH_RA];
+  const bool dense = c.hdr[CH_DENSE] != 0;
+  bool ok = ra == c.nrounds && c.bkt.bytes == (size_t)nk * sizeof(Ld);
+  const size_t items_len = word(c.off, nk);
+  ok = ok && items_len * 4 <= c.items.bytes;
+  size_t words = CAPTURE_HDR_WORDS + (size_t)nk + (nk + 1) + items_len + (size_t)nk * (sizeof(Ld) / 4);
+  for (uint32_t r = 0; ok && r < ra; ++r) {
+    const size_t total = word(c.rounds[r].ooff, nk), dw = r == 0 ? 0 : (dense ? 2 : 1) * total;
+    ok = total * sizeof(Aff) <= c.rounds[r].pts.bytes && dw * 4 <= c.rounds[r].desc.bytes;
+    c.hdr[CH_TOTAL + r] = (uint32_t)total;
+    words += (size_t)nk + (nk + 1) + dw + total * (sizeof(Aff) / 4);
+  }
+  if (!ok) {  // cannot happen: every region was copied at its upper bound
+    c.release();
+    return DVP_EHIP;
+  }
+  c.hdr[CH_ITEMS_LEN] = (uint32_t)items_len;
+  if (need) *need = words * 4;
+  if (!out) return DVP_OK;  // the size alone; the capture stays
+  if (cap_bytes < words * 4) return DVP_EINVAL;  // nothing written; the capture stays
+  uint32_t* o = (uint32_t*)out;
+  auto put = [&](const void* src, size_t n_words) { memcpy(o, src, n_words * 4); o += n_words; };
+  auto sec = [&](const MsmCapture::Sec& s, size_t n_words) { put(a.data() + s.at / 4, n_words); };
+  put(c.hdr, CAPTURE_HDR_WORDS);
+  sec(c.cnt, nk);
+  sec(c.off, (size_t)nk + 1);
+  sec(c.items, items_len);
+  for (uint32_t r = 0; r < ra; ++r) {
+    const size_t total = c.hdr[CH_TOTAL + r];
+    sec(c.rounds[r].ocnt, nk);
+    sec(c.rounds[r].ooff, (size_t)nk + 1);
+    sec(c.rounds[r].desc, r == 0 ? 0 : (dense ? 2 : 1) * total);
+    sec(c.rounds[r].pts, total * (sizeof(Aff) / 4));
+  }
+  sec(c.bkt, (size_t)nk * (sizeof(Ld) / 4));
+  c.release();
   return DVP_OK;
 }
 

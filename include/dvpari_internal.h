@@ -44,6 +44,28 @@ int dvp_debug_launch_names(char* buf, size_t cap);
  * during the calling thread's last MSM, read from its workspace after waiting for that MSM's stream.  DVP_EINVAL before the first MSM. */
 int dvp_debug_msm_rest_len(uint32_t* n);
 
+/* TEST ONLY: the intermediate arrays of ONE MSM, stage by stage (tests/msm_stage_cases.py parses the blob and restates every stage).
+ * dvp_debug_msm_capture_arm(arena_bytes) arms the calling thread's NEXT MSM -- one-shot or dvp_msm_ctx_run, host or _dev entry -- and
+ * allocates a device arena of that size (0 = disarm and free).  That MSM runs as any other, plus device-to-device copies into the arena
+ * enqueued on its own stream at the stage boundaries (no kernel, no event, no wait); an MSM of a thread that has not armed does nothing
+ * of this.  dvp_debug_msm_capture_fetch waits for that MSM's stream and writes one blob of 32-bit words:
+ *   header, 104 words: [0] 0x43505644, [1] version 1, [2] 104, [3] flavour (bit 0 fixed-base, bit 1 signed digits), [4] c, [5] W,
+ *     [6] n_narrow, [7] nkeys, [8] sign mask of an item, [9] n_total (row stride of the table; one-shot: n), [10] i0, [11] n, [12] ra
+ *     (pair rounds run), [13] ra_plan, [14] dense descriptors, [15] bookkeeping (0 per round, 1 all rounds on a side stream, 2 all rounds
+ *     on the caller's), [16] workgroup size of the rounds, [17] aff_cap (resident round threads), [18] bmax, [19] bmin, [20] leftover
+ *     route (0 k_bucket_gather_items, 1 k_bucket_gather_aff, 2 k_bucket_pairs + k_bucket_rest, 3 fan-in-K reducer with the exception-free
+ *     first level, 4 with the general one), [21] K, [22] the largest bucket, [23] items_len = off[nkeys], [24 + r] round r shared its
+ *     inversions, [64 + r] total_r = output slots of round r;
+ *   after the sort: cnt[nkeys], off[nkeys + 1], items[items_len];
+ *   per round r < ra: its output counts [nkeys] and offsets [nkeys + 1], its descriptor words as the kernel read them (round 0: none,
+ *     it reads the item list; later rounds total_r words, 2 total_r on the dense path), its output points total_r x 16 words (x, y);
+ *   after the leftover reducer: bkt[nkeys] x 24 words, raw (X, Y, Z).
+ * fetch(NULL, 0, &need) reports the blob's size and keeps the capture; a buffer smaller than that is DVP_EINVAL, nothing written.  An
+ * arena too small for what the MSM had to copy: DVP_EINVAL, no blob at all, dvp_last_error_index() = the arena bytes it wanted.  A
+ * fetch without a captured MSM is DVP_EINVAL.  A successful fetch, a failed one and a new arming free the arena. */
+int dvp_debug_msm_capture_arm(size_t arena_bytes);
+int dvp_debug_msm_capture_fetch(void* out, size_t cap_bytes, size_t* need);
+
 /* "msm_affine_round0" split by launch shape: entry k = (pairs of the MSM, summed ms, launches) for every distinct MSM size
  * since the last reset; returns the number of shapes (fills at most `cap`), < 0 on error */
 int dvp_profile_round0_shapes(uint64_t* pairs, double* total_ms, uint64_t* launches, int cap);

@@ -13,6 +13,7 @@ import pyref as o
 import c_oracle as co
 from util import to_limbs, from_limbs, pts_to_np, np_to_pt, rand_fr_np, np_dot_mod, np_dot_mod_fast, tau_adversarial_scalars
 from msm_cases import exceptional_pairs_input, assert_census, rest_len
+from msm_stage_cases import signed_recode
 
 pytestmark = pytest.mark.gpu
 OSSL = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "k233_openssl.json")))["vectors"]
@@ -559,7 +560,7 @@ def test_one_shot_randomised_shapes_and_knobs(dvp):
 @pytest.mark.parametrize("c", [8, 13, 18, 19, 20, 21])
 def test_signed_recode_words_vs_restatement(dvp, c):
     """k_recode_signed (the small-table flavour: aligned windows of signed binary digits) word for word against the textbook
-    signed-digit decomposition restated here: 234 bits in W = ceil(234 / c) windows, the W c - 234 LOW windows one bit
+    signed-digit decomposition restated in tests/msm_stage_cases.py (signed_recode): 234 bits in W = ceil(234 / c) windows, the W c - 234 LOW windows one bit
     narrower (so no window is short: a short top window would pile every scalar into a handful of buckets); window w holds
     its bits plus the carry from below, a digit above half its range becomes digit - 2^width with a carry;
     sum_w d_w 2^(o_w) is the scalar and |d_w| <= 2^(width_w - 1).  A c whose windows would all be narrow is refused
@@ -589,15 +590,8 @@ def test_signed_recode_words_vs_restatement(dvp, c):
     words = np.zeros((W.value, len(vals)), dtype=np.uint32)
     dvp.check(dvp.lib.dvp_debug_recode_signed(s.ctypes.data, len(vals), c, words.ctypes.data, C.byref(W)), "recode")
     for i, x in enumerate(vals):
-        exp, carry, off = [], 0, 0
-        for wd in widths:
-            d = ((x >> off) & ((1 << wd) - 1)) + carry
-            carry = 0
-            if d > (1 << (wd - 1)):
-                d, carry = d - (1 << wd), 1
-            exp.append((off, d))
-            off += wd
-        assert carry == 0 and sum(d << o_w for o_w, d in exp) == x
+        exp = signed_recode(x, c)  # the restatement (tests/msm_stage_cases.py): [(o_w, d_w)], sum_w d_w 2^(o_w) = x asserted there
+        assert len(exp) == n_win and sum(d << o_w for o_w, d in exp) == x
         for w, (_, d) in enumerate(exp):
             word = int(words[w, i])
             if d == 0:
