@@ -72,6 +72,16 @@ _SIGS = {
     "dvp_debug_fr_from_be32_host": (C.c_int, [u8p, sz, u64p]),
     "dvp_prove_be32": (C.c_int, [vp, u8p, sz, u8p]),
     "dvp_prove_cache_dir_witness_file": (C.c_int, [C.c_char_p, u32, C.c_char_p, u8p, u64p]),
+    "dvp_fr_from_ark": (C.c_int, [u64p, sz, u64p]),
+    "dvp_fr_to_ark": (C.c_int, [u64p, sz, u64p]),
+    "dvp_fr_from_ark_dev": (C.c_int, [vp, sz, vp, vp]),
+    "dvp_fr_to_ark_dev": (C.c_int, [vp, sz, vp, vp]),
+    "dvp_debug_fr_ark_host": (C.c_int, [C.c_int, u64p, sz, u64p]),
+    "dvp_debug_fr_ark_is_one": (C.c_int, [u8p]),
+    "dvp_prove_ark": (C.c_int, [vp, u64p, u32, u64p, u32, u8p]),
+    "dvp_prove_cache_dir_ark": (C.c_int, [C.c_char_p, u64p, u32, u64p, u32, u8p]),
+    "dvp_msm_xsk233_ark": (C.c_int, [u64p, u8p, sz, u8p]),
+    "dvp_msm_ctx_run_ark": (C.c_int, [vp, u64p, sz, sz, u64p, C.POINTER(C.c_int)]),
     "dvp_debug_fr_op": (C.c_int, [C.c_int, C.POINTER(vp), sz, C.c_int, C.POINTER(vp)]),
     "dvp_debug_gf_op": (C.c_int, [C.c_int, C.c_int, C.POINTER(vp), sz, C.c_uint64, C.POINTER(vp)]),
     "dvp_barycentric_eval": (C.c_int, [u64p, u64p, u64p, u64p, sz, u64p, u64p]),

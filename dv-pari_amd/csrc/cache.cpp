@@ -517,6 +517,14 @@ extern "C" int dvp_prove_cache_dir(const char* cache_dir, const uint64_t* public
                         [&](dvp_prover* pv) { return dvp_prove(pv, public_inputs, n_public, private_inputs, n_private, proof); });
 }
 
+// Proof::prove(cache_dir, Vec<Fr>, &[Fr]) with both vectors as the caller's memory holds them (dvp_prove_ark on the entry's prover)
+extern "C" int dvp_prove_cache_dir_ark(const char* cache_dir, const uint64_t* public_ark, uint32_t n_public, const uint64_t* private_ark,
+                                       uint32_t n_private, uint8_t proof[118]) {
+  if (!cache_dir || !proof || (n_public && !public_ark) || (n_private && !private_ark)) return DVP_EINVAL;
+  return prove_on_entry(cache_dir, n_public,
+                        [&](dvp_prover* pv) { return dvp_prove_ark(pv, public_ark, n_public, private_ark, n_private, proof); });
+}
+
 // load_witness_from_file + Proof::prove in one call (src/gnark_r1cs.rs:188-211, src/dvsnark_test.rs:189-229): the file is mapped and its
 // payload handed to dvp_prove_be32 as it is -- the elements are reduced mod p on the device.  Everything that can be said about the file
 // without a device (header, count against the length, element 0 == 1) is said BEFORE the cache_dir entry is opened.

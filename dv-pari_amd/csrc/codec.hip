@@ -553,8 +553,9 @@ extern "C" int dvp_ubench_points_mul(const void* d_scalars, const void* d_xy, si
   return DVP_OK;
 }
 
-// scalars: n x 32 B canonical LE; bases: n x 30 B xsk233 encodings; out: 30 B encoding of the sum
-extern "C" int dvp_msm_xsk233(const uint8_t* scalars, const uint8_t* bases_enc, size_t n, uint8_t out_enc[30]) {
+// scalars: n x 32 B canonical LE (ark: as arkworks holds them, converted in the device buffer they were copied into, fr_ark.hip);
+// bases: n x 30 B xsk233 encodings; out: 30 B encoding of the sum
+static int msm_xsk233(const uint8_t* scalars, bool ark, const uint8_t* bases_enc, size_t n, uint8_t out_enc[30]) {
   if ((n && (!scalars || !bases_enc)) || !out_enc) return DVP_EINVAL;
   DevBuf ds, dp, di, de, dout;
   DVP_TRY(ds.alloc(n * 32));
@@ -564,6 +565,7 @@ extern "C" int dvp_msm_xsk233(const uint8_t* scalars, const uint8_t* bases_enc, 
   DVP_TRY(dout.alloc(64 + 16));
   if (n) {
     DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
+    if (ark) DVP_TRY(dvp_fr_from_ark_dev(ds.p, n, ds.p, nullptr));
     DVP_HIP(hipMemcpy(de.p, bases_enc, n * 30, hipMemcpyHostToDevice));
     DVP_TRY(decode_dev(de.as<uint8_t>(), n, dp.as<Aff>(), di.as<uint8_t>(), 0));
   }
@@ -576,6 +578,13 @@ extern "C" int dvp_msm_xsk233(const uint8_t* scalars, const uint8_t* bases_enc, 
   DVP_TRY(encode_dev(dout.as<Aff>(), (uint8_t*)dout.p + 72, 1, de.as<uint8_t>(), 0));
   DVP_HIP(hipMemcpy(out_enc, de.p, 30, hipMemcpyDeviceToHost));
   return DVP_OK;
+}
+extern "C" int dvp_msm_xsk233(const uint8_t* scalars, const uint8_t* bases_enc, size_t n, uint8_t out_enc[30]) {
+  return msm_xsk233(scalars, false, bases_enc, n, out_enc);
+}
+// multi_scalar_mul(&[Fr], &[CurvePoint]) with the scalars as the slice holds them (src/curve.rs:141-158)
+extern "C" int dvp_msm_xsk233_ark(const uint64_t* scalars_ark, const uint8_t* bases_enc, size_t n, uint8_t out_enc[30]) {
+  return msm_xsk233((const uint8_t*)scalars_ark, true, bases_enc, n, out_enc);
 }
 
 // which presentation of the encoded field element the 30 bytes hold (see the table at the top of this file); 0 = the default

@@ -32,6 +32,18 @@ struct Fr {
   { 0x0e8c5421u, 0x9104e52au, 0x46ea432bu, 0xfff962a4u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x0000007fu }
 #define DVP_FR_R2_LIMBS \
   { 0xfd830525u, 0xf2ae10f8u, 0x70af2a02u, 0x13f123b3u, 0xd80293c8u, 0x7b59bebeu, 0x04193b9au, 0x0000002fu }
+// The arkworks boundary (fr_ark.cuh): ark_ff's MontBackend<_, 4> keeps a 2^256 in memory, this library's radix is 2^232, and
+// fr_mul(x, k) = x k 2^-232.  Each constant is pow(2, e, p) in Python integers, cut into 32-bit limbs, least significant first:
+//   e = -24  (pow(2, -24, p), the inverse of 2^24): fr_mul(a 2^256, 2^-24) = a 2^(256 - 24 - 232) = a          (from arkworks form)
+//   e = 488:                                        fr_mul(a, 2^488)       = a 2^(488 - 232)      = a 2^256    (to arkworks form)
+//   e = 256: arkworks' one, the constant wire as a host holds it
+// (DVP_FR_R2_LIMBS above is the same recipe with e = 464: the check that the recipe is read right.)
+#define DVP_FR_2M24_LIMBS \
+  { 0x6caeab0cu, 0x3e3e0383u, 0xc4a159f8u, 0x000173a8u, 0x00000000u, 0x00000000u, 0x17f08000u, 0x0000001cu }
+#define DVP_FR_2P488_LIMBS \
+  { 0x43277672u, 0x988ced37u, 0xd8cc68e7u, 0xb58d1f7bu, 0xc813eeb5u, 0xbed80293u, 0x9a7b59beu, 0x0000003bu }
+#define DVP_FR_2P256_LIMBS \
+  { 0x3373abdfu, 0xc318337eu, 0x1037c69eu, 0x489471e2u, 0xfffff2c5u, 0xffffffffu, 0xffffffffu, 0x0000007fu }
 #define DVP_FR_P29_LIMBS \
   { 0x1173abdfu, 0x17d8d6afu, 0x056f351bu, 0x0d3ab772u, 0x00000000u, 0x00000000u, 0x00000000u, 0x10000000u }
 #define DVP_FR_PM2_LIMBS \

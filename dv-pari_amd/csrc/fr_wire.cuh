@@ -54,6 +54,42 @@ DVP_WIRE_HD void fr_from_be32_words(const uint32_t be[8], uint32_t out[8]) {
   }
 }
 
+// The same reduction on a value that is little-endian already: le[k] = bits 32k .. 32k+31 of any x < 2^256, out = x mod p, canonical.
+// fr_from_be32_words minus its byte swap (the arkworks-form entries of fr_ark.cuh reduce with it before they scale).
+DVP_WIRE_HD void fr_reduce_le_words(const uint32_t le[8], uint32_t out[8]) {
+  constexpr uint32_t P32[8] = {0xf173abdfu, 0x6efb1ad5u, 0xb915bcd4u, 0x00069d5bu, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000080u};
+  uint32_t x[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) x[i] = le[i];
+  const uint32_t q = x[7] >> 7;  // bit 231 is bit 7 of limb 7
+  x[7] &= 0x7fu;                 // r
+  uint32_t t[8];                 // q c, as in fr_from_be32_words
+  uint64_t acc = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    acc += (uint64_t)q * P32[i];  // < 2^57 + 2^32
+    t[i] = (uint32_t)acc;
+    acc >>= 32;
+  }
+  t[4] = (uint32_t)acc;
+  t[5] = t[6] = t[7] = 0;
+  uint32_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t d = (uint64_t)x[i] - t[i] - borrow;
+    x[i] = (uint32_t)d;
+    borrow = (uint32_t)(d >> 63);
+  }
+  const uint32_t mask = 0u - borrow;  // r < q c: add p back (the carry out of limb 7 cancels the borrow)
+  uint32_t carry = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t s = (uint64_t)x[i] + (P32[i] & mask) + carry;
+    out[i] = (uint32_t)s;
+    carry = (uint32_t)(s >> 32);
+  }
+}
+
 // does the element at `be` (32 bytes, any alignment) reduce to 1?  The constant wire of a witness (src/proving.rs:449-452): the one
 // element the host looks at, in dvp_prove_be32 and, before cache_dir is opened, in dvp_prove_cache_dir_witness_file
 DVP_WIRE_HD bool fr_be32_is_one(const uint8_t* be) {

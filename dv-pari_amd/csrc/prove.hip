@@ -1609,6 +1609,25 @@ extern "C" int dvp_prove_be32(dvp_prover* p, const uint8_t* witness_be32, size_t
   return dvp_prove_dev(p, p->w, proof, p->own_stream);
 }
 
+// dvp_prove with both vectors as arkworks holds them (Proof::prove's Vec<Fr> and &[Fr], src/proving.rs:426-452; four LE u64 of
+// a 2^256 mod p each, src/curve.rs:16-22).  dvp_prove step for step, except that the bytes go into p->w as they are and k_fr_from_ark
+// (fr_ark.hip) converts elements 1 .. n_wires-1 there, in place, in one launch behind the wait for the copy: the kernel runs while the
+// host enqueues the proof, and the proof still has one host wait.  The constant wire is the library's own canonical 1.
+extern "C" int dvp_prove_ark(dvp_prover* p, const uint64_t* public_ark, uint32_t n_public, const uint64_t* private_ark, uint32_t n_private,
+                             uint8_t proof[118]) {
+  if (!p || !proof || n_public != p->n_pub || 1 + n_public + n_private != p->n_wires) return DVP_EINVAL;
+  if ((n_public && !public_ark) || (n_private && !private_ark)) return DVP_EINVAL;
+  if (!prover_ready(p)) return DVP_EINVAL;
+  if (!p->own_stream) DVP_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
+  Fr one = fr_one_canon();
+  DVP_HIP(hipMemcpyAsync(p->w, &one, sizeof(Fr), hipMemcpyHostToDevice, p->own_stream));
+  if (n_public) DVP_HIP(hipMemcpyAsync(p->w + 1, public_ark, (size_t)n_public * 32, hipMemcpyHostToDevice, p->own_stream));
+  if (n_private) DVP_HIP(hipMemcpyAsync(p->w + 1 + n_public, private_ark, (size_t)n_private * 32, hipMemcpyHostToDevice, p->own_stream));
+  DVP_HIP(hipStreamSynchronize(p->own_stream));  // as in dvp_prove: `one` and the caller's buffers are free again
+  DVP_TRY(dvp_fr_from_ark_dev(p->w + 1, (size_t)p->n_wires - 1, p->w + 1, p->own_stream));
+  return dvp_prove_dev(p, p->w, proof, p->own_stream);
+}
+
 // Parity-test access to the intermediates of the last dvp_prove call.  name in:
 //  "a","b","c","i" (m each), "a2","b2","c2","i2", "r2", "q2", "ka","kb" (m), "kr" (2m),
 //  "alpha","a0","b0","i0","r0" (1), "bar_wts","z_vals2inv","D","D2" (m, canonical)

@@ -227,6 +227,20 @@ def multi_scalar_mul_bytes(scalars32: np.ndarray, bases30: np.ndarray) -> bytes:
     return out.tobytes()
 
 
+def multi_scalar_mul_bytes_ark(scalars_ark: np.ndarray, bases30: np.ndarray) -> bytes:
+    """multi_scalar_mul_bytes with the scalars as arkworks holds them in memory (uint64 [n, 4] of a * 2^256 mod p, fr.to_ark),
+    converted on the GPU (dvp_msm_xsk233_ark)"""
+    from . import fr
+
+    s = fr._ark_arg(scalars_ark, "multi_scalar_mul_bytes_ark")
+    b = np.ascontiguousarray(bases30, dtype=np.uint8).reshape(-1, 30)
+    if s.shape[0] != b.shape[0]:
+        raise ValueError(f"multi_scalar_mul_bytes_ark: {s.shape[0]} scalars for {b.shape[0]} bases")
+    out = np.zeros(30, dtype=np.uint8)
+    check(lib.dvp_msm_xsk233_ark(ptr(s), ptr(b), s.shape[0], ptr(out)), "dvp_msm_xsk233_ark")
+    return out.tobytes()
+
+
 class FixedBaseMsm:
     """multi_scalar_mul against a fixed base vector (an SRS vector): dvp_msm_ctx_* in include/dvpari.h."""
 
@@ -267,4 +281,17 @@ class FixedBaseMsm:
         out = np.zeros(8, dtype=np.uint64)
         is_inf = C.c_int(0)
         check(lib.dvp_msm_ctx_run(self._h, ptr(s), lo, hi, ptr(out), C.byref(is_inf)), "dvp_msm_ctx_run")
+        return out, bool(is_inf.value)
+
+    def run_ark(self, scalars_ark: np.ndarray, lo: int = 0, hi: int = None):
+        """run with the scalars as arkworks holds them in memory (fr.to_ark), converted on the GPU (dvp_msm_ctx_run_ark)"""
+        from . import fr
+
+        hi = self.n if hi is None else hi
+        s = fr._ark_arg(scalars_ark, "run_ark")
+        if s.shape[0] != hi - lo:
+            raise ValueError(f"run_ark: {s.shape[0]} scalars for bases [{lo}, {hi})")
+        out = np.zeros(8, dtype=np.uint64)
+        is_inf = C.c_int(0)
+        check(lib.dvp_msm_ctx_run_ark(self._h, ptr(s), lo, hi, ptr(out), C.byref(is_inf)), "dvp_msm_ctx_run_ark")
         return out, bool(is_inf.value)

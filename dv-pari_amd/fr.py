@@ -111,6 +111,69 @@ def from_be32_dev(d_be32: int, n: int, d_out: int = None, stream: int = 0):
     check(lib.dvp_fr_from_be32_dev(d_be32 or None, n, (d_be32 if d_out is None else d_out) or None, stream or None), "dvp_fr_from_be32_dev")
 
 
+def _ark_arg(v, who: str) -> np.ndarray:
+    """n elements of four u64 each (a uint64 array of shape [n, 4] / [4 n], or bytes of 32 n) as a uint64 [n, 4] view; the memory may
+    start at any address (a byte-offset view is passed on as it is)"""
+    if isinstance(v, (bytes, bytearray, memoryview)):
+        if len(v) % 32:
+            raise ValueError(f"{who}: expected n x 32 bytes, got {len(v)}")
+        return np.frombuffer(v, dtype=np.uint64).reshape(-1, 4)
+    a = np.asarray(v)
+    if a.dtype != np.uint64:
+        raise ValueError(f"{who}: expected a uint64 array, got {a.dtype}")
+    if a.ndim == 2 and a.shape[1] != 4 or a.ndim > 2 or a.size % 4:
+        raise ValueError(f"{who}: expected n x 4 limbs, got shape {a.shape}")
+    return np.ascontiguousarray(a).reshape(-1, 4)
+
+
+def _ark_call(fn, name, v, *lead):
+    a = _ark_arg(v, name)
+    out = np.zeros((a.shape[0], 4), dtype=np.uint64)
+    if a.shape[0]:
+        check(fn(*lead, ptr(a), a.shape[0], ptr(out)), name)
+    return out
+
+
+def from_ark(ark) -> np.ndarray:
+    """Fr as arkworks holds it in memory (four LE u64 of a * 2^256 mod p, src/curve.rs:16-22) -> uint64 [n, 4] canonical, on the GPU
+    (dvp_fr_from_ark): into_bigint() over a vector.  Total: any value below 2^256 is reduced first."""
+    return _ark_call(lib.dvp_fr_from_ark, "dvp_fr_from_ark", ark)
+
+
+def to_ark(limbs_) -> np.ndarray:
+    """canonical limbs (any value below 2^256, reduced first) -> the arkworks in-memory form, on the GPU (dvp_fr_to_ark)"""
+    return _ark_call(lib.dvp_fr_to_ark, "dvp_fr_to_ark", limbs_)
+
+
+def from_ark_host(ark) -> np.ndarray:
+    """the host build of from_ark's per-element function (dvp_debug_fr_ark_host): no GPU needed; for tests and baselines"""
+    return _ark_call(lib.dvp_debug_fr_ark_host, "dvp_debug_fr_ark_host", ark, 0)
+
+
+def to_ark_host(limbs_) -> np.ndarray:
+    """the host build of to_ark's per-element function (dvp_debug_fr_ark_host): no GPU needed"""
+    return _ark_call(lib.dvp_debug_fr_ark_host, "dvp_debug_fr_ark_host", limbs_, 1)
+
+
+def from_ark_dev(d_in: int, n: int, d_out: int = None, stream: int = 0):
+    """dvp_fr_from_ark_dev: n elements at the device address d_in -> d_out (None = in place), both 16-byte aligned; only enqueues on
+    `stream`"""
+    check(lib.dvp_fr_from_ark_dev(d_in or None, n, d_out or None, stream or None), "dvp_fr_from_ark_dev")
+
+
+def to_ark_dev(d_in: int, n: int, d_out: int = None, stream: int = 0):
+    """dvp_fr_to_ark_dev: the other direction, same rules"""
+    check(lib.dvp_fr_to_ark_dev(d_in or None, n, d_out or None, stream or None), "dvp_fr_to_ark_dev")
+
+
+def ark_is_one(ark32) -> bool:
+    """fr_ark_is_one on 32 bytes: is this arkworks-form element the field's one (2^256 mod p, any representative below 2^256)?"""
+    a = np.frombuffer(bytes(ark32), dtype=np.uint8)
+    if a.size != 32:
+        raise ValueError(f"ark_is_one: expected 32 bytes, got {a.size}")
+    return bool(lib.dvp_debug_fr_ark_is_one(ptr(a)))
+
+
 # enum dvp_fr_op (include/dvpari_internal.h): name -> (number, inputs, outputs)
 DEBUG_OPS = {name: (k, n_in, n_out) for k, (name, n_in, n_out) in enumerate([
     ("add", 2, 1), ("sub", 2, 1), ("neg", 1, 1), ("dbl", 1, 1), ("cond_sub_p", 1, 1), ("is_canonical", 1, 1), ("mul", 2, 1),

@@ -54,6 +54,18 @@ class Proof:
         return Proof.from_bytes(out.tobytes())
 
     @staticmethod
+    def prove_ark(cache_dir, public_ark, private_ark) -> "Proof":
+        """Proof.prove with both vectors as arkworks holds them in memory (uint64 [n, 4] of a * 2^256 mod p, fr.to_ark): they are
+        converted on the GPU, in the prover's witness buffer (dvp_prove_cache_dir_ark)"""
+        import os
+
+        pub, prv = fr._ark_arg(public_ark, "prove_ark"), fr._ark_arg(private_ark, "prove_ark")
+        out = np.zeros(118, dtype=np.uint8)
+        check(lib.dvp_prove_cache_dir_ark(os.fspath(cache_dir).encode(), ptr(pub) if pub.shape[0] else None, pub.shape[0],
+                                          ptr(prv) if prv.shape[0] else None, prv.shape[0], ptr(out)), "dvp_prove_cache_dir_ark")
+        return Proof.from_bytes(out.tobytes())
+
+    @staticmethod
     def prove_witness_file(cache_dir, num_public_inputs: int, witness_path=None):
         """load_witness_from_file + Proof::prove in one call (dvp_prove_cache_dir_witness_file): the witness file (None =
         cache_dir/witness_to_dvsnark) is mapped and its elements are reduced mod p on the GPU.  Returns (Proof, public_inputs as
@@ -285,6 +297,15 @@ class Prover:
         a = fr._be32_arg(raw)
         out = np.zeros(118, dtype=np.uint8)
         check(lib.dvp_prove_be32(self._h, ptr(a) if a.shape[0] else None, a.shape[0], ptr(out)), "dvp_prove_be32")
+        return Proof.from_bytes(out.tobytes())
+
+    def prove_ark(self, public_ark, private_ark) -> Proof:
+        """prove with both vectors as arkworks holds them in memory (uint64 [n, 4] of a * 2^256 mod p, fr.to_ark): converted on the
+        GPU, in place in the witness buffer (dvp_prove_ark)"""
+        pub, prv = fr._ark_arg(public_ark, "prove_ark"), fr._ark_arg(private_ark, "prove_ark")
+        out = np.zeros(118, dtype=np.uint8)
+        check(lib.dvp_prove_ark(self._h, ptr(pub) if pub.shape[0] else None, pub.shape[0], ptr(prv) if prv.shape[0] else None,
+                                prv.shape[0], ptr(out)), "dvp_prove_ark")
         return Proof.from_bytes(out.tobytes())
 
     def debug(self, name: str, n: int = None):

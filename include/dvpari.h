@@ -122,6 +122,17 @@ int dvp_barycentric_eval(const uint64_t* domain, const uint64_t* bar_weights, co
  * pointer with n > 0, for a pointer that is not 16-byte aligned and for n > 2^32 - 256 (one launch; the file format counts in 32 bits). */
 int dvp_fr_from_be32(const uint8_t* be32, size_t n, uint64_t* out /* n x 4 */);
 int dvp_fr_from_be32_dev(const void* d_be32, size_t n, void* d_out /* may equal d_be32 */, void* stream);
+/* Fr as arkworks holds it in memory <-> canonical limbs.  The crate's Fr is Fp256<MontBackend<FqConfig, 4>> (src/curve.rs:16-22): four
+ * little-endian u64 holding a * 2^256 mod p, below p -- what `slice.as_ptr() as *const u64` points at.  from_ark is into_bigint() over a
+ * vector (out = x * 2^-256 mod p), to_ark is Fr::from_bigint (out = a * 2^256 mod p); one lane per element on the device.  Both are
+ * total: any value below 2^256 is reduced mod p first, the result is canonical.  n = 0 is DVP_OK and touches nothing.  The host
+ * flavours take any alignment.  The _dev flavours only enqueue on `stream`; d_out NULL or == d_in converts in place (a lane reads and
+ * writes only its own 32 bytes); DVP_EINVAL before any device call for d_in NULL with n > 0, for a pointer that is not 16-byte aligned
+ * and for n > 2^32 - 256 (one launch). */
+int dvp_fr_from_ark(const uint64_t* ark /* n x 4 */, size_t n, uint64_t* out /* n x 4 */);
+int dvp_fr_to_ark(const uint64_t* limbs /* n x 4 */, size_t n, uint64_t* out_ark /* n x 4 */);
+int dvp_fr_from_ark_dev(const void* d_in, size_t n, void* d_out /* NULL or == d_in: in place */, void* stream);
+int dvp_fr_to_ark_dev(const void* d_in, size_t n, void* d_out /* NULL or == d_in: in place */, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* sect233k1 / xsk233 group                                                                     */
@@ -155,9 +166,15 @@ int dvp_msm_ctx_plan(const dvp_msm_ctx* ctx, int* c_bits, int* windows);
 uint64_t dvp_msm_ctx_table_bytes(const dvp_msm_ctx* ctx, int* signed_windows);
 int dvp_msm_ctx_run(dvp_msm_ctx* ctx, const uint64_t* scalars, size_t lo, size_t hi, uint64_t out_xy[8], int* out_is_infinity);
 int dvp_msm_ctx_run_dev(dvp_msm_ctx* ctx, const void* d_scalars, size_t lo, size_t hi, void* d_out_xy, void* d_out_inf, void* stream);
+/* dvp_msm_ctx_run with the hi - lo scalars as arkworks holds them (the &[Fr] of multi_scalar_mul, src/curve.rs:141-158; see
+ * dvp_fr_from_ark): they are copied into the call's own device buffer and converted there. */
+int dvp_msm_ctx_run_ark(dvp_msm_ctx* ctx, const uint64_t* scalars_ark, size_t lo, size_t hi, uint64_t out_xy[8], int* out_is_infinity);
 /* same seam with the reference's own wire formats: scalars n x 32 B canonical LE, bases n x 30 B
  * xsk233 encodings (read_point_vec_from_file payload, src/io_utils.rs:187-239). */
 int dvp_msm_xsk233(const uint8_t* scalars, const uint8_t* bases_enc, size_t n, uint8_t out_enc[30]);
+/* multi_scalar_mul(&[Fr], &[CurvePoint]) itself, src/curve.rs:141-158: the scalars are the slice's memory (n x 4 u64, arkworks form,
+ * see dvp_fr_from_ark), converted on the device; everything else is dvp_msm_xsk233. */
+int dvp_msm_xsk233_ark(const uint64_t* scalars_ark, const uint8_t* bases_enc, size_t n, uint8_t out_enc[30]);
 
 /* point_scalar_mul_gen over a vector + to_bytes: the SRS commitment loop of
  * compute_srs_matrices, src/srs.rs:126-160 (one fixed-base multiplication per scalar). */
@@ -310,6 +327,13 @@ int dvp_prove_dev(dvp_prover* p, const void* d_assignment, uint8_t proof[118], v
  * reads the first n_wires elements only (the reference's zip truncates the same way).  Element 0 must reduce to 1 (1 + p is
  * accepted), else DVP_EINVAL with dvp_last_error_index() = 0, before any device work; no other element is looked at on the host. */
 int dvp_prove_be32(dvp_prover* p, const uint8_t* witness_be32, size_t n, uint8_t proof[118]);
+/* dvp_prove with both vectors as arkworks holds them (Proof::prove's public_inputs: Vec<Fr> and private_inputs: &[Fr],
+ * src/proving.rs:426-452; the layout is dvp_fr_from_ark's): the bytes are copied into the prover's witness buffer and converted there,
+ * on the device, in place (one dvp_fr_from_ark_dev over elements 1 .. n_wires - 1 on the prover's own stream); the constant wire is
+ * written by the library.  No host-side conversion and no host wait beyond dvp_prove's.  Everything else is dvp_prove: counts and
+ * NULL pointers are DVP_EINVAL, an unsatisfied witness is DVP_EUNSAT with the same row. */
+int dvp_prove_ark(dvp_prover* p, const uint64_t* public_ark, uint32_t n_public, const uint64_t* private_ark, uint32_t n_private,
+                  uint8_t proof[118]);
 /* prove in phases, so that the two MSMs -- the only stages that shard across GPUs -- can be split by
  * index range and their partial sums combined by the caller (all-gather + local add):
  *   begin -> msm_partial(0, lo, hi) -> challenge(commit point) -> msm_partial(1, lo, hi) -> finish */
@@ -564,6 +588,11 @@ int dvp_prover_open_cache_dir(const char* cache_dir, uint32_t n_public, dvp_prov
  * rule are supported until that rule is pinned against xs233 (tools/pin_xsk233.py). */
 int dvp_prove_cache_dir(const char* cache_dir, const uint64_t* public_inputs, uint32_t n_public, const uint64_t* private_inputs,
                         uint32_t n_private, uint8_t proof[118]);
+/* Proof::prove(cache_dir, public_inputs: Vec<Fr>, private_inputs: &[Fr]), src/proving.rs:426, with both vectors as the caller's memory
+ * holds them: dvp_prove_ark on the entry's prover, under the locking and replica rules of dvp_prove_cache_dir.  A NULL vector with a
+ * non-zero count is DVP_EINVAL before cache_dir is opened. */
+int dvp_prove_cache_dir_ark(const char* cache_dir, const uint64_t* public_ark, uint32_t n_public, const uint64_t* private_ark,
+                            uint32_t n_private, uint8_t proof[118]);
 /* load_witness_from_file + Proof::prove in one call (src/gnark_r1cs.rs:188-211 -> src/proving.rs:426): the witness file
  * (witness_path == NULL reads <cache_dir>/witness_to_dvsnark) is mapped and proved through dvp_prove_be32 on the entry's prover, under
  * the locking and replica rules of dvp_prove_cache_dir; its elements are reduced on the device.  The header is checked by the rules

@@ -208,6 +208,11 @@ int dvp_debug_fr_op(int op, const uint64_t* const in[6], size_t n, int on_device
 /* TEST ONLY: the HOST build of the function k_fr_from_be32 runs per element (csrc/fr_wire.cuh) over n x 32 big-endian bytes -> n x 4
  * limbs; makes no HIP call (runs without a GPU).  The public entries are dvp_fr_from_be32 / dvp_fr_from_be32_dev. */
 int dvp_debug_fr_from_be32_host(const uint8_t* be32, size_t n, uint64_t* out);
+/* TEST ONLY: the HOST build of the functions k_fr_from_ark (to_ark = 0) and k_fr_to_ark (to_ark != 0) run per element
+ * (csrc/fr_ark.cuh) over n x 4 limbs at any alignment; makes no HIP call (runs without a GPU).  dvp_debug_fr_ark_is_one: fr_ark_is_one
+ * on the 32 bytes at `ark` (1 / 0; DVP_EINVAL for NULL).  The public entries are dvp_fr_from_ark / dvp_fr_to_ark and their _dev flavours. */
+int dvp_debug_fr_ark_host(int to_ark, const uint64_t* in, size_t n, uint64_t* out);
+int dvp_debug_fr_ark_is_one(const uint8_t* ark);
 
 /* TEST ONLY: one function of the GF(2^233) arithmetic (csrc/gf233.cuh) or of the K-233 point formulas (csrc/k233.cuh) per element, on
  * the device (tests/gf_cases.py holds the case sets; oracle/pyref.py is the reference).  Every value is a raw 256-bit integer (4 x u64,
