@@ -106,50 +106,68 @@ LaunchCounter* census_register(const char* file, const char* tag_type) {
   return slot;
 }
 
+// Every knob once: its name and its field of Tune (common.h holds the fields, their defaults and what they do).  The environment, dvp_tune_set,
+// dvp_tune_get and dvp_tune_reset all go through this table, in the order of the fields; a field without a row does not compile.
+struct Knob {
+  const char* name;
+  long long Tune::*field;
+};
+static constexpr Knob kKnobs[] = {
+    {"DVP_MSM_C", &Tune::msm_c},
+    {"DVP_MSM_K", &Tune::msm_k},
+    {"DVP_MSM_FIXED_C", &Tune::msm_fixed_c},
+    {"DVP_FX_HI", &Tune::fx_hi},
+    {"DVP_MSM_PROJ", &Tune::msm_proj},  // settable under this name; from the environment only as DVP_MSM_MODE=proj
+    {"DVP_MSM_AFF_MIN", &Tune::msm_aff_min},
+    {"DVP_MSM_GATE_MIN", &Tune::msm_gate_min},
+    {"DVP_MSM_WS_SLOTS", &Tune::msm_ws_slots},
+    {"DVP_CACHE_REPLICAS", &Tune::cache_replicas},
+    {"DVP_MSM_AFF_TPB", &Tune::msm_aff_tpb},
+    {"DVP_MSM_AFF_BMIN", &Tune::msm_aff_bmin},
+    {"DVP_MSM_AFF_SHARE_INV", &Tune::msm_aff_share_inv},
+    {"DVP_MSM_AFF_SHARE_MIN", &Tune::msm_aff_share_min},
+    {"DVP_MSM_AFF_BMAX", &Tune::msm_aff_bmax},
+    {"DVP_ECFFT_RADIX4", &Tune::ecfft_radix4},
+    {"DVP_ECFFT_FOLD", &Tune::ecfft_fold},
+    {"DVP_MSM_ACCUM_FAST", &Tune::msm_accum_fast},
+    {"DVP_MSM_TAIL_GROUPS", &Tune::msm_tail_groups},
+    {"DVP_MSM_ACCUM_HEX_MAX", &Tune::msm_accum_hex_max},
+    {"DVP_GF_INV_TABS", &Tune::gf_inv_tabs},
+    {"DVP_MSM_ACCUM_QUAD_MAX", &Tune::msm_accum_quad_max},
+    {"DVP_MSM_BUCKET_PAIRS_MAX", &Tune::msm_bucket_pairs_max},
+    {"DVP_MSM_SORT_FUSED", &Tune::msm_sort_fused},
+    {"DVP_MSM_ROUND_PIPELINE", &Tune::msm_round_pipeline},
+    {"DVP_MSM_ROUND_DENSE", &Tune::msm_round_dense},
+    {"DVP_MSM_HEX_MAX", &Tune::msm_hex_max},
+    {"DVP_MSM_QUAD_MAX", &Tune::msm_quad_max},
+    {"DVP_MSM_FIXED_MIN", &Tune::msm_fixed_min},
+    {"DVP_FR_BI_SHAPE", &Tune::fr_bi_shape},
+    {"DVP_HORNER_MAX_PUB", &Tune::horner_max_pub},
+    {"DVP_PROVE_HOST_TRANSCRIPT", &Tune::prove_host_transcript},
+    {"DVP_TABLE_BUDGET_BYTES", &Tune::table_budget_bytes},
+    {"DVP_MSM_TABLE_REFUSE", &Tune::msm_table_refuse},
+    {"DVP_POINTS_MUL_W", &Tune::points_mul_w},
+    {"DVP_MSM_SEG_PIECE", &Tune::msm_seg_piece},
+    {"DVP_CIRCUIT_HASH_WINDOW", &Tune::circuit_hash_window},
+    {"DVP_MSM_ALIGNED_SIGNED", &Tune::msm_aligned_signed},
+};
+static_assert(sizeof(Tune) == sizeof(kKnobs) / sizeof(kKnobs[0]) * sizeof(long long), "every field of Tune needs exactly one row of kKnobs");
+
 static void tune_from_env(Tune& t) {
   t = Tune();
-  auto geti = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
-  t.msm_c = geti("DVP_MSM_C", t.msm_c);
-  t.msm_k = geti("DVP_MSM_K", t.msm_k);
-  t.msm_fixed_c = geti("DVP_MSM_FIXED_C", t.msm_fixed_c);
-  t.fx_hi = geti("DVP_FX_HI", t.fx_hi);
+  for (const Knob& k : kKnobs) {
+    if (k.field == &Tune::msm_proj) continue;  // a variable DVP_MSM_PROJ is ignored: the mode below sets the field
+    const char* e = getenv(k.name);
+    if (!e) continue;
+    if (k.field == &Tune::table_budget_bytes) {  // the full u64 range: UINT64_MAX and anything above LLONG_MAX read as "no limit"
+      const unsigned long long v = strtoull(e, nullptr, 10);
+      t.*k.field = v > (unsigned long long)LLONG_MAX ? -1 : (long long)v;
+    } else {
+      t.*k.field = atoll(e);
+    }
+  }
   const char* m = getenv("DVP_MSM_MODE");
   t.msm_proj = (m && !strcmp(m, "proj")) ? 1 : 0;
-  t.msm_aff_min = geti("DVP_MSM_AFF_MIN", t.msm_aff_min);
-  t.msm_hex_max = geti("DVP_MSM_HEX_MAX", t.msm_hex_max);
-  t.msm_round_pipeline = geti("DVP_MSM_ROUND_PIPELINE", t.msm_round_pipeline);
-  t.msm_round_dense = geti("DVP_MSM_ROUND_DENSE", t.msm_round_dense);
-  t.msm_sort_fused = geti("DVP_MSM_SORT_FUSED", t.msm_sort_fused);
-  t.msm_bucket_pairs_max = geti("DVP_MSM_BUCKET_PAIRS_MAX", t.msm_bucket_pairs_max);
-  t.msm_aff_bmax = geti("DVP_MSM_AFF_BMAX", t.msm_aff_bmax);
-  t.msm_aff_bmin = geti("DVP_MSM_AFF_BMIN", t.msm_aff_bmin);
-  t.msm_aff_share_inv = geti("DVP_MSM_AFF_SHARE_INV", t.msm_aff_share_inv);
-  t.msm_aff_share_min = geti("DVP_MSM_AFF_SHARE_MIN", t.msm_aff_share_min);
-  t.ecfft_radix4 = geti("DVP_ECFFT_RADIX4", t.ecfft_radix4);
-  t.ecfft_fold = geti("DVP_ECFFT_FOLD", t.ecfft_fold);
-  t.msm_accum_fast = geti("DVP_MSM_ACCUM_FAST", t.msm_accum_fast);
-  t.msm_tail_groups = geti("DVP_MSM_TAIL_GROUPS", t.msm_tail_groups);
-  t.msm_accum_hex_max = geti("DVP_MSM_ACCUM_HEX_MAX", t.msm_accum_hex_max);
-  t.gf_inv_tabs = geti("DVP_GF_INV_TABS", t.gf_inv_tabs);
-  t.msm_ws_slots = geti("DVP_MSM_WS_SLOTS", t.msm_ws_slots);
-  t.msm_gate_min = geti("DVP_MSM_GATE_MIN", t.msm_gate_min);
-  t.msm_aff_tpb = geti("DVP_MSM_AFF_TPB", t.msm_aff_tpb);
-  t.cache_replicas = geti("DVP_CACHE_REPLICAS", t.cache_replicas);
-  t.msm_quad_max = geti("DVP_MSM_QUAD_MAX", t.msm_quad_max);
-  t.msm_accum_quad_max = geti("DVP_MSM_ACCUM_QUAD_MAX", t.msm_accum_quad_max);
-  t.msm_fixed_min = geti("DVP_MSM_FIXED_MIN", t.msm_fixed_min);
-  t.horner_max_pub = geti("DVP_HORNER_MAX_PUB", t.horner_max_pub);
-  t.fr_bi_shape = geti("DVP_FR_BI_SHAPE", t.fr_bi_shape);
-  t.msm_aligned_signed = geti("DVP_MSM_ALIGNED_SIGNED", t.msm_aligned_signed);
-  t.points_mul_w = geti("DVP_POINTS_MUL_W", t.points_mul_w);
-  t.msm_seg_piece = geti("DVP_MSM_SEG_PIECE", t.msm_seg_piece);
-  t.circuit_hash_window = geti("DVP_CIRCUIT_HASH_WINDOW", t.circuit_hash_window);
-  t.prove_host_transcript = geti("DVP_PROVE_HOST_TRANSCRIPT", t.prove_host_transcript);
-  t.msm_table_refuse = geti("DVP_MSM_TABLE_REFUSE", t.msm_table_refuse);
-  if (const char* e = getenv("DVP_TABLE_BUDGET_BYTES")) {  // the full u64 range: UINT64_MAX and anything above LLONG_MAX read as "no limit"
-    const unsigned long long v = strtoull(e, nullptr, 10);
-    t.table_budget_bytes = v > (unsigned long long)LLONG_MAX ? -1 : (long long)v;
-  }
 }
 static std::mutex g_dev_mu;
 static std::vector<int> g_devices;
@@ -165,16 +183,8 @@ Tune& tune() {
 
 static long long* tune_slot(const char* name) {
   dvp::Tune& t = dvp::tune();
-  struct { const char* n; long long* v; } tab[] = {
-      {"DVP_MSM_C", &t.msm_c}, {"DVP_MSM_K", &t.msm_k}, {"DVP_MSM_FIXED_C", &t.msm_fixed_c}, {"DVP_FX_HI", &t.fx_hi},
-      {"DVP_MSM_PROJ", &t.msm_proj}, {"DVP_MSM_AFF_MIN", &t.msm_aff_min}, {"DVP_MSM_HEX_MAX", &t.msm_hex_max}, {"DVP_MSM_ROUND_PIPELINE", &t.msm_round_pipeline}, {"DVP_MSM_ROUND_DENSE", &t.msm_round_dense}, {"DVP_MSM_SORT_FUSED", &t.msm_sort_fused}, {"DVP_MSM_BUCKET_PAIRS_MAX", &t.msm_bucket_pairs_max}, {"DVP_MSM_AFF_BMAX", &t.msm_aff_bmax}, {"DVP_MSM_AFF_BMIN", &t.msm_aff_bmin}, {"DVP_MSM_AFF_SHARE_INV", &t.msm_aff_share_inv}, {"DVP_MSM_AFF_SHARE_MIN", &t.msm_aff_share_min}, {"DVP_ECFFT_RADIX4", &t.ecfft_radix4}, {"DVP_ECFFT_FOLD", &t.ecfft_fold}, {"DVP_MSM_ACCUM_FAST", &t.msm_accum_fast}, {"DVP_MSM_TAIL_GROUPS", &t.msm_tail_groups}, {"DVP_MSM_ACCUM_HEX_MAX", &t.msm_accum_hex_max}, {"DVP_GF_INV_TABS", &t.gf_inv_tabs}, {"DVP_MSM_WS_SLOTS", &t.msm_ws_slots}, {"DVP_MSM_GATE_MIN", &t.msm_gate_min}, {"DVP_MSM_AFF_TPB", &t.msm_aff_tpb}, {"DVP_CACHE_REPLICAS", &t.cache_replicas},
-      {"DVP_MSM_QUAD_MAX", &t.msm_quad_max}, {"DVP_MSM_ACCUM_QUAD_MAX", &t.msm_accum_quad_max}, {"DVP_MSM_FIXED_MIN", &t.msm_fixed_min}, {"DVP_HORNER_MAX_PUB", &t.horner_max_pub}, {"DVP_FR_BI_SHAPE", &t.fr_bi_shape},
-      {"DVP_MSM_ALIGNED_SIGNED", &t.msm_aligned_signed}, {"DVP_PROVE_HOST_TRANSCRIPT", &t.prove_host_transcript},
-      {"DVP_TABLE_BUDGET_BYTES", &t.table_budget_bytes}, {"DVP_MSM_TABLE_REFUSE", &t.msm_table_refuse},
-      {"DVP_POINTS_MUL_W", &t.points_mul_w}, {"DVP_MSM_SEG_PIECE", &t.msm_seg_piece},
-      {"DVP_CIRCUIT_HASH_WINDOW", &t.circuit_hash_window}};
-  for (auto& e : tab)
-    if (!strcmp(name, e.n)) return e.v;
+  for (const dvp::Knob& k : dvp::kKnobs)
+    if (!strcmp(name, k.name)) return &(t.*k.field);
   return nullptr;
 }
 extern "C" int dvp_tune_set(const char* name, long long value) {

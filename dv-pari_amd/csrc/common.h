@@ -72,7 +72,8 @@ struct DevBuf {
 
 // Tuning knobs (tools/README.md).  Defaults are the measured optima; the environment (DVP_MSM_C, ...) is read ONCE, at
 // the first use, and dvp_tune_set / dvp_tune_reset (include/dvpari.h) change a knob at run time -- that is how the tests
-// force every window size / sort flavour / round shape, and how tools/ sweep.  Never read on a hot path.
+// force every window size / sort flavour / round shape, and how tools/ sweep.  Never read on a hot path.  Every field is a long long
+// and has one row of kKnobs (capi.cpp), which gives it its name: a field without a row does not compile.
 struct Tune {
   long long msm_c = 0;          // DVP_MSM_C: one-shot window bits (0 = cost model)
   long long msm_k = 0;          // DVP_MSM_K: fan-in of the projective reducer (0 = default)
@@ -85,9 +86,9 @@ struct Tune {
   long long cache_replicas = 1;  // DVP_CACHE_REPLICAS: provers dvp_prove_cache_dir may hold per cache_dir (1 = callers take turns on one prover, the default since the end of round 4: with the witness in host memory a second prover's latency chains land in the first one's pair rounds and two callers got 23.3-23.8 ms per proof where taking turns gives 21.2-21.4; 2 = a second one is opened when two callers overlap)
   long long msm_aff_tpb = 256;  // DVP_MSM_AFF_TPB: workgroup size of the pair rounds (64, 128 or 256)
   long long msm_aff_bmin = 8;   // DVP_MSM_AFF_BMIN: fewest slots a round thread owns (small rounds then use fewer threads, each sharing its inversion among more additions)
-  long long msm_aff_share_inv = 2;  // DVP_MSM_AFF_SHARE_INV: the pair rounds' inversion once per WORKGROUP instead of once per wave (msm.hip: AFF_SHARE_INV): 0 = never, 1 = whenever the workgroup has more than one wave, 2 = in rounds of at least DVP_MSM_AFF_SHARE_MIN planned additions
+  long long msm_aff_share_inv = 2;  // DVP_MSM_AFF_SHARE_INV: the pair rounds' inversion once per WORKGROUP instead of once per wave (msm_rounds.cuh: AFF_SHARE_INV): 0 = never, 1 = whenever the workgroup has more than one wave, 2 = in rounds of at least DVP_MSM_AFF_SHARE_MIN planned additions
   long long msm_aff_share_min = 0;  // DVP_MSM_AFF_SHARE_MIN: with DVP_MSM_AFF_SHARE_INV=2 a round shares when it plans this many additions (0 = one chip-full at DVP_MSM_AFF_BMIN slots per thread); smaller rounds keep the private inversions, which have less latency
-  long long msm_aff_bmax = 136; // DVP_MSM_AFF_BMAX: most slots (additions per shared inversion) a round thread owns (48 through round 4; msm.hip: AFF_BMAX)
+  long long msm_aff_bmax = 136; // DVP_MSM_AFF_BMAX: most slots (additions per shared inversion) a round thread owns (48 through round 4; msm_rounds.cuh: AFF_BMAX)
   long long ecfft_radix4 = 3;   // DVP_ECFFT_RADIX4: the unfused top of an extend: 3 = up to nine layers in ONE LDS-tiled launch (k_extend_top; what is above them as under 2), 2 = three layers per pass (k_butterfly8, then k_butterfly4 / k_butterfly for what is left), 1 = two, 0 = one
   long long ecfft_fold = 1;     // DVP_ECFFT_FOLD: enter / exit fold their pointwise stages into the first / last pass of their extends (0 = the separate launches of rounds 1-5: the parity tests run both)
   long long msm_accum_fast = 1;  // DVP_MSM_ACCUM_FAST: the fan-in-K reducer's first level without exceptional branches, exceptional tasks redone from a list (0 = the general kernel of rounds 1-5)

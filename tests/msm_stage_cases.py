@@ -1,4 +1,4 @@
-"""The MSM bucket pipeline restated stage by stage in plain Python, from the comments of csrc/msm.hip (not from its code), and the parser
+"""The MSM bucket pipeline restated stage by stage in plain Python, from the comments of csrc/msm.hip and its stage headers msm_*.cuh (not from their code), and the parser
 of the stage capture (dvp_debug_msm_capture_arm / _fetch, include/dvpari_internal.h).  Nothing here touches a device.
 
 Every base of a test is k_i G with a known k_i, so every point the pipeline ever holds has a known discrete logarithm modulo the group

@@ -1,4 +1,4 @@
-"""GPU parity tests (-m gpu) of the pair rounds' two forms (msm.hip: k_affine_round, k_round_desc_all):
+"""GPU parity tests (-m gpu) of the pair rounds' two forms (msm_rounds.cuh: k_affine_round, k_round_desc_all):
   * the numerator multiplied into the prefix in pass 1 (AFF_NUM1, compiled in): every result below goes through it;
   * the later rounds in dense order (DVP_MSM_ROUND_DENSE, default 0): a round's additions in slots [0, A), its odd leftovers behind
     them, two descriptor words per slot -- only with the all-rounds bookkeeping (DVP_MSM_ROUND_PIPELINE 1 / 2, and then only when

@@ -1,4 +1,4 @@
-"""GPU parity tests (-m gpu) of the pair rounds' two forms of the field inversion (msm.hip: k_affine_round, AFF_SHARE_INV):
+"""GPU parity tests (-m gpu) of the pair rounds' two forms of the field inversion (msm_rounds.cuh: k_affine_round, AFF_SHARE_INV):
 one per wave (DVP_MSM_AFF_SHARE_INV=0) or one per workgroup, the waves' running products multiplied up a tree in LDS and the
 inverse handed back down (1: whenever the workgroup has more than one wave; 2: in rounds of at least DVP_MSM_AFF_SHARE_MIN
 planned additions).  The field inverse is exact, so both forms must return the same bytes; every result is also compared with

@@ -44,6 +44,24 @@ def _kernels(text):
     return out
 
 
+def _includers():
+    """header -> the .hip / .cpp sources whose translation unit holds it, through their #include "..." lines and those of the headers"""
+    direct = {f: set(re.findall(r'^#include "(\w+\.(?:cuh|h))"', _text(f), flags=re.M)) for f in SOURCES}
+    out = {}
+    for f in SOURCES:
+        if not f.endswith((".hip", ".cpp")):
+            continue
+        seen, todo = set(), [f]
+        while todo:
+            for h in direct.get(todo.pop(), ()):
+                if h not in seen:
+                    seen.add(h)
+                    todo.append(h)
+        for h in seen:
+            out.setdefault(h, set()).add(f)
+    return out
+
+
 @pytest.fixture(scope="module")
 def names():
     if not os.path.exists(LIB):
@@ -57,14 +75,20 @@ def test_every_kernel_has_a_census_name(names):
     for nm in names:
         f, v = nm.split(":", 1)
         listed.setdefault(f, set()).add(v.split("<", 1)[0])
+    inc = _includers()
     found = 0
     for f in SOURCES:
         for k in _kernels(_text(f)):
             found += 1
-            # a kernel defined in a header is launched from the files that include it
-            where = [f] if f.endswith(".hip") else sorted(listed)
-            assert any(k in listed.get(w, ()) for w in where), (f, k)
-    assert found > 100 and len(_kernels(_text("msm.hip"))) > 40  # the scan itself sees the kernels
+            # a kernel defined in a header is launched from the files that include it: the one source where there is only one (the stage
+            # headers of msm.hip), any listed file where several sources share the header
+            by = sorted(inc.get(f, ()))
+            where = [f] if f.endswith(".hip") else by if len(by) == 1 else sorted(listed)
+            assert any(k in listed.get(w, ()) for w in where), (f, k, where)
+    stages = sorted(f for f in SOURCES if re.fullmatch(r"msm_\w+\.cuh", f))
+    assert len(stages) >= 8 and all(inc.get(h) == {"msm.hip"} for h in stages), {h: inc.get(h) for h in stages}
+    # the scan itself sees the kernels: msm.hip's are its own and those of the headers only it includes
+    assert found > 100 and sum(len(_kernels(_text(f))) for f in ["msm.hip"] + sorted(h for h, by in inc.items() if by == {"msm.hip"})) > 40
 
 
 def test_names_carry_instantiated_arguments(names):
