@@ -262,6 +262,42 @@ def test_sharded_challenge_simulated_ranks(dvp, world):
     assert proof == ref and dvp.srs.verify(td, pub, proof)
 
 
+def test_challenge_equals_partial_over_everything(dvp):
+    """What the comment above dvp_prove_challenge_partial claims: dvp_prove_challenge == part 1 over everything + part 2 on the own
+    record.  Two provers, same SRS, witness and commitment: one runs challenge, the other challenge_partial over (0, m), (0, 4m) and
+    challenge_finish on its single record; alpha, a0 b0 i0 r0 and every K scalar are equal and both proofs are pv.prove's bytes.
+    m = 256 fills one whole 256-lane block of the barycentric reduction (the grid-stride case stays with the full-size test)."""
+    import torch
+
+    inst, pub, prv = dvp.gnark_r1cs.synthetic_dense(8)
+    rnd = random.Random(80)
+    td = dvp.srs.Trapdoor(rnd.randrange(1, o.P), rnd.randrange(1, o.P), rnd.randrange(1, o.P))
+    dev = torch.device("cuda", 0)
+    assignment = torch.from_numpy(dvp.fr.vec([1] + pub + prv).view(np.int64)).to(dev)
+    bes = []
+    for _ in range(2):
+        q = dvp.proving.Prover(inst)
+        q.set_srs(dvp.srs.verifier_runs_setup(q, inst, td))
+        bes.append(dvp.distributed.GpuBackend(q, dev))
+    whole, split = bes
+    m = whole.prover.m
+    assert m == 256
+    ref = whole.prover.prove(pub, prv)
+    for be in bes:
+        be.begin(assignment, True)
+    commit = whole.msm_partial(0, 0, whole.msm_size(0)).clone()
+    whole.challenge(commit)
+    rec = split.challenge_partial(commit, (0, m), (0, 4 * m)).clone()
+    split.challenge_finish(rec.reshape(1, 16), (0, 4 * m))
+    for n in ("alpha", "a0", "b0", "i0", "r0", "ka", "kb", "kr"):
+        assert np.array_equal(split.prover.debug(n), whole.prover.debug(n)), n
+    for be in bes:
+        proof = be.finish(be.msm_partial(1, 0, be.msm_size(1)).clone())
+        assert proof == ref
+        be.prover.close()
+    assert dvp.srs.verify(td, pub, ref)
+
+
 @pytest.mark.parametrize("horner_max_pub", [-1, 0])
 def test_extends_by_vector_simulated_ranks(dvp, horner_max_pub):
     """The extends split by VECTOR over the ranks that need q2 / r2 (SURVEY 8e option A; distributed.prove_sharded from three

@@ -87,6 +87,12 @@ def test_every_kernel_has_a_census_name(names):
             assert any(k in listed.get(w, ()) for w in where), (f, k, where)
     stages = sorted(f for f in SOURCES if re.fullmatch(r"msm_\w+\.cuh", f))
     assert len(stages) >= 8 and all(inc.get(h) == {"msm.hip"} for h in stages), {h: inc.get(h) for h in stages}
+    # the same for prove.hip's phase headers; its kernels live in prove_kernels.cuh and are listed under prove.hip
+    phases = sorted(f for f in SOURCES if re.fullmatch(r"prove_\w+\.cuh", f))
+    assert len(phases) >= 7 and all(inc.get(h) == {"prove.hip"} for h in phases), {h: inc.get(h) for h in phases}
+    prove_kernels = _kernels(_text("prove_kernels.cuh"))
+    assert len(prove_kernels) >= 16 and set(prove_kernels) <= listed["prove.hip"], set(prove_kernels) - listed["prove.hip"]
+    assert not _kernels(_text("prove.hip")) and "k_bary3_partial" not in listed["prove.hip"]
     # the scan itself sees the kernels: msm.hip's are its own and those of the headers only it includes
     assert found > 100 and sum(len(_kernels(_text(f))) for f in ["msm.hip"] + sorted(h for h, by in inc.items() if by == {"msm.hip"})) > 40
 
