@@ -1,7 +1,8 @@
 // Host functions and structs that one translation unit of libdvpari_hip.so defines and another uses, declared ONCE.  Every file that
 // defines or calls one of them includes this header, so a changed signature is a compile error instead of a silently different
 // symbol.  Only the host runtime's API header is needed: the types of the device headers are forward-declared.
-// (The ECFFT context's own view, with extend_inplace / extend_from, is ecfft_internal.h; the C ABI is include/dvpari*.h.)
+// (The ECFFT context -- struct dvp_ecfft with every table built for it, its lock and its destructor -- and extend_inplace / extend_from
+// are ecfft_internal.h; the code behind them is ecfft.hip's stage headers ecfft_*.cuh; the C ABI is include/dvpari*.h.)
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
@@ -17,7 +18,7 @@ struct MsmFixedCtx;
 }  // namespace dvp
 
 // ---- ecfft.hip, prove.hip (the context is a global type of the C ABI) ----------------------------------------------------------
-int ecfft_device_consts(dvp_ecfft* c);
+int ecfft_device_consts(dvp_ecfft* c);  // ecfft_enter_exit.cuh; takes the context's lock
 int ecfft_domain_tables_dev(dvp_ecfft* t, int which, dvp::Fr* d_bar_weights, dvp::Fr* d_zinv_other, hipStream_t st);  // prove.hip
 
 namespace dvp {

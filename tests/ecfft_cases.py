@@ -1,4 +1,4 @@
-"""Which ECFFT kernel variants a size and a knob select, restated from csrc/ecfft.hip (extend_io, enter_core, exit_core) for the
+"""Which ECFFT kernel variants a size and a knob select, restated from csrc/ecfft_extend.cuh (extend_io) and ecfft_enter_exit.cuh (enter_core, exit_core) for the
 launch census: the path tests assert these beside their oracle comparisons."""
 E = "ecfft.hip:"
 FUSE_LOG, TOP_MAX = 11, 9  # layers one k_extend_fused block / one k_extend_top launch covers

@@ -87,6 +87,39 @@ def test_multiblock_extend_enter_exit_vs_oracle(dvp, log_n, shifted):
     t.close()
 
 
+def test_contexts_side_by_side_and_in_succession(dvp):
+    """Every table of an ECFFT context (butterfly constants, x^h, the leaf-8 matrices, enter's and exit's folded tables) belongs to
+    that context alone: trees that live side by side, and a tree created after another was closed -- the allocator may hand it the
+    closed one's address -- each compute their own enter / exit, element for element against the oracle.  A = 2^3 is the smallest size
+    whose enter / exit is the k_leaf_matmul8 pass alone; B = 2^12 has folded levels with enter and exit tables and the one level
+    ext_io_ok refuses (h = 2048); C is B's size on the shifted domain, so a table of B's served to C would show."""
+    oA, oB, oC = co.FFTree(3), co.FFTree(12), co.FFTree(12, True, 13)
+    seeds = iter(range(300, 400))
+
+    def enter(t, ot, what):
+        c = rand_fr_np(t.n, next(seeds))
+        assert np.array_equal(t.enter(c), ot.enter(c)), what
+
+    def exit_(t, ot, what):
+        ev = rand_fr_np(t.n, next(seeds))  # not an enter image
+        assert np.array_equal(t.exit(ev), ot.exit(ev)), what
+
+    A = dvp.ec_fft.FFTree(1 << 3)
+    B = dvp.ec_fft.FFTree(1 << 12)
+    enter(A, oA, "A.enter")
+    enter(B, oB, "B.enter")
+    exit_(A, oA, "A.exit")
+    exit_(B, oB, "B.exit")
+    A.close()
+    C = dvp.ec_fft.FFTree(1 << 12, shift_by_one=True, base_log_n=13)
+    enter(C, oC, "C.enter")
+    exit_(C, oC, "C.exit")
+    enter(B, oB, "B.enter after C")
+    exit_(B, oB, "B.exit after C")
+    for t in (B, C, oA, oB, oC):
+        t.close()
+
+
 def _edge_vectors(n, seed):
     """name -> n canonical values that push the lazy values of the butterflies away from their mean"""
     import fr_cases as fc

@@ -93,6 +93,12 @@ def test_every_kernel_has_a_census_name(names):
     prove_kernels = _kernels(_text("prove_kernels.cuh"))
     assert len(prove_kernels) >= 16 and set(prove_kernels) <= listed["prove.hip"], set(prove_kernels) - listed["prove.hip"]
     assert not _kernels(_text("prove.hip")) and "k_bary3_partial" not in listed["prove.hip"]
+    # and for ecfft.hip's stage headers: every kernel of theirs is listed under ecfft.hip, which defines none itself
+    ecfft = sorted(f for f in SOURCES if re.fullmatch(r"ecfft_\w+\.cuh", f))
+    assert len(ecfft) >= 6 and all(inc.get(h) == {"ecfft.hip"} for h in ecfft), {h: inc.get(h) for h in ecfft}
+    ecfft_kernels = [k for h in ecfft for k in _kernels(_text(h))]
+    assert len(ecfft_kernels) >= 30 and set(ecfft_kernels) <= listed["ecfft.hip"], set(ecfft_kernels) - listed["ecfft.hip"]
+    assert not _kernels(_text("ecfft.hip"))
     # the scan itself sees the kernels: msm.hip's are its own and those of the headers only it includes
     assert found > 100 and sum(len(_kernels(_text(f))) for f in ["msm.hip"] + sorted(h for h, by in inc.items() if by == {"msm.hip"})) > 40
 
