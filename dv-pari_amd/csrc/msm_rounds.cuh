@@ -240,15 +240,23 @@ k_round_desc(const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ off,
 #ifndef AFF_PRIO
 #define AFF_PRIO 1
 #endif
-#ifndef AFF_XY
-#define AFF_XY 1
-#endif
-// 1: pass 1 multiplies the slope's NUMERATOR into the prefix as well -- run * num and run * den are one gf_mul2 against one table of
+// Pass 1 multiplies the slope's NUMERATOR into the prefix as well -- run * num and run * den are one gf_mul2 against one table of
 // `run` --, and pass 2 gets lam = (run num) * inv and the stripped inverse den * inv from one gf_mul2 against `inv`: three table
-// builds per addition.  0: the arithmetic of rounds 1-6 (run * den; then pre * inv | den * inv; then num * dinv: four tables).
-#ifndef AFF_NUM1
-#define AFF_NUM1 1
-#endif
+// builds per addition.  (The compile-time switches back to the arithmetic of rounds 1-6 -- AFF_NUM1 = 0: four tables, AFF_XY = 0: y
+// fetched a slot after x -- went when the rare cases left the slot loops: DESIGN.md and docs/HISTORY.md keep their measurements.)
+//
+// RARE slots.  A pair slot whose addition is not the chord formula -- an operand is infinity (x == 0), or x1 == x2: a doubling or
+// P - P -- does not occur in real use (table points of distinct bases are distinct, and infinity only comes out of P - P), so the
+// straight-line code of the slot loops only DETECTS it (tools/round_isa_budget.py: what a slot executes beside its products) and
+// everything else sits behind wave-uniform branches no wave of a real input takes.  There pass 1 gives a doubling the tangent's
+// den = x, num = y (lambda = x + y / x) and any other rare slot den = 1, num = 0, and says which it was in the free bits of word 7 of
+// the prefix it parks (a field element's word 7 is below 2^9); pass 2 finds the flag in the entry it loads anyway: a doubling goes
+// through the same products with its denominator put right before and lambda after, the others are finished on the spot without
+// arithmetic -- p or q passed on, or infinity for P - P.  The arithmetic is the one these cases always had, so the bytes are too.
+constexpr uint32_t AFF_W7_MASK = 0x1ffu, AFF_W7_DBL = 1u << 30, AFF_W7_SKIP = 1u << 31;
+__device__ __forceinline__ uint32_t aff_or8(const Gf& a) {
+  return ((a.w[0] | a.w[1] | a.w[2]) | (a.w[3] | a.w[4])) | ((a.w[5] | a.w[6]) | a.w[7]);
+}
 __device__ __forceinline__ void aff_set_prio(uint32_t v) {
   switch (v % 3u) {
     case 0: __builtin_amdgcn_s_setprio(0); break;
@@ -318,6 +326,34 @@ struct WaveTrace {
 struct AffSlot {
   uint32_t a, b, o;
 };
+// a whole point.  Signed-digit flavours (first round only: the operands are table entries named by sorted items): bit 31 of an item
+// says "subtract"; -(x, y) = (x, x + y), applied as the point is loaded (one and-xor per word under the sign's mask, no branch)
+template <bool FIRST>
+__device__ __forceinline__ void aff_ld_point(const Aff* __restrict__ pts, uint32_t sm, uint32_t v, Gf& x, Gf& y) {
+  const Aff* p = pts + (v & ~sm);
+  x = p->x;
+  y = p->y;
+  if (FIRST) {
+    const uint32_t neg = 0u - (uint32_t)((v & sm) != 0u);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) y.w[i] = gf_andxor(neg, x.w[i], y.w[i]);
+  }
+}
+// Slot k of a thread is slot sk = k nthr + tid of the round: the loops carry sk along (one addition per slot) for the descriptors, the
+// prefix entries and the outputs.  lim = the round's slots for a thread below nthr, 0 beyond (there sk would name another thread's
+// slot).  The load is unconditional from a clamped index and the VALUE is selected (round 6: returning `none` from an early exit made
+// hipcc select between two ADDRESSES -- &desc[sk] and a private copy of `none`: 16 B of scratch per lane and, worse, a FLAT load per
+// descriptor, which counts on lgkmcnt beside the multiplier's LDS reads).
+template <bool FIRST, bool DENSE>
+__device__ __forceinline__ AffSlot aff_ld_desc(const uint2* __restrict__ desc, int k, int B, uint32_t sk, uint32_t lim) {
+  const bool ok = k >= 0 && k < B && sk < lim;
+  const uint32_t at = ok ? sk : 0u;
+  // first round: the item pair; later rounds: one word per slot, or two on the DENSE path
+  const uint2 d = (FIRST || DENSE) ? desc[at] : make_uint2(((const uint32_t*)desc)[at], 0u);
+  if (FIRST) return AffSlot{ok ? d.x : AFF_NONE, ok ? d.y : AFF_NONE, 0u};
+  const uint32_t a = d.x & ~DESC_PAIR;
+  return AffSlot{ok ? a : AFF_NONE, (ok && (d.x & DESC_PAIR)) ? a + 1 : AFF_NONE, d.y};
+}
 // DENSE (later rounds whose bookkeeping k_round_desc_all<.., true> did): two-word descriptors, additions first, leftovers last
 template <bool FIRST, bool TRACE = false, bool DENSE = false>
 __global__ void __launch_bounds__(EC_TPB) __attribute__((amdgpu_waves_per_eu(3, 3)))
@@ -331,15 +367,9 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
 #if AFF_PRIO
   const uint32_t wslot = __builtin_amdgcn_s_getreg(((4 - 1) << 11) | 4);  // HW_ID.wave_id: this wave's slot in its SIMD
 #endif
-  // signed-digit flavours (first round only: the operands are table entries named by sorted items): bit 31 of an item says
-  // "subtract"; -(x, y) = (x, x + y), applied as the y-coordinate is loaded
   const uint32_t sm = FIRST ? sign_mask : 0u;
   auto ldx = [&](uint32_t v) -> Gf { return pts[v & ~sm].x; };
-  auto ldy = [&](uint32_t v, const Gf& x) -> Gf {
-    Gf y = pts[v & ~sm].y;
-    if (v & sm) y = gf_add(y, x);
-    return y;
-  };
+  auto ldp = [&](uint32_t v, Gf& x, Gf& y) { aff_ld_point<FIRST>(pts, sm, v, x, y); };
   const uint32_t total = *total_ptr;
   const int B = (int)aff_slots_per_thread(total, cap, bmax);
   const uint32_t nthr = (total + B - 1) / B;
@@ -349,77 +379,66 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
   const bool share = (bmax & AFF_SHARE_INV) != 0 && blockDim.x > 64;
   if (share ? blockIdx.x * blockDim.x >= nthr : tid >= nthr) return;
   const bool wave_live = __builtin_amdgcn_readfirstlane(tid & ~63u) < nthr;
-  const uint2 none = make_uint2(AFF_NONE, AFF_NONE);
-  // (round 6: the load is unconditional from a clamped index and the VALUE is selected.  Returning `none` from the early exits made
-  // hipcc select between two ADDRESSES -- &desc[sk] and a private copy of `none`: 16 B of scratch per lane and, worse, a FLAT load per
-  // descriptor, which counts on lgkmcnt beside the multiplier's LDS reads)
-  auto ld_desc = [&](int k) -> AffSlot {
-    const uint32_t sk = (uint32_t)k * nthr + tid;
-    const bool ok = k >= 0 && k < B && sk < total && tid < nthr;  // (tid >= nthr: sk would name another thread's slot)
-    if (FIRST) {
-      uint2 v = none;
-      if (ok) v = desc[sk];
-      return AffSlot{v.x, v.y, 0u};
-    }
-    // later rounds: one word per slot, or two on the DENSE path
-    const uint2 d = DENSE ? desc[ok ? sk : 0u] : make_uint2(((const uint32_t*)desc)[ok ? sk : 0u], 0u);
-    const uint32_t a = d.x & ~DESC_PAIR;
-    return AffSlot{ok ? a : AFF_NONE, (ok && (d.x & DESC_PAIR)) ? a + 1 : AFF_NONE, d.y};
-  };
+  const uint32_t lim = tid < nthr ? total : 0u;
+  auto ld_desc = [&](int k, uint32_t sk) -> AffSlot { return aff_ld_desc<FIRST, DENSE>(desc, k, B, sk, lim); };
   const Gf one = gf_one();
-  // pass 1: the running product of the denominators; AFF_NUM1: and every slot's numerator times the product before it (x and y of a
-  // point share a 64-byte half line: no request more than for x alone).  Without AFF_NUM1 y is touched only when x1 == x2.
-  // A slot that adds nothing (no partner, an infinity, P - P) multiplies the product by one; a wave whose lanes all hold leftovers
-  // -- the top rows of a DENSE round -- skips the product.  Only pairs park a prefix: pass 2 reads it for them alone.
+  // pass 1: the running product of the denominators, and every slot's numerator times the product before it (x and y of a point
+  // share a 64-byte half line: no request more than for x alone).  A slot's operands are consumed -- den = x1 + x2, num = y1 + y2, the
+  // three zero tests -- before the next slot's are asked for INTO THE SAME REGISTERS: nothing is handed down the pipeline by copying.
+  // A lane whose slot is no pair loads point 0 twice, so its den comes out 0 and becomes the one it multiplies with by an OR.
+  // A wave whose lanes all hold leftovers -- the top rows of a DENSE round -- skips loads and product.
   Gf run = one;
   if (wave_live) {
-    AffSlot d0 = ld_desc(0), d1 = ld_desc(1);
-    Gf xa = gf_zero(), xb = gf_zero();
-    if (d0.b != AFF_NONE) { xa = ldx(d0.a); xb = ldx(d0.b); }
-#if AFF_NUM1
-    Gf ya = gf_zero(), yb = gf_zero();
-    if (d0.b != AFF_NONE) { ya = ldy(d0.a, xa); yb = ldy(d0.b, xb); }
-#endif
+    uint32_t sk = tid, sp = tid;  // the slot whose descriptor is asked for next, and slot k itself
+    AffSlot d0 = ld_desc(0, sk);
+    sk += nthr;
+    AffSlot d1 = ld_desc(1, sk);
+    sk += nthr;
+    Gf xa, ya, xb, yb;
+    {
+      const bool p = d0.b != AFF_NONE;
+      ldp(p ? d0.a : 0u, xa, ya);
+      ldp(p ? d0.b : 0u, xb, yb);
+    }
 #pragma unroll 1
     for (int k = 0; k < B; ++k) {
 #if AFF_PRIO
       aff_set_prio(wslot + (uint32_t)k);
 #endif
-      const AffSlot d2 = ld_desc(k + 2);
-      Gf nxa = gf_zero(), nxb = gf_zero();
-      if (d1.b != AFF_NONE) { nxa = ldx(d1.a); nxb = ldx(d1.b); }
-#if AFF_NUM1
-      Gf nya = gf_zero(), nyb = gf_zero();
-      if (d1.b != AFF_NONE) { nya = ldy(d1.a, nxa); nyb = ldy(d1.b, nxb); }
-#endif
       const bool pair = d0.b != AFF_NONE;
-      if (!DENSE || __any(pair)) {
-        Gf den = one;
-#if AFF_NUM1
-        Gf num = gf_zero();
-        if (pair && !gf_is_zero(xa) && !gf_is_zero(xb)) {
-          const Gf dd = gf_add(xa, xb), ys = gf_add(ya, yb);
-          if (!gf_is_zero(dd)) { den = dd; num = ys; }
-          else if (gf_is_zero(ys)) { den = xa; num = ya; }  // doubling: lambda = x + y/x
+      Gf den = gf_add(xa, xb), num = gf_add(ya, yb);
+      const bool ainf = aff_or8(xa) == 0u, binf = aff_or8(xb) == 0u;
+      const bool rare = pair & (ainf | binf | (aff_or8(den) == 0u));
+      bool dbl = false;
+      den.w[0] |= pair ? 0u : 1u;
+      if (__any(rare)) {
+        if (rare) {
+          dbl = !ainf & !binf & (aff_or8(num) == 0u);  // x1 == x2 and y1 == y2
+          den = dbl ? xa : one;
+          num = dbl ? ya : gf_zero();
         }
+      }
+      const AffSlot d2 = ld_desc(k + 2, sk);
+      sk += nthr;
+      {
+        const bool p = d1.b != AFF_NONE;
+        if (!DENSE || __any(p)) {
+          ldp(p ? d1.a : 0u, xa, ya);
+          ldp(p ? d1.b : 0u, xb, yb);
+        }
+      }
+      if (!DENSE || __any(pair)) {
         Gf np, nrun;
         gf_mul2(num, den, run, L, np, nrun);
-        if (pair) prefix[(size_t)k * nthr + tid] = np;
-        run = nrun;
-#else
-        if (pair && !gf_is_zero(xa) && !gf_is_zero(xb)) {
-          Gf dd = gf_add(xa, xb);
-          if (!gf_is_zero(dd)) den = dd;
-          else if (gf_eq(ldy(d0.a, xa), ldy(d0.b, xb))) den = xa;  // doubling: lambda = x + y/x
+        if (__any(rare)) {
+          if (rare) np.w[7] |= dbl ? AFF_W7_DBL : AFF_W7_SKIP;
         }
-        if (pair) prefix[(size_t)k * nthr + tid] = run;
-        run = gf_mul(run, den, L);
-#endif
+        if (pair) prefix[sp] = np;
+        run = nrun;
       }
-      d0 = d1; d1 = d2; xa = nxa; xb = nxb;
-#if AFF_NUM1
-      ya = nya; yb = nyb;
-#endif
+      sp += nthr;
+      d0 = d1;
+      d1 = d2;
     }
   }
   if (TRACE) tr_t1 = wall_clock64();
@@ -462,97 +481,79 @@ k_affine_round(const Aff* __restrict__ pts, const uint2* __restrict__ desc, cons
     inv = gf_mul(aff_x_get(xa, W == 4 ? 4 + (w >> 1) : 2), aff_x_get(xa, w ^ 1u), L);
   }
   if (TRACE) tr_t2 = wall_clock64();
-  // pass 2 (backwards): recover each inverse and finish the addition
+  // pass 2 (backwards): recover each inverse and finish the addition.  The next slot's WHOLE point p and its prefix entry are asked
+  // for a slot ahead (x and y of a point share a 128-byte line, and a y fetched one slot after its x found the line evicted from the
+  // L2 again: 6.3 line requests per addition, 4.3 so); of q only x is wanted -- the numerator is in the prefix already --, and it is
+  // consumed into dd = x1 + x2 before the next one lands in its registers.  A pair runs straight-line code: one gf_mul2, the
+  // squaring, one gf_mul, two stores; a leftover is copied.
   if (wave_live) {
-    AffSlot e0 = ld_desc(B - 1), e1 = ld_desc(B - 2);
-    Gf px = gf_zero(), qx = gf_zero(), pre = one;
-    if (e0.a != AFF_NONE) px = ldx(e0.a);
-    if (e0.b != AFF_NONE) { qx = ldx(e0.b); pre = prefix[(size_t)(B - 1) * nthr + tid]; }
-    // AFF_NUM1: the numerator is in the prefix already, so q's y-coordinate is wanted only where p is infinity or x1 == x2 and is
-    // fetched there (q_y below) instead of riding the pipeline
-#if AFF_XY
-    Gf py = gf_zero();
-    if (e0.a != AFF_NONE) py = ldy(e0.a, px);
-#if !AFF_NUM1
-    Gf qy = gf_zero();
-    if (e0.b != AFF_NONE) qy = ldy(e0.b, qx);
-#endif
-#endif
+    uint32_t sp = (uint32_t)(B - 1) * nthr + tid, sk = sp;
+    auto ld_slot = [&](const AffSlot& e, uint32_t s, Gf& x1, Gf& y1, Gf& x2, Gf& pre) {
+      const bool pair = e.b != AFF_NONE;
+      ldp(e.a != AFF_NONE ? e.a : 0u, x1, y1);
+      x2 = ldx(pair ? e.b : 0u);
+      pre = prefix[pair ? s : 0u];
+    };
+    AffSlot e0 = ld_desc(B - 1, sk);
+    sk -= nthr;
+    AffSlot e1 = ld_desc(B - 2, sk);
+    sk -= nthr;
+    Gf px, py, qx, pre;
+    ld_slot(e0, sp, px, py, qx, pre);
 #pragma unroll 1
     for (int k = B - 1; k >= 0; --k) {
 #if AFF_PRIO
       aff_set_prio(wslot + (uint32_t)k);
 #endif
-      const AffSlot e2 = ld_desc(k - 2);
-#if AFF_XY
-      // the next slot's WHOLE points and prefix product: x and y of a point share a 128-byte line, and a y fetched one slot
-      // after its x (the round-3 pipeline) found the line evicted from the L2 again: 6.3 line requests per addition, 4.3 now
-      Gf npx = gf_zero(), nqx = gf_zero(), npy = gf_zero(), npre = one;
-      if (e1.a != AFF_NONE) { npx = ldx(e1.a); npy = ldy(e1.a, npx); }
-#if AFF_NUM1
-      if (e1.b != AFF_NONE) { nqx = ldx(e1.b); npre = prefix[(size_t)(k - 1) * nthr + tid]; }
-#else
-      Gf nqy = gf_zero();
-      if (e1.b != AFF_NONE) { nqx = ldx(e1.b); nqy = ldy(e1.b, nqx); npre = prefix[(size_t)(k - 1) * nthr + tid]; }
-#endif
-#else
-      // this slot's y-coordinates (needed after the two products of the inverse recovery) ...
-      Gf py = gf_zero();
-      if (e0.a != AFF_NONE) py = ldy(e0.a, px);
-#if !AFF_NUM1
-      Gf qy = gf_zero();
-      if (e0.b != AFF_NONE) qy = ldy(e0.b, qx);
-#endif
-      // ... and the next slot's x-coordinates and prefix product
-      Gf npx = gf_zero(), nqx = gf_zero(), npre = one;
-      if (e1.a != AFF_NONE) npx = ldx(e1.a);
-      if (e1.b != AFF_NONE) { nqx = ldx(e1.b); npre = prefix[(size_t)(k - 1) * nthr + tid]; }
-#endif
-#if AFF_NUM1
-      auto q_y = [&]() -> Gf { return ldy(e0.b, qx); };
-#else
-      auto q_y = [&]() -> Gf { return qy; };
-#endif
-      if (e0.a != AFF_NONE) {
-        const uint32_t sidx = DENSE ? e0.o : (uint32_t)k * nthr + tid;
-        Gf ox = px, oy = py;  // odd leftover, or q == infinity: pass p through
-        if (e0.b != AFF_NONE) {
-          if (gf_is_zero(px)) { ox = qx; oy = q_y(); }
-          else if (!gf_is_zero(qx)) {
-            Gf dd = gf_add(px, qx);
-            const bool same_x = gf_is_zero(dd);
-            const bool dbl = same_x && gf_eq(py, q_y());
-            if (same_x && !dbl) {  // p == -q
-              ox = gf_zero(); oy = gf_zero();
-            } else {
-              Gf den = dbl ? px : dd;
-#if AFF_NUM1
-              Gf lam, inv_next;
-              gf_mul2(pre, den, inv, L, lam, inv_next);  // num/den (pre = num times the product before this slot), and the running inverse stripped of this slot's factor
-              inv = inv_next;
-#else
-              Gf dinv, inv_next;
-              gf_mul2(pre, den, inv, L, dinv, inv_next);  // 1/den, and the running inverse stripped of this slot's factor
-              inv = inv_next;
-              Gf num = dbl ? py : gf_add(py, qy);
-              Gf lam = gf_mul(num, dinv, L);
-#endif
-              if (dbl) lam = gf_add(lam, px);
-              ox = gf_add(gf_add(gf_sqr(lam), lam), dd);  // dd == 0 when doubling (curve a = 0)
-              // y3 = lam (x1 + x3) + x3 + y1   (the same expression covers the doubling)
-              oy = gf_add(gf_add(gf_mul(gf_add(px, ox), lam, L), ox), py);
-            }
+      const bool pair = e0.b != AFF_NONE, flagged = pair & (pre.w[7] > AFF_W7_MASK);
+      const uint32_t sidx = DENSE ? e0.o : sp;
+      Gf dd = gf_add(px, qx);
+      bool add = pair, dbl = false;
+      if (__any(flagged)) {
+        if (flagged) {
+          dbl = (pre.w[7] & AFF_W7_DBL) != 0u;
+          if (dbl) {  // the tangent: the denominator pass 1 used is x (dd is 0 here)
+            pre.w[7] &= AFF_W7_MASK;
+            dd = px;
+          } else {  // p == infinity: q; q == infinity: p; else p == -q: infinity
+            add = false;
+            const bool pinf = aff_or8(px) == 0u, qinf = aff_or8(qx) == 0u;
+            Gf qy, unused;
+            ldp(e0.b, unused, qy);
+            out[sidx].x = pinf ? qx : qinf ? px : gf_zero();
+            out[sidx].y = pinf ? qy : qinf ? py : gf_zero();
           }
         }
-        out[sidx].x = ox; out[sidx].y = oy;
       }
-      e0 = e1; e1 = e2; px = npx; qx = nqx; pre = npre;
-#if AFF_XY
+      const AffSlot e2 = ld_desc(k - 2, sk);
+      sk -= nthr;
+      Gf npx, npy, npre;
+      ld_slot(e1, sp - nthr, npx, npy, qx, npre);
+      if (add) {
+        Gf lam, inv_next;
+        gf_mul2(pre, dd, inv, L, lam, inv_next);  // num/den (pre = num times the product before this slot), and the running inverse stripped of this slot's factor
+        inv = inv_next;
+        if (__any(dbl)) {
+          if (dbl) {  // lambda = x + y / x; x3 = lambda^2 + lambda (curve a = 0)
+            lam = gf_add(lam, px);
+            dd = gf_zero();
+          }
+        }
+        const Gf ox = gf_add(gf_add(gf_sqr(lam), lam), dd);
+        // y3 = lam (x1 + x3) + x3 + y1   (the same expression covers the doubling)
+        const Gf oy = gf_add(gf_add(gf_mul(gf_add(px, ox), lam, L), ox), py);
+        out[sidx].x = ox;
+        out[sidx].y = oy;
+      } else if (e0.a != AFF_NONE && !pair) {  // a bucket's odd leftover: p is passed on
+        out[sidx].x = px;
+        out[sidx].y = py;
+      }
+      sp -= nthr;
+      e0 = e1;
+      e1 = e2;
+      px = npx;
       py = npy;
-#if !AFF_NUM1
-      qy = nqy;
-#endif
-#endif
+      pre = npre;
     }
   }
 #if AFF_PRIO
