@@ -32,57 +32,18 @@
 
 #include "../../include/dvpari.h"
 #include "../../include/dvpari_internal.h"  // dvp_tune_get (DVP_CACHE_REPLICAS)
-#include "fr_wire.cuh"                      // fr_from_be32_words: element 0 and the public inputs of a witness file
+#include "fr.cuh"                           // fr_first_noncanonical: the range check of the 29-byte files
+#include "fr_wire.cuh"                      // fr_from_be32_words: every 32-byte big-endian element
 #include "host_api.h"
 
 namespace {
 
-// p, little-endian 64-bit limbs (src/curve.rs:17)
-const uint64_t P64[4] = {0x6efb1ad5f173abdfull, 0x00069d5bb915bcd4ull, 0x0000000000000000ull, 0x0000008000000000ull};
-
-struct U256 {
-  uint64_t w[4];
-};
-inline bool geq(const U256& a, const U256& b) {
-  for (int i = 3; i >= 0; --i)
-    if (a.w[i] != b.w[i]) return a.w[i] > b.w[i];
-  return true;
-}
-inline void sub(U256& a, const U256& b) {
-  uint64_t br = 0;
-  for (int i = 0; i < 4; ++i) {
-    uint64_t d = a.w[i] - b.w[i], d2 = d - br;
-    br = (uint64_t)(a.w[i] < b.w[i]) | (uint64_t)(d < br);
-    a.w[i] = d2;
-  }
-}
-inline U256 shl(const U256& a, int k) {  // k < 64
-  if (k == 0) return a;
-  U256 r;
-  for (int i = 3; i >= 0; --i) r.w[i] = (a.w[i] << k) | (i ? a.w[i - 1] >> (64 - k) : 0);
-  return r;
-}
-// from_be_bytes_mod_order on 32 bytes: x < 2^256, p has 232 bits -> 25 conditional subtractions
-inline void be32_mod_p(const uint8_t* be, uint64_t out[4]) {
-  U256 x;
-  for (int i = 0; i < 4; ++i) {
-    uint64_t v = 0;
-    for (int j = 0; j < 8; ++j) v = (v << 8) | be[8 * (3 - i) + j];
-    x.w[i] = v;
-  }
-  U256 p;
-  memcpy(p.w, P64, 32);
-  for (int k = 24; k >= 0; --k) {
-    U256 s = shl(p, k);
-    if (geq(x, s)) sub(x, s);
-  }
-  memcpy(out, x.w, 32);
-}
-inline bool canonical(const uint64_t v[4]) {
-  U256 a, p;
-  memcpy(a.w, v, 32);
-  memcpy(p.w, P64, 32);
-  return !geq(a, p);
+// from_be_bytes_mod_order on 32 big-endian bytes at any address (gnark_element_to_fr): fr_wire.cuh's reduction, on the host
+inline void be32_to_fr(const uint8_t* be, uint64_t out[4]) {
+  uint32_t w[8], r[8];
+  memcpy(w, be, 32);
+  dvp::fr_from_be32_words(w, r);
+  memcpy(out, r, 32);
 }
 
 struct Mapped {
@@ -185,7 +146,7 @@ int dump_scan(const uint8_t* buf, size_t len, DumpView* v) {
 }
 
 void dump_fill(const DumpView& v, uint64_t* coeffs, uint32_t* const row_ptr[3], uint32_t* const wire[3], uint32_t* const coeff[3]) {
-  for (uint32_t i = 0; i < v.n_coeffs; ++i) be32_mod_p(v.coeffs + 32 * (size_t)i, coeffs + 4 * (size_t)i);
+  for (uint32_t i = 0; i < v.n_coeffs; ++i) be32_to_fr(v.coeffs + 32 * (size_t)i, coeffs + 4 * (size_t)i);
   const uint8_t* q = v.rows;
   uint32_t pos[3] = {0, 0, 0};
   for (int k = 0; k < 3; ++k) row_ptr[k][0] = 0;
@@ -287,7 +248,7 @@ extern "C" int dvp_file_fr_vec_write(const char* path, const uint64_t* limbs, si
   if (!path || (!limbs && n)) return DVP_EINVAL;
   std::vector<uint8_t> packed(n * 29);
   for (size_t i = 0; i < n; ++i) {
-    if (!canonical(limbs + 4 * i)) return DVP_EINVAL;
+    if (dvp::fr_first_noncanonical(limbs + 4 * i, 1) != 1) return DVP_EINVAL;
     memcpy(packed.data() + 29 * i, limbs + 4 * i, 29);  // little-endian host: the low 29 bytes of the 32
   }
   return write_counted(path, nullptr, n, 29, &packed);
@@ -308,7 +269,7 @@ extern "C" int dvp_file_fr_vec_read(const char* path, uint64_t* out, size_t cap,
     memcpy(v, pl + 29 * i, 29);
     // deserialize_uncompressed_unchecked (src/io_utils.rs:160) does not range-check; this boundary carries
     // canonical values only, so a value >= p is rejected instead of being passed on
-    if (!canonical(v)) return DVP_EINVAL;
+    if (dvp::fr_first_noncanonical(v, 1) != 1) return DVP_EINVAL;
     memcpy(out + 4 * i, v, 32);
   }
   return DVP_OK;
@@ -344,7 +305,7 @@ extern "C" int dvp_file_witness_read(const char* path, uint64_t* out, size_t cap
   *n = cnt;
   if (!out) return DVP_OK;
   if (cap < cnt) return DVP_EINVAL;
-  for (uint32_t i = 0; i < cnt; ++i) be32_mod_p(f.p + 4 + 32 * (size_t)i, out + 4 * (size_t)i);  // gnark_element_to_fr
+  for (uint32_t i = 0; i < cnt; ++i) be32_to_fr(f.p + 4 + 32 * (size_t)i, out + 4 * (size_t)i);  // gnark_element_to_fr
   return DVP_OK;
 }
 
@@ -540,12 +501,7 @@ extern "C" int dvp_prove_cache_dir_witness_file(const char* cache_dir, uint32_t 
   if ((f.len - 4) / 32 < cnt) return DVP_EIO;
   if (cnt < 1 + (uint64_t)n_public) return DVP_EINVAL;  // [1, public.., private..]
   const uint8_t* payload = f.p + 4;
-  auto reduce = [&](size_t i, uint64_t out[4]) {
-    uint32_t be[8], r[8];
-    memcpy(be, payload + 32 * i, 32);
-    dvp::fr_from_be32_words(be, r);
-    memcpy(out, r, 32);
-  };
+  auto reduce = [&](size_t i, uint64_t out[4]) { be32_to_fr(payload + 32 * i, out); };
   if (!dvp::fr_be32_is_one(payload)) {  // the constant wire (src/proving.rs:449-452)
     dvp::g_last_error_index = 0;
     return DVP_EINVAL;

@@ -13,10 +13,8 @@
 //   P = (x,y) that is  w = sqrt(x + y/x + 1)  (lambda-coordinate of P plus one); neutral -> 0.
 //   Decoding: e = w^2 + w, solve x^2 + e x + 1 = 0 (half-trace), roots are x(P) and x(P+N) = 1/x;
 //   y = x (w^2 + 1 + x); keep the root whose point lies in E[r] = 4E (two trace tests).
-#include <algorithm>
 #include <atomic>
 #include <cstdlib>
-#include <mutex>
 
 #include "common.h"
 #include "k233.cuh"
@@ -216,50 +214,33 @@ static int codec_rule() {
 
 int codec_rule_now() { return codec_rule(); }  // verify.hip
 
-static std::mutex g_gen_mu;
-static Aff* g_gen_tab[16] = {nullptr};
+static PerDevice<Aff> g_gen_tab;
 
 int gen_table(const Aff** out, hipStream_t st) {
-  int dev;
-  DVP_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return DVP_EINVAL;
-  std::lock_guard<std::mutex> g(g_gen_mu);
-  if (!g_gen_tab[dev]) {
-    Aff* t;
-    size_t cnt = (size_t)GEN_W << GEN_C;
-    DVP_HIP(hipMalloc((void**)&t, cnt * sizeof(Aff)));
-    DVP_LAUNCH(k_gen_table, dim3(cdiv(cnt, 256)), dim3(256), 0, st, t);
+  Aff* tab;
+  DVP_TRY(g_gen_tab.get(&tab, [&](Aff** t) -> int {
+    const size_t cnt = (size_t)GEN_W << GEN_C;
+    DVP_HIP(hipMalloc((void**)t, cnt * sizeof(Aff)));
+    DVP_LAUNCH(k_gen_table, dim3(cdiv(cnt, 256)), dim3(256), 0, st, *t);
     DVP_HIP(hipGetLastError());
     DVP_HIP(hipStreamSynchronize(st));
-    g_gen_tab[dev] = t;
-  }
-  *out = g_gen_tab[dev];
-  return DVP_OK;
-}
-
-static int read_err(unsigned long long* d_err, hipStream_t st, int code) {
-  unsigned long long e;
-  DVP_HIP(hipMemcpyAsync(&e, d_err, 8, hipMemcpyDeviceToHost, st));
-  DVP_HIP(hipStreamSynchronize(st));
-  if (e != ~0ull) {
-    g_last_error_index = (int64_t)e;
-    return code;
-  }
+    return DVP_OK;
+  }));
+  *out = tab;
   return DVP_OK;
 }
 
 int mulgen_dev(const void* d_scalars, size_t n, Aff* d_out, uint8_t* d_inf, hipStream_t st) {
   const Aff* tab;
   DVP_TRY(gen_table(&tab, st));
-  DevBuf err;
-  DVP_TRY(err.alloc(8));
-  DVP_HIP(hipMemsetAsync(err.p, 0xff, 8, st));
+  ErrWord err;
+  DVP_TRY(err.arm(st));
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
   DVP_LAUNCH(k_mulgen, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, (const uint32_t*)d_scalars, n, tab, T, d_out,
-                     d_inf, err.as<unsigned long long>());
+                     d_inf, err.word());
   DVP_HIP(hipGetLastError());
-  return read_err(err.as<unsigned long long>(), st, DVP_EINVAL);
+  return err.verdict(st, DVP_EINVAL);
 }
 
 int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out, hipStream_t st) {
@@ -279,21 +260,18 @@ int encode_point_dev(const Aff* d_pt, const uint32_t* d_inf32, uint8_t* d_out, h
 }
 
 int decode_dev(const uint8_t* d_enc, size_t n, Aff* d_out, uint8_t* d_inf, hipStream_t st) {
-  DevBuf err;
-  DVP_TRY(err.alloc(8));
-  DVP_HIP(hipMemsetAsync(err.p, 0xff, 8, st));
+  ErrWord err;
+  DVP_TRY(err.arm(st));
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
-  DVP_LAUNCH(k_decode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, d_enc, n, T, d_out, d_inf,
-                     err.as<unsigned long long>(), codec_rule());
+  DVP_LAUNCH(k_decode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, st, d_enc, n, T, d_out, d_inf, err.word(), codec_rule());
   DVP_HIP(hipGetLastError());
-  return read_err(err.as<unsigned long long>(), st, DVP_EDECODE);
+  return err.verdict(st, DVP_EDECODE);
 }
 
 // enqueue only: d_summary (16 bytes) is reset here, then k_points_check fills it
 int points_check_dev(const void* d_xy, const void* d_inf, size_t n, void* d_classes, void* d_summary, hipStream_t st) {
-  DVP_HIP(hipMemsetAsync(d_summary, 0xff, 8, st));
-  DVP_HIP(hipMemsetAsync((char*)d_summary + 8, 0, 8, st));
+  DVP_TRY(summary_reset(d_summary, st));
   if (!n) return DVP_OK;
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
@@ -305,18 +283,10 @@ int points_check_dev(const void* d_xy, const void* d_inf, size_t n, void* d_clas
 
 // the check and its verdict: waits for `st`.  DVP_EPOINT with g_last_error_index = the first bad point
 int points_check_wait(const void* d_xy, const void* d_inf, size_t n, void* d_classes, size_t* n_bad, hipStream_t st) {
-  DevBuf sum;
+  ErrWord sum;
   DVP_TRY(sum.alloc(16));
-  DVP_TRY(points_check_dev(d_xy, d_inf, n, d_classes, sum.p, st));
-  unsigned long long s[2];
-  DVP_HIP(hipMemcpyAsync(s, sum.p, 16, hipMemcpyDeviceToHost, st));
-  DVP_HIP(hipStreamSynchronize(st));
-  if (n_bad) *n_bad = (size_t)s[1];
-  if (s[0] != ~0ull) {
-    g_last_error_index = (int64_t)s[0];
-    return DVP_EPOINT;
-  }
-  return DVP_OK;
+  DVP_TRY(points_check_dev(d_xy, d_inf, n, d_classes, sum.p, st));  // resets the summary
+  return sum.verdict(st, DVP_EPOINT, n_bad);
 }
 
 // strict mode: DVP_POINTS_STRICT from the environment at first use, dvp_points_set_strict at run time
@@ -359,46 +329,37 @@ extern "C" int dvp_mulgen_batch_affine(const uint64_t* scalars, size_t n, uint64
   if (!n) return DVP_OK;
   if (!scalars || !out_xy || !out_inf) return DVP_EINVAL;
   DevBuf ds, dp, di;
-  DVP_TRY(ds.alloc(n * 32));
+  DVP_TRY(ds.up(scalars, n * 32));
   DVP_TRY(dp.alloc(n * 64));
   DVP_TRY(di.alloc(n));
-  DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
   DVP_TRY(mulgen_dev(ds.p, n, dp.as<Aff>(), di.as<uint8_t>(), 0));
-  DVP_HIP(hipMemcpy(out_xy, dp.p, n * 64, hipMemcpyDeviceToHost));
-  DVP_HIP(hipMemcpy(out_inf, di.p, n, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  DVP_TRY(dp.down(out_xy, n * 64));
+  return di.down(out_inf, n);
 }
 
 extern "C" int dvp_mulgen_batch(const uint64_t* scalars, size_t n, uint8_t* out_enc) {
   if (!n) return DVP_OK;
   if (!scalars || !out_enc) return DVP_EINVAL;
   DevBuf ds, dp, di, de;
-  DVP_TRY(ds.alloc(n * 32));
+  DVP_TRY(ds.up(scalars, n * 32));
   DVP_TRY(dp.alloc(n * 64));
   DVP_TRY(di.alloc(n));
   DVP_TRY(de.alloc(n * 30));
-  DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
   DVP_TRY(mulgen_dev(ds.p, n, dp.as<Aff>(), di.as<uint8_t>(), 0));
   DVP_TRY(encode_dev(dp.as<Aff>(), di.as<uint8_t>(), n, de.as<uint8_t>(), 0));
-  DVP_HIP(hipMemcpy(out_enc, de.p, n * 30, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return de.down(out_enc, n * 30);
 }
 
 extern "C" int dvp_points_encode(const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_enc) {
   if (!n) return DVP_OK;
   if (!xy || !out_enc) return DVP_EINVAL;
   DevBuf dp, di, de;
-  DVP_TRY(dp.alloc(n * 64));
+  DVP_TRY(dp.up(xy, n * 64));
+  DVP_TRY(di.up_opt(inf, n));
   DVP_TRY(de.alloc(n * 30));
-  DVP_HIP(hipMemcpy(dp.p, xy, n * 64, hipMemcpyHostToDevice));
-  if (inf) {
-    DVP_TRY(di.alloc(n));
-    DVP_HIP(hipMemcpy(di.p, inf, n, hipMemcpyHostToDevice));
-  }
   DVP_TRY(points_check_strict(dp.p, di.p, n, 0));
   DVP_TRY(encode_dev(dp.as<Aff>(), di.as<uint8_t>(), n, de.as<uint8_t>(), 0));
-  DVP_HIP(hipMemcpy(out_enc, de.p, n * 30, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return de.down(out_enc, n * 30);
 }
 
 extern "C" int dvp_points_add(const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, size_t n,
@@ -406,28 +367,19 @@ extern "C" int dvp_points_add(const uint64_t* a_xy, const uint8_t* a_inf, const 
   if (!n) return DVP_OK;
   if (!a_xy || !b_xy || !out_xy || !out_inf) return DVP_EINVAL;
   DevBuf da, db, dai, dbi, dout, doi;
-  DVP_TRY(da.alloc(n * 64));
-  DVP_TRY(db.alloc(n * 64));
+  DVP_TRY(da.up(a_xy, n * 64));
+  DVP_TRY(db.up(b_xy, n * 64));
+  DVP_TRY(dai.up_opt(a_inf, n));
+  DVP_TRY(dbi.up_opt(b_inf, n));
   DVP_TRY(dout.alloc(n * 64));
   DVP_TRY(doi.alloc(n));
-  DVP_HIP(hipMemcpy(da.p, a_xy, n * 64, hipMemcpyHostToDevice));
-  DVP_HIP(hipMemcpy(db.p, b_xy, n * 64, hipMemcpyHostToDevice));
-  if (a_inf) {
-    DVP_TRY(dai.alloc(n));
-    DVP_HIP(hipMemcpy(dai.p, a_inf, n, hipMemcpyHostToDevice));
-  }
-  if (b_inf) {
-    DVP_TRY(dbi.alloc(n));
-    DVP_HIP(hipMemcpy(dbi.p, b_inf, n, hipMemcpyHostToDevice));
-  }
   DVP_TRY(points_check_strict(da.p, dai.p, n, 0));  // operand a first: the index is b's only when a is clean
   DVP_TRY(points_check_strict(db.p, dbi.p, n, 0));
   DVP_LAUNCH(k_points_add, dim3(cdiv(n, 128)), dim3(128), 0, 0, da.as<Aff>(), dai.as<uint8_t>(), db.as<Aff>(), dbi.as<uint8_t>(), n,
                      dout.as<Aff>(), doi.as<uint8_t>());
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out_xy, dout.p, n * 64, hipMemcpyDeviceToHost));
-  DVP_HIP(hipMemcpy(out_inf, doi.p, n, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  DVP_TRY(dout.down(out_xy, n * 64));
+  return doi.down(out_inf, n);
 }
 
 extern "C" int dvp_points_decode(const uint8_t* enc, size_t n, uint64_t* out_xy, uint8_t* out_inf) {
@@ -436,11 +388,11 @@ extern "C" int dvp_points_decode(const uint8_t* enc, size_t n, uint64_t* out_xy,
   DevBuf dp, di, de;
   DVP_TRY(dp.alloc(n * 64));
   DVP_TRY(di.alloc(n));
-  DVP_TRY(de.alloc(n * 30));
-  DVP_HIP(hipMemcpy(de.p, enc, n * 30, hipMemcpyHostToDevice));
-  int rc = decode_dev(de.as<uint8_t>(), n, dp.as<Aff>(), di.as<uint8_t>(), 0);
-  DVP_HIP(hipMemcpy(out_xy, dp.p, n * 64, hipMemcpyDeviceToHost));
-  DVP_HIP(hipMemcpy(out_inf, di.p, n, hipMemcpyDeviceToHost));
+  DVP_TRY(de.up(enc, n * 30));
+  const int rc = decode_dev(de.as<uint8_t>(), n, dp.as<Aff>(), di.as<uint8_t>(), 0);
+  // the outputs go back even when an encoding was bad (DVP_EDECODE): that lane is flagged, the others hold their points
+  DVP_TRY(dp.down(out_xy, n * 64));
+  DVP_TRY(di.down(out_inf, n));
   return rc;
 }
 
@@ -448,15 +400,11 @@ extern "C" int dvp_points_check(const uint64_t* xy, const uint8_t* inf, size_t n
   if (!n) return DVP_OK;
   if (!xy) return DVP_EINVAL;
   DevBuf dp, di, dc;
-  DVP_TRY(dp.alloc(n * 64));
-  DVP_HIP(hipMemcpy(dp.p, xy, n * 64, hipMemcpyHostToDevice));
-  if (inf) {
-    DVP_TRY(di.alloc(n));
-    DVP_HIP(hipMemcpy(di.p, inf, n, hipMemcpyHostToDevice));
-  }
+  DVP_TRY(dp.up(xy, n * 64));
+  DVP_TRY(di.up_opt(inf, n));
   if (classes) DVP_TRY(dc.alloc(n));
-  int rc = points_check_wait(dp.p, di.p, n, dc.p, n_bad, 0);
-  if (classes && (rc == DVP_OK || rc == DVP_EPOINT)) DVP_HIP(hipMemcpy(classes, dc.p, n, hipMemcpyDeviceToHost));
+  const int rc = points_check_wait(dp.p, di.p, n, dc.p, n_bad, 0);
+  if (classes && (rc == DVP_OK || rc == DVP_EPOINT)) DVP_TRY(dc.down(classes, n));  // a bad point is a finding: its classes go back with it
   return rc;
 }
 
@@ -480,35 +428,18 @@ extern "C" int dvp_ubench_points_check(const void* d_xy, const void* d_inf, cons
   DevBuf sum;
   DVP_TRY(sum.alloc(16));
   DVP_HIP(hipMemset(sum.p, 0xff, 16));
-  hipEvent_t e0, e1;
-  DVP_HIP(hipEventCreate(&e0));
-  DVP_HIP(hipEventCreate(&e1));
   const int rule = codec_rule();
-  float t[2][99];
-  hipError_t err = hipSuccess;
-  for (int k = 0; k < 2 && err == hipSuccess; ++k)
-    for (int r = -1; r < reps && err == hipSuccess; ++r) {
-      (void)hipEventRecord(e0, 0);
-      if (k == 0)
-        DVP_LAUNCH(k_points_check, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const Aff*)d_xy, (const uint8_t*)d_inf, n, T,
-                           (uint8_t*)nullptr, sum.as<unsigned long long>());
-      else
-        DVP_LAUNCH(k_decode, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint8_t*)d_enc, n, T, (Aff*)d_scratch,
-                           (uint8_t*)d_scratch + n * 64, sum.as<unsigned long long>(), rule);
-      err = hipGetLastError();
-      (void)hipEventRecord(e1, 0);
-      if (err == hipSuccess) err = hipEventSynchronize(e1);
-      float ms = 0;
-      if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-      if (r >= 0) t[k][r] = ms;
-    }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (err != hipSuccess) return hip_fail(err, "dvp_ubench_points_check", __FILE__, __LINE__);
-  for (int k = 0; k < 2; ++k) std::sort(t[k], t[k] + reps);
-  *check_ms = t[0][reps / 2];
-  *decode_ms = t[1][reps / 2];
-  return DVP_OK;
+  const dim3 grid(cdiv(n, 256)), block(256);
+  DVP_TRY(median_ms(reps, "dvp_ubench_points_check", [&]() -> int {
+    DVP_LAUNCH(k_points_check, grid, block, 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const Aff*)d_xy, (const uint8_t*)d_inf, n, T, (uint8_t*)nullptr,
+                       sum.as<unsigned long long>());
+    return DVP_OK;
+  }, check_ms));
+  return median_ms(reps, "dvp_ubench_points_check", [&]() -> int {
+    DVP_LAUNCH(k_decode, grid, block, 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint8_t*)d_enc, n, T, (Aff*)d_scratch, (uint8_t*)d_scratch + n * 64,
+                       sum.as<unsigned long long>(), rule);
+    return DVP_OK;
+  }, decode_ms);
 }
 
 // dvp_points_mul_dev (its two 8-byte fills and k_points_mul at the width in force) and k_mulgen alone on the same scalars and count, device
@@ -522,35 +453,14 @@ extern "C" int dvp_ubench_points_mul(const void* d_scalars, const void* d_xy, si
   DevBuf sum;
   DVP_TRY(sum.alloc(16));
   DVP_HIP(hipMemset(sum.p, 0xff, 16));
-  hipEvent_t e0, e1;
-  DVP_HIP(hipEventCreate(&e0));
-  DVP_HIP(hipEventCreate(&e1));
-  float t[2][99];
-  hipError_t err = hipSuccess;
-  int rc = DVP_OK;
-  for (int k = 0; k < 2 && err == hipSuccess && rc == DVP_OK; ++k)
-    for (int r = -1; r < reps && err == hipSuccess && rc == DVP_OK; ++r) {
-      (void)hipEventRecord(e0, 0);
-      if (k == 0)
-        rc = points_mul_dev(d_scalars, n, d_xy, nullptr, n, d_scratch, (uint8_t*)d_scratch + n * 64, sum.p, 0);
-      else
-        DVP_LAUNCH(k_mulgen, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint32_t*)d_scalars, n, tab, T, (Aff*)d_scratch,
-                           (uint8_t*)d_scratch + n * 64, sum.as<unsigned long long>());
-      err = hipGetLastError();
-      (void)hipEventRecord(e1, 0);
-      if (err == hipSuccess) err = hipEventSynchronize(e1);
-      float ms = 0;
-      if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-      if (r >= 0) t[k][r] = ms;
-    }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (rc != DVP_OK) return rc;
-  if (err != hipSuccess) return hip_fail(err, "dvp_ubench_points_mul", __FILE__, __LINE__);
-  for (int k = 0; k < 2; ++k) std::sort(t[k], t[k] + reps);
-  *mul_ms = t[0][reps / 2];
-  *mulgen_ms = t[1][reps / 2];
-  return DVP_OK;
+  DVP_TRY(median_ms(reps, "dvp_ubench_points_mul", [&]() -> int {
+    return points_mul_dev(d_scalars, n, d_xy, nullptr, n, d_scratch, (uint8_t*)d_scratch + n * 64, sum.p, 0);
+  }, mul_ms));
+  return median_ms(reps, "dvp_ubench_points_mul", [&]() -> int {
+    DVP_LAUNCH(k_mulgen, dim3(cdiv(n, 256)), dim3(256), 4 * GF_LDSK_BYTES_PER_WAVE, 0, (const uint32_t*)d_scalars, n, tab, T, (Aff*)d_scratch,
+                       (uint8_t*)d_scratch + n * 64, sum.as<unsigned long long>());
+    return DVP_OK;
+  }, mulgen_ms);
 }
 
 // scalars: n x 32 B canonical LE (ark: as arkworks holds them, converted in the device buffer they were copied into, fr_ark.hip);
@@ -558,26 +468,20 @@ extern "C" int dvp_ubench_points_mul(const void* d_scalars, const void* d_xy, si
 static int msm_xsk233(const uint8_t* scalars, bool ark, const uint8_t* bases_enc, size_t n, uint8_t out_enc[30]) {
   if ((n && (!scalars || !bases_enc)) || !out_enc) return DVP_EINVAL;
   DevBuf ds, dp, di, de, dout;
-  DVP_TRY(ds.alloc(n * 32));
+  MsmResult sum;
+  DVP_TRY(ds.up(scalars, n * 32));  // a byte copy: the scalars may sit at any address
+  DVP_TRY(de.up(bases_enc, n * 30));
   DVP_TRY(dp.alloc(n * 64));
   DVP_TRY(di.alloc(n));
-  DVP_TRY(de.alloc(n * 30 + 32));
-  DVP_TRY(dout.alloc(64 + 16));
+  DVP_TRY(dout.alloc(30));
+  DVP_TRY(sum.init());
   if (n) {
-    DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
     if (ark) DVP_TRY(dvp_fr_from_ark_dev(ds.p, n, ds.p, nullptr));
-    DVP_HIP(hipMemcpy(de.p, bases_enc, n * 30, hipMemcpyHostToDevice));
     DVP_TRY(decode_dev(de.as<uint8_t>(), n, dp.as<Aff>(), di.as<uint8_t>(), 0));
   }
-  DVP_TRY(msm_affine_dev(ds.p, dp.p, di.p, n, MsmOut{dout.p, (char*)dout.p + 64}, 0));
-  // the infinity flag of the result is a u32; k_encode wants a byte mask
-  uint32_t inf32;
-  DVP_HIP(hipMemcpy(&inf32, (char*)dout.p + 64, 4, hipMemcpyDeviceToHost));
-  uint8_t inf8 = inf32 ? 1 : 0;
-  DVP_HIP(hipMemcpy((char*)dout.p + 72, &inf8, 1, hipMemcpyHostToDevice));
-  DVP_TRY(encode_dev(dout.as<Aff>(), (uint8_t*)dout.p + 72, 1, de.as<uint8_t>(), 0));
-  DVP_HIP(hipMemcpy(out_enc, de.p, 30, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  DVP_TRY(msm_affine_dev(ds.p, dp.p, di.p, n, sum.out(), 0));
+  DVP_TRY(encode_dev(sum.as<Aff>(), sum.inf8(), 1, dout.as<uint8_t>(), 0));
+  return dout.down(out_enc, 30);
 }
 extern "C" int dvp_msm_xsk233(const uint8_t* scalars, const uint8_t* bases_enc, size_t n, uint8_t out_enc[30]) {
   return msm_xsk233(scalars, false, bases_enc, n, out_enc);

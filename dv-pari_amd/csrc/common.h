@@ -3,12 +3,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
+#include <algorithm>
 #include <atomic>
+#include <mutex>
 #include <typeinfo>
 #include <vector>
 
 #include "../../include/dvpari_internal.h"
+#include "fr.cuh"
 #include "host_api.h"
 
 namespace dvp {
@@ -68,7 +72,137 @@ struct DevBuf {
   T* as() const {
     return reinterpret_cast<T*>(p);
   }
+  // ---- staging of the host-pointer flavours: allocate and copy up (0 bytes allocates 16 and copies nothing), copy down ----
+  int up(const void* host, size_t n) {
+    DVP_TRY(alloc(n));
+    if (n) DVP_HIP(hipMemcpy(p, host, n, hipMemcpyHostToDevice));
+    return DVP_OK;
+  }
+  // an optional input, which is what every `inf` argument is: a null host pointer leaves p null
+  int up_opt(const void* host, size_t n) { return host ? up(host, n) : DVP_OK; }
+  int down(void* host, size_t n) const {
+    DVP_HIP(hipMemcpy(host, p, n, hipMemcpyDeviceToHost));
+    return DVP_OK;
+  }
 };
+
+// the host range check of an entry's n scalars (32 little-endian bytes each, any alignment): DVP_EINVAL with g_last_error_index = the
+// first one that is not below p
+inline int scalars_in_range(const void* le32, size_t n) {
+  const size_t bad = fr_first_noncanonical(le32, n);
+  if (bad == n) return DVP_OK;
+  g_last_error_index = (int64_t)bad;
+  return DVP_EINVAL;
+}
+
+// the 80-byte result of an MSM: x || y (64 bytes), then the infinity flag as a u32 that holds 0 or 1
+struct MsmResult : DevBuf {
+  int init() { return alloc(80); }
+  void* inf() const { return (char*)p + 64; }
+  MsmOut out() const { return MsmOut{p, inf()}; }
+  const uint8_t* inf8() const { return (const uint8_t*)inf(); }  // little-endian: the flag's first byte is the byte mask the codec kernels take
+  int down(uint64_t out_xy[8], int* out_is_infinity) const {
+    uint32_t r[20];
+    DVP_TRY(DevBuf::down(r, sizeof r));
+    memcpy(out_xy, r, 64);
+    *out_is_infinity = (int)r[16];
+    return DVP_OK;
+  }
+};
+
+// a caller's 16-byte summary {u64 first bad index, u64 how many} as a checking kernel expects it: {~0, 0}
+inline int summary_reset(void* d_summary, hipStream_t st) {
+  DVP_HIP(hipMemsetAsync(d_summary, 0xff, 8, st));
+  DVP_HIP(hipMemsetAsync((char*)d_summary + 8, 0, 8, st));
+  return DVP_OK;
+}
+// The "first bad index" word of a call that owns it: armed to ~0 on the stream, lowered by the kernel's atomicMin, read by verdict().
+// It is the first word of a summary, so a kernel that counts (k_points_check) gets the whole of one: reset it with summary_reset.
+struct ErrWord : DevBuf {
+  int arm(hipStream_t st) {
+    DVP_TRY(alloc(16));
+    DVP_HIP(hipMemsetAsync(p, 0xff, 8, st));
+    return DVP_OK;
+  }
+  unsigned long long* word() const { return as<unsigned long long>(); }
+  // waits for `st`: DVP_OK, or `code` with g_last_error_index = the index; count (optional) receives the summary's second word
+  int verdict(hipStream_t st, int code, size_t* count = nullptr) const {
+    unsigned long long s[2] = {~0ull, 0};
+    DVP_HIP(hipMemcpyAsync(s, p, count ? 16 : 8, hipMemcpyDeviceToHost, st));
+    DVP_HIP(hipStreamSynchronize(st));
+    if (count) *count = (size_t)s[1];
+    if (s[0] == ~0ull) return DVP_OK;
+    g_last_error_index = (int64_t)s[0];
+    return code;
+  }
+};
+
+// 256-byte carving of a workspace: take(bytes) gives the next region's offset, take<T>(bytes) its pointer over `base`; o is the total
+struct Carver {
+  uintptr_t base = 0;
+  size_t o = 0;
+  static size_t align(size_t v) { return (v + 255) & ~(size_t)255; }
+  size_t take(size_t bytes) {
+    const size_t at = o;
+    o = align(o + bytes);
+    return at;
+  }
+  template <class T>
+  T* take(size_t bytes) {
+    return (T*)(base + take(bytes));
+  }
+};
+
+// one table per device, built at its first use on that device and kept for the life of the process (gen_table, gf_sqr_tables)
+constexpr int DVP_MAX_DEVICES = 16;
+template <class T>
+struct PerDevice {
+  std::mutex mu;
+  T* tab[DVP_MAX_DEVICES] = {nullptr};
+  // build(T** out): allocate and fill the current device's table, and wait for it
+  template <class F>
+  int get(T** out, F&& build) {
+    int dev;
+    DVP_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= DVP_MAX_DEVICES) return DVP_EINVAL;
+    std::lock_guard<std::mutex> g(mu);
+    if (!tab[dev]) {
+      T* t = nullptr;
+      DVP_TRY(build(&t));
+      tab[dev] = t;
+    }
+    *out = tab[dev];
+    return DVP_OK;
+  }
+};
+
+// median of `reps` (odd, at most 99) timed runs of `launch` on the null stream after one warm-up run, by device events (dvp_ubench_*)
+template <class F>
+int median_ms(int reps, const char* what, F&& launch, double* out_ms) {
+  hipEvent_t e0, e1;
+  DVP_HIP(hipEventCreate(&e0));
+  DVP_HIP(hipEventCreate(&e1));
+  float t[99];
+  hipError_t err = hipSuccess;
+  int rc = DVP_OK;
+  for (int r = -1; r < reps && err == hipSuccess && rc == DVP_OK; ++r) {
+    (void)hipEventRecord(e0, 0);
+    rc = launch();
+    err = hipGetLastError();
+    (void)hipEventRecord(e1, 0);
+    if (err == hipSuccess) err = hipEventSynchronize(e1);
+    float ms = 0;
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+    if (r >= 0) t[r] = ms;
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc != DVP_OK) return rc;
+  if (err != hipSuccess) return hip_fail(err, what, __FILE__, __LINE__);
+  std::sort(t, t + reps);
+  *out_ms = t[reps / 2];
+  return DVP_OK;
+}
 
 // Tuning knobs (tools/README.md).  Defaults are the measured optima; the environment (DVP_MSM_C, ...) is read ONCE, at
 // the first use, and dvp_tune_set / dvp_tune_reset (include/dvpari.h) change a knob at run time -- that is how the tests

@@ -72,18 +72,10 @@ extern "C" uint32_t dvp_ecfft_log2_leaves(const dvp_ecfft* c) { return c ? (uint
 extern "C" int dvp_ecfft_leaves(const dvp_ecfft* c, uint64_t* out) { return layer_to_host(c, 0, out); }
 
 static int check_canonical_dev(const Fr* d, size_t n, hipStream_t st) {
-  DevBuf bad;
-  DVP_TRY(bad.alloc(8));
-  unsigned long long init = ~0ull;
-  DVP_HIP(hipMemcpyAsync(bad.p, &init, 8, hipMemcpyHostToDevice, st));
-  DVP_LAUNCH(k_check_canonical, dim3(cdiv(n, TPB)), dim3(TPB), 0, st, d, n, bad.as<unsigned long long>());
-  DVP_HIP(hipMemcpyAsync(&init, bad.p, 8, hipMemcpyDeviceToHost, st));
-  DVP_HIP(hipStreamSynchronize(st));
-  if (init != ~0ull) {
-    g_last_error_index = (int64_t)init;
-    return DVP_EINVAL;
-  }
-  return DVP_OK;
+  ErrWord bad;
+  DVP_TRY(bad.arm(st));
+  DVP_LAUNCH(k_check_canonical, dim3(cdiv(n, TPB)), dim3(TPB), 0, st, d, n, bad.word());
+  return bad.verdict(st, DVP_EINVAL);
 }
 
 extern "C" int dvp_ecfft_extend_dev(dvp_ecfft* c, const void* d_in, uint32_t batch, void* d_out, void* stream) {
@@ -95,12 +87,10 @@ extern "C" int dvp_ecfft_extend(dvp_ecfft* c, const uint64_t* evals, uint32_t ba
   if (!c || !evals || !out || batch == 0) return DVP_EINVAL;
   size_t bytes = (size_t)batch * (c->n_leaves >> 1) * sizeof(Fr);
   DevBuf buf;
-  DVP_TRY(buf.alloc(bytes));
-  DVP_HIP(hipMemcpy(buf.p, evals, bytes, hipMemcpyHostToDevice));
+  DVP_TRY(buf.up(evals, bytes));
   DVP_TRY(check_canonical_dev(buf.as<Fr>(), bytes / sizeof(Fr), 0));
   DVP_TRY(extend_inplace(c, 0, 0, buf.as<Fr>(), batch, 0));
-  DVP_HIP(hipMemcpy(out, buf.p, bytes, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return buf.down(out, bytes);
 }
 
 // enter / exit on the whole tree: the entries take the context's lock, enter_core / exit_core and the table builders run under it
@@ -119,13 +109,11 @@ static int host_roundtrip(dvp_ecfft* c, const uint64_t* in, uint64_t* out, bool 
   if (!c || !in || !out) return DVP_EINVAL;
   size_t bytes = (size_t)c->n_leaves * sizeof(Fr);
   DevBuf i, o;
-  DVP_TRY(i.alloc(bytes));
+  DVP_TRY(i.up(in, bytes));
   DVP_TRY(o.alloc(bytes));
-  DVP_HIP(hipMemcpy(i.p, in, bytes, hipMemcpyHostToDevice));
   DVP_TRY(check_canonical_dev(i.as<Fr>(), c->n_leaves, 0));
   DVP_TRY(is_exit ? dvp_ecfft_exit_dev(c, i.p, o.p, nullptr) : dvp_ecfft_enter_dev(c, i.p, o.p, nullptr));
-  DVP_HIP(hipMemcpy(out, o.p, bytes, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return o.down(out, bytes);
 }
 extern "C" int dvp_ecfft_enter(dvp_ecfft* c, const uint64_t* coeffs, uint64_t* out) { return host_roundtrip(c, coeffs, out, false); }
 extern "C" int dvp_ecfft_exit(dvp_ecfft* c, const uint64_t* evals, uint64_t* out) { return host_roundtrip(c, evals, out, true); }

@@ -34,8 +34,7 @@ extern "C" int dvp_debug_ecfft_matrices(dvp_ecfft* c, int to_even, int which, ui
   }
   DVP_LAUNCH(k_mats_export, dim3(cdiv(n, TPB)), dim3(TPB), 0, 0, which ? rec.as<Fr29>() : dec.as<Fr29>(), tmp.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out, tmp.p, n * sizeof(Fr), hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return tmp.down(out, n * sizeof(Fr));
 }
 // layer d (N >> d values), out of Montgomery form, to the host (dvp_ecfft_leaves: d = 0)
 static int layer_to_host(const dvp_ecfft* c, uint32_t d, uint64_t* out) {
@@ -45,7 +44,6 @@ static int layer_to_host(const dvp_ecfft* c, uint32_t d, uint64_t* out) {
   DVP_TRY(tmp.alloc(n * sizeof(Fr)));
   DVP_LAUNCH(k_from_mont, dim3(cdiv(n, TPB)), dim3(TPB), 0, 0, c->layer((int)d), tmp.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out, tmp.p, n * sizeof(Fr), hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return tmp.down(out, n * sizeof(Fr));
 }
 extern "C" int dvp_debug_ecfft_layer(const dvp_ecfft* c, uint32_t d, uint64_t* out) { return layer_to_host(c, d, out); }

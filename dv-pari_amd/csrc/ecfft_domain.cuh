@@ -143,10 +143,8 @@ static int ecfft_init(dvp_ecfft* c, uint32_t log_n, int shifted, uint32_t base_l
     std::vector<Fr> tx(log_n), ty(log_n);
     for (uint32_t j = 0; j < log_n; ++j) { tx[j] = tab[j].x; ty[j] = tab[j].y; }
     DevBuf dx, dy;
-    DVP_TRY(dx.alloc(log_n * sizeof(Fr)));
-    DVP_TRY(dy.alloc(log_n * sizeof(Fr)));
-    DVP_HIP(hipMemcpy(dx.p, tx.data(), log_n * sizeof(Fr), hipMemcpyHostToDevice));
-    DVP_HIP(hipMemcpy(dy.p, ty.data(), log_n * sizeof(Fr), hipMemcpyHostToDevice));
+    DVP_TRY(dx.up(tx.data(), log_n * sizeof(Fr)));
+    DVP_TRY(dy.up(ty.data(), log_n * sizeof(Fr)));
     DVP_LAUNCH(k_leaves, dim3(cdiv(N, TPB)), dim3(TPB), 0, 0, dx.as<Fr>(), dy.as<Fr>(), C.x, C.y, (int)log_n,
                        c->layer(0), N);
     for (uint32_t d = 0; d < log_n; ++d) {

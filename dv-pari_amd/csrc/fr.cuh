@@ -10,6 +10,7 @@
 // p = 2^231 + 0x69d5bb915bcd46efb1ad5f173abdf: its 29-bit limbs 4..6 are zero, which the reduction half of
 // the multiplier exploits.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -653,6 +654,17 @@ DVP_HD bool fr_is_canonical(const Fr& a) {
     borrow = (t >> 63) & 1;
   }
   return borrow != 0;
+}
+
+// Host: the first of n 32-byte little-endian values that is not below p, or n.  Each value is read through a copy, so `le32` may sit
+// at any address (the wire formats); a shorter element is checked by zero extension (tree_io.cpp's 29 bytes).
+inline size_t fr_first_noncanonical(const void* le32, size_t n) {
+  for (size_t k = 0; k < n; ++k) {
+    Fr v;
+    __builtin_memcpy(v.v, (const unsigned char*)le32 + 32 * k, 32);
+    if (!fr_is_canonical(v)) return k;
+  }
+  return n;
 }
 
 }  // namespace dvp

@@ -55,11 +55,9 @@ static int ark_host_ptr(bool to_ark, const uint64_t* in, size_t n, uint64_t* out
   if (!n) return DVP_OK;
   if (!in || !out || n > FR_ARK_MAX_N) return DVP_EINVAL;  // before the allocation, not behind it
   DevBuf b;
-  DVP_TRY(b.alloc(n * 32));
-  DVP_HIP(hipMemcpy(b.p, in, n * 32, hipMemcpyHostToDevice));  // any host alignment
+  DVP_TRY(b.up(in, n * 32));  // any host alignment
   DVP_TRY(ark_dev(to_ark, b.p, n, b.p, nullptr));
-  DVP_HIP(hipMemcpy(out, b.p, n * 32, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return b.down(out, n * 32);
 }
 
 }  // namespace dvp
@@ -94,15 +92,11 @@ extern "C" int dvp_debug_fr_ark_is_one(const uint8_t* ark) { return ark ? (fr_ar
 // stream the MSM then runs on
 extern "C" int dvp_msm_ctx_run_ark(dvp_msm_ctx* c, const uint64_t* scalars_ark, size_t lo, size_t hi, uint64_t out_xy[8], int* out_is_infinity) {
   if (!c || !scalars_ark || !out_xy || !out_is_infinity || lo > hi || hi >= ((size_t)1 << 27)) return DVP_EINVAL;  // a context holds fewer than 2^27 bases
-  DevBuf ds, dout;
-  DVP_TRY(ds.alloc((hi - lo) * 32));
-  DVP_TRY(dout.alloc(80));
-  if (hi > lo) DVP_HIP(hipMemcpy(ds.p, scalars_ark, (hi - lo) * 32, hipMemcpyHostToDevice));
+  DevBuf ds;
+  MsmResult sum;
+  DVP_TRY(ds.up(scalars_ark, (hi - lo) * 32));
+  DVP_TRY(sum.init());
   DVP_TRY(ark_dev(false, ds.p, hi - lo, ds.p, nullptr));
-  DVP_TRY(dvp_msm_ctx_run_dev(c, ds.p, lo, hi, dout.p, (char*)dout.p + 64, nullptr));  // hi against the context's length: DVP_EINVAL there
-  uint32_t inf;
-  DVP_HIP(hipMemcpy(out_xy, dout.p, 64, hipMemcpyDeviceToHost));
-  DVP_HIP(hipMemcpy(&inf, (char*)dout.p + 64, 4, hipMemcpyDeviceToHost));
-  *out_is_infinity = (int)inf;
-  return DVP_OK;
+  DVP_TRY(dvp_msm_ctx_run_dev(c, ds.p, lo, hi, sum.p, sum.inf(), nullptr));  // hi against the context's length: DVP_EINVAL there
+  return sum.down(out_xy, out_is_infinity);
 }

@@ -184,8 +184,7 @@ extern "C" int dvp_debug_fr_op(int op, const uint64_t* const in[6], size_t n, in
   DevBuf d_in[6], d_out[2];
   FrDebugPtrs p = {};
   for (int k = 0; k < n_in; ++k) {
-    DVP_TRY(d_in[k].alloc(n * sizeof(Fr)));
-    DVP_HIP(hipMemcpy(d_in[k].p, in[k], n * sizeof(Fr), hipMemcpyHostToDevice));
+    DVP_TRY(d_in[k].up(in[k], n * sizeof(Fr)));
     p.in[k] = d_in[k].as<Fr>();
   }
   for (int k = 0; k < n_out; ++k) {
@@ -198,6 +197,6 @@ extern "C" int dvp_debug_fr_op(int op, const uint64_t* const in[6], size_t n, in
 #undef X
   }
   DVP_HIP(hipGetLastError());
-  for (int k = 0; k < n_out; ++k) DVP_HIP(hipMemcpy(out[k], d_out[k].p, n * sizeof(Fr), hipMemcpyDeviceToHost));
+  for (int k = 0; k < n_out; ++k) DVP_TRY(d_out[k].down(out[k], n * sizeof(Fr)));
   return DVP_OK;
 }

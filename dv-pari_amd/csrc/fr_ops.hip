@@ -246,32 +246,26 @@ extern "C" int dvp_fr_batch_inverse(uint64_t* vals, size_t n) {
   if (!n) return DVP_OK;
   if (!vals) return DVP_EINVAL;
   DevBuf b;
-  DVP_TRY(b.alloc(n * sizeof(Fr)));
-  DVP_HIP(hipMemcpy(b.p, vals, n * sizeof(Fr), hipMemcpyHostToDevice));
+  DVP_TRY(b.up(vals, n * sizeof(Fr)));
   DVP_TRY(batch_inverse_dev(b.as<Fr>(), n, 0));
-  DVP_HIP(hipMemcpy(vals, b.p, n * sizeof(Fr), hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return b.down(vals, n * sizeof(Fr));
 }
 
 extern "C" int dvp_barycentric_eval(const uint64_t* domain, const uint64_t* bar_weights, const uint64_t z_at_alpha[4],
                                     const uint64_t* evals, size_t n, const uint64_t alpha[4], uint64_t out[4]) {
   if (!domain || !bar_weights || !z_at_alpha || !evals || !alpha || !out || !n) return DVP_EINVAL;
   DevBuf d, w, e, part, o;
-  DVP_TRY(d.alloc(n * sizeof(Fr)));
-  DVP_TRY(w.alloc(n * sizeof(Fr)));
-  DVP_TRY(e.alloc(n * sizeof(Fr)));
+  DVP_TRY(d.up(domain, n * sizeof(Fr)));
+  DVP_TRY(w.up(bar_weights, n * sizeof(Fr)));
+  DVP_TRY(e.up(evals, n * sizeof(Fr)));
   DVP_TRY(part.alloc((n / (256 * INV_CHUNK) + 2) * sizeof(Fr)));
   DVP_TRY(o.alloc(sizeof(Fr)));
-  DVP_HIP(hipMemcpy(d.p, domain, n * sizeof(Fr), hipMemcpyHostToDevice));
-  DVP_HIP(hipMemcpy(w.p, bar_weights, n * sizeof(Fr), hipMemcpyHostToDevice));
-  DVP_HIP(hipMemcpy(e.p, evals, n * sizeof(Fr), hipMemcpyHostToDevice));
   Fr a, z;
   memcpy(a.v, alpha, 32);
   memcpy(z.v, z_at_alpha, 32);
   if (!fr_is_canonical(a) || !fr_is_canonical(z)) return DVP_EINVAL;
   DVP_TRY(barycentric_dev(d.as<Fr>(), w.as<Fr>(), e.as<Fr>(), n, fr_to_mont(a), fr_to_mont(z), 0, part.as<Fr>(), o.as<Fr>(), 0));
-  DVP_HIP(hipMemcpy(out, o.p, sizeof(Fr), hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return o.down(out, sizeof(Fr));
 }
 
 // ---- generic pointwise / reduction helpers (the rayon maps of src/proving.rs:492-654 and the setup
@@ -331,22 +325,15 @@ k_spmv(const uint32_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, c
 }
 }  // namespace dvp
 
-static int up(DevBuf& b, const void* h, size_t bytes) {
-  DVP_TRY(b.alloc(bytes));
-  DVP_HIP(hipMemcpy(b.p, h, bytes, hipMemcpyHostToDevice));
-  return DVP_OK;
-}
-
 extern "C" int dvp_fr_vec_mul(const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
   if (!n) return DVP_OK;
   if (!a || !b || !out) return DVP_EINVAL;
   DevBuf da, db;
-  DVP_TRY(up(da, a, n * 32));
-  DVP_TRY(up(db, b, n * 32));
+  DVP_TRY(da.up(a, n * 32));
+  DVP_TRY(db.up(b, n * 32));
   DVP_LAUNCH(k_vec_mul, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), db.as<Fr>(), da.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out, da.p, n * 32, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return da.down(out, n * 32);
 }
 extern "C" int dvp_fr_vec_scale(const uint64_t* a, const uint64_t s[4], size_t n, uint64_t* out) {
   if (!n) return DVP_OK;
@@ -355,11 +342,10 @@ extern "C" int dvp_fr_vec_scale(const uint64_t* a, const uint64_t s[4], size_t n
   memcpy(sc.v, s, 32);
   if (!fr_is_canonical(sc)) return DVP_EINVAL;
   DevBuf da;
-  DVP_TRY(up(da, a, n * 32));
+  DVP_TRY(da.up(a, n * 32));
   DVP_LAUNCH(k_vec_scale, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), fr_to_mont(sc), da.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out, da.p, n * 32, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return da.down(out, n * 32);
 }
 extern "C" int dvp_fr_vec_axpy(const uint64_t* a, const uint64_t s[4], const uint64_t* b, size_t n, uint64_t* out) {
   if (!n) return DVP_OK;
@@ -368,12 +354,11 @@ extern "C" int dvp_fr_vec_axpy(const uint64_t* a, const uint64_t s[4], const uin
   memcpy(sc.v, s, 32);
   if (!fr_is_canonical(sc)) return DVP_EINVAL;
   DevBuf da, db;
-  DVP_TRY(up(da, a, n * 32));
-  DVP_TRY(up(db, b, n * 32));
+  DVP_TRY(da.up(a, n * 32));
+  DVP_TRY(db.up(b, n * 32));
   DVP_LAUNCH(k_vec_axpy, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), fr_to_mont(sc), db.as<Fr>(), da.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out, da.p, n * 32, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return da.down(out, n * 32);
 }
 extern "C" int dvp_fr_vec_scalar_sub(const uint64_t s[4], const uint64_t* a, size_t n, uint64_t* out) {
   if (!n) return DVP_OK;
@@ -382,11 +367,10 @@ extern "C" int dvp_fr_vec_scalar_sub(const uint64_t s[4], const uint64_t* a, siz
   memcpy(sc.v, s, 32);
   if (!fr_is_canonical(sc)) return DVP_EINVAL;
   DevBuf da;
-  DVP_TRY(up(da, a, n * 32));
+  DVP_TRY(da.up(a, n * 32));
   DVP_LAUNCH(k_vec_scalar_sub, dim3(cdiv(n, 256)), dim3(256), 0, 0, sc, da.as<Fr>(), da.as<Fr>(), n);
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out, da.p, n * 32, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return da.down(out, n * 32);
 }
 extern "C" int dvp_fr_vec_dot(const uint64_t* a, const uint64_t* b, size_t n, uint64_t out[4]) {
   if (!out) return DVP_EINVAL;
@@ -396,8 +380,8 @@ extern "C" int dvp_fr_vec_dot(const uint64_t* a, const uint64_t* b, size_t n, ui
   }
   if (!a || !b) return DVP_EINVAL;
   DevBuf da, db, part, o;
-  DVP_TRY(up(da, a, n * 32));
-  DVP_TRY(up(db, b, n * 32));
+  DVP_TRY(da.up(a, n * 32));
+  DVP_TRY(db.up(b, n * 32));
   uint32_t nb = cdiv(n, 256);
   if (nb > 1024) nb = 1024;
   DVP_TRY(part.alloc(nb * sizeof(Fr)));
@@ -405,8 +389,7 @@ extern "C" int dvp_fr_vec_dot(const uint64_t* a, const uint64_t* b, size_t n, ui
   DVP_LAUNCH(k_vec_dot_partial, dim3(nb), dim3(256), 0, 0, da.as<Fr>(), db.as<Fr>(), n, part.as<Fr>());
   DVP_LAUNCH(k_sum_final, dim3(1), dim3(256), 0, 0, part.as<Fr>(), nb, o.as<Fr>());
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out, o.p, 32, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return o.down(out, 32);
 }
 extern "C" int dvp_fr_spmv(const uint32_t* row_ptr, const uint32_t* col, const uint32_t* coeff_ids, uint32_t n_rows,
                            const uint64_t* coeffs, uint32_t n_coeffs, const uint64_t* x, uint32_t n_cols, uint64_t* out) {
@@ -420,20 +403,19 @@ extern "C" int dvp_fr_spmv(const uint32_t* row_ptr, const uint32_t* col, const u
   for (size_t k = 0; k < nnz; ++k)
     if (col[k] >= n_cols || coeff_ids[k] >= n_coeffs) { g_last_error_index = (int64_t)k; return DVP_EINVAL; }
   DevBuf rp, c, id, cf, dx, o;
-  DVP_TRY(up(rp, row_ptr, ((size_t)n_rows + 1) * 4));
+  DVP_TRY(rp.up(row_ptr, ((size_t)n_rows + 1) * 4));
   if (nnz) {
-    DVP_TRY(up(c, col, nnz * 4));
-    DVP_TRY(up(id, coeff_ids, nnz * 4));
+    DVP_TRY(c.up(col, nnz * 4));
+    DVP_TRY(id.up(coeff_ids, nnz * 4));
   } else {  // all rows empty: the kernel reads neither, and the host arrays may be empty or null
     DVP_TRY(c.alloc(4));
     DVP_TRY(id.alloc(4));
   }
-  DVP_TRY(up(cf, coeffs, (size_t)n_coeffs * 32));
-  DVP_TRY(up(dx, x, (size_t)n_cols * 32));
+  DVP_TRY(cf.up(coeffs, (size_t)n_coeffs * 32));
+  DVP_TRY(dx.up(x, (size_t)n_cols * 32));
   DVP_TRY(o.alloc((size_t)n_rows * 32));
   DVP_LAUNCH(k_spmv, dim3(cdiv(n_rows, 256)), dim3(256), 0, 0, rp.as<uint32_t>(), c.as<uint32_t>(), id.as<uint32_t>(),
                      cf.as<Fr>(), dx.as<Fr>(), n_rows, o.as<Fr>());
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out, o.p, (size_t)n_rows * 32, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return o.down(out, (size_t)n_rows * 32);
 }

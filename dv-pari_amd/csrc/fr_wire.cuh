@@ -1,7 +1,7 @@
 // gnark_element_to_fr (src/gnark_r1cs.rs:58-77) on one element: 32 bytes big-endian, any x < 2^256, -> x mod p as the canonical
 // 8 x 32-bit little-endian limbs of the ABI.  Exactly Fr::from_be_bytes_mod_order, without a loop over bits and without a division:
 //
-//   p = 2^231 + c, c = 0x69d5bb915bcd46efb1ad5f173abdf (115 bits).  Write x = q 2^231 + r with q = x >> 231 < 2^25, r < 2^231.
+//   p = 2^231 + c, c = limbs 0..3 of DVP_FR_P_LIMBS (fr.cuh; 115 bits).  Write x = q 2^231 + r with q = x >> 231 < 2^25, r < 2^231.
 //   2^231 = p - c, so x = q p + (r - q c): x mod p is r - q c when r >= q c, and r - q c + p otherwise.  Both lie in [0, p):
 //   q c < 2^140 < p, so r - q c + p > 0, and r - q c < 2^231 < p.
 //
@@ -9,6 +9,8 @@
 // no branch, the same source on the host (cache.cpp's file entry, dvp_debug_fr_from_be32_host) and in k_fr_from_be32 (fr_wire.hip).
 #pragma once
 #include <stdint.h>
+
+#include "fr.cuh"  // DVP_FR_P_LIMBS
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -19,12 +21,13 @@
 
 namespace dvp {
 
-// be[k] = the k-th 32-bit word of the 32 bytes as a little-endian machine loads it (be[0] holds the four most significant bytes)
-DVP_WIRE_HD void fr_from_be32_words(const uint32_t be[8], uint32_t out[8]) {
-  constexpr uint32_t P32[8] = {0xf173abdfu, 0x6efb1ad5u, 0xb915bcd4u, 0x00069d5bu, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000080u};
+// The reduction itself, on a value that is little-endian already: le[k] = bits 32k .. 32k+31 of any x < 2^256, out = x mod p, canonical
+// (the arkworks-form entries of fr_ark.cuh reduce with it before they scale).
+DVP_WIRE_HD void fr_reduce_le_words(const uint32_t le[8], uint32_t out[8]) {
+  constexpr uint32_t P32[8] = DVP_FR_P_LIMBS;
   uint32_t x[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) x[i] = __builtin_bswap32(be[7 - i]);  // byte reversal = word reversal + a swap inside each word
+  for (int i = 0; i < 8; ++i) x[i] = le[i];
   const uint32_t q = x[7] >> 7;  // bit 231 is bit 7 of limb 7
   x[7] &= 0x7fu;                 // r
   uint32_t t[8];                 // q c: limbs 0..3 of c are those of p, the carry out of limb 3 is limb 4 (q c < 2^140)
@@ -54,20 +57,20 @@ DVP_WIRE_HD void fr_from_be32_words(const uint32_t be[8], uint32_t out[8]) {
   }
 }
 
-// The same reduction on a value that is little-endian already: le[k] = bits 32k .. 32k+31 of any x < 2^256, out = x mod p, canonical.
-// fr_from_be32_words minus its byte swap (the arkworks-form entries of fr_ark.cuh reduce with it before they scale).
-DVP_WIRE_HD void fr_reduce_le_words(const uint32_t le[8], uint32_t out[8]) {
-  constexpr uint32_t P32[8] = {0xf173abdfu, 0x6efb1ad5u, 0xb915bcd4u, 0x00069d5bu, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000080u};
+// be[k] = the k-th 32-bit word of the 32 bytes as a little-endian machine loads it (be[0] holds the four most significant bytes)
+DVP_WIRE_HD void fr_from_be32_words(const uint32_t be[8], uint32_t out[8]) {
+  constexpr uint32_t P32[8] = DVP_FR_P_LIMBS;
   uint32_t x[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) x[i] = le[i];
-  const uint32_t q = x[7] >> 7;  // bit 231 is bit 7 of limb 7
-  x[7] &= 0x7fu;                 // r
-  uint32_t t[8];                 // q c, as in fr_from_be32_words
+  for (int i = 0; i < 8; ++i) x[i] = __builtin_bswap32(be[7 - i]);  // byte reversal = word reversal + a swap inside each word
+  // from here on the body of fr_reduce_le_words, repeated: calling it instead moves k_fr_from_be32's device code (same size, other bytes)
+  const uint32_t q = x[7] >> 7;
+  x[7] &= 0x7fu;
+  uint32_t t[8];
   uint64_t acc = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    acc += (uint64_t)q * P32[i];  // < 2^57 + 2^32
+    acc += (uint64_t)q * P32[i];
     t[i] = (uint32_t)acc;
     acc >>= 32;
   }
@@ -80,7 +83,7 @@ DVP_WIRE_HD void fr_reduce_le_words(const uint32_t le[8], uint32_t out[8]) {
     x[i] = (uint32_t)d;
     borrow = (uint32_t)(d >> 63);
   }
-  const uint32_t mask = 0u - borrow;  // r < q c: add p back (the carry out of limb 7 cancels the borrow)
+  const uint32_t mask = 0u - borrow;
   uint32_t carry = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {

@@ -41,11 +41,9 @@ extern "C" int dvp_fr_from_be32(const uint8_t* be32, size_t n, uint64_t* out) {
   if (!n) return DVP_OK;
   if (!be32 || !out || n > FR_WIRE_MAX_N) return DVP_EINVAL;  // before the allocation, not behind it
   DevBuf b;
-  DVP_TRY(b.alloc(n * 32));
-  DVP_HIP(hipMemcpy(b.p, be32, n * 32, hipMemcpyHostToDevice));  // any host alignment: a witness file's payload starts at byte 4
+  DVP_TRY(b.up(be32, n * 32));  // any host alignment: a witness file's payload starts at byte 4
   DVP_TRY(dvp_fr_from_be32_dev(b.p, n, b.p, nullptr));
-  DVP_HIP(hipMemcpy(out, b.p, n * 32, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return b.down(out, n * 32);
 }
 
 // the host build of the same function, no HIP call (tests/test_witness_wire_cpu.py)

@@ -250,8 +250,7 @@ extern "C" int dvp_debug_gf_op(int op, int form, const uint64_t* const in[6], si
   DevBuf d_in[6], d_out[4];
   GfDebugPtrs p = {};
   for (int k = 0; k < n_in; ++k) {
-    DVP_TRY(d_in[k].alloc(n * sizeof(Gf)));
-    DVP_HIP(hipMemcpy(d_in[k].p, in[k], n * sizeof(Gf), hipMemcpyHostToDevice));
+    DVP_TRY(d_in[k].up(in[k], n * sizeof(Gf)));
     p.in[k] = d_in[k].as<Gf>();
   }
   for (int k = 0; k < 4; ++k) {
@@ -268,6 +267,6 @@ extern "C" int dvp_debug_gf_op(int op, int form, const uint64_t* const in[6], si
   DVP_TRY(rc);
   DVP_HIP(hipDeviceSynchronize());
   for (int k = 0; k < 4; ++k)
-    if (p.out[k]) DVP_HIP(hipMemcpy(out[k], d_out[k].p, n * G * sizeof(Gf), hipMemcpyDeviceToHost));
+    if (p.out[k]) DVP_TRY(d_out[k].down(out[k], n * G * sizeof(Gf)));
   return DVP_OK;
 }

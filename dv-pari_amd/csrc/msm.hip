@@ -160,16 +160,15 @@ struct MsmWorkspace {
 // prove.hip) run concurrently, and so do up to MSM_WS_SLOTS MSMs on the SAME GPU (two provers on two host threads and two
 // streams: the latency-bound stretches of one proof -- merge levels, tail, small rounds, host round trips -- are filled by the
 // other's kernels); a further caller waits for slot 0.  The second slot allocates only when two calls do overlap.
-constexpr int MSM_MAX_DEVICES = 16;
 constexpr int MSM_WS_SLOTS = 2;
-static MsmWorkspace g_ws_dev[MSM_MAX_DEVICES][MSM_WS_SLOTS];
+static MsmWorkspace g_ws_dev[DVP_MAX_DEVICES][MSM_WS_SLOTS];
 // where the calling thread's last MSM ran (dvp_debug_msm_rest_len)
 struct LastMsm {
   int dev = -1, slot = 0;
   hipStream_t st = nullptr;
 };
 static thread_local LastMsm g_last_msm;
-static std::atomic<size_t> g_ws_need[MSM_MAX_DEVICES];
+static std::atomic<size_t> g_ws_need[DVP_MAX_DEVICES];
 
 // ---- stage capture (TEST ONLY: dvp_debug_msm_capture_arm / _fetch, include/dvpari_internal.h) -------------------------------------
 // A thread arms the capture for its NEXT MSM.  That MSM runs msm_core as it always does and, at the stage boundaries, enqueues
@@ -199,7 +198,7 @@ struct MsmCapture {
   Round rounds[CAPTURE_MAX_ROUNDS] = {};
   uint32_t nrounds = 0;
   Sec grab(const void* src, size_t bytes, hipStream_t s) {
-    const size_t at = (wanted + 255) & ~(size_t)255;
+    const size_t at = Carver::align(wanted);
     wanted = at + bytes;
     if (wanted > cap) return Sec{0, 0};  // (the fetch sees wanted > cap)
     if (!bytes) return Sec{at, 0};
@@ -228,7 +227,7 @@ struct HeavyGate {
   std::mutex mu;
   hipEvent_t last = nullptr;
 };
-static HeavyGate g_heavy[MSM_MAX_DEVICES];
+static HeavyGate g_heavy[DVP_MAX_DEVICES];
 
 struct MsmPlan {
   uint32_t n;
@@ -332,11 +331,10 @@ static MsmPlan msm_plan(size_t n, const MsmFixedCtx* fx) {
   return p;
 }
 
-static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 // dynamic-LDS limits are a per-device property of a kernel: set them once on every device that runs an MSM
 static int msm_set_lds_limits(int dev) {
   static std::mutex attr_mu;
-  static bool attr_done[MSM_MAX_DEVICES] = {false};
+  static bool attr_done[DVP_MAX_DEVICES] = {false};
   std::lock_guard<std::mutex> ga(attr_mu);
   if (attr_done[dev]) return DVP_OK;
   const struct { const void* f; int bytes; } sort_lim[] = {
@@ -408,11 +406,6 @@ struct MsmBuffers {
   uint32_t* gdesc;  // one word per output slot (rounds after the first; dense: two)
   uint32_t* rp;     // (counts, offsets) of rounds 1 .. ra_plan
   uint32_t* bsum2;  // scan scratch of the all-rounds bookkeeping: a row of block sums per round
-};
-struct Carver {
-  uintptr_t base;
-  size_t o = 0;
-  template <class T> T* take(size_t bytes) { T* r = (T*)(base + o); o = align_up(o + bytes); return r; }
 };
 // the regions over `base`, and their total (with base = 0 the only thing of use)
 static MsmBuffers msm_carve(size_t n, const MsmPlan& p, const MsmFixedCtx* fx, const MsmLayout& L, void* base, size_t* bytes = nullptr) {
@@ -999,7 +992,7 @@ static int msm_core(const void* d_scalars, const void* d_bases, const void* d_in
     if ((uint64_t)m.p.e_max >= 0xfffffff0ull || tab >= (m.sign_mask ? 0x7ffffff0ull : 0xfffffff0ull)) return DVP_EINVAL;
   }
   DVP_HIP(hipGetDevice(&m.dev));
-  if (m.dev < 0 || m.dev >= MSM_MAX_DEVICES) return DVP_EINVAL;
+  if (m.dev < 0 || m.dev >= DVP_MAX_DEVICES) return DVP_EINVAL;
   DVP_TRY(msm_set_lds_limits(m.dev));
   m.tn = tune();
   m.ws_slots = m.tn.msm_ws_slots >= 1 && m.tn.msm_ws_slots <= MSM_WS_SLOTS ? (int)m.tn.msm_ws_slots : 1;
@@ -1239,25 +1232,15 @@ extern "C" int dvp_points_sum_dev(const void* d_records, uint32_t n, void* d_out
 extern "C" int dvp_msm_affine(const uint64_t* scalars, const uint64_t* bases_xy, const uint8_t* bases_inf, size_t n,
                               uint64_t out_xy[8], int* out_is_infinity) {
   if ((n && (!scalars || !bases_xy)) || !out_xy || !out_is_infinity) return DVP_EINVAL;
-  DevBuf ds, db, di, dout;
-  DVP_TRY(ds.alloc(n * 32));
-  DVP_TRY(db.alloc(n * 64));
-  DVP_TRY(dout.alloc(64 + 16));
-  if (n) {
-    DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
-    DVP_HIP(hipMemcpy(db.p, bases_xy, n * 64, hipMemcpyHostToDevice));
-  }
-  if (bases_inf && n) {
-    DVP_TRY(di.alloc(n));
-    DVP_HIP(hipMemcpy(di.p, bases_inf, n, hipMemcpyHostToDevice));
-  }
+  DevBuf ds, db, di;
+  MsmResult sum;
+  DVP_TRY(ds.up(scalars, n * 32));
+  DVP_TRY(db.up(bases_xy, n * 64));
+  DVP_TRY(di.up_opt(bases_inf, n));
+  DVP_TRY(sum.init());
   DVP_TRY(points_check_strict(db.p, di.p, n, 0));
-  DVP_TRY(msm_affine_dev(ds.p, db.p, di.p, n, MsmOut{dout.p, (char*)dout.p + 64}, 0));
-  uint32_t inf;
-  DVP_HIP(hipMemcpy(out_xy, dout.p, 64, hipMemcpyDeviceToHost));
-  DVP_HIP(hipMemcpy(&inf, (char*)dout.p + 64, 4, hipMemcpyDeviceToHost));
-  *out_is_infinity = (int)inf;
-  return DVP_OK;
+  DVP_TRY(msm_affine_dev(ds.p, db.p, di.p, n, sum.out(), 0));
+  return sum.down(out_xy, out_is_infinity);
 }
 
 // ---- public fixed-base MSM context: many MSMs over one base vector (an SRS) -----------------------------
@@ -1271,8 +1254,7 @@ extern "C" int dvp_msm_ctx_create(const uint64_t* bases_xy, const uint8_t* bases
   if (!bases_xy || !out || !n || n >= ((size_t)1 << 27)) return DVP_EINVAL;
   if (!range_hint || range_hint > n) range_hint = n;
   DevBuf db;
-  DVP_TRY(db.alloc(n * sizeof(Aff)));
-  DVP_HIP(hipMemcpy(db.p, bases_xy, n * sizeof(Aff), hipMemcpyHostToDevice));
+  DVP_TRY(db.up(bases_xy, n * sizeof(Aff)));
   dvp_msm_ctx* c = new dvp_msm_ctx();
   c->n = n;
   auto fail = [&](int rc) { dvp_msm_ctx_destroy(c); return rc; };
@@ -1304,14 +1286,10 @@ extern "C" int dvp_msm_ctx_run_dev(dvp_msm_ctx* c, const void* d_scalars, size_t
 }
 extern "C" int dvp_msm_ctx_run(dvp_msm_ctx* c, const uint64_t* scalars, size_t lo, size_t hi, uint64_t out_xy[8], int* out_is_infinity) {
   if (!c || !scalars || !out_xy || !out_is_infinity || lo > hi || hi > c->n) return DVP_EINVAL;
-  DevBuf ds, dout;
-  DVP_TRY(ds.alloc((hi - lo) * 32));
-  DVP_TRY(dout.alloc(80));
-  if (hi > lo) DVP_HIP(hipMemcpy(ds.p, scalars, (hi - lo) * 32, hipMemcpyHostToDevice));
-  DVP_TRY(msm_fixed_dev(c->fx, ds.p, c->d_inf + lo, (uint32_t)lo, (uint32_t)hi, MsmOut{dout.p, (char*)dout.p + 64}, 0));
-  uint32_t inf;
-  DVP_HIP(hipMemcpy(out_xy, dout.p, 64, hipMemcpyDeviceToHost));
-  DVP_HIP(hipMemcpy(&inf, (char*)dout.p + 64, 4, hipMemcpyDeviceToHost));
-  *out_is_infinity = (int)inf;
-  return DVP_OK;
+  DevBuf ds;
+  MsmResult sum;
+  DVP_TRY(ds.up(scalars, (hi - lo) * 32));
+  DVP_TRY(sum.init());
+  DVP_TRY(msm_fixed_dev(c->fx, ds.p, c->d_inf + lo, (uint32_t)lo, (uint32_t)hi, sum.out(), 0));
+  return sum.down(out_xy, out_is_infinity);
 }

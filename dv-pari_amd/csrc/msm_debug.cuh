@@ -221,17 +221,16 @@ extern "C" int dvp_debug_recode_signed(const uint64_t* scalars, size_t n, int c,
   if (!out_words) return DVP_OK;
   if (!scalars || !n) return DVP_EINVAL;
   DevBuf ds, dw, de;
-  DVP_TRY(ds.alloc(n * 32));
+  DVP_TRY(ds.up(scalars, n * 32));
   DVP_TRY(dw.alloc((size_t)*windows * n * 4));
   DVP_TRY(de.alloc(8));
-  DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
   DVP_HIP(hipMemset(de.p, 0xff, 8));
   DVP_LAUNCH(k_recode_signed, dim3(cdiv(n, 256)), dim3(256), 0, 0, ds.as<uint32_t>(), (const uint8_t*)nullptr, (uint32_t)n, c, *windows, plan.n_narrow,
                      dw.as<uint32_t>(), de.as<unsigned long long>());
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(out_words, dw.p, (size_t)*windows * n * 4, hipMemcpyDeviceToHost));
+  DVP_TRY(dw.down(out_words, (size_t)*windows * n * 4));
   unsigned long long e = 0;
-  DVP_HIP(hipMemcpy(&e, de.p, 8, hipMemcpyDeviceToHost));
+  DVP_TRY(de.down(&e, 8));
   if (e != ~0ull) {
     g_last_error_index = (int64_t)(e & 0xffffffffull);
     return DVP_EINVAL;

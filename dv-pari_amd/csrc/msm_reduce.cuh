@@ -271,28 +271,23 @@ k_build_sqr_tables(Gf* __restrict__ tabs /* t29 | t58 | t116 | th | t14 | t7, 30
   const int k = which == 0 ? 29 : which == 1 ? 58 : which == 2 ? 116 : which == 4 ? 14 : 7;
   tabs[tid] = gf_sqr_n(v, k);
 }
-static std::mutex g_sqr_mu;
-static Gf* g_sqr_tab[16] = {nullptr};
+static PerDevice<Gf> g_sqr_tab;
 int gf_sqr_tables(GfSqrTables* out, hipStream_t st) {
-  int dev;
-  DVP_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return DVP_EINVAL;
-  std::lock_guard<std::mutex> g(g_sqr_mu);
-  if (!g_sqr_tab[dev]) {
-    Gf* t;
-    DVP_HIP(hipMalloc((void**)&t, (size_t)6 * 30 * 256 * sizeof(Gf)));
-    DVP_LAUNCH(k_build_sqr_tables, dim3(cdiv(6 * 30 * 256, 256)), dim3(256), 0, st, t);
+  Gf* tab;
+  DVP_TRY(g_sqr_tab.get(&tab, [&](Gf** t) -> int {
+    DVP_HIP(hipMalloc((void**)t, (size_t)6 * 30 * 256 * sizeof(Gf)));
+    DVP_LAUNCH(k_build_sqr_tables, dim3(cdiv(6 * 30 * 256, 256)), dim3(256), 0, st, *t);
     DVP_HIP(hipGetLastError());
     DVP_HIP(hipStreamSynchronize(st));
-    g_sqr_tab[dev] = t;
-  }
-  out->t29 = g_sqr_tab[dev];
-  out->t58 = g_sqr_tab[dev] + 30 * 256;
-  out->t116 = g_sqr_tab[dev] + 2 * 30 * 256;
-  out->th = g_sqr_tab[dev] + 3 * 30 * 256;
+    return DVP_OK;
+  }));
+  out->t29 = tab;
+  out->t58 = tab + 30 * 256;
+  out->t116 = tab + 2 * 30 * 256;
+  out->th = tab + 3 * 30 * 256;
   const long long tabs = tune().gf_inv_tabs;  // 0: the three long runs only (rounds 1-5), 1: + the run of 14, 2: + the run of 7
-  out->t14 = tabs >= 1 ? g_sqr_tab[dev] + 4 * 30 * 256 : nullptr;
-  out->t7 = tabs >= 2 ? g_sqr_tab[dev] + 5 * 30 * 256 : nullptr;
+  out->t14 = tabs >= 1 ? tab + 4 * 30 * 256 : nullptr;
+  out->t7 = tabs >= 2 ? tab + 5 * 30 * 256 : nullptr;
   return DVP_OK;
 }
 

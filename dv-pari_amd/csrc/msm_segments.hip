@@ -115,7 +115,6 @@ static uint32_t seg_piece() {
 struct SegLayout {
   size_t prod, flags, buf[2], cap[2], geo, geo_levels, total;
 };
-static size_t seg_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static SegLayout seg_layout(size_t n, size_t n_seg) {
   SegLayout w;
   w.cap[0] = (n + std::min(n, n_seg)) / 2;
@@ -123,12 +122,13 @@ static SegLayout seg_layout(size_t n, size_t n_seg) {
   size_t lg = 1;
   while (lg < 40 && ((size_t)1 << lg) < n) ++lg;
   w.geo_levels = lg + 1;
-  w.prod = 0;
-  w.flags = seg_align(n * sizeof(Aff));
-  w.buf[0] = w.flags + seg_align(n);
-  w.buf[1] = w.buf[0] + seg_align(w.cap[0] * sizeof(Ld));
-  w.geo = w.buf[1] + seg_align(w.cap[1] * sizeof(Ld));
-  w.total = w.geo + seg_align(w.geo_levels * (n_seg + 1) * sizeof(uint32_t));
+  Carver c;
+  w.prod = c.take(n * sizeof(Aff));
+  w.flags = c.take(n);
+  w.buf[0] = c.take(w.cap[0] * sizeof(Ld));
+  w.buf[1] = c.take(w.cap[1] * sizeof(Ld));
+  w.geo = c.take(w.geo_levels * (n_seg + 1) * sizeof(uint32_t));
+  w.total = c.o;
   return w;
 }
 
@@ -269,17 +269,6 @@ static int msm_segments_dev(const void* d_scalars, const void* d_xy, const void*
   return DVP_OK;
 }
 
-static bool seg_scalar_canonical(const uint64_t* v) {
-  static const uint64_t r[4] = {0x6efb1ad5f173abdfull, 0x00069d5bb915bcd4ull, 0ull, 0x0000008000000000ull};
-  for (int k = 3; k >= 0; --k)
-    if (v[k] != r[k]) return v[k] < r[k];
-  return false;
-}
-static size_t seg_first_bad_scalar(const uint64_t* scalars, size_t n) {
-  for (size_t k = 0; k < n; ++k)
-    if (!seg_scalar_canonical(scalars + 4 * k)) return k;
-  return n;
-}
 
 }  // namespace dvp
 
@@ -312,28 +301,18 @@ extern "C" int dvp_msm_segments(const uint64_t* scalars, const uint64_t* xy, con
   }
   const size_t work_bytes = seg_layout(n, n_seg).total;
   DevBuf ds, dp, di, dox, doi, dw, dsum;
-  DVP_TRY(ds.alloc(n * 32));
-  DVP_TRY(dp.alloc(n * 64));
+  DVP_TRY(dp.up(xy, n * 64));
+  DVP_TRY(di.up_opt(inf, n));
   DVP_TRY(dox.alloc(n_seg * 64));
   DVP_TRY(doi.alloc(n_seg));
   DVP_TRY(dw.alloc(work_bytes));
   DVP_TRY(dsum.alloc(16));
-  DVP_HIP(hipMemcpy(dp.p, xy, n * 64, hipMemcpyHostToDevice));
-  if (inf) {
-    DVP_TRY(di.alloc(n));
-    DVP_HIP(hipMemcpy(di.p, inf, n, hipMemcpyHostToDevice));
-  }
-  DVP_TRY(points_check_strict(dp.p, di.p, n, 0));  // the points before the scalars
-  const size_t badk = seg_first_bad_scalar(scalars, n);
-  if (badk != n) {
-    g_last_error_index = (int64_t)badk;
-    return DVP_EINVAL;
-  }
-  DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
+  DVP_TRY(points_check_strict(dp.p, di.p, n, 0));  // the points before the scalars, which go up only once both have passed
+  DVP_TRY(scalars_in_range(scalars, n));
+  DVP_TRY(ds.up(scalars, n * 32));
   DVP_TRY(msm_segments_dev(ds.p, dp.p, di.p, n, seg_ptr, n_seg, dox.p, doi.p, dw.p, dsum.p, 0));
-  DVP_HIP(hipMemcpy(out_xy, dox.p, n_seg * 64, hipMemcpyDeviceToHost));
-  DVP_HIP(hipMemcpy(out_inf, doi.p, n_seg, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  DVP_TRY(dox.down(out_xy, n_seg * 64));
+  return doi.down(out_inf, n_seg);
 }
 
 extern "C" int dvp_msm_segments_xsk233(const uint8_t* scalars, const uint8_t* enc, size_t n, const uint64_t* seg_ptr, size_t n_seg, uint8_t* out_enc) {
@@ -346,29 +325,19 @@ extern "C" int dvp_msm_segments_xsk233(const uint8_t* scalars, const uint8_t* en
   }
   const size_t work_bytes = seg_layout(n, n_seg).total;
   DevBuf ds, dp, di, dox, doi, de, doe, dw, dsum;
-  DVP_TRY(ds.alloc(n * 32));
   DVP_TRY(dp.alloc(n * 64));
   DVP_TRY(di.alloc(n));
-  DVP_TRY(de.alloc(n * 30));
+  DVP_TRY(de.up(enc, n * 30));
   DVP_TRY(dox.alloc(n_seg * 64));
   DVP_TRY(doi.alloc(n_seg));
   DVP_TRY(doe.alloc(n_seg * 30));
   DVP_TRY(dw.alloc(work_bytes));
   DVP_TRY(dsum.alloc(16));
-  DVP_HIP(hipMemcpy(de.p, enc, n * 30, hipMemcpyHostToDevice));
   DVP_TRY(decode_dev(de.as<uint8_t>(), n, dp.as<Aff>(), di.as<uint8_t>(), 0));
-  {  // 32 little-endian bytes are the four limbs on the hosts this library runs on; read through a copy, whatever the alignment
-    std::vector<uint64_t> tmp(n * 4);
-    memcpy(tmp.data(), scalars, n * 32);
-    const size_t badk = seg_first_bad_scalar(tmp.data(), n);
-    if (badk != n) {
-      g_last_error_index = (int64_t)badk;
-      return DVP_EINVAL;
-    }
-  }
-  DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
+  // 32 little-endian bytes are the four limbs on the hosts this library runs on; the check reads each through a copy, whatever the alignment
+  DVP_TRY(scalars_in_range(scalars, n));
+  DVP_TRY(ds.up(scalars, n * 32));
   DVP_TRY(msm_segments_dev(ds.p, dp.p, di.p, n, seg_ptr, n_seg, dox.p, doi.p, dw.p, dsum.p, 0));
   DVP_TRY(encode_dev(dox.as<Aff>(), doi.as<uint8_t>(), n_seg, doe.as<uint8_t>(), 0));
-  DVP_HIP(hipMemcpy(out_enc, doe.p, n_seg * 30, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return doe.down(out_enc, n_seg * 30);
 }

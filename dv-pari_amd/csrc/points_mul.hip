@@ -268,13 +268,6 @@ __global__ void __launch_bounds__(256) k_recode_tnaf(const uint32_t* __restrict_
   for (int j = 0; j < PmShape<W>::DIGITS; ++j) o[j] = (int8_t)tnaf_step<W>(r0, r1);
 }
 
-static bool scalar_host_canonical(const uint64_t* v) {
-  static const uint64_t r[4] = {0x6efb1ad5f173abdfull, 0x00069d5bb915bcd4ull, 0ull, 0x0000008000000000ull};
-  for (int k = 3; k >= 0; --k)
-    if (v[k] != r[k]) return v[k] < r[k];
-  return false;
-}
-
 static int points_mul_w() {
   const long long w = tune().points_mul_w;
   return (w >= 3 && w <= 5) ? (int)w : PM_DEFAULT_W;
@@ -291,8 +284,7 @@ static void pm_launch(const void* d_scalars, uint32_t stride, const void* d_xy, 
 // enqueue only: d_summary (16 bytes) is reset here, then the kernel fills it
 int points_mul_dev(const void* d_scalars, size_t n_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf,
                    void* d_summary, hipStream_t st) {
-  DVP_HIP(hipMemsetAsync(d_summary, 0xff, 8, st));
-  DVP_HIP(hipMemsetAsync((char*)d_summary + 8, 0, 8, st));
+  DVP_TRY(summary_reset(d_summary, st));
   if (!n) return DVP_OK;
   GfSqrTables T;
   DVP_TRY(gf_sqr_tables(&T, st));
@@ -306,12 +298,6 @@ int points_mul_dev(const void* d_scalars, size_t n_scalars, const void* d_xy, co
   return DVP_OK;
 }
 
-// first non-canonical scalar of a host vector, or n_scalars
-static size_t first_bad_scalar(const uint64_t* scalars, size_t n_scalars) {
-  for (size_t k = 0; k < n_scalars; ++k)
-    if (!scalar_host_canonical(scalars + 4 * k)) return k;
-  return n_scalars;
-}
 
 }  // namespace dvp
 
@@ -329,54 +315,34 @@ extern "C" int dvp_points_mul(const uint64_t* scalars, size_t n_scalars, const u
   if (!n) return DVP_OK;
   if (!scalars || !xy || !out_xy || !out_inf || (n_scalars != 1 && n_scalars != n)) return DVP_EINVAL;
   DevBuf ds, dp, di, doi, dsum;
-  DVP_TRY(ds.alloc(n_scalars * 32));
-  DVP_TRY(dp.alloc(n * 64));
+  DVP_TRY(dp.up(xy, n * 64));
+  DVP_TRY(di.up_opt(inf, n));
   DVP_TRY(doi.alloc(n));
   DVP_TRY(dsum.alloc(16));
-  DVP_HIP(hipMemcpy(dp.p, xy, n * 64, hipMemcpyHostToDevice));
-  if (inf) {
-    DVP_TRY(di.alloc(n));
-    DVP_HIP(hipMemcpy(di.p, inf, n, hipMemcpyHostToDevice));
-  }
-  DVP_TRY(points_check_strict(dp.p, di.p, n, 0));  // the points before the scalars
-  const size_t badk = first_bad_scalar(scalars, n_scalars);
-  if (badk != n_scalars) {
-    g_last_error_index = (int64_t)badk;
-    return DVP_EINVAL;
-  }
-  DVP_HIP(hipMemcpy(ds.p, scalars, n_scalars * 32, hipMemcpyHostToDevice));
+  DVP_TRY(points_check_strict(dp.p, di.p, n, 0));  // the points before the scalars, which go up only once both have passed
+  DVP_TRY(scalars_in_range(scalars, n_scalars));
+  DVP_TRY(ds.up(scalars, n_scalars * 32));
   DVP_TRY(points_mul_dev(ds.p, n_scalars, dp.p, di.p, n, dp.p, doi.p, dsum.p, 0));  // in place
-  DVP_HIP(hipMemcpy(out_xy, dp.p, n * 64, hipMemcpyDeviceToHost));
-  DVP_HIP(hipMemcpy(out_inf, doi.p, n, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  DVP_TRY(dp.down(out_xy, n * 64));
+  return doi.down(out_inf, n);
 }
 
 extern "C" int dvp_points_mul_xsk233(const uint8_t* scalars, size_t n_scalars, const uint8_t* enc, size_t n, uint8_t* out_enc) {
   if (!n) return DVP_OK;
   if (!scalars || !enc || !out_enc || (n_scalars != 1 && n_scalars != n)) return DVP_EINVAL;
   DevBuf ds, dp, di, doi, de, dsum;
-  DVP_TRY(ds.alloc(n_scalars * 32));
   DVP_TRY(dp.alloc(n * 64));
   DVP_TRY(di.alloc(n));
   DVP_TRY(doi.alloc(n));
-  DVP_TRY(de.alloc(n * 30));
+  DVP_TRY(de.up(enc, n * 30));
   DVP_TRY(dsum.alloc(16));
-  DVP_HIP(hipMemcpy(de.p, enc, n * 30, hipMemcpyHostToDevice));
   DVP_TRY(decode_dev(de.as<uint8_t>(), n, dp.as<Aff>(), di.as<uint8_t>(), 0));
-  {  // 32 little-endian bytes are the four limbs on the hosts this library runs on; read through a copy, whatever the alignment
-    std::vector<uint64_t> tmp(n_scalars * 4);
-    memcpy(tmp.data(), scalars, n_scalars * 32);
-    const size_t badk = first_bad_scalar(tmp.data(), n_scalars);
-    if (badk != n_scalars) {
-      g_last_error_index = (int64_t)badk;
-      return DVP_EINVAL;
-    }
-  }
-  DVP_HIP(hipMemcpy(ds.p, scalars, n_scalars * 32, hipMemcpyHostToDevice));
+  // 32 little-endian bytes are the four limbs on the hosts this library runs on; the check reads each through a copy, whatever the alignment
+  DVP_TRY(scalars_in_range(scalars, n_scalars));
+  DVP_TRY(ds.up(scalars, n_scalars * 32));
   DVP_TRY(points_mul_dev(ds.p, n_scalars, dp.p, di.p, n, dp.p, doi.p, dsum.p, 0));
   DVP_TRY(encode_dev(dp.as<Aff>(), doi.as<uint8_t>(), n, de.as<uint8_t>(), 0));
-  DVP_HIP(hipMemcpy(out_enc, de.p, n * 30, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return de.down(out_enc, n * 30);
 }
 
 // digits[i * *n_digits + j] = the signed digit of scalar i at position j; alpha[2 e] + alpha[2 e + 1] tau = alpha_(2e+1)
@@ -392,20 +358,14 @@ extern "C" int dvp_debug_recode_tnaf(const uint64_t* scalars, size_t n, int w, i
     }
   if (!digits) return DVP_OK;
   if (!scalars || !n) return DVP_EINVAL;
-  const size_t badk = first_bad_scalar(scalars, n);
-  if (badk != n) {
-    g_last_error_index = (int64_t)badk;
-    return DVP_EINVAL;
-  }
+  DVP_TRY(scalars_in_range(scalars, n));
   DevBuf ds, dd;
-  DVP_TRY(ds.alloc(n * 32));
+  DVP_TRY(ds.up(scalars, n * 32));
   DVP_TRY(dd.alloc(n * (size_t)nd));
-  DVP_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
   const dim3 grid(cdiv(n, 256)), block(256);
   if (w == 3) DVP_LAUNCH(k_recode_tnaf<3>, grid, block, 0, 0, ds.as<uint32_t>(), n, dd.as<int8_t>());
   else if (w == 4) DVP_LAUNCH(k_recode_tnaf<4>, grid, block, 0, 0, ds.as<uint32_t>(), n, dd.as<int8_t>());
   else DVP_LAUNCH(k_recode_tnaf<5>, grid, block, 0, 0, ds.as<uint32_t>(), n, dd.as<int8_t>());
   DVP_HIP(hipGetLastError());
-  DVP_HIP(hipMemcpy(digits, dd.p, n * (size_t)nd, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return dd.down(digits, n * (size_t)nd);
 }

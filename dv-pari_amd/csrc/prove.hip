@@ -215,7 +215,7 @@ extern "C" int dvp_prover_debug_read(dvp_prover* p, const char* name, uint64_t* 
     DevBuf tmp;
     DVP_TRY(tmp.alloc(n * sizeof(Fr)));
     DVP_LAUNCH(k_from_mont_vec, dim3(cdiv(n, PT)), dim3(PT), 0, 0, src, tmp.as<Fr>(), n);
-    DVP_HIP(hipMemcpy(out, tmp.p, n * sizeof(Fr), hipMemcpyDeviceToHost));
+    DVP_TRY(tmp.down(out, n * sizeof(Fr)));
   } else {
     DVP_HIP(hipMemcpy(out, src, n * sizeof(Fr), hipMemcpyDeviceToHost));
   }
@@ -244,9 +244,8 @@ extern "C" int dvp_ecfft_domain_tables(dvp_ecfft* t, int which, uint64_t* bar_we
   DVP_TRY(bw.alloc(m * sizeof(Fr)));
   DVP_TRY(zi.alloc(m * sizeof(Fr)));
   DVP_TRY(ecfft_domain_tables_dev(t, which, bw.as<Fr>(), zi.as<Fr>(), 0));
-  DVP_HIP(hipMemcpy(bar_weights, bw.p, m * sizeof(Fr), hipMemcpyDeviceToHost));
-  DVP_HIP(hipMemcpy(zinv_other, zi.p, m * sizeof(Fr), hipMemcpyDeviceToHost));
-  return DVP_OK;
+  DVP_TRY(bw.down(bar_weights, m * sizeof(Fr)));
+  return zi.down(zinv_other, m * sizeof(Fr));
 }
 extern "C" int dvp_prover_domain_tables(dvp_prover* p, int which, uint64_t* bar_weights, uint64_t* zinv_other) {
   if (!p) return DVP_EINVAL;

@@ -107,8 +107,7 @@ extern "C" int dvp_prover_set_coeffs(dvp_prover* p, const uint64_t* coeffs, uint
   if (p->coeffs_m) (void)hipFree(p->coeffs_m);
   DVP_HIP(hipMalloc((void**)&p->coeffs_m, (size_t)n * sizeof(Fr)));
   DevBuf tmp;
-  DVP_TRY(tmp.alloc((size_t)n * sizeof(Fr)));
-  DVP_HIP(hipMemcpy(tmp.p, coeffs, (size_t)n * sizeof(Fr), hipMemcpyHostToDevice));
+  DVP_TRY(tmp.up(coeffs, (size_t)n * sizeof(Fr)));
   DVP_LAUNCH(k_to_mont_vec, dim3(cdiv(n, PT)), dim3(PT), 0, 0, tmp.as<Fr>(), p->coeffs_m, (size_t)n);
   DVP_HIP(hipDeviceSynchronize());
   p->n_coeffs = n;
@@ -196,8 +195,7 @@ extern "C" int dvp_prover_set_srs_encoded(dvp_prover* p, int which, const uint8_
   Aff* base; uint8_t* inf;
   DVP_TRY(srs_slot(p, which, n, &base, &inf));
   DevBuf de;
-  DVP_TRY(de.alloc(n * 30));
-  DVP_HIP(hipMemcpy(de.p, enc, n * 30, hipMemcpyHostToDevice));
+  DVP_TRY(de.up(enc, n * 30));
   DVP_TRY(decode_dev(de.as<uint8_t>(), n, base, inf, 0));
   return srs_set_done(p, which);
 }

@@ -177,11 +177,6 @@ void transpose(uint32_t n_rows, uint32_t n_wires, const uint32_t* rp, const uint
     }
 }
 
-int up(DevBuf& b, const void* h, size_t bytes) {
-  DVP_TRY(b.alloc(bytes));
-  if (bytes) DVP_HIP(hipMemcpy(b.p, h, bytes, hipMemcpyHostToDevice));
-  return DVP_OK;
-}
 Fr load_fr(const uint64_t v[4]) {
   Fr r;
   memcpy(r.v, v, 32);
@@ -224,13 +219,13 @@ int setup_scalars_core(const SetupCircuit& cc, const uint64_t tau[4], const Fr& 
   const uint32_t n_coeffs = cc.n_coeffs, n_rows = cc.n_rows, n_wires = cc.n_wires;
   const size_t m = S.m;
   DevBuf d_coeffs, tptr[3], trow[3], tcid[3];
-  DVP_TRY(up(d_coeffs, cc.coeffs, (size_t)n_coeffs * 32));
+  DVP_TRY(d_coeffs.up(cc.coeffs, (size_t)n_coeffs * 32));
   for (int k = 0; k < 3; ++k) {
     std::vector<uint32_t> a, b, c;
     transpose(n_rows, n_wires, cc.rp[k], cc.wi[k], cc.ci[k], a, b, c);
-    DVP_TRY(up(tptr[k], a.data(), a.size() * 4));
-    DVP_TRY(up(trow[k], b.data(), b.size() * 4));
-    DVP_TRY(up(tcid[k], c.data(), c.size() * 4));
+    DVP_TRY(tptr[k].up(a.data(), a.size() * 4));
+    DVP_TRY(trow[k].up(b.data(), b.size() * 4));
+    DVP_TRY(tcid[k].up(c.data(), c.size() * 4));
   }
   // ---- the domains and their tables (TREE_2N, src/srs.rs:216-346) ----
   DVP_TRY(dvp_ecfft_create(S.log_m + 1, 0, 0, &S.tree));

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fr.cuh"  // DVP_FR_P_LIMBS
+
 namespace dvp {
 
 // constants: oracle/pyref.py tau_constants()
@@ -82,7 +84,7 @@ __device__ __forceinline__ void tau_round_mul(const uint32_t* s, const uint32_t*
 
 // s < r ?
 __device__ __forceinline__ bool tau_scalar_is_canonical(const uint32_t* s) {
-  const uint32_t p[8] = {0xf173abdfu, 0x6efb1ad5u, 0xb915bcd4u, 0x00069d5bu, 0, 0, 0, 0x00000080u};
+  const uint32_t p[8] = DVP_FR_P_LIMBS;
   uint64_t borrow = 0;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {

@@ -28,11 +28,11 @@
 #include <vector>
 
 #include "../../include/dvpari.h"
+#include "fr.cuh"  // fr_first_noncanonical
 
 namespace {
 
 const uint8_t MAGIC[8] = {'F', 'F', 'T', 'R', 0, 0, 0, 0};
-const uint64_t P64[4] = {0x6efb1ad5f173abdfull, 0x00069d5bb915bcd4ull, 0x0000000000000000ull, 0x0000008000000000ull};
 
 struct Map {
   const uint8_t* p = nullptr;
@@ -96,12 +96,10 @@ int find_node(const Map& f, uint32_t depth, const uint8_t** node, size_t* node_l
     *node_len = (size_t)sub->len;
   }
 }
-bool canonical29(const uint8_t* e) {  // value < p ?
-  uint64_t v[4] = {0, 0, 0, 0};
+bool canonical29(const uint8_t* e) {  // 29 little-endian bytes, zero-extended: value < p ?
+  uint8_t v[32] = {0};
   memcpy(v, e, 29);
-  for (int i = 3; i >= 0; --i)
-    if (v[i] != P64[i]) return v[i] < P64[i];
-  return false;
+  return dvp::fr_first_noncanonical(v, 1) == 1;
 }
 
 }  // namespace

@@ -461,14 +461,6 @@ k_rlc_check(const uint32_t* __restrict__ out_inf, const unsigned long long* __re
 
 static void fr_from_u64(const uint64_t* v, Fr* out) { memcpy(out->v, v, 32); }
 
-static bool fr_host_canonical(const uint64_t* v) {
-  for (int k = 3; k >= 0; --k) {
-    const uint64_t pk = (uint64_t)fr_p_limb(2 * k) | ((uint64_t)fr_p_limb(2 * k + 1) << 32);
-    if (v[k] != pk) return v[k] < pk;
-  }
-  return false;
-}
-
 // dvp_verify_set_binding: the two hashes of the transcript's compile-time half, process-wide like the codec rule.  NULL = BLAKE3(""),
 // the reference's value.  verify_consts reads them once per call, under the mutex: a call in flight keeps what it started with.
 static std::mutex g_bind_mu;
@@ -496,7 +488,7 @@ extern "C" int dvp_verify_get_binding(uint8_t srs_hash[32], uint8_t circuit_hash
 
 static int verify_consts(const uint64_t tau[4], const uint64_t delta[4], const uint64_t eps[4], VerifyConsts* c) {
   if (!tau || !delta || !eps) return DVP_EINVAL;
-  if (!fr_host_canonical(tau) || !fr_host_canonical(delta) || !fr_host_canonical(eps)) return DVP_EINVAL;
+  if (fr_first_noncanonical(tau, 1) != 1 || fr_first_noncanonical(delta, 1) != 1 || fr_first_noncanonical(eps, 1) != 1) return DVP_EINVAL;
   Fr t, d, e;
   fr_from_u64(tau, &t);
   fr_from_u64(delta, &d);
@@ -594,17 +586,16 @@ struct RlcLayout {
 };
 static RlcLayout rlc_layout(size_t n) {
   const size_t N = 2 * n + 1;
-  size_t o = 0;
-  auto carve = [&](size_t b) { const size_t r = o; o = (o + b + 255) & ~(size_t)255; return r; };
+  Carver c;
   RlcLayout l;
-  l.sc = carve(32 * N);
-  l.bases = carve(64 * N);
-  l.inf = carve(N);
-  l.ur = carve(32 * n);
-  l.part = carve(32 * (size_t)RLC_SUM_BLOCKS);
-  l.part_w = carve(4 * (size_t)RLC_SUM_BLOCKS);
-  l.ctrl = carve(128);  // MSM x, y [0, 64) | MSM infinity u32 [64] | scalar-range word u64 [72] | |W| [80] | gate [84] | report [88]
-  l.total = o;
+  l.sc = c.take(32 * N);
+  l.bases = c.take(64 * N);
+  l.inf = c.take(N);
+  l.ur = c.take(32 * n);
+  l.part = c.take(32 * (size_t)RLC_SUM_BLOCKS);
+  l.part_w = c.take(4 * (size_t)RLC_SUM_BLOCKS);
+  l.ctrl = c.take(128);  // MSM x, y [0, 64) | MSM infinity u32 [64] | scalar-range word u64 [72] | |W| [80] | gate [84] | report [88]
+  l.total = c.o;
   return l;
 }
 
@@ -672,6 +663,8 @@ static int rlc_enqueue(const VerifyConsts& c, const uint8_t key[32], const void*
 
 using namespace dvp;
 
+// Every flavour checks in this order: the trapdoor, n_public, n == 0 (DVP_OK; the host _rlc flavour also writes *report = 0), then the
+// pointers, then the public inputs.
 extern "C" int dvp_verify_batch_dev(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const void* d_public_inputs,
                                     uint32_t n_public, const void* d_proofs, size_t n, void* d_verdicts, void* stream) {
   VerifyConsts c;
@@ -690,20 +683,13 @@ extern "C" int dvp_verify_batch(const uint64_t tau[4], const uint64_t delta[4], 
   if (!n) return DVP_OK;
   if (!proofs || !verdicts || (n_public && !public_inputs)) return DVP_EINVAL;
   const size_t npub_all = (size_t)n_public * n;
-  for (size_t k = 0; k < npub_all; ++k)
-    if (!fr_host_canonical(public_inputs + 4 * k)) {
-      g_last_error_index = (int64_t)k;
-      return DVP_EINVAL;
-    }
+  DVP_TRY(scalars_in_range(public_inputs, npub_all));  // the flat index of the first bad one
   DevBuf dp, dpub, dv;
-  DVP_TRY(dp.alloc(n * 118));
-  DVP_TRY(dpub.alloc(npub_all * 32));
+  DVP_TRY(dp.up(proofs, n * 118));
+  DVP_TRY(dpub.up(public_inputs, npub_all * 32));
   DVP_TRY(dv.alloc(n));
-  DVP_HIP(hipMemcpy(dp.p, proofs, n * 118, hipMemcpyHostToDevice));
-  if (npub_all) DVP_HIP(hipMemcpy(dpub.p, public_inputs, npub_all * 32, hipMemcpyHostToDevice));
   DVP_TRY(verify_enqueue(c, dpub.p, n_public, dp.p, n, dv.p, 0));
-  DVP_HIP(hipMemcpy(verdicts, dv.p, n, hipMemcpyDeviceToHost));
-  return DVP_OK;
+  return dv.down(verdicts, n);
 }
 
 extern "C" int dvp_verify_batch_rlc_dev(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const void* d_public_inputs,
@@ -731,24 +717,18 @@ extern "C" int dvp_verify_batch_rlc(const uint64_t tau[4], const uint64_t delta[
   }
   if (!proofs || !verdicts || (n_public && !public_inputs) || n > DVP_VERIFY_RLC_MAX_PROOFS) return DVP_EINVAL;
   const size_t npub_all = (size_t)n_public * n;
-  for (size_t k = 0; k < npub_all; ++k)
-    if (!fr_host_canonical(public_inputs + 4 * k)) {
-      g_last_error_index = (int64_t)k;
-      return DVP_EINVAL;
-    }
+  DVP_TRY(scalars_in_range(public_inputs, npub_all));  // the flat index of the first bad one
   uint8_t key[32];
   rlc_key(tau, delta, epsilon, seed, key);
   DevBuf dp, dpub, dv, drep;
-  DVP_TRY(dp.alloc(n * 118));
-  DVP_TRY(dpub.alloc(npub_all * 32));
+  DVP_TRY(dp.up(proofs, n * 118));
+  DVP_TRY(dpub.up(public_inputs, npub_all * 32));
   DVP_TRY(dv.alloc(n));
   DVP_TRY(drep.alloc(4));
-  DVP_HIP(hipMemcpy(dp.p, proofs, n * 118, hipMemcpyHostToDevice));
-  if (npub_all) DVP_HIP(hipMemcpy(dpub.p, public_inputs, npub_all * 32, hipMemcpyHostToDevice));
   DVP_TRY(rlc_enqueue(c, key, dpub.p, n_public, dp.p, n, dv.p, drep.p, 0));
-  DVP_HIP(hipMemcpy(verdicts, dv.p, n, hipMemcpyDeviceToHost));
+  DVP_TRY(dv.down(verdicts, n));
   uint32_t rep = 0;
-  DVP_HIP(hipMemcpy(&rep, drep.p, 4, hipMemcpyDeviceToHost));
+  DVP_TRY(drep.down(&rep, 4));
   if (report) *report = rep;
   return DVP_OK;
 }

@@ -187,3 +187,44 @@ def test_r1cs_dump_parser_survives_corruption(dvp):
         if isinstance(exp, tuple) and exp[1] == 0:
             continue  # zero rows: accepted by the walk, padded to one row by the host mirror
         assert got == (exp if not isinstance(exp, tuple) else (exp[0], exp[1], exp[2])), (it, exp, got)
+
+
+def p_boundary():
+    """(accepted, rejected) around p: 0, 1, p - 1 | p, p + 1, 2^256 - 1, and per 64-bit limb k of p where it can be done: limb k raised by
+    one over zeros (rejected), limb k lowered by one over all-ones limbs (accepted)"""
+    m = (1 << 64) - 1
+    limbs = [(o.P >> (64 * i)) & m for i in range(4)]
+    join = lambda l: sum(v << (64 * i) for i, v in enumerate(l))
+    acc, rej = [0, 1, o.P - 1], [o.P, o.P + 1, (1 << 256) - 1]
+    for k in range(4):
+        if limbs[k] < m:
+            rej.append(join([0] * k + [limbs[k] + 1] + limbs[k + 1:]))
+        if limbs[k] > 0:
+            acc.append(join([m] * k + [limbs[k] - 1] + limbs[k + 1:]))
+    return acc, rej
+
+
+def test_range_check_and_reduction_at_p(dvp, tmp_path):
+    """the 29-byte files take values below p only, reading and writing; the 32-byte big-endian formats reduce any value"""
+    acc, rej = p_boundary()
+    assert all(v < o.P for v in acc) and all(o.P <= v < 1 << 256 for v in rej)
+    path = tmp_path / "z_poly"
+    dvp.io_utils.write_fr_vec_to_file(path, to_limbs(acc))
+    assert from_limbs(dvp.io_utils.read_fr_vec_from_file(path)) == acc
+    for r in rej:
+        for pos in (0, len(acc)):  # first and last
+            vals = acc[:pos] + [r] + acc[pos:]
+            with pytest.raises(dvp.DvpError) as e:
+                dvp.io_utils.write_fr_vec_to_file(path, to_limbs(vals))
+            assert e.value.status == -1, hex(r)
+            if r < 1 << 232:  # what 29 bytes can hold
+                path.write_bytes(struct.pack("<Q", len(vals)) + b"".join(v.to_bytes(29, "little") for v in vals))
+                with pytest.raises(dvp.DvpError) as e:
+                    dvp.io_utils.read_fr_vec_from_file(path)
+                assert e.value.status == -1, hex(r)
+    vals = acc + rej
+    assert [v % o.P for v in rej[:3]] == [0, 1, ((1 << 256) - 1) % o.P]
+    path.write_bytes(struct.pack(">I", len(vals)) + b"".join(v.to_bytes(32, "big") for v in vals))
+    assert from_limbs(dvp.gnark_r1cs.load_witness_from_file(path)) == [v % o.P for v in vals]
+    dump = py_dump([([(0, 0)], [(0, 1)], [(0, 0)])], vals)
+    assert from_limbs(dvp.gnark_r1cs.R1CSInstance.from_dump_bytes(dump, 0).coeffs) == [v % o.P for v in vals]

@@ -103,3 +103,31 @@ def test_fftr_corruption_fuzz(dvp, tmp_path):
             rejected += 1
         assert idx >= n_struct or rejected == before + 1, idx
     assert rejected >= 25  # header / table / count / range damage is caught; payload damage below p is data, not structure
+
+
+def test_fftr_range_check_at_p(dvp, tmp_path):
+    """29-byte elements are read by zero extension and must lie below p, in every 64-bit limb: p - 1 and p with limb k lowered over
+    all-ones limbs pass the writer and the reader; p, p + 1, the largest 29-byte value and p with limb k raised over zeros pass neither"""
+    from test_cache_formats import p_boundary
+
+    acc, rej = p_boundary()
+    path = tmp_path / "tree"
+    dvp.tree_io.write_tree_file(path, {"f": to_limbs(acc)})
+    assert path.read_bytes() == file_bytes(node_bytes([(0, fr_blob(acc))]))
+    assert from_limbs(dvp.tree_io.read_section(path, "f")) == acc
+    for r in rej:
+        for pos in (0, len(acc) - 1):
+            vals = list(acc)
+            vals[pos] = r
+            with pytest.raises(dvp.DvpError):
+                dvp.tree_io.write_tree_file(tmp_path / "bad", {"f": to_limbs(vals)})
+            if r < 1 << 232:
+                path.write_bytes(file_bytes(node_bytes([(0, fr_blob(vals))])))
+                with pytest.raises(dvp.DvpError) as e:
+                    dvp.tree_io.read_section(path, "f")
+                assert e.value.status == -6, hex(r)
+    top = (1 << 232) - 1  # 29 bytes of ones: what the zero extension must still compare as >= p
+    path.write_bytes(file_bytes(node_bytes([(0, fr_blob([1, top]))])))
+    with pytest.raises(dvp.DvpError) as e:
+        dvp.tree_io.read_section(path, "f")
+    assert e.value.status == -6
