@@ -11,11 +11,6 @@
 // dvp_prover_open_cache_dir is the loading half of Proof::prove (src/proving.rs:435-470,509-511,666-672): the R1CS
 // dump and the five SRS vectors are parsed / decoded ONCE and stay in HBM; dvp_prove_cache_dir keeps the opened
 // contexts in a process-wide table so that repeated prove(cache_dir, ..) calls only pay for the proof.
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -35,6 +30,7 @@
 #include "fr.cuh"                           // fr_first_noncanonical: the range check of the 29-byte files
 #include "fr_wire.cuh"                      // fr_from_be32_words: every 32-byte big-endian element
 #include "host_api.h"
+#include "mapped_file.h"
 
 namespace {
 
@@ -46,44 +42,12 @@ inline void be32_to_fr(const uint8_t* be, uint64_t out[4]) {
   memcpy(out, r, 32);
 }
 
-struct Mapped {
-  const uint8_t* p = nullptr;
-  size_t len = 0;
-  int fd = -1;
-  ~Mapped() {
-    if (p && len) munmap((void*)p, len);
-    if (fd >= 0) close(fd);
-  }
-  int open_ro(const char* path) {
-    fd = ::open(path, O_RDONLY);
-    if (fd < 0) return DVP_EIO;
-    struct stat st;
-    if (fstat(fd, &st) != 0) return DVP_EIO;
-    len = (size_t)st.st_size;
-    if (len == 0) return DVP_OK;
-    void* q = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (q == MAP_FAILED) {
-      len = 0;
-      return DVP_EIO;
-    }
-    p = (const uint8_t*)q;
-    return DVP_OK;
-  }
-};
-
-inline uint64_t rd64le(const uint8_t* p) {
-  uint64_t v;
-  memcpy(&v, p, 8);
-  return v;
-}
-inline uint32_t rd32le(const uint8_t* p) {
-  uint32_t v;
-  memcpy(&v, p, 4);
-  return v;
-}
+using dvp::MappedFile;
+using dvp::rd32le;
+using dvp::rd64le;
 
 // u64-LE count || count x elt bytes: returns the payload
-int counted_payload(const Mapped& f, size_t elt, const uint8_t** payload, size_t* n) {
+int counted_payload(const MappedFile& f, size_t elt, const uint8_t** payload, size_t* n) {
   if (f.len < 8) return DVP_EIO;  // "File too short for length prefix"
   uint64_t cnt = rd64le(f.p);
   if (cnt > (f.len - 8) / elt) return DVP_EIO;  // "File too short for expected point data"
@@ -256,7 +220,7 @@ extern "C" int dvp_file_fr_vec_write(const char* path, const uint64_t* limbs, si
 
 extern "C" int dvp_file_fr_vec_read(const char* path, uint64_t* out, size_t cap, size_t* n) {
   if (!path || !n) return DVP_EINVAL;
-  Mapped f;
+  MappedFile f;
   int rc = f.open_ro(path);
   if (rc) return rc;
   const uint8_t* pl;
@@ -282,7 +246,7 @@ extern "C" int dvp_file_point_vec_write(const char* path, const uint8_t* enc, si
 
 extern "C" int dvp_file_point_vec_read(const char* path, uint8_t* out, size_t cap, size_t* n) {
   if (!path || !n) return DVP_EINVAL;
-  Mapped f;
+  MappedFile f;
   int rc = f.open_ro(path);
   if (rc) return rc;
   const uint8_t* pl;
@@ -296,7 +260,7 @@ extern "C" int dvp_file_point_vec_read(const char* path, uint8_t* out, size_t ca
 
 extern "C" int dvp_file_witness_read(const char* path, uint64_t* out, size_t cap, size_t* n) {
   if (!path || !n) return DVP_EINVAL;
-  Mapped f;
+  MappedFile f;
   int rc = f.open_ro(path);
   if (rc) return rc;
   if (f.len < 4) return DVP_EIO;
@@ -354,7 +318,7 @@ extern "C" int dvp_r1cs_dump_fill(const uint8_t* buf, size_t len, uint64_t* coef
 extern "C" int dvp_prover_open_cache_dir(const char* cache_dir, uint32_t n_public, dvp_prover** out) {
   if (!cache_dir || !out) return DVP_EINVAL;
   *out = nullptr;
-  Mapped dump;
+  MappedFile dump;
   int rc = dump.open_ro(join(cache_dir, "r1cs_to_dvsnark").c_str());  // R1CS_CONSTRAINTS_FILE, src/artifacts.rs:76
   if (rc) return rc;
   DumpView v;
@@ -365,7 +329,7 @@ extern "C" int dvp_prover_open_cache_dir(const char* cache_dir, uint32_t n_publi
     if (v.nnz[k] > 0xffffffffull) return DVP_EINVAL;
   // the witness length is fixed by the commitment key: multi_scalar_mul asserts |assignment| == |g_m| (src/curve.rs:142)
   static const char* const names[5] = {"g_m", "g_q", "g_k_0", "g_k_1", "g_k_2"};  // src/artifacts.rs:18-27
-  Mapped srs[5];
+  MappedFile srs[5];
   const uint8_t* payload[5];
   size_t cnt[5];
   for (int i = 0; i < 5; ++i) {
@@ -493,7 +457,7 @@ extern "C" int dvp_prove_cache_dir_witness_file(const char* cache_dir, uint32_t 
                                                 uint64_t* public_inputs_out) {
   if (!cache_dir || !proof) return DVP_EINVAL;
   const std::string path = witness_path ? std::string(witness_path) : join(cache_dir, "witness_to_dvsnark");  // src/artifacts.rs
-  Mapped f;
+  MappedFile f;
   int rc = f.open_ro(path.c_str());
   if (rc) return rc;
   if (f.len < 4) return DVP_EIO;
@@ -570,7 +534,7 @@ extern "C" int dvp_circuit_hash_cache_dir(const char* cache_dir, uint32_t n_publ
     e->slot_cv.notify_all();
     return rc;
   }
-  Mapped dump;
+  MappedFile dump;
   int rc = dump.open_ro(join(cache_dir, "r1cs_to_dvsnark").c_str());  // R1CS_CONSTRAINTS_FILE, src/artifacts.rs:76
   if (rc) return rc;
   DumpView v;

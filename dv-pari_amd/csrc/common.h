@@ -95,6 +95,13 @@ inline int scalars_in_range(const void* le32, size_t n) {
   return DVP_EINVAL;
 }
 
+// a caller's trapdoor (tau, delta, epsilon): DVP_EINVAL for a null pointer or a value that is not below p.  Zero passes here: the
+// verifier takes it as it takes any scalar, and the setup refuses it itself (setup.hip: setup_check_trapdoor)
+inline int load_trapdoor(const uint64_t tau[4], const uint64_t delta[4], const uint64_t eps[4], Fr* t, Fr* d, Fr* e) {
+  if (!tau || !delta || !eps) return DVP_EINVAL;
+  return fr_load(tau, t) && fr_load(delta, d) && fr_load(eps, e) ? DVP_OK : DVP_EINVAL;
+}
+
 // the 80-byte result of an MSM: x || y (64 bytes), then the infinity flag as a u32 that holds 0 or 1
 struct MsmResult : DevBuf {
   int init() { return alloc(80); }

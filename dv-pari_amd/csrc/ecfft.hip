@@ -122,8 +122,7 @@ extern "C" int dvp_ecfft_exit(dvp_ecfft* c, const uint64_t* evals, uint64_t* out
 extern "C" int dvp_ecfft_vanish_at(const dvp_ecfft* c, int which, const uint64_t x[4], uint64_t out[4]) {
   if (!c || !x || !out || (which != 0 && which != 1)) return DVP_EINVAL;
   Fr xc;
-  memcpy(xc.v, x, 32);
-  if (!fr_is_canonical(xc)) return DVP_EINVAL;
+  if (!fr_load(x, &xc)) return DVP_EINVAL;
   int kk = c->log_n - 1;
   Fr cpt[2];  // the two leaves of layer kk (Montgomery): even leaves collapse to [0], odd leaves to [1]
   DVP_HIP(hipMemcpy(cpt, c->layer(kk), 2 * sizeof(Fr), hipMemcpyDeviceToHost));

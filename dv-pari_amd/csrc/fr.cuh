@@ -656,13 +656,18 @@ DVP_HD bool fr_is_canonical(const Fr& a) {
   return borrow != 0;
 }
 
+// Host: a caller's Fr argument -- four u64, 32 little-endian bytes at any address -- into *out; false when it is not below p
+inline bool fr_load(const void* le32, Fr* out) {
+  __builtin_memcpy(out->v, le32, 32);
+  return fr_is_canonical(*out);
+}
+
 // Host: the first of n 32-byte little-endian values that is not below p, or n.  Each value is read through a copy, so `le32` may sit
 // at any address (the wire formats); a shorter element is checked by zero extension (tree_io.cpp's 29 bytes).
 inline size_t fr_first_noncanonical(const void* le32, size_t n) {
   for (size_t k = 0; k < n; ++k) {
     Fr v;
-    __builtin_memcpy(v.v, (const unsigned char*)le32 + 32 * k, 32);
-    if (!fr_is_canonical(v)) return k;
+    if (!fr_load((const unsigned char*)le32 + 32 * k, &v)) return k;
   }
   return n;
 }

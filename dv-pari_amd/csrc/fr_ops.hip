@@ -7,6 +7,7 @@
 #include "common.h"
 #include "host_api.h"
 #include "fr.cuh"
+#include "fr_block.cuh"
 
 namespace dvp {
 
@@ -131,13 +132,8 @@ k_bary_partial(const Fr* __restrict__ dom, const Fr* __restrict__ wts, const Fr*
       sum = fr_add(sum, term);
     }
   }
-  sh[threadIdx.x] = sum;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = fr_add(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+  const Fr total = block_sum256(sum, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
 }
 
 // out = z_alpha * sum(partials), canonical
@@ -145,13 +141,8 @@ __global__ void __launch_bounds__(256) k_bary_final(const Fr* __restrict__ parti
   __shared__ Fr sh[256];
   Fr s = fr_zero();
   for (uint32_t i = threadIdx.x; i < nb; i += 256) s = fr_add(s, partial[i]);
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = fr_add(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = fr_from_mont(fr_mul(sh[0], z_alpha_m));
+  const Fr total = block_sum256(s, sh);
+  if (threadIdx.x == 0) *out = fr_from_mont(fr_mul(total, z_alpha_m));
 }
 
 // microbenchmark of the ECFFT's multiplier alone (bench.py's work model for configs #3 / #4's extends): pairs of independent
@@ -261,15 +252,14 @@ extern "C" int dvp_barycentric_eval(const uint64_t* domain, const uint64_t* bar_
   DVP_TRY(part.alloc((n / (256 * INV_CHUNK) + 2) * sizeof(Fr)));
   DVP_TRY(o.alloc(sizeof(Fr)));
   Fr a, z;
-  memcpy(a.v, alpha, 32);
-  memcpy(z.v, z_at_alpha, 32);
-  if (!fr_is_canonical(a) || !fr_is_canonical(z)) return DVP_EINVAL;
+  if (!fr_load(alpha, &a) || !fr_load(z_at_alpha, &z)) return DVP_EINVAL;
   DVP_TRY(barycentric_dev(d.as<Fr>(), w.as<Fr>(), e.as<Fr>(), n, fr_to_mont(a), fr_to_mont(z), 0, part.as<Fr>(), o.as<Fr>(), 0));
   return o.down(out, sizeof(Fr));
 }
 
 // ---- generic pointwise / reduction helpers (the rayon maps of src/proving.rs:492-654 and the setup
-// loops of src/srs.rs:53-84,138-160 expressed as reusable vector ops; host-pointer flavours) ---------
+// loops of src/srs.rs:53-84,138-160 expressed as reusable vector ops: the kernels, the host functions that
+// enqueue them on a stream for setup.hip and the entries below, and the host-pointer entries) ---------
 namespace dvp {
 __global__ void __launch_bounds__(256) k_vec_mul(const Fr* __restrict__ a, const Fr* __restrict__ b, Fr* __restrict__ o, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -293,25 +283,15 @@ __global__ void __launch_bounds__(256) k_vec_dot_partial(const Fr* __restrict__ 
   Fr s = fr_zero();
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     s = fr_add(s, fr_mul(fr_to_mont(a[i]), b[i]));
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = fr_add(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+  const Fr total = block_sum256(s, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
 }
 __global__ void __launch_bounds__(256) k_sum_final(const Fr* __restrict__ partial, uint32_t nb, Fr* __restrict__ out) {
   __shared__ Fr sh[256];
   Fr s = fr_zero();
   for (uint32_t i = threadIdx.x; i < nb; i += 256) s = fr_add(s, partial[i]);
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = fr_add(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = sh[0];
+  const Fr total = block_sum256(s, sh);
+  if (threadIdx.x == 0) *out = total;
 }
 // out[r] = sum_k coeffs[cid[k]] * x[col[k]] over row r (eval_row, src/gnark_r1cs.rs:273-280)
 __global__ void __launch_bounds__(256)
@@ -323,54 +303,63 @@ k_spmv(const uint32_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, c
   for (uint32_t k = row_ptr[r]; k < row_ptr[r + 1]; ++k) acc = fr_add(acc, fr_mul(fr_to_mont(coeffs[cid[k]]), x[col[k]]));
   out[r] = acc;
 }
+
+// the kernels above on a stream (host_api.h): one thread per element
+template <auto K, class... A>
+static int vec_launch(size_t n, hipStream_t st, A... args) {
+  if (n) DVP_LAUNCH(K, dim3(cdiv(n, 256)), dim3(256), 0, st, args..., n);
+  DVP_HIP(hipGetLastError());
+  return DVP_OK;
+}
+int vec_mul_dev(const Fr* a, const Fr* b, Fr* o, size_t n, hipStream_t st) { return vec_launch<k_vec_mul>(n, st, a, b, o); }
+int vec_scale_dev(const Fr* a, Fr s_m, Fr* o, size_t n, hipStream_t st) { return vec_launch<k_vec_scale>(n, st, a, s_m, o); }
+int vec_scalar_sub_dev(Fr s, const Fr* a, Fr* o, size_t n, hipStream_t st) { return vec_launch<k_vec_scalar_sub>(n, st, s, a, o); }
+int vec_axpy_dev(const Fr* a, Fr s_m, const Fr* b, Fr* o, size_t n, hipStream_t st) { return vec_launch<k_vec_axpy>(n, st, a, s_m, b, o); }
+// fr_to_mont(a) is fr_mul(a, R^2), and R^2 is R in Montgomery form
+int vec_to_mont_dev(const Fr* a, Fr* o, size_t n, hipStream_t st) { return vec_scale_dev(a, fr_r2(), o, n, st); }
+int vec_dot_dev(const Fr* a, const Fr* b, size_t n, Fr* d_partial, Fr* d_out, hipStream_t st) {
+  const uint32_t nb = std::min(cdiv(n, 256), VEC_DOT_BLOCKS);  // k_vec_dot_partial strides over the grid
+  DVP_LAUNCH(k_vec_dot_partial, dim3(nb), dim3(256), 0, st, a, b, n, d_partial);
+  DVP_LAUNCH(k_sum_final, dim3(1), dim3(256), 0, st, d_partial, nb, d_out);
+  DVP_HIP(hipGetLastError());
+  return DVP_OK;
+}
 }  // namespace dvp
 
+// the element-wise entries: stage a (and b), run one vector function in place on a, copy it down
+template <class F>
+static int vec_entry(const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, F&& run) {
+  DevBuf da, db;
+  DVP_TRY(da.up(a, n * 32));
+  if (b) DVP_TRY(db.up(b, n * 32));
+  DVP_TRY(run(da.as<Fr>(), db.as<Fr>()));
+  return da.down(out, n * 32);
+}
 extern "C" int dvp_fr_vec_mul(const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
   if (!n) return DVP_OK;
   if (!a || !b || !out) return DVP_EINVAL;
-  DevBuf da, db;
-  DVP_TRY(da.up(a, n * 32));
-  DVP_TRY(db.up(b, n * 32));
-  DVP_LAUNCH(k_vec_mul, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), db.as<Fr>(), da.as<Fr>(), n);
-  DVP_HIP(hipGetLastError());
-  return da.down(out, n * 32);
+  return vec_entry(a, b, n, out, [&](Fr* x, Fr* y) { return vec_mul_dev(x, y, x, n, 0); });
 }
 extern "C" int dvp_fr_vec_scale(const uint64_t* a, const uint64_t s[4], size_t n, uint64_t* out) {
   if (!n) return DVP_OK;
   if (!a || !s || !out) return DVP_EINVAL;
   Fr sc;
-  memcpy(sc.v, s, 32);
-  if (!fr_is_canonical(sc)) return DVP_EINVAL;
-  DevBuf da;
-  DVP_TRY(da.up(a, n * 32));
-  DVP_LAUNCH(k_vec_scale, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), fr_to_mont(sc), da.as<Fr>(), n);
-  DVP_HIP(hipGetLastError());
-  return da.down(out, n * 32);
+  if (!fr_load(s, &sc)) return DVP_EINVAL;
+  return vec_entry(a, nullptr, n, out, [&](Fr* x, Fr*) { return vec_scale_dev(x, fr_to_mont(sc), x, n, 0); });
 }
 extern "C" int dvp_fr_vec_axpy(const uint64_t* a, const uint64_t s[4], const uint64_t* b, size_t n, uint64_t* out) {
   if (!n) return DVP_OK;
   if (!a || !b || !s || !out) return DVP_EINVAL;
   Fr sc;
-  memcpy(sc.v, s, 32);
-  if (!fr_is_canonical(sc)) return DVP_EINVAL;
-  DevBuf da, db;
-  DVP_TRY(da.up(a, n * 32));
-  DVP_TRY(db.up(b, n * 32));
-  DVP_LAUNCH(k_vec_axpy, dim3(cdiv(n, 256)), dim3(256), 0, 0, da.as<Fr>(), fr_to_mont(sc), db.as<Fr>(), da.as<Fr>(), n);
-  DVP_HIP(hipGetLastError());
-  return da.down(out, n * 32);
+  if (!fr_load(s, &sc)) return DVP_EINVAL;
+  return vec_entry(a, b, n, out, [&](Fr* x, Fr* y) { return vec_axpy_dev(x, fr_to_mont(sc), y, x, n, 0); });
 }
 extern "C" int dvp_fr_vec_scalar_sub(const uint64_t s[4], const uint64_t* a, size_t n, uint64_t* out) {
   if (!n) return DVP_OK;
   if (!a || !s || !out) return DVP_EINVAL;
   Fr sc;
-  memcpy(sc.v, s, 32);
-  if (!fr_is_canonical(sc)) return DVP_EINVAL;
-  DevBuf da;
-  DVP_TRY(da.up(a, n * 32));
-  DVP_LAUNCH(k_vec_scalar_sub, dim3(cdiv(n, 256)), dim3(256), 0, 0, sc, da.as<Fr>(), da.as<Fr>(), n);
-  DVP_HIP(hipGetLastError());
-  return da.down(out, n * 32);
+  if (!fr_load(s, &sc)) return DVP_EINVAL;
+  return vec_entry(a, nullptr, n, out, [&](Fr* x, Fr*) { return vec_scalar_sub_dev(sc, x, x, n, 0); });
 }
 extern "C" int dvp_fr_vec_dot(const uint64_t* a, const uint64_t* b, size_t n, uint64_t out[4]) {
   if (!out) return DVP_EINVAL;
@@ -382,13 +371,9 @@ extern "C" int dvp_fr_vec_dot(const uint64_t* a, const uint64_t* b, size_t n, ui
   DevBuf da, db, part, o;
   DVP_TRY(da.up(a, n * 32));
   DVP_TRY(db.up(b, n * 32));
-  uint32_t nb = cdiv(n, 256);
-  if (nb > 1024) nb = 1024;
-  DVP_TRY(part.alloc(nb * sizeof(Fr)));
+  DVP_TRY(part.alloc(VEC_DOT_BLOCKS * sizeof(Fr)));
   DVP_TRY(o.alloc(sizeof(Fr)));
-  DVP_LAUNCH(k_vec_dot_partial, dim3(nb), dim3(256), 0, 0, da.as<Fr>(), db.as<Fr>(), n, part.as<Fr>());
-  DVP_LAUNCH(k_sum_final, dim3(1), dim3(256), 0, 0, part.as<Fr>(), nb, o.as<Fr>());
-  DVP_HIP(hipGetLastError());
+  DVP_TRY(vec_dot_dev(da.as<Fr>(), db.as<Fr>(), n, part.as<Fr>(), o.as<Fr>(), 0));
   return o.down(out, 32);
 }
 extern "C" int dvp_fr_spmv(const uint32_t* row_ptr, const uint32_t* col, const uint32_t* coeff_ids, uint32_t n_rows,

@@ -73,6 +73,16 @@ int points_mul_dev(const void* d_scalars, size_t n_scalars, const void* d_xy, co
 int batch_inverse_dev(Fr* d, size_t n, hipStream_t st);
 int barycentric_dev(const Fr* dom, const Fr* wts, const Fr* ev, size_t n, Fr alpha_m, Fr z_alpha_m, int tables_mont, Fr* d_partial, Fr* d_out,
                     hipStream_t st);
+// The Fr vector kernels, enqueued on st: n elements, canonical in and out, a scalar s_m in Montgomery form; o may be an input; n == 0
+// launches nothing.  (What the dvp_fr_vec_* entries, the setup and dvp_prover_prepares_precomputes are made of.)
+int vec_mul_dev(const Fr* a, const Fr* b, Fr* o, size_t n, hipStream_t st);               // o = a b
+int vec_scale_dev(const Fr* a, Fr s_m, Fr* o, size_t n, hipStream_t st);                  // o = s a
+int vec_scalar_sub_dev(Fr s, const Fr* a, Fr* o, size_t n, hipStream_t st);               // o = s - a (s canonical)
+int vec_axpy_dev(const Fr* a, Fr s_m, const Fr* b, Fr* o, size_t n, hipStream_t st);      // o = a + s b
+int vec_to_mont_dev(const Fr* a, Fr* o, size_t n, hipStream_t st);                        // o = a R: the scale by R
+constexpr uint32_t VEC_DOT_BLOCKS = 1024;  // block partials of a dot product at most
+// *d_out = <a, b> (n >= 1): block partials into d_partial (VEC_DOT_BLOCKS Fr of scratch), then one block over them
+int vec_dot_dev(const Fr* a, const Fr* b, size_t n, Fr* d_partial, Fr* d_out, hipStream_t st);
 
 // ---- blake3_tree.hip ---------------------------------------------------------------------------------------------------------
 int b3_leaves_dev(const uint8_t* d_data, size_t len, uint64_t chunk_base, uint32_t* d_cvs, hipStream_t st);

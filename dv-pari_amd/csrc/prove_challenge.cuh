@@ -52,7 +52,7 @@ static int challenge_alpha_host(dvp_prover* p, const void* d_commit_xy, const vo
   uint8_t ch[32];
   transcript_challenge(p->commit_p_host, p->pub_host.data(), p->n_pub, (const uint8_t*)p->h_ct.w, ch);
   Fr alpha;
-  memcpy(alpha.v, ch, 32);
+  (void)fr_load(ch, &alpha);  // 224 bits: always below p
   p->alpha_canon = alpha;
   *alpha_m = fr_to_mont(alpha);
   *neg_z = fr_neg(host_vanish(p, 0, *alpha_m));

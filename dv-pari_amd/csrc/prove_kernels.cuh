@@ -5,6 +5,7 @@
 #include "blake3_dev.cuh"
 #include "common.h"
 #include "ecfft_internal.h"
+#include "fr_block.cuh"  // block_sum256
 
 namespace dvp {
 
@@ -118,19 +119,6 @@ k_alpha_denoms(const Fr* __restrict__ d_m, const Fr* __restrict__ d2_m, const Fr
   den2[i] = fr_from_mont(y);
 }
 
-// sum over a 256-lane block of one Fr per lane, through sh[256]: every lane gets the total, and the closing barrier leaves sh free for
-// the next call.  (Callers unroll their loop over the three sums: a runtime index put s[] / res[] into 112 B of scratch per lane.)
-__device__ __forceinline__ Fr block_sum256(const Fr& x, Fr* sh) {
-  sh[threadIdx.x] = x;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = fr_add(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  const Fr total = sh[0];
-  __syncthreads();
-  return total;
-}
 // out[0..2] = a0, b0, i0 (canonical); out[3] = r0 = a0 b0 - i0, from the three Montgomery values
 __device__ __forceinline__ void bary3_close(const Fr& a0_m, const Fr& b0_m, const Fr& i0_m, Fr* __restrict__ out) {
   out[0] = fr_from_mont(a0_m);

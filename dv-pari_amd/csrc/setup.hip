@@ -11,10 +11,7 @@
 //       with C' = C - D, D_ij = d_i^j on the public wires                              src/gnark_r1cs.rs:333-386
 //   g_m[j] = eps m_j G,  g_q[i] = eps Z_D(tau) delta^2 L'_i(tau) G,
 //   g_k[0][i] = L_i(tau) G,  g_k[1][i] = delta L_i(tau) G,  g_k[2] = delta^2 (unified-domain Lagrange values) G    src/srs.rs:126-160
-#include <sys/mman.h>
 #include <sys/stat.h>
-#include <fcntl.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cerrno>
@@ -26,6 +23,7 @@
 #include "ecfft_internal.h"
 #include "host_api.h"
 #include "k233.cuh"
+#include "mapped_file.h"
 
 namespace dvp {
 
@@ -38,45 +36,15 @@ __global__ void __launch_bounds__(TPB) ks_domains(const Fr* __restrict__ L0, uin
   d[i] = fr_from_mont(L0[2 * (size_t)i]);
   d2[i] = fr_from_mont(L0[2 * (size_t)i + 1]);
 }
-__global__ void __launch_bounds__(TPB) ks_scalar_sub(Fr s, const Fr* __restrict__ a, Fr* __restrict__ o, size_t n) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = fr_sub(s, a[i]);
-}
-// o = s * a * b   (a, b canonical; s in Montgomery form)
-__global__ void __launch_bounds__(TPB) ks_mul_scale(const Fr* __restrict__ a, const Fr* __restrict__ b, Fr s_m, Fr* __restrict__ o, size_t n) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = fr_mul(s_m, fr_mul(fr_to_mont(a[i]), b[i]));
-}
-// o[stride * i + off] = s * a[i] * b[i]
-__global__ void __launch_bounds__(TPB) ks_mul_scale_strided(const Fr* __restrict__ a, const Fr* __restrict__ b, Fr s_m, Fr* __restrict__ o, size_t n,
-                                                            uint32_t stride, uint32_t off) {
+// o[stride * i + off] = s * a[i] * b[i]   (a, b canonical; s in Montgomery form)
+__global__ void __launch_bounds__(TPB) ks_mul_scale(const Fr* __restrict__ a, const Fr* __restrict__ b, Fr s_m, Fr* __restrict__ o, size_t n, uint32_t stride,
+                                                    uint32_t off) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) o[(size_t)stride * i + off] = fr_mul(s_m, fr_mul(fr_to_mont(a[i]), b[i]));
-}
-__global__ void __launch_bounds__(TPB) ks_scale(const Fr* __restrict__ a, Fr s_m, Fr* __restrict__ o, size_t n) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = fr_mul(s_m, a[i]);
-}
-__global__ void __launch_bounds__(TPB) ks_mul(const Fr* __restrict__ a, const Fr* __restrict__ b, Fr* __restrict__ o, size_t n) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = fr_mul(fr_to_mont(a[i]), b[i]);
 }
 __global__ void __launch_bounds__(TPB) ks_fill_one(Fr* __restrict__ o, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) o[i] = fr_one_canon();
-}
-__global__ void __launch_bounds__(TPB) ks_dot_partial(const Fr* __restrict__ a, const Fr* __restrict__ b, size_t n, Fr* __restrict__ partial) {
-  __shared__ Fr sh[TPB];
-  Fr s = fr_zero();
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    s = fr_add(s, fr_mul(fr_to_mont(a[i]), b[i]));
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = TPB / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = fr_add(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
 }
 // accumulate_m_values on the TRANSPOSED matrices: thread j owns wire j and sums (A_ij + delta B_ij + delta^2 C_ij) L_i over the
 // rows i that mention it (src/srs.rs:53-84 walks the rows and scatters; a gather per wire needs no atomics).  One CSR per
@@ -97,23 +65,6 @@ __global__ void __launch_bounds__(TPB) ks_m_values(CsrT A, CsrT B, CsrT C, const
   };
   Fr v = fr_add(fr_add(gather(A), fr_mul(delta_m, gather(B))), fr_mul(delta2_m, gather(C)));
   out[j] = fr_mul(eps_m, v);
-}
-// target -= s_m x (sum of the nb block partials of ks_dot_partial)   (canonical values, s_m Montgomery; one block)
-__global__ void __launch_bounds__(TPB) ks_fold_apply(const Fr* __restrict__ partial, uint32_t nb, Fr s_m, Fr* __restrict__ target) {
-  __shared__ Fr sh[TPB];
-  Fr acc = fr_zero();
-  for (uint32_t k = threadIdx.x; k < nb; k += TPB) acc = fr_add(acc, partial[k]);
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = TPB / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = fr_add(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *target = fr_sub(*target, fr_mul(s_m, sh[0]));
-}
-__global__ void __launch_bounds__(TPB) ks_to_mont(const Fr* __restrict__ a, Fr* __restrict__ o, size_t n) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = fr_to_mont(a[i]);
 }
 // evaluations of Z_S on the 2m leaves: 0 on S's own half, 1 / zinv_other on the other half
 __global__ void __launch_bounds__(TPB) ks_vanish_evals(const Fr* __restrict__ z_other /* canonical Z_S on the other half */, uint32_t m, int which,
@@ -138,27 +89,6 @@ __global__ void __launch_bounds__(TPB) ks_first_nonzero_even(const Fr* __restric
   if (!fr_is_zero(ev[2 * (size_t)i])) atomicMin(first_bad, i);
 }
 
-struct File {
-  const uint8_t* p = nullptr;
-  size_t len = 0;
-  int fd = -1;
-  ~File() {
-    if (p) munmap((void*)p, len);
-    if (fd >= 0) close(fd);
-  }
-  int open_ro(const char* path) {
-    fd = ::open(path, O_RDONLY);
-    if (fd < 0) return DVP_EIO;
-    struct stat st;
-    if (fstat(fd, &st) != 0 || st.st_size <= 0) return DVP_EIO;
-    len = (size_t)st.st_size;
-    void* m = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (m == MAP_FAILED) return DVP_EIO;
-    p = (const uint8_t*)m;
-    return DVP_OK;
-  }
-};
-
 // wire-major copy of a row-major CSR (counting sort by wire; stable, so rows ascend inside a wire)
 void transpose(uint32_t n_rows, uint32_t n_wires, const uint32_t* rp, const uint32_t* wire, const uint32_t* cid, std::vector<uint32_t>& tp,
                std::vector<uint32_t>& trow, std::vector<uint32_t>& tcid) {
@@ -177,11 +107,24 @@ void transpose(uint32_t n_rows, uint32_t n_wires, const uint32_t* rp, const uint
     }
 }
 
-Fr load_fr(const uint64_t v[4]) {
-  Fr r;
-  memcpy(r.v, v, 32);
-  return r;
+// n Fr of device memory on the host (waits for st), and from there into an Fr vector file
+int fr_vec_down(const void* d, size_t n, std::vector<uint64_t>& host, hipStream_t st) {
+  host.resize(4 * n);
+  DVP_HIP(hipMemcpyAsync(host.data(), d, n * sizeof(Fr), hipMemcpyDeviceToHost, st));
+  DVP_HIP(hipStreamSynchronize(st));
+  return DVP_OK;
 }
+int fr_vec_to_file(const void* d, size_t n, const std::string& path, std::vector<uint64_t>& host, hipStream_t st) {
+  DVP_TRY(fr_vec_down(d, n, host, st));
+  return dvp_file_fr_vec_write(path.c_str(), host.data(), n);
+}
+// a regenerated tree for the length of a call
+struct TreeOwner {
+  dvp_ecfft* t = nullptr;
+  ~TreeOwner() {
+    if (t) dvp_ecfft_destroy(t);
+  }
+};
 }  // namespace
 }  // namespace dvp
 
@@ -200,19 +143,23 @@ struct SetupCircuit {
   const uint32_t* ci[3] = {nullptr, nullptr, nullptr};
 };
 struct SetupState {
-  dvp_ecfft* tree = nullptr;
-  uint32_t log_m = 0;
-  size_t m = 0, n_sc = 0;
+  const uint32_t log_m, n_wires;
+  const size_t m;
+  TreeOwner tree;
   DevBuf d, d2, bar, z2inv, bard, z2dinv, t1, l_tau, l_taud, sc;
+  SetupState(uint32_t log_m_, uint32_t n_wires_) : log_m(log_m_), n_wires(n_wires_), m((size_t)1 << log_m_) {}
   ~SetupState() {
     // the discrete logs of the SRS and the Lagrange values at tau are trapdoor material (src/srs.rs:41-50): zeroed before their memory
     // goes back to the allocator, on every exit
     for (DevBuf* b : {&sc, &l_tau, &l_taud, &t1})
       if (b->p) (void)hipMemset(b->p, 0, b->bytes);
     (void)hipDeviceSynchronize();
-    if (tree) dvp_ecfft_destroy(tree);
   }
-  Fr* s_gm() { return sc.as<Fr>(); }
+  // sc holds the five scalar vectors in file order: G_M | G_Q | G_K0 | G_K1 | G_K2
+  enum { G_M, G_Q, G_K0, G_K1, G_K2 };
+  size_t count(int i) const { return i == G_M ? n_wires : i == G_K2 ? 2 * m : m; }
+  size_t n_sc() const { return (size_t)n_wires + 5 * m; }
+  Fr* vec(int i) const { return sc.as<Fr>() + (i == G_M ? 0 : n_wires + (size_t)(i - 1) * m); }
 };
 int setup_scalars_core(const SetupCircuit& cc, const uint64_t tau[4], const Fr& tau_c, const Fr& delta_c, const Fr& eps_c, uint32_t n_public, SetupState& S,
                        hipStream_t st) {
@@ -228,82 +175,74 @@ int setup_scalars_core(const SetupCircuit& cc, const uint64_t tau[4], const Fr& 
     DVP_TRY(tcid[k].up(c.data(), c.size() * 4));
   }
   // ---- the domains and their tables (TREE_2N, src/srs.rs:216-346) ----
-  DVP_TRY(dvp_ecfft_create(S.log_m + 1, 0, 0, &S.tree));
-  dvp_ecfft* tree = S.tree;
-  DevBuf &d = S.d, &d2 = S.d2, &bar = S.bar, &z2inv = S.z2inv, &bard = S.bard, &z2dinv = S.z2dinv, &t1 = S.t1, &l_tau = S.l_tau, &l_taud = S.l_taud, &sc = S.sc;
-  for (DevBuf* b : {&d, &d2, &bar, &z2inv, &bard, &z2dinv, &t1, &l_tau, &l_taud}) DVP_TRY(b->alloc(m * sizeof(Fr)));
-  S.n_sc = (size_t)n_wires + 5 * m;  // g_m | g_q | g_k_0 | g_k_1 | g_k_2
-  DVP_TRY(sc.alloc(S.n_sc * sizeof(Fr)));
-  Fr* s_gm = sc.as<Fr>();
-  Fr* s_gq = s_gm + n_wires;
-  Fr* s_k0 = s_gq + m;
-  Fr* s_k1 = s_k0 + m;
-  Fr* s_k2 = s_k1 + m;
+  DVP_TRY(dvp_ecfft_create(S.log_m + 1, 0, 0, &S.tree.t));
+  dvp_ecfft* tree = S.tree.t;
+  for (DevBuf* b : {&S.d, &S.d2, &S.bar, &S.z2inv, &S.bard, &S.z2dinv, &S.t1, &S.l_tau, &S.l_taud}) DVP_TRY(b->alloc(m * sizeof(Fr)));
+  DVP_TRY(S.sc.alloc(S.n_sc() * sizeof(Fr)));
+  Fr *d = S.d.as<Fr>(), *d2 = S.d2.as<Fr>(), *bar = S.bar.as<Fr>(), *z2inv = S.z2inv.as<Fr>(), *bard = S.bard.as<Fr>(), *z2dinv = S.z2dinv.as<Fr>();
+  Fr *t1 = S.t1.as<Fr>(), *l_tau = S.l_tau.as<Fr>(), *l_taud = S.l_taud.as<Fr>(), *s_gm = S.vec(S.G_M);
   const dim3 gm(cdiv(m, TPB)), bt(TPB);
-  DVP_LAUNCH(ks_domains, gm, bt, 0, st, tree->layer(0), (uint32_t)m, d.as<Fr>(), d2.as<Fr>());
-  DVP_TRY(ecfft_domain_tables_dev(tree, 0, bar.as<Fr>(), z2inv.as<Fr>(), st));    // 1/Z_D'(D_i),  1/Z_D(D'_i)
-  DVP_TRY(ecfft_domain_tables_dev(tree, 1, bard.as<Fr>(), z2dinv.as<Fr>(), st));  // 1/Z_D''(D'_i), 1/Z_D'(D_i)
+  DVP_LAUNCH(ks_domains, gm, bt, 0, st, tree->layer(0), (uint32_t)m, d, d2);
+  DVP_TRY(ecfft_domain_tables_dev(tree, 0, bar, z2inv, st));    // 1/Z_D'(D_i),  1/Z_D(D'_i)
+  DVP_TRY(ecfft_domain_tables_dev(tree, 1, bard, z2dinv, st));  // 1/Z_D''(D'_i), 1/Z_D'(D_i)
   uint64_t zt[4], zdt[4];
   DVP_TRY(dvp_ecfft_vanish_at(tree, 0, tau, zt));
   DVP_TRY(dvp_ecfft_vanish_at(tree, 1, tau, zdt));
-  const Fr z_tau = load_fr(zt), zd_tau = load_fr(zdt);
+  Fr z_tau, zd_tau;
+  (void)fr_load(zt, &z_tau), (void)fr_load(zdt, &zd_tau);
   if (fr_is_zero(z_tau) || fr_is_zero(zd_tau)) return DVP_EINVAL;  // tau lies in a domain
   const Fr z_tau_m = fr_to_mont(z_tau), zd_tau_m = fr_to_mont(zd_tau), delta_m = fr_to_mont(delta_c), eps_m = fr_to_mont(eps_c);
   const Fr delta2_m = fr_to_mont(fr_mul(delta_m, delta_c));  // fr_mul(Montgomery, canonical) = canonical product
   // L_i(tau), L'_i(tau)
-  DVP_LAUNCH(ks_scalar_sub, gm, bt, 0, st, tau_c, d.as<Fr>(), t1.as<Fr>(), m);
-  DVP_TRY(batch_inverse_dev(t1.as<Fr>(), m, st));
-  DVP_LAUNCH(ks_mul_scale, gm, bt, 0, st, t1.as<Fr>(), bar.as<Fr>(), z_tau_m, l_tau.as<Fr>(), m);
-  DVP_LAUNCH(ks_scalar_sub, gm, bt, 0, st, tau_c, d2.as<Fr>(), t1.as<Fr>(), m);
-  DVP_TRY(batch_inverse_dev(t1.as<Fr>(), m, st));
-  DVP_LAUNCH(ks_mul_scale, gm, bt, 0, st, t1.as<Fr>(), bard.as<Fr>(), zd_tau_m, l_taud.as<Fr>(), m);
+  DVP_TRY(vec_scalar_sub_dev(tau_c, d, t1, m, st));
+  DVP_TRY(batch_inverse_dev(t1, m, st));
+  DVP_LAUNCH(ks_mul_scale, gm, bt, 0, st, t1, bar, z_tau_m, l_tau, m, 1u, 0u);
+  DVP_TRY(vec_scalar_sub_dev(tau_c, d2, t1, m, st));
+  DVP_TRY(batch_inverse_dev(t1, m, st));
+  DVP_LAUNCH(ks_mul_scale, gm, bt, 0, st, t1, bard, zd_tau_m, l_taud, m, 1u, 0u);
   // g_k_0 = L(tau), g_k_1 = delta L(tau), g_k_2 = delta^2 x the unified-domain values, interleaved [D_i, D'_i] (src/ec_fft.rs:445-448)
-  DVP_HIP(hipMemcpyAsync(s_k0, l_tau.p, m * sizeof(Fr), hipMemcpyDeviceToDevice, st));
-  DVP_LAUNCH(ks_scale, gm, bt, 0, st, l_tau.as<Fr>(), delta_m, s_k1, m);
+  DVP_HIP(hipMemcpyAsync(S.vec(S.G_K0), l_tau, m * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+  DVP_TRY(vec_scale_dev(l_tau, delta_m, S.vec(S.G_K1), m, st));
   const Fr zd_d2_m = fr_to_mont(fr_mul(delta2_m, zd_tau)), z_d2_m = fr_to_mont(fr_mul(delta2_m, z_tau));
-  DVP_LAUNCH(ks_mul_scale_strided, gm, bt, 0, st, l_tau.as<Fr>(), z2dinv.as<Fr>(), zd_d2_m, s_k2, m, 2u, 0u);
-  DVP_LAUNCH(ks_mul_scale_strided, gm, bt, 0, st, l_taud.as<Fr>(), z2inv.as<Fr>(), z_d2_m, s_k2, m, 2u, 1u);
+  DVP_LAUNCH(ks_mul_scale, gm, bt, 0, st, l_tau, z2dinv, zd_d2_m, S.vec(S.G_K2), m, 2u, 0u);
+  DVP_LAUNCH(ks_mul_scale, gm, bt, 0, st, l_taud, z2inv, z_d2_m, S.vec(S.G_K2), m, 2u, 1u);
   // g_q = eps Z_D(tau) delta^2 L'(tau)
   const Fr gq_m = fr_to_mont(fr_mul(eps_m, fr_mul(delta2_m, z_tau)));
-  DVP_LAUNCH(ks_scale, gm, bt, 0, st, l_taud.as<Fr>(), gq_m, s_gq, m);
+  DVP_TRY(vec_scale_dev(l_taud, gq_m, S.vec(S.G_Q), m, st));
   // g_m = eps m(tau, delta): gather per wire over the transposed matrices
   {
     DevBuf coeffs_m;
     DVP_TRY(coeffs_m.alloc((size_t)(n_coeffs ? n_coeffs : 1) * sizeof(Fr)));
-    if (n_coeffs) DVP_LAUNCH(ks_to_mont, dim3(cdiv(n_coeffs, TPB)), bt, 0, st, d_coeffs.as<Fr>(), coeffs_m.as<Fr>(), (size_t)n_coeffs);
+    DVP_TRY(vec_to_mont_dev(d_coeffs.as<Fr>(), coeffs_m.as<Fr>(), n_coeffs, st));
     CsrT A{tptr[0].as<uint32_t>(), trow[0].as<uint32_t>(), tcid[0].as<uint32_t>()};
     CsrT B{tptr[1].as<uint32_t>(), trow[1].as<uint32_t>(), tcid[1].as<uint32_t>()};
     CsrT Cm{tptr[2].as<uint32_t>(), trow[2].as<uint32_t>(), tcid[2].as<uint32_t>()};
-    DVP_LAUNCH(ks_m_values, dim3(cdiv(n_wires, TPB)), bt, 0, st, A, B, Cm, coeffs_m.as<Fr>(), l_tau.as<Fr>(), delta_m, delta2_m, eps_m,
-                       n_wires, s_gm);
+    DVP_LAUNCH(ks_m_values, dim3(cdiv(n_wires, TPB)), bt, 0, st, A, B, Cm, coeffs_m.as<Fr>(), l_tau, delta_m, delta2_m, eps_m, n_wires, s_gm);
     DVP_HIP(hipGetLastError());
     DVP_HIP(hipStreamSynchronize(st));
   }
   // the Vandermonde fold C' = C - D: wire 1 + j of EVERY row carries -d_i^j (src/gnark_r1cs.rs:333-386)
   if (n_public) {
-    DevBuf pw, part;
-    const uint32_t nb = std::min<uint32_t>(cdiv(m, TPB), 1024u);
+    DevBuf pw, part, dot;
     DVP_TRY(pw.alloc(m * sizeof(Fr)));
-    DVP_TRY(part.alloc((size_t)nb * sizeof(Fr)));
+    DVP_TRY(part.alloc(VEC_DOT_BLOCKS * sizeof(Fr)));
+    DVP_TRY(dot.alloc(sizeof(Fr)));
     DVP_LAUNCH(ks_fill_one, gm, bt, 0, st, pw.as<Fr>(), m);
-    const Fr ed2_m = fr_to_mont(fr_mul(eps_m, fr_mul(delta2_m, fr_one_canon())));  // eps delta^2
-    // per public input: block partials of <d^j, L(tau)>, then ONE block folds them and subtracts eps delta^2 x the sum from the wire's
-    // scalar in place -- no copy to the host and no wait inside the loop (the first version took two host round trips per input)
+    const Fr neg_ed2_m = fr_neg(fr_to_mont(fr_mul(eps_m, fr_mul(delta2_m, fr_one_canon()))));  // -eps delta^2
+    // per public input: <d^j, L(tau)> into one device Fr, then the wire's scalar -= eps delta^2 x that sum in place, as an axpy of length
+    // one -- no copy to the host and no wait inside the loop (the first version took two host round trips per input)
     for (uint32_t j = 0; j < n_public; ++j) {
-      DVP_LAUNCH(ks_dot_partial, dim3(nb), bt, 0, st, pw.as<Fr>(), l_tau.as<Fr>(), m, part.as<Fr>());
-      DVP_LAUNCH(ks_fold_apply, dim3(1), bt, 0, st, part.as<Fr>(), nb, ed2_m, s_gm + 1 + j);
-      if (j + 1 < n_public) DVP_LAUNCH(ks_mul, gm, bt, 0, st, pw.as<Fr>(), d.as<Fr>(), pw.as<Fr>(), m);
+      DVP_TRY(vec_dot_dev(pw.as<Fr>(), l_tau, m, part.as<Fr>(), dot.as<Fr>(), st));
+      DVP_TRY(vec_axpy_dev(s_gm + 1 + j, neg_ed2_m, dot.as<Fr>(), s_gm + 1 + j, 1, st));
+      if (j + 1 < n_public) DVP_TRY(vec_mul_dev(pw.as<Fr>(), d, pw.as<Fr>(), m, st));
     }
-    DVP_HIP(hipGetLastError());
-    DVP_HIP(hipStreamSynchronize(st));  // pw / part go out of scope
+    DVP_HIP(hipStreamSynchronize(st));  // pw / part / dot go out of scope
   }
   DVP_HIP(hipGetLastError());
   return DVP_OK;
 }
 int setup_check_trapdoor(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], Fr& tau_c, Fr& delta_c, Fr& eps_c) {
-  if (!tau || !delta || !epsilon) return DVP_EINVAL;
-  tau_c = load_fr(tau); delta_c = load_fr(delta); eps_c = load_fr(epsilon);
-  if (!fr_is_canonical(tau_c) || !fr_is_canonical(delta_c) || !fr_is_canonical(eps_c)) return DVP_EINVAL;
+  DVP_TRY(load_trapdoor(tau, delta, epsilon, &tau_c, &delta_c, &eps_c));
   if (fr_is_zero(tau_c) || fr_is_zero(delta_c) || fr_is_zero(eps_c)) return DVP_EINVAL;  // src/srs.rs:199-201
   return DVP_OK;
 }
@@ -331,13 +270,11 @@ extern "C" int dvp_setup_scalars(const uint64_t tau[4], const uint64_t delta[4],
       if (wire_ids[k][e] >= n_wires || coeff_ids[k][e] >= n_coeffs) { g_last_error_index = (int64_t)e; return DVP_EINVAL; }
     cc.rp[k] = row_ptr[k]; cc.wi[k] = wire_ids[k]; cc.ci[k] = coeff_ids[k];
   }
-  SetupState S;
-  S.log_m = log2_m;
-  S.m = (size_t)1 << log2_m;
-  if (out_cap < (size_t)n_wires + 5 * S.m) return DVP_EINVAL;
+  SetupState S(log2_m, n_wires);
+  if (out_cap < S.n_sc()) return DVP_EINVAL;
   hipStream_t st = nullptr;
   DVP_TRY(setup_scalars_core(cc, tau, tau_c, delta_c, eps_c, n_public, S, st));
-  DVP_HIP(hipMemcpyAsync(out_scalars, S.sc.p, S.n_sc * sizeof(Fr), hipMemcpyDeviceToHost, st));
+  DVP_HIP(hipMemcpyAsync(out_scalars, S.sc.p, S.n_sc() * sizeof(Fr), hipMemcpyDeviceToHost, st));
   DVP_HIP(hipStreamSynchronize(st));
   return DVP_OK;
 }
@@ -353,8 +290,9 @@ extern "C" int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delt
   const std::string dir(cache_dir);
   auto path = [&](const char* name) { return dir + "/" + name; };
   // ---- the circuit (src/gnark_r1cs.rs:121-185) ----
-  File dump;
+  MappedFile dump;
   DVP_TRY(dump.open_ro(path("r1cs_to_dvsnark").c_str()));  // R1CS_CONSTRAINTS_FILE, src/artifacts.rs:76
+  if (!dump.len) return DVP_EIO;                           // an empty dump is unreadable, not a circuit without rows
   uint32_t n_coeffs = 0, n_rows = 0, n_wires = 0;
   uint64_t nnz[3] = {0, 0, 0};
   DVP_TRY(dvp_r1cs_dump_sizes(dump.p, dump.len, &n_coeffs, &n_rows, nnz, &n_wires));
@@ -382,41 +320,31 @@ extern "C" int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delt
   SetupCircuit cc;
   cc.n_coeffs = n_coeffs; cc.n_rows = n_rows; cc.n_wires = n_wires; cc.coeffs = coeffs.data();
   for (int k = 0; k < 3; ++k) { cc.rp[k] = rpp[k]; cc.wi[k] = wip[k]; cc.ci[k] = cip[k]; }
-  SetupState S;
-  S.log_m = log_m;
-  S.m = m;
+  SetupState S(log_m, n_wires);
   hipStream_t st = nullptr;
   DVP_TRY(setup_scalars_core(cc, tau, tau_c, delta_c, eps_c, n_public, S, st));
-  dvp_ecfft* tree = S.tree;
-  DevBuf &bar = S.bar, &z2inv = S.z2inv, &bard = S.bard, &z2dinv = S.z2dinv, &t1 = S.t1, &sc = S.sc;
-  const size_t n_sc = S.n_sc;
-  Fr* s_gm = sc.as<Fr>();
-  Fr* s_gq = s_gm + n_wires;
-  Fr* s_k0 = s_gq + m;
-  Fr* s_k1 = s_k0 + m;
-  Fr* s_k2 = s_k1 + m;
   const dim3 gm(cdiv(m, TPB)), bt(TPB);
   if (out_scalars) {
-    DVP_HIP(hipMemcpyAsync(out_scalars, sc.p, n_sc * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    DVP_HIP(hipMemcpyAsync(out_scalars, S.sc.p, S.n_sc() * sizeof(Fr), hipMemcpyDeviceToHost, st));
     DVP_HIP(hipStreamSynchronize(st));
   }
   // ---- compute_srs_matrices: one batched fixed-base multiplication + encoding per vector, then the files (src/srs.rs:126-167) ----
   {
-    static const char* const names[5] = {"g_m", "g_q", "g_k_0", "g_k_1", "g_k_2"};  // src/artifacts.rs:18-27
-    const Fr* vec[5] = {s_gm, s_gq, s_k0, s_k1, s_k2};
-    const size_t cnt[5] = {n_wires, m, m, m, 2 * m};
+    static const char* const names[5] = {"g_m", "g_q", "g_k_0", "g_k_1", "g_k_2"};  // src/artifacts.rs:18-27, SetupState's order
+    const size_t most = std::max<size_t>(2 * m, n_wires);
     DevBuf pts, inf, enc;
-    DVP_TRY(pts.alloc(2 * m > n_wires ? 2 * m * sizeof(Aff) : (size_t)n_wires * sizeof(Aff)));
-    DVP_TRY(inf.alloc(2 * m > n_wires ? 2 * m : (size_t)n_wires));
-    DVP_TRY(enc.alloc((2 * m > n_wires ? 2 * m : (size_t)n_wires) * 30));
+    DVP_TRY(pts.alloc(most * sizeof(Aff)));
+    DVP_TRY(inf.alloc(most));
+    DVP_TRY(enc.alloc(most * 30));
     std::vector<uint8_t> host;
     for (int i = 0; i < 5; ++i) {
-      DVP_TRY(mulgen_dev(vec[i], cnt[i], pts.as<Aff>(), inf.as<uint8_t>(), st));
-      DVP_TRY(encode_dev(pts.as<Aff>(), inf.as<uint8_t>(), cnt[i], enc.as<uint8_t>(), st));
-      host.resize(cnt[i] * 30);
-      DVP_HIP(hipMemcpyAsync(host.data(), enc.p, cnt[i] * 30, hipMemcpyDeviceToHost, st));
+      const size_t cnt = S.count(i);
+      DVP_TRY(mulgen_dev(S.vec(i), cnt, pts.as<Aff>(), inf.as<uint8_t>(), st));
+      DVP_TRY(encode_dev(pts.as<Aff>(), inf.as<uint8_t>(), cnt, enc.as<uint8_t>(), st));
+      host.resize(cnt * 30);
+      DVP_HIP(hipMemcpyAsync(host.data(), enc.p, cnt * 30, hipMemcpyDeviceToHost, st));
       DVP_HIP(hipStreamSynchronize(st));
-      DVP_TRY(dvp_file_point_vec_write(path(names[i]).c_str(), host.data(), cnt[i]));
+      DVP_TRY(dvp_file_point_vec_write(path(names[i]).c_str(), host.data(), cnt));
     }
   }
   // ---- the domain files (src/srs.rs:216-346; the reference quotes "2 hrs+" for z_poly at 2^23, src/artifacts.rs:92) ----
@@ -428,29 +356,24 @@ extern "C" int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delt
     DVP_TRY(ev.alloc(2 * m * sizeof(Fr)));
     DVP_TRY(co.alloc(2 * m * sizeof(Fr)));
     DVP_TRY(flag.alloc(4));
-    std::vector<uint64_t> host(4 * (m + 1));
+    std::vector<uint64_t> host;
+    host.reserve(4 * (m + 1));  // z_poly, the longest of the six
     for (int which = 0; which < 2; ++which) {
-      Fr* b = which ? bard.as<Fr>() : bar.as<Fr>();
-      Fr* z = which ? z2dinv.as<Fr>() : z2inv.as<Fr>();
-      DVP_HIP(hipMemcpyAsync(host.data(), b, m * sizeof(Fr), hipMemcpyDeviceToHost, st));
-      DVP_HIP(hipStreamSynchronize(st));
-      DVP_TRY(dvp_file_fr_vec_write(path(bw[which]).c_str(), host.data(), m));
-      DVP_HIP(hipMemcpyAsync(host.data(), z, m * sizeof(Fr), hipMemcpyDeviceToHost, st));
-      DVP_HIP(hipStreamSynchronize(st));
-      DVP_TRY(dvp_file_fr_vec_write(path(zi[which]).c_str(), host.data(), m));
+      const DevBuf& z = which ? S.z2dinv : S.z2inv;
+      DVP_TRY(fr_vec_to_file((which ? S.bard : S.bar).p, m, path(bw[which]), host, st));
+      DVP_TRY(fr_vec_to_file(z.p, m, path(zi[which]), host, st));
       // compute_vanishing_polynomial (src/ec_fft.rs:241-282): Z_S on the 2m leaves (0 on S, 1 / zinv on the other half) -> exit
-      DVP_HIP(hipMemcpyAsync(t1.p, z, m * sizeof(Fr), hipMemcpyDeviceToDevice, st));
-      DVP_TRY(batch_inverse_dev(t1.as<Fr>(), m, st));
-      DVP_LAUNCH(ks_vanish_evals, gm, bt, 0, st, t1.as<Fr>(), (uint32_t)m, which, ev.as<Fr>());
-      DVP_TRY(dvp_ecfft_exit_dev(tree, ev.p, co.p, st));
+      DVP_HIP(hipMemcpyAsync(S.t1.p, z.p, m * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+      DVP_TRY(batch_inverse_dev(S.t1.as<Fr>(), m, st));
+      DVP_LAUNCH(ks_vanish_evals, gm, bt, 0, st, S.t1.as<Fr>(), (uint32_t)m, which, ev.as<Fr>());
+      DVP_TRY(dvp_ecfft_exit_dev(S.tree.t, ev.p, co.p, st));
       DVP_HIP(hipMemsetAsync(flag.p, 0, 4, st));
       DVP_LAUNCH(ks_check_monic, gm, bt, 0, st, co.as<Fr>(), (uint32_t)m, flag.as<unsigned int>());
       unsigned int bad = 0;
       DVP_HIP(hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, st));
-      DVP_HIP(hipMemcpyAsync(host.data(), co.p, (m + 1) * sizeof(Fr), hipMemcpyDeviceToHost, st));
       DVP_HIP(hipStreamSynchronize(st));
       if (bad) return DVP_EINVAL;  // not monic of degree m: the tree and the tables disagree
-      DVP_TRY(dvp_file_fr_vec_write(path(zp[which]).c_str(), host.data(), m + 1));
+      DVP_TRY(fr_vec_to_file(co.p, m + 1, path(zp[which]), host, st));
     }
   }
   return DVP_OK;
@@ -568,10 +491,7 @@ extern "C" int dvp_ecfft_check_tree_file(dvp_ecfft* tree, const char* path, int 
 //   validate_precompute: z_poly must not be all zero and must vanish on D (the reference's two asserts, :281-296 / :307-321);
 //   beyond the reference, files that were FOUND (tree2n, bar_wts, z_vals2inv) are compared with the regenerated values.
 // *report (optional): DVP_PREP_* bits of include/dvpari.h.  DVP_EINVAL = a validation failed (the bits say which).
-extern "C" int dvp_prover_prepares_precomputes(const char* cache_dir, int validate_precompute, uint32_t* report) {
-  if (!cache_dir) return DVP_EINVAL;
-  uint32_t rep = 0;
-  struct Rep { uint32_t* out; uint32_t* v; ~Rep() { if (out) *out = *v; } } rep_guard{report, &rep};
+static int prepares_precomputes(const char* cache_dir, int validate_precompute, uint32_t& rep) {
   const std::string dir(cache_dir);
   auto path = [&](const char* name) { return dir + "/" + name; };
   DVP_TRY(mkdir_p(dir));
@@ -585,9 +505,9 @@ extern "C" int dvp_prover_prepares_precomputes(const char* cache_dir, int valida
   if (log_m > DVP_MAX_LOG2_CONSTRAINTS) return DVP_EINVAL;
   std::vector<uint64_t> zpoly(nz * 4);
   DVP_TRY(dvp_file_fr_vec_read(path("z_poly").c_str(), zpoly.data(), nz, &nz));
-  dvp_ecfft* tree = nullptr;
-  DVP_TRY(dvp_ecfft_create(log_m + 1, 0, 0, &tree));
-  struct TreeGuard { dvp_ecfft* t; ~TreeGuard() { if (t) dvp_ecfft_destroy(t); } } tree_guard{tree};
+  TreeOwner owner;
+  DVP_TRY(dvp_ecfft_create(log_m + 1, 0, 0, &owner.t));
+  dvp_ecfft* tree = owner.t;
   // ---- TREE_2N (load_tree, :250-275) ----
   const std::string t2n = path("tree2n");
   if (!file_exists(t2n)) {
@@ -618,17 +538,15 @@ extern "C" int dvp_prover_prepares_precomputes(const char* cache_dir, int valida
   const bool monic = zpoly[m * 4] == 1 && !zpoly[m * 4 + 1] && !zpoly[m * 4 + 2] && !zpoly[m * 4 + 3];
   if (!monic) {
     Fr c;
-    memcpy(c.v, &zpoly[m * 4], 32);
-    if (fr_is_zero(c) || !fr_is_canonical(c)) {
+    if (!fr_load(&zpoly[m * 4], &c) || fr_is_zero(c)) {
       rep |= DVP_PREP_Z_POLY_NOT_MONIC | DVP_PREP_BAD_Z_POLY;
       return DVP_EINVAL;
     }
-    const Fr cinv_m = fr_inv(fr_to_mont(c));  // Montgomery: ks_scale(canonical, Montgomery) -> canonical
-    DVP_LAUNCH(ks_scale, gm, bt, 0, st, bar.as<Fr>(), cinv_m, bar.as<Fr>(), m);
-    DVP_LAUNCH(ks_scale, gm, bt, 0, st, zinv.as<Fr>(), cinv_m, zinv.as<Fr>(), m);
-    DVP_HIP(hipGetLastError());
+    const Fr cinv_m = fr_inv(fr_to_mont(c));  // Montgomery: a canonical vector scaled by it stays canonical
+    DVP_TRY(vec_scale_dev(bar.as<Fr>(), cinv_m, bar.as<Fr>(), m, st));
+    DVP_TRY(vec_scale_dev(zinv.as<Fr>(), cinv_m, zinv.as<Fr>(), m, st));
   }
-  std::vector<uint64_t> host(m * 4), found(m * 4);
+  std::vector<uint64_t> host, found(m * 4);
   static const struct { const char* name; uint32_t wrote, bad; } files[2] = {{"bar_wts", DVP_PREP_WROTE_BAR_WTS, DVP_PREP_BAD_BAR_WTS},
                                                                             {"z_vals2inv", DVP_PREP_WROTE_Z_VALS2INV, DVP_PREP_BAD_Z_VALS2INV}};
   int verdict = DVP_OK;
@@ -636,13 +554,12 @@ extern "C" int dvp_prover_prepares_precomputes(const char* cache_dir, int valida
     const std::string p = path(files[k].name);
     const bool have = file_exists(p);
     if (have && !validate_precompute) continue;
-    DVP_HIP(hipMemcpyAsync(host.data(), k ? zinv.p : bar.p, m * sizeof(Fr), hipMemcpyDeviceToHost, st));
-    DVP_HIP(hipStreamSynchronize(st));
     if (!have) {
-      DVP_TRY(dvp_file_fr_vec_write(p.c_str(), host.data(), m));
+      DVP_TRY(fr_vec_to_file(k ? zinv.p : bar.p, m, p, host, st));
       rep |= files[k].wrote;
       continue;
     }
+    DVP_TRY(fr_vec_down(k ? zinv.p : bar.p, m, host, st));
     size_t cnt = 0;
     DVP_TRY(dvp_file_fr_vec_read(p.c_str(), nullptr, 0, &cnt));
     bool same = cnt == m;
@@ -683,4 +600,11 @@ extern "C" int dvp_prover_prepares_precomputes(const char* cache_dir, int valida
     }
   }
   return verdict;
+}
+extern "C" int dvp_prover_prepares_precomputes(const char* cache_dir, int validate_precompute, uint32_t* report) {
+  if (!cache_dir) return DVP_EINVAL;
+  uint32_t rep = 0;
+  const int rc = prepares_precomputes(cache_dir, validate_precompute, rep);
+  if (report) *report = rep;  // on every path: after a failed validation the bits say which
+  return rc;
 }

@@ -18,57 +18,33 @@
 // Use: the GPU prover regenerates its twiddles from the curve constants (src/ec_fft.rs:205-229) and reads no tree
 // file; this reader exists to CHECK a reference-built tree2n / treen against the regenerated domain
 // (dv-pari_amd/tree_io.py: check_tree_file) and to write files in the same container.
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "../../include/dvpari.h"
 #include "fr.cuh"  // fr_first_noncanonical
+#include "mapped_file.h"
 
 namespace {
 
 const uint8_t MAGIC[8] = {'F', 'F', 'T', 'R', 0, 0, 0, 0};
 
-struct Map {
-  const uint8_t* p = nullptr;
-  size_t len = 0;
-  int fd = -1;
-  ~Map() {
-    if (p && len) munmap((void*)p, len);
-    if (fd >= 0) close(fd);
-  }
-  int open_ro(const char* path) {
-    fd = ::open(path, O_RDONLY);
-    if (fd < 0) return DVP_EIO;
-    struct stat st;
-    if (fstat(fd, &st) != 0) return DVP_EIO;
-    len = (size_t)st.st_size;
-    if (!len) return DVP_EIO;
-    void* q = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (q == MAP_FAILED) { len = 0; return DVP_EIO; }
-    p = (const uint8_t*)q;
-    return DVP_OK;
-  }
-};
-uint64_t rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
-uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
+using dvp::MappedFile;
+using dvp::rd32le;
+using dvp::rd64le;
 
 struct Sec { uint8_t id; uint64_t off, len; };
 // the node that starts at `node` (node_len bytes): its section table, every range checked against the node
 int parse_node(const uint8_t* node, size_t node_len, std::vector<Sec>* out) {
   if (node_len < 8) return DVP_EIO;
-  const uint32_t cnt = rd32(node);
+  const uint32_t cnt = rd32le(node);
   if (cnt > 13 || (node_len - 8) / 24 < cnt) return DVP_EIO;
   const size_t table_end = 8 + (size_t)24 * cnt;
   out->clear();
   for (uint32_t i = 0; i < cnt; ++i) {
     const uint8_t* m = node + 8 + 24 * (size_t)i;
-    Sec s{m[0], rd64(m + 8), rd64(m + 16)};
+    Sec s{m[0], rd64le(m + 8), rd64le(m + 16)};
     if (s.id > 12) return DVP_EIO;                                          // "unknown section id", :50-70
     if (s.off < table_end || s.off > node_len || s.len > node_len - s.off) return DVP_EIO;
     for (const Sec& t : *out)
@@ -78,9 +54,10 @@ int parse_node(const uint8_t* node, size_t node_len, std::vector<Sec>* out) {
   return DVP_OK;
 }
 // walks `depth` subtree links down from the root node
-int find_node(const Map& f, uint32_t depth, const uint8_t** node, size_t* node_len, std::vector<Sec>* secs) {
-  if (f.len < 16 || memcmp(f.p, MAGIC, 8) != 0) return DVP_EIO;  // "not an FFTR file", :225
-  const uint64_t total = rd64(f.p + 8);
+int find_node(const MappedFile& f, uint32_t depth, const uint8_t** node, size_t* node_len, std::vector<Sec>* secs) {
+  // "not an FFTR file", :225 -- an empty file, which MappedFile opens with len == 0 and nothing mapped, is refused here
+  if (f.len < 16 || memcmp(f.p, MAGIC, 8) != 0) return DVP_EIO;
+  const uint64_t total = rd64le(f.p + 8);
   if (total > f.len - 16) return DVP_EIO;
   *node = f.p + 16;
   *node_len = (size_t)total;
@@ -107,10 +84,9 @@ bool canonical29(const uint8_t* e) {  // 29 little-endian bytes, zero-extended: 
 // Sections of the node `depth` subtree links below the root: ids[k], lens[k] (blob bytes), k < *n_sections (<= 13).
 extern "C" int dvp_fftr_sections(const char* path, uint32_t depth, uint8_t ids[13], uint64_t lens[13], uint32_t* n_sections) {
   if (!path || !ids || !lens || !n_sections) return DVP_EINVAL;
-  Map f;
+  MappedFile f;
   int rc = f.open_ro(path);
-  if (rc) return rc;
-  const uint8_t* node;
+  if (rc) return rc;  const uint8_t* node;
   size_t node_len;
   std::vector<Sec> secs;
   rc = find_node(f, depth, &node, &node_len, &secs);
@@ -125,10 +101,9 @@ extern "C" int dvp_fftr_sections(const char* path, uint32_t depth, uint8_t ids[1
 // -> DVP_EIO.
 extern "C" int dvp_fftr_read_fr(const char* path, uint32_t depth, uint8_t id, uint64_t* out, size_t cap, size_t* n) {
   if (!path || !n || id == 3 || id > 11) return DVP_EINVAL;
-  Map f;
+  MappedFile f;
   int rc = f.open_ro(path);
-  if (rc) return rc;
-  const uint8_t* node;
+  if (rc) return rc;  const uint8_t* node;
   size_t node_len;
   std::vector<Sec> secs;
   rc = find_node(f, depth, &node, &node_len, &secs);
@@ -139,7 +114,7 @@ extern "C" int dvp_fftr_read_fr(const char* path, uint32_t depth, uint8_t id, ui
   if (!s) return DVP_EINVAL;  // "missing section"
   if (s->len < 8) return DVP_EIO;
   const uint8_t* blob = node + s->off;
-  const uint64_t cnt = rd64(blob);
+  const uint64_t cnt = rd64le(blob);
   const uint64_t per = (id == 1 || id == 2) ? 4 : 1;
   if (cnt > (s->len - 8) / (29 * per) || 8 + cnt * 29 * per != s->len) return DVP_EIO;
   *n = (size_t)(cnt * per);

@@ -32,6 +32,7 @@
 #include "codec.cuh"
 #include "common.h"
 #include "fr.cuh"
+#include "fr_block.cuh"
 #include "host_api.h"
 #include "k233.cuh"
 #include "tau.cuh"
@@ -392,25 +393,19 @@ k_verify_rlc_prep(const uint8_t* __restrict__ proofs, size_t n, const Fr* __rest
 constexpr uint32_t RLC_SUM_TPB = 256;
 constexpr uint32_t RLC_SUM_BLOCKS = 1024;  // level-1 blocks at most: level 2 is one block over their partials
 
-// sum mod p of a block's values and count of its well-formed proofs; the tree over the block's lanes is fixed, and Fr addition is
-// exact, so the result does not depend on the order in which blocks run
+// sum mod p of a block's values and count of its well-formed proofs; Fr addition is exact and the count is an integer, so the result
+// does not depend on the order in which lanes or blocks run
+static_assert(RLC_SUM_TPB == 256, "block_sum256");
 __device__ __forceinline__ void rlc_block_sum(Fr s, uint32_t w, Fr* out, uint32_t* out_w) {
   __shared__ Fr ls[RLC_SUM_TPB];
-  __shared__ uint32_t lw[RLC_SUM_TPB];
-  ls[threadIdx.x] = s;
-  lw[threadIdx.x] = w;
+  __shared__ uint32_t lw;
+  if (threadIdx.x == 0) lw = 0;
+  const Fr total = block_sum256(s, ls);  // its barriers put the zero before the additions
+  atomicAdd(&lw, w);
   __syncthreads();
-#pragma unroll 1
-  for (uint32_t h = RLC_SUM_TPB / 2; h > 0; h >>= 1) {
-    if (threadIdx.x < h) {
-      ls[threadIdx.x] = fr_add(ls[threadIdx.x], ls[threadIdx.x + h]);
-      lw[threadIdx.x] += lw[threadIdx.x + h];
-    }
-    __syncthreads();
-  }
   if (threadIdx.x == 0) {
-    *out = ls[0];
-    *out_w = lw[0];
+    *out = total;
+    *out_w = lw;
   }
 }
 
@@ -459,8 +454,6 @@ k_rlc_check(const uint32_t* __restrict__ out_inf, const unsigned long long* __re
   if (user_report) *user_report = rep;
 }
 
-static void fr_from_u64(const uint64_t* v, Fr* out) { memcpy(out->v, v, 32); }
-
 // dvp_verify_set_binding: the two hashes of the transcript's compile-time half, process-wide like the codec rule.  NULL = BLAKE3(""),
 // the reference's value.  verify_consts reads them once per call, under the mutex: a call in flight keeps what it started with.
 static std::mutex g_bind_mu;
@@ -487,12 +480,8 @@ extern "C" int dvp_verify_get_binding(uint8_t srs_hash[32], uint8_t circuit_hash
 }
 
 static int verify_consts(const uint64_t tau[4], const uint64_t delta[4], const uint64_t eps[4], VerifyConsts* c) {
-  if (!tau || !delta || !eps) return DVP_EINVAL;
-  if (fr_first_noncanonical(tau, 1) != 1 || fr_first_noncanonical(delta, 1) != 1 || fr_first_noncanonical(eps, 1) != 1) return DVP_EINVAL;
   Fr t, d, e;
-  fr_from_u64(tau, &t);
-  fr_from_u64(delta, &d);
-  fr_from_u64(eps, &e);
+  DVP_TRY(load_trapdoor(tau, delta, eps, &t, &d, &e));
   c->tau = t;
   c->delta_m = fr_to_mont(d);
   c->delta2_m = fr_to_mont(fr_mul(c->delta_m, d));  // delta^2 (canonical), then times R

@@ -228,3 +228,38 @@ def test_range_check_and_reduction_at_p(dvp, tmp_path):
     assert from_limbs(dvp.gnark_r1cs.load_witness_from_file(path)) == [v % o.P for v in vals]
     dump = py_dump([([(0, 0)], [(0, 1)], [(0, 0)])], vals)
     assert from_limbs(dvp.gnark_r1cs.R1CSInstance.from_dump_bytes(dump, 0).coeffs) == [v % o.P for v in vals]
+
+
+EIO, EINVAL = -6, -1
+
+
+@pytest.mark.parametrize("size", [0, 7])
+def test_empty_and_short_files_are_eio(dvp, tmp_path, size):
+    """a zero-byte file and one shorter than any length prefix: every reader answers DVP_EIO and writes no count.  (The mapping
+    itself admits an empty file; it is each format's look for its prefix that refuses it.)"""
+    import ctypes as C
+
+    path = tmp_path / "short"
+    path.write_bytes(bytes(range(1, size + 1)))
+    pth = os.fsencode(str(path))
+    for read in (dvp.lib.dvp_file_fr_vec_read, dvp.lib.dvp_file_point_vec_read):
+        n = C.c_size_t(77)
+        assert read(pth, None, 0, C.byref(n)) == EIO and n.value == 77, read.__name__
+    # the witness file's prefix is four bytes: seven bytes hold a count (0x01020304) the file is far too short for
+    n = C.c_size_t(77)
+    assert dvp.lib.dvp_file_witness_read(pth, None, 0, C.byref(n)) == EIO and n.value == 77
+
+
+def test_setup_cache_dir_with_an_empty_dump_is_eio(dvp, tmp_path):
+    """dvp_setup_cache_dir on a cache_dir whose r1cs_to_dvsnark is empty: DVP_EIO, before any device work (no GPU is needed to ask);
+    a missing dump likewise; the trapdoor is judged first"""
+    from importlib import import_module
+
+    nat = import_module("dv-pari_amd._native")
+    t, d, e = (dvp.fr.limbs(x) for x in (5, 6, 7))
+    cache = os.fsencode(str(tmp_path))
+    assert dvp.lib.dvp_setup_cache_dir(nat.ptr(t), nat.ptr(d), nat.ptr(e), cache, 0, 0) == EIO  # missing
+    (tmp_path / dvp.artifacts.R1CS_CONSTRAINTS_FILE).write_bytes(b"")
+    assert dvp.lib.dvp_setup_cache_dir(nat.ptr(t), nat.ptr(d), nat.ptr(e), cache, 0, 0) == EIO
+    assert dvp.lib.dvp_setup_cache_dir(nat.ptr(t), nat.ptr(d), nat.ptr(dvp.fr.limbs(0)), cache, 0, 0) == EINVAL
+    assert sorted(os.listdir(tmp_path)) == [dvp.artifacts.R1CS_CONSTRAINTS_FILE]  # nothing was written

@@ -258,6 +258,29 @@ def test_setup_cache_dir_entry_scalars(dvp, tmp_path, shape):
     pv.close()
 
 
+@pytest.mark.parametrize("n_pub", [0, 1, 3])
+@pytest.mark.parametrize("log_m", [1, 8, 9])
+def test_setup_scalars_public_fold_at_workgroup_boundaries(dvp, log_m, n_pub):
+    """dvp_setup_scalars where the Vandermonde fold's dot product <d^j, L(tau)> changes shape: m = 2 (one lane's worth), 256 (exactly
+    one workgroup) and 512 (two workgroups: the first size with more than one block partial), each without public inputs, with one
+    (no power of d is taken) and with three.  All n_wires + 5 m scalars against the oracle's brute-force setup in Python integers."""
+    m, n_wires = 1 << log_m, 8
+    rnd = random.Random(100 * log_m + n_pub)
+    coeffs = [rnd.randrange(o.P) for _ in range(5)]
+    rows = [tuple([(rnd.randrange(n_wires), rnd.randrange(5)) for _ in range(rnd.randrange(3))] for _ in range(3)) for _ in range(m)]
+    rows[0][0].append((n_wires - 1, 0))  # the highest wire is used: the oracle sizes g_m by it
+    trap = (rnd.randrange(1, o.P), rnd.randrange(1, o.P), rnd.randrange(1, o.P))
+    inst = dvp.gnark_r1cs.R1CSInstance.from_rows(rows, coeffs, n_pub, n_wires)
+    assert inst.num_constraints == m and inst.n_rows == m
+    g_m, g_q, g_k = dvp.srs.srs_scalars(None, inst, dvp.srs.Trapdoor(*trap))
+    st = o.setup_srs_scalars(o.FFTree(log_m + 1), rows, coeffs, n_pub, trap)
+    assert len(st["g_m"]) == n_wires and len(g_q) == m and [len(v) for v in g_k] == [m, m, 2 * m]
+    assert from_limbs(g_m) == st["g_m"]
+    assert from_limbs(g_q) == st["g_q"]
+    for j in range(3):
+        assert from_limbs(g_k[j]) == st["g_k"][j], j
+
+
 def test_sparse_cache_dir_with_witness_file(dvp, tmp_path):
     """BASELINE config #5 stand-in at 2^12: SP1-format dump + witness file in, proof out, verifier accepts; the
     Horner and the extend route for i(X) on D' give the same bytes."""

@@ -429,6 +429,30 @@ def test_public_inputs_of_verify_batch(dvp):
                 assert ex.value.status == EINVAL and ex.value.index == j, (j, hex(r))
 
 
+def test_trapdoor_arguments_of_setup_and_verify(dvp):
+    """tau, delta and epsilon, one at a time: a null pointer and p are DVP_EINVAL for dvp_setup_scalars and for dvp_verify_batch
+    (n = 0: the trapdoor is judged before anything else).  Zero is where the two DIFFER, on purpose: the setup refuses a zero
+    trapdoor entry (src/srs.rs:199-201), the verifier takes it as it takes any scalar below p -- the shared loader must not unify that."""
+    good = [to_limbs([v])[0] for v in (5, 6, 7)]
+    rp = np.array([0, 0, 0], dtype=np.uint32)  # two empty rows per matrix, one wire, no coefficient
+    mats = (C.c_void_p * 3)(*[rp.ctypes.data] * 3)
+    none3 = (C.c_void_p * 3)(None, None, None)
+    out = np.zeros((1 + 5 * 2, 4), dtype=np.uint64)
+
+    def setup(td):
+        return dvp.lib.dvp_setup_scalars(vp(td[0]), vp(td[1]), vp(td[2]), 1, 0, 2, 1, None, 0, mats, none3, none3, vp(out), out.shape[0])
+
+    def verify(td):
+        return dvp.lib.dvp_verify_batch(vp(td[0]), vp(td[1]), vp(td[2]), None, 0, None, 0, None)
+
+    assert setup(good) == OK and verify(good) == OK
+    for k in range(3):
+        for bad, want_setup, want_verify in ((None, EINVAL, EINVAL), (to_limbs([P])[0], EINVAL, EINVAL), (to_limbs([0])[0], EINVAL, OK)):
+            td = list(good)
+            td[k] = bad
+            assert (setup(td), verify(td)) == (want_setup, want_verify), (k, bad)
+
+
 def test_strict_points_come_before_scalars(dvp, data):
     """strict mode: a bad point and a bad scalar (at a smaller index) together report the point"""
     n = 65

@@ -131,3 +131,18 @@ def test_fftr_range_check_at_p(dvp, tmp_path):
     with pytest.raises(dvp.DvpError) as e:
         dvp.tree_io.read_section(path, "f")
     assert e.value.status == -6
+
+
+@pytest.mark.parametrize("size", [0, 7])
+def test_empty_and_short_tree_files_are_eio(dvp, tmp_path, size):
+    """a zero-byte file and one shorter than the magic: DVP_EIO from both readers, nothing written to the outputs"""
+    import ctypes as C
+    import os
+
+    path = tmp_path / "tree"
+    path.write_bytes(MAGIC[:size])
+    pth = os.fsencode(str(path))
+    ids, lens, ns = (C.c_uint8 * 13)(), (C.c_uint64 * 13)(), C.c_uint32(77)
+    assert dvp.lib.dvp_fftr_sections(pth, 0, ids, lens, C.byref(ns)) == -6 and ns.value == 77
+    n = C.c_size_t(77)
+    assert dvp.lib.dvp_fftr_read_fr(pth, 0, 0, None, 0, C.byref(n)) == -6 and n.value == 77
