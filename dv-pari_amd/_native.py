@@ -25,7 +25,23 @@ lib = C.CDLL(LIB_PATH)
 
 vp, u32, u64p, u8p, sz = C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t
 
+
+class DlogReport(C.Structure):
+    """dvp_dlog_report (include/dvpari.h)"""
+    _fields_ = [("verdict", C.c_uint32), ("path", C.c_uint32), ("first_bad", C.c_int64), ("point_class", C.c_uint8)]
+
+
+class SrsCheckReport(C.Structure):
+    """dvp_srs_check_report (include/dvpari.h)"""
+    _fields_ = [("verdict", C.c_uint32), ("bad_vectors", C.c_uint32), ("path", C.c_uint32 * 5), ("status", C.c_uint32 * 5),
+                ("first_bad", C.c_int64 * 5), ("count", C.c_uint64 * 5)]
+
+
 _SIGS = {
+    "dvp_points_check_dlog": (C.c_int, [u64p, u64p, u8p, sz, u8p, u32, C.POINTER(DlogReport)]),
+    "dvp_points_check_dlog_dev": (C.c_int, [vp, vp, vp, sz, u8p, u32, vp, sz, C.POINTER(DlogReport), vp]),
+    "dvp_points_check_dlog_work_bytes": (sz, [sz]),
+    "dvp_srs_check_cache_dir": (C.c_int, [u64p, u64p, u64p, C.c_char_p, u32, u8p, u32, C.POINTER(SrsCheckReport)]),
     "dvp_strerror": (C.c_char_p, [C.c_int]),
     "dvp_version": (C.c_int, []),
     "dvp_device_count": (C.c_int, []),

@@ -6,6 +6,12 @@
 
 namespace dvp {
 
+// A two-level sum over a vector: level 1 is at most FR_SUM_BLOCKS blocks of FR_SUM_LANES lanes, each lane striding the vector by the
+// whole grid, level 2 one block over their partials.  A vector longer than FR_SUM_LANES * FR_SUM_BLOCKS makes lanes take a second
+// element (srs_check.hip sizes its level 1 by these; the tests read them from here).
+constexpr uint32_t FR_SUM_LANES = 256;
+constexpr uint32_t FR_SUM_BLOCKS = 1024;
+
 // sum over a 256-lane block of one Fr per lane, through sh[256]: every lane gets the total, and the closing barrier leaves sh free for
 // the next call.  (Callers unroll their loop over the three sums: a runtime index put s[] / res[] into 112 B of scratch per lane.)
 __device__ __forceinline__ Fr block_sum256(const Fr& x, Fr* sh) {

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 struct dvp_ecfft;
+struct dvp_dlog_report;  // include/dvpari.h
 namespace dvp {
 struct Aff;
 struct Fr;
@@ -64,6 +65,15 @@ int encode_dev(const Aff* d_pts, const uint8_t* d_inf, size_t n, uint8_t* d_out,
 int encode_point_dev(const Aff* d_pt, const uint32_t* d_inf32, uint8_t* d_out, hipStream_t st);
 int decode_dev(const uint8_t* d_enc, size_t n, Aff* d_out, uint8_t* d_inf, hipStream_t st);
 int points_check_strict(const void* d_xy, const void* d_inf, size_t n, hipStream_t st);  // a no-op unless strict mode is on
+// enqueue only: resets d_summary (16 bytes: first bad index or ~0, number of bad points), then classifies; d_inf / d_classes may be null
+int points_check_dev(const void* d_xy, const void* d_inf, size_t n, void* d_classes, void* d_summary, hipStream_t st);
+
+// ---- srs_check.hip -----------------------------------------------------------------------------------------------------------
+// dvp_points_check_dlog_dev with the key already settled (the caller's seed, or what it derives when there is none); d_work holds
+// dlog_check_work_bytes(n) bytes, 256-byte aligned.  Waits on `st`.
+size_t dlog_check_work_bytes(size_t n);
+int dlog_check_dev(const void* d_scalars, const void* d_xy, const void* d_inf, size_t n, const uint8_t key[32], uint32_t flags, void* d_work,
+                   dvp_dlog_report* report, hipStream_t st);
 
 // ---- points_mul.hip ----------------------------------------------------------------------------------------------------------
 int points_mul_dev(const void* d_scalars, size_t n_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf,

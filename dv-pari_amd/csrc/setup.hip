@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "blake3.h"
 #include "common.h"
 #include "ecfft_internal.h"
 #include "host_api.h"
@@ -246,6 +247,44 @@ int setup_check_trapdoor(const uint64_t tau[4], const uint64_t delta[4], const u
   if (fr_is_zero(tau_c) || fr_is_zero(delta_c) || fr_is_zero(eps_c)) return DVP_EINVAL;  // src/srs.rs:199-201
   return DVP_OK;
 }
+// cache_dir/r1cs_to_dvsnark as the setup reads it (src/gnark_r1cs.rs:121-185): open() maps the dump and settles the sizes, fill()
+// parses it into `cc`.  What dvp_setup_cache_dir_ex and dvp_srs_check_cache_dir start from.
+struct SetupDump {
+  MappedFile dump;
+  uint32_t n_coeffs = 0, n_rows = 0, n_wires = 0, log_m = 0;
+  uint64_t nnz[3] = {0, 0, 0};
+  std::vector<uint64_t> coeffs;
+  std::vector<uint32_t> rp[3], wi[3], ci[3];
+  SetupCircuit cc;
+  size_t m() const { return (size_t)1 << log_m; }
+  int open(const std::string& dir, uint32_t n_public) {
+    DVP_TRY(dump.open_ro((dir + "/r1cs_to_dvsnark").c_str()));  // R1CS_CONSTRAINTS_FILE, src/artifacts.rs:76
+    if (!dump.len) return DVP_EIO;                              // an empty dump is unreadable, not a circuit without rows
+    DVP_TRY(dvp_r1cs_dump_sizes(dump.p, dump.len, &n_coeffs, &n_rows, nnz, &n_wires));
+    if (n_rows == 0 || n_wires < 1 + (uint64_t)n_public) return DVP_EINVAL;
+    for (int k = 0; k < 3; ++k)
+      if (nnz[k] > 0xffffffffull) return DVP_EINVAL;
+    while ((1ull << log_m) < n_rows) ++log_m;  // next_power_of_two, src/gnark_r1cs.rs:291
+    if (log_m < 1) log_m = 1;
+    if (log_m > DVP_MAX_LOG2_CONSTRAINTS) return DVP_EINVAL;
+    return DVP_OK;
+  }
+  int fill() {
+    coeffs.resize((size_t)4 * n_coeffs);
+    uint32_t *rpp[3], *wip[3], *cip[3];
+    for (int k = 0; k < 3; ++k) {
+      rp[k].resize((size_t)n_rows + 1);
+      wi[k].resize(nnz[k] ? nnz[k] : 1);
+      ci[k].resize(nnz[k] ? nnz[k] : 1);
+      rpp[k] = rp[k].data(); wip[k] = wi[k].data(); cip[k] = ci[k].data();
+    }
+    DVP_TRY(dvp_r1cs_dump_fill(dump.p, dump.len, coeffs.data(), rpp, wip, cip));
+    cc.n_coeffs = n_coeffs; cc.n_rows = n_rows; cc.n_wires = n_wires; cc.coeffs = coeffs.data();
+    for (int k = 0; k < 3; ++k) { cc.rp[k] = rpp[k]; cc.wi[k] = wip[k]; cc.ci[k] = cip[k]; }
+    return DVP_OK;
+  }
+};
+const char* const kSrsNames[5] = {"g_m", "g_q", "g_k_0", "g_k_1", "g_k_2"};  // src/artifacts.rs:18-27, SetupState's order
 }  // namespace
 
 // TEST / HARNESS ONLY (include/dvpari_internal.h): the SRS scalars (discrete logs: trapdoor material) of an IN-MEMORY circuit -- CSR
@@ -290,39 +329,17 @@ extern "C" int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delt
   const std::string dir(cache_dir);
   auto path = [&](const char* name) { return dir + "/" + name; };
   // ---- the circuit (src/gnark_r1cs.rs:121-185) ----
-  MappedFile dump;
-  DVP_TRY(dump.open_ro(path("r1cs_to_dvsnark").c_str()));  // R1CS_CONSTRAINTS_FILE, src/artifacts.rs:76
-  if (!dump.len) return DVP_EIO;                           // an empty dump is unreadable, not a circuit without rows
-  uint32_t n_coeffs = 0, n_rows = 0, n_wires = 0;
-  uint64_t nnz[3] = {0, 0, 0};
-  DVP_TRY(dvp_r1cs_dump_sizes(dump.p, dump.len, &n_coeffs, &n_rows, nnz, &n_wires));
-  if (n_rows == 0 || n_wires < 1 + (uint64_t)n_public) return DVP_EINVAL;
-  for (int k = 0; k < 3; ++k)
-    if (nnz[k] > 0xffffffffull) return DVP_EINVAL;
-  uint32_t log_m = 0;
-  while ((1ull << log_m) < n_rows) ++log_m;  // next_power_of_two, src/gnark_r1cs.rs:291
-  if (log_m < 1) log_m = 1;
-  if (log_m > DVP_MAX_LOG2_CONSTRAINTS) return DVP_EINVAL;
-  const size_t m = (size_t)1 << log_m;
+  SetupDump D;
+  DVP_TRY(D.open(dir, n_public));
+  const uint32_t n_wires = D.n_wires;
+  const size_t m = D.m();
   if (out_n_wires) *out_n_wires = n_wires;
-  if (out_log2_m) *out_log2_m = log_m;
+  if (out_log2_m) *out_log2_m = D.log_m;
   if (out_scalars && out_cap < (size_t)n_wires + 5 * m) return DVP_EINVAL;
-  std::vector<uint64_t> coeffs((size_t)4 * n_coeffs);
-  std::vector<uint32_t> rp[3], wi[3], ci[3];
-  uint32_t *rpp[3], *wip[3], *cip[3];
-  for (int k = 0; k < 3; ++k) {
-    rp[k].resize((size_t)n_rows + 1);
-    wi[k].resize(nnz[k] ? nnz[k] : 1);
-    ci[k].resize(nnz[k] ? nnz[k] : 1);
-    rpp[k] = rp[k].data(); wip[k] = wi[k].data(); cip[k] = ci[k].data();
-  }
-  DVP_TRY(dvp_r1cs_dump_fill(dump.p, dump.len, coeffs.data(), rpp, wip, cip));
-  SetupCircuit cc;
-  cc.n_coeffs = n_coeffs; cc.n_rows = n_rows; cc.n_wires = n_wires; cc.coeffs = coeffs.data();
-  for (int k = 0; k < 3; ++k) { cc.rp[k] = rpp[k]; cc.wi[k] = wip[k]; cc.ci[k] = cip[k]; }
-  SetupState S(log_m, n_wires);
+  DVP_TRY(D.fill());
+  SetupState S(D.log_m, n_wires);
   hipStream_t st = nullptr;
-  DVP_TRY(setup_scalars_core(cc, tau, tau_c, delta_c, eps_c, n_public, S, st));
+  DVP_TRY(setup_scalars_core(D.cc, tau, tau_c, delta_c, eps_c, n_public, S, st));
   const dim3 gm(cdiv(m, TPB)), bt(TPB);
   if (out_scalars) {
     DVP_HIP(hipMemcpyAsync(out_scalars, S.sc.p, S.n_sc() * sizeof(Fr), hipMemcpyDeviceToHost, st));
@@ -330,7 +347,6 @@ extern "C" int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delt
   }
   // ---- compute_srs_matrices: one batched fixed-base multiplication + encoding per vector, then the files (src/srs.rs:126-167) ----
   {
-    static const char* const names[5] = {"g_m", "g_q", "g_k_0", "g_k_1", "g_k_2"};  // src/artifacts.rs:18-27, SetupState's order
     const size_t most = std::max<size_t>(2 * m, n_wires);
     DevBuf pts, inf, enc;
     DVP_TRY(pts.alloc(most * sizeof(Aff)));
@@ -344,7 +360,7 @@ extern "C" int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delt
       host.resize(cnt * 30);
       DVP_HIP(hipMemcpyAsync(host.data(), enc.p, cnt * 30, hipMemcpyDeviceToHost, st));
       DVP_HIP(hipStreamSynchronize(st));
-      DVP_TRY(dvp_file_point_vec_write(path(names[i]).c_str(), host.data(), cnt));
+      DVP_TRY(dvp_file_point_vec_write(path(kSrsNames[i]).c_str(), host.data(), cnt));
     }
   }
   // ---- the domain files (src/srs.rs:216-346; the reference quotes "2 hrs+" for z_poly at 2^23, src/artifacts.rs:92) ----
@@ -382,6 +398,90 @@ extern "C" int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delt
 extern "C" int dvp_setup_cache_dir(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const char* cache_dir,
                                    uint32_t n_public, int write_precomputes) {
   return dvp_setup_cache_dir_ex(tau, delta, epsilon, cache_dir, n_public, write_precomputes, nullptr, 0, nullptr, nullptr);
+}
+
+// ---- the audit: is the SRS in cache_dir the one of this trapdoor? (include/dvpari.h: dvp_srs_check_cache_dir) ----------------
+
+namespace {
+// key of vector v: BLAKE3(seed || LE32(v)), or without a seed BLAKE3("dv-pari srs check v1" || tau || delta || epsilon || LE32(v))
+void srs_check_key(const uint64_t tau[4], const uint64_t delta[4], const uint64_t eps[4], const uint8_t* seed, uint32_t v, uint8_t key[32]) {
+  static const char tag[] = "dv-pari srs check v1";
+  constexpr size_t T = sizeof(tag) - 1;
+  uint8_t buf[T + 96 + 4];
+  size_t len = 0;
+  if (seed) {
+    memcpy(buf, seed, 32);
+    len = 32;
+  } else {
+    memcpy(buf, tag, T);
+    const uint64_t* t[3] = {tau, delta, eps};
+    for (int s = 0; s < 3; ++s)
+      for (int b = 0; b < 32; ++b) buf[T + 32 * s + b] = (uint8_t)(t[s][b >> 3] >> (8 * (b & 7)));
+    len = T + 96;
+  }
+  for (int b = 0; b < 4; ++b) buf[len + b] = (uint8_t)(v >> (8 * b));
+  b3::hash(buf, len + 4, key);
+  memset(buf, 0, sizeof buf);  // it held the trapdoor
+}
+}  // namespace
+
+extern "C" int dvp_srs_check_cache_dir(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const char* cache_dir,
+                                       uint32_t n_public, const uint8_t* seed, uint32_t flags, dvp_srs_check_report* report) {
+  if (!cache_dir || !report || (flags & ~DVP_SRS_CHECK_EXACT)) return DVP_EINVAL;
+  memset(report, 0, sizeof *report);
+  for (int v = 0; v < 5; ++v) report->first_bad[v] = -1;
+  Fr tau_c, delta_c, eps_c;
+  DVP_TRY(setup_check_trapdoor(tau, delta, epsilon, tau_c, delta_c, eps_c));
+  const std::string dir(cache_dir);
+  SetupDump D;
+  DVP_TRY(D.open(dir, n_public));
+  DVP_TRY(D.fill());
+  SetupState S(D.log_m, D.n_wires);  // zeroes the scalars on every exit
+  hipStream_t st = nullptr;
+  DVP_TRY(setup_scalars_core(D.cc, tau, tau_c, delta_c, eps_c, n_public, S, st));
+  // one decoded vector and one workspace, sized for the longest vector, serve all five
+  const size_t most = std::max<size_t>(2 * S.m, D.n_wires);
+  DevBuf enc, pts, inf, work;
+  DVP_TRY(enc.alloc(most * 30));
+  DVP_TRY(pts.alloc(most * sizeof(Aff)));
+  DVP_TRY(inf.alloc(most));
+  DVP_TRY(work.alloc(dlog_check_work_bytes(most)));
+  for (int v = 0; v < 5; ++v) {
+    const size_t cnt = S.count(v);
+    report->count[v] = cnt;
+    auto fail = [&](uint32_t status, int64_t index) {
+      report->status[v] = status;
+      report->first_bad[v] = index;
+      report->bad_vectors |= 1u << v;
+    };
+    MappedFile f;
+    if (f.open_ro((dir + "/" + kSrsNames[v]).c_str()) != DVP_OK) {
+      fail(DVP_SRS_VEC_MISSING, -1);
+      continue;
+    }
+    // u64-LE count || count x 30 B (src/io_utils.rs:83-111): the entries that are really there against the entries expected
+    const uint64_t said = f.len >= 8 ? rd64le(f.p) : 0;
+    const uint64_t held = f.len >= 8 ? std::min<uint64_t>(said, (f.len - 8) / 30) : 0;
+    if (f.len < 8 || said != cnt || held != cnt) {
+      fail(DVP_SRS_VEC_LENGTH, (int64_t)std::min<uint64_t>(held, cnt));
+      continue;
+    }
+    DVP_HIP(hipMemcpy(enc.p, f.p + 8, cnt * 30, hipMemcpyHostToDevice));
+    const int rc = decode_dev(enc.as<uint8_t>(), cnt, pts.as<Aff>(), inf.as<uint8_t>(), st);
+    if (rc == DVP_EDECODE) {
+      fail(DVP_SRS_VEC_DECODE, g_last_error_index);
+      continue;
+    }
+    DVP_TRY(rc);
+    uint8_t key[32];
+    srs_check_key(tau, delta, epsilon, seed, (uint32_t)v, key);
+    dvp_dlog_report r;
+    DVP_TRY(dlog_check_dev(S.vec(v), pts.p, inf.p, cnt, key, (flags & DVP_SRS_CHECK_EXACT) ? DVP_DLOG_CHECK_EXACT : 0u, work.p, &r, st));
+    report->path[v] = r.path;
+    if (r.verdict) fail((r.verdict & DVP_DLOG_BAD_POINT) ? DVP_SRS_VEC_BAD_POINT : DVP_SRS_VEC_WRONG, r.first_bad);
+  }
+  report->verdict = report->bad_vectors ? 1u : 0u;
+  return DVP_OK;
 }
 
 // ---- FFTR tree files from a regenerated tree, and prover_prepares_precomputes (src/proving.rs:225-325) ----------------------

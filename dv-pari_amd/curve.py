@@ -3,10 +3,11 @@
 Points are numpy uint64 [n, 8] = x||y (4 limbs each) of the prime-order representative on
 y^2+xy=x^3+1, plus an optional uint8 [n] infinity mask; scalars are uint64 [n, 4] canonical."""
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
-from ._native import lib, check, ptr, EPOINT
+from ._native import lib, check, ptr, EPOINT, DlogReport as _DlogReport
 
 FR_MODULUS = 3450873173395281893717377931138512760570940988862252126328087024741343
 
@@ -190,6 +191,76 @@ def check_points(points_xy: np.ndarray, points_inf: np.ndarray = None):
 def check_points_dev(d_xy: int, d_inf: int, n: int, d_classes: int, d_summary: int, stream: int = 0):
     """dvp_points_check_dev: enqueue only; d_summary (16 bytes) = {u64 first bad index or ~0, u64 bad points}, reset by the call"""
     check(lib.dvp_points_check_dev(d_xy, d_inf, n, d_classes, d_summary, stream), "dvp_points_check_dev")
+
+
+# dvp_points_check_dlog (include/dvpari.h: DVP_DLOG_*)
+DLOG_CHECK_EXACT = 0x1
+DLOG_BAD_POINT, DLOG_WRONG = 0x1, 0x2
+DLOG_PATH_COMBINED, DLOG_PATH_LOCATED, DLOG_PATH_EXACT = 1, 2, 3
+
+
+@dataclass
+class DlogReport:
+    """verdict: 0 = every point is its scalar's multiple of G, else DLOG_BAD_POINT / DLOG_WRONG; path: DLOG_PATH_*; first_bad: index of
+    the first wrong or ill-formed point, or None; point_class: its POINT_* class (0 for a well-formed wrong point)"""
+    verdict: int
+    path: int
+    first_bad: int
+    point_class: int
+
+    @property
+    def ok(self) -> bool:
+        return self.verdict == 0
+
+
+def _seed_arg(seed):
+    if seed is None:
+        return None
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("seed must be 32 bytes")
+    return np.frombuffer(seed, dtype=np.uint8).copy()
+
+
+def _dlog_report(rep) -> DlogReport:
+    return DlogReport(int(rep.verdict), int(rep.path), None if rep.first_bad < 0 else int(rep.first_bad), int(rep.point_class))
+
+
+def check_dlogs(scalars: np.ndarray, points_xy: np.ndarray, points_inf: np.ndarray = None, seed=None, exact: bool = False) -> DlogReport:
+    """dvp_points_check_dlog: is points[i] == scalars[i] * G for every i?  One combined MSM of n + 1 points under coefficients hashed
+    from the points themselves (wrong vectors pass with probability <= 2^-127), then -- only when that fails, or alone with exact --
+    the entry-for-entry comparison that names the first wrong index.  seed: 32 bytes or None.  A bad point (outside E[r], unreduced,
+    off the curve) is the report's verdict; a non-canonical scalar raises DvpError(DVP_EINVAL) with .index."""
+    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    b = np.ascontiguousarray(points_xy, dtype=np.uint64).reshape(-1, 8)
+    n = b.shape[0]
+    assert s.shape[0] == n, (s.shape, b.shape)
+    pi = None
+    if points_inf is not None:
+        pi = np.ascontiguousarray(points_inf, dtype=np.uint8)
+        assert pi.shape == (n,)
+    sd = _seed_arg(seed)
+    rep = _DlogReport()
+    check(lib.dvp_points_check_dlog(ptr(s) if n else None, ptr(b) if n else None, None if pi is None or not n else ptr(pi), n,
+                                    None if sd is None else ptr(sd), DLOG_CHECK_EXACT if exact else 0, C.byref(rep)), "dvp_points_check_dlog")
+    return _dlog_report(rep)
+
+
+def check_dlogs_work_bytes(n: int) -> int:
+    """dvp_points_check_dlog_work_bytes: the d_work a check_dlogs_dev call over n points needs (host arithmetic)"""
+    return int(lib.dvp_points_check_dlog_work_bytes(n))
+
+
+def check_dlogs_dev(d_scalars: int, d_xy: int, d_inf: int, n: int, d_work: int, work_bytes: int, seed=None, exact: bool = False,
+                    stream: int = 0) -> DlogReport:
+    """dvp_points_check_dlog_dev: the same on device buffers; d_inf may be 0; d_work: check_dlogs_work_bytes(n) bytes, 256-byte aligned.
+    Waits for its verdict."""
+    sd = _seed_arg(seed)
+    rep = _DlogReport()
+    check(lib.dvp_points_check_dlog_dev(d_scalars or None, d_xy or None, d_inf or None, n, None if sd is None else ptr(sd),
+                                        DLOG_CHECK_EXACT if exact else 0, d_work or None, work_bytes, C.byref(rep), stream),
+          "dvp_points_check_dlog_dev")
+    return _dlog_report(rep)
 
 
 def set_strict_points(on: bool):

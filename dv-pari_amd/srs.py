@@ -132,6 +132,60 @@ def verifier_runs_setup_cache_dir(td: Trapdoor, cache_dir, num_public_inputs: in
     return inst, pv
 
 
+# dvp_srs_check_cache_dir (include/dvpari.h: DVP_SRS_VEC_*)
+SRS_VEC_MISSING, SRS_VEC_LENGTH, SRS_VEC_DECODE, SRS_VEC_BAD_POINT, SRS_VEC_WRONG = 1, 2, 3, 4, 5
+SRS_VECTORS = ("g_m", "g_q", "g_k_0", "g_k_1", "g_k_2")
+
+
+@dataclass
+class SrsVectorCheck:
+    """one vector of an SrsCheckReport: status 0 or SRS_VEC_*, path curve.DLOG_PATH_* (0: never reached the check), first_bad the index
+    of its first offending entry or None, count the entries expected"""
+    name: str
+    status: int
+    path: int
+    first_bad: int
+    count: int
+
+    @property
+    def ok(self) -> bool:
+        return self.status == 0
+
+
+@dataclass
+class SrsCheckReport:
+    """verdict 0 = the directory holds the SRS of the trapdoor; bad_vectors: bit v = vector v failed; vectors: the five
+    SrsVectorCheck in file order, also reachable by name (report["g_k_2"])"""
+    verdict: int
+    bad_vectors: int
+    vectors: tuple
+
+    @property
+    def ok(self) -> bool:
+        return self.verdict == 0
+
+    def __getitem__(self, name):
+        return self.vectors[SRS_VECTORS.index(name)]
+
+
+def check_cache_dir(td: Trapdoor, cache_dir, num_public_inputs: int, seed=None, exact: bool = False) -> SrsCheckReport:
+    """dvp_srs_check_cache_dir: are g_m, g_q, g_k_0..2 in cache_dir the SRS of `td` for cache_dir's R1CS dump and num_public_inputs?
+    One combined MSM per vector (curve.check_dlogs on the scalars the setup would compute); every vector is checked and a wrong entry
+    is named.  A missing, short or undecodable file is that vector's status; a zero trapdoor element raises DvpError(DVP_EINVAL)."""
+    import ctypes as C
+
+    from ._native import lib, check, ptr, SrsCheckReport as _Rep
+
+    keep, (t, d, e) = _trapdoor_args(td)
+    sd = curve._seed_arg(seed)
+    rep = _Rep()
+    check(lib.dvp_srs_check_cache_dir(t, d, e, os.fsencode(cache_dir), num_public_inputs, None if sd is None else ptr(sd),
+                                      1 if exact else 0, C.byref(rep)), "dvp_srs_check_cache_dir")
+    vecs = tuple(SrsVectorCheck(SRS_VECTORS[v], int(rep.status[v]), int(rep.path[v]), None if rep.first_bad[v] < 0 else int(rep.first_bad[v]),
+                                int(rep.count[v])) for v in range(5))
+    return SrsCheckReport(int(rep.verdict), int(rep.bad_vectors), vecs)
+
+
 def _t(csr, n_wires):
     t = csr.transpose(n_wires)
     return t.row_ptr, t.wire, t.coeff

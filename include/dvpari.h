@@ -291,6 +291,50 @@ int dvp_points_check_dev(const void* d_xy, const void* d_inf, size_t n, void* d_
 int dvp_points_set_strict(int on);
 int dvp_points_get_strict(void);
 
+/* "Are these points the given multiples of G?": P_i == s_i G for every i < n, checked on the device (csrc/srs_check.hip).  The claims
+ * are linear in the group, so they fold into ONE multi-scalar multiplication of n + 1 points, the argument of dvp_verify_batch_rlc:
+ *     sum_i r_i P_i + (p - sum_i r_i s_i) G == O      <=>      sum_i r_i (P_i - s_i G) == O.
+ * scalars: n x 4 limbs, canonical; xy / inf as everywhere (inf may be NULL); inf[i] != 0 means O, which is right exactly when s_i = 0.
+ * The return value is DVP_OK whenever the check ran: the answer is in *report.  A scalar that is not below p is DVP_EINVAL with
+ * dvp_last_error_index() = its index (the host flavour finds it before any device work, the _dev flavour after the points were
+ * checked); n = 0 gives verdict 0 and touches nothing but *report; n >= 2^27 is DVP_EINVAL (the one-shot MSM's limit).
+ *   1. dvp_points_check_dev over the points.  A bad point gives DVP_DLOG_BAD_POINT with its index and class and nothing further runs:
+ *      the MSM never sees a point outside E[r] (see DVP_POINT_COSET_N above: its kernels assume E[r]).
+ *   2. h = BLAKE3 of the points as given -- the n x 64 xy bytes, then the n infinity bytes (NULL: n zero bytes) -- by the device hash
+ *      of dvp_blake3_dev; key = seed (32 bytes), or BLAKE3("dv-pari dlog check v1") for seed == NULL; k = BLAKE3(key || h);
+ *      r_i = (first 16 bytes of BLAKE3(k || LE64(i)), read little-endian) | 2^127.  Hashing the points into k fixes the coefficients
+ *      only after the points are, so the check stays sound under a predictable seed -- which the seed is when none is passed.
+ *   3. one lane per element computes r_i (MSM scalar i) and r_i s_i; block sums give MSM scalar n = p - sum r_i s_i, MSM base n = G.
+ *   4. the one-shot MSM.  O: verdict 0, path DVP_DLOG_PATH_COMBINED.  Error bound: fix every coefficient but one; at most one value
+ *      mod p of the last cancels a non-zero error and the coefficient takes 2^127 values, so a wrong vector passes with probability at
+ *      most 2^-127 (BLAKE3 read as a random oracle).
+ *   5. otherwise (path DVP_DLOG_PATH_LOCATED), or alone under DVP_DLOG_CHECK_EXACT (path DVP_DLOG_PATH_EXACT, no hash involved): s_i G
+ *      by the batched fixed-base multiplication in batches of at most 2^20, compared entry for entry in index order up to the first
+ *      batch that differs: verdict DVP_DLOG_WRONG with first_bad exact.
+ * The scalars may be trapdoor material (the discrete logs of an SRS): every buffer of the library that held s_i, r_i s_i or their sums
+ * is zeroed before it is freed or handed back, on every exit.
+ * dvp_points_check_dlog_dev: device pointers; d_work is the caller's, 256-byte aligned, dvp_points_check_dlog_work_bytes(n) bytes
+ * (pure host arithmetic, at most about 170 bytes per point) that nothing else in flight uses; fewer is DVP_EINVAL.  It allocates nothing on
+ * the device.  It waits on the host for the verdict of step 1 (so that no MSM kernel is enqueued over bad points), for the MSM's
+ * result, and per batch when it has to locate; *report is complete when it returns. */
+#define DVP_DLOG_CHECK_EXACT 0x1u /* skip the combined check: compare every point */
+#define DVP_DLOG_BAD_POINT 0x1u   /* a point outside E[r] / unreduced / off the curve */
+#define DVP_DLOG_WRONG 0x2u       /* well-formed, but some P_i != s_i G */
+#define DVP_DLOG_PATH_COMBINED 1u
+#define DVP_DLOG_PATH_LOCATED 2u /* the combined check failed, then the entry was located */
+#define DVP_DLOG_PATH_EXACT 3u
+typedef struct dvp_dlog_report {
+  uint32_t verdict;    /* 0 = every P_i equals s_i G; else DVP_DLOG_* bits */
+  uint32_t path;       /* DVP_DLOG_PATH_* */
+  int64_t first_bad;   /* index of the first wrong or ill-formed point, -1 when none */
+  uint8_t point_class; /* dvp_points_check class of that point, 0 when it is a well-formed wrong point */
+} dvp_dlog_report;
+int dvp_points_check_dlog(const uint64_t* scalars /* n x 4, canonical */, const uint64_t* xy, const uint8_t* inf /* may be NULL */, size_t n,
+                          const uint8_t* seed /* 32 bytes or NULL */, uint32_t flags, dvp_dlog_report* report);
+int dvp_points_check_dlog_dev(const void* d_scalars, const void* d_xy, const void* d_inf, size_t n, const uint8_t* seed, uint32_t flags,
+                              void* d_work, size_t work_bytes, dvp_dlog_report* report, void* stream);
+size_t dvp_points_check_dlog_work_bytes(size_t n);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Prover -- Proof::prove(cache_dir, public_inputs, private_inputs), src/proving.rs:426-688,      */
 /* with the cache_dir artefacts handed over once and kept resident in HBM.                      */
@@ -544,6 +588,35 @@ int dvp_fftr_write(const char* path, uint32_t n_sections, const uint8_t* ids, co
  * tau lies in an evaluation domain).  The is_fresh_setup / checksum bookkeeping of the reference is not part of this entry. */
 int dvp_setup_cache_dir(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const char* cache_dir,
                         uint32_t n_public, int write_precomputes);
+
+/* The audit of an SRS by whoever holds its trapdoor (the verifier after a transfer or a restore, an auditor of an opened instance):
+ * are g_m, g_q, g_k_0, g_k_1, g_k_2 in cache_dir the SRS of (tau, delta, epsilon) for cache_dir/r1cs_to_dvsnark and n_public?  The
+ * five scalar vectors are computed as dvp_setup_cache_dir computes them; each file is mapped, decoded on the GPU (under the codec rule
+ * in force) and handed with its scalars to dvp_points_check_dlog_dev: one combined MSM per vector instead of n_wires + 5m fixed-base
+ * multiplications and a file comparison, and a wrong entry is named.  All five vectors are always checked, so one call reports every
+ * bad vector.  The files are only read.
+ * A missing file, a wrong entry count or an undecodable encoding is that vector's status (with first_bad = the first entry that is
+ * missing or surplus / the first bad encoding), not a failure of the call.  The call fails with DVP_EINVAL for a zero trapdoor
+ * element or a tau inside an evaluation domain, as the setup does, and with DVP_EIO for an unreadable dump.
+ * seed == NULL: vector v is checked under the key BLAKE3("dv-pari srs check v1" || tau || delta || epsilon || LE32(v)), each trapdoor
+ * element as 32 little-endian bytes; otherwise under BLAKE3(seed || LE32(v)).  DVP_SRS_CHECK_EXACT = DVP_DLOG_CHECK_EXACT for every
+ * vector.  Needs no prover; frees what it allocated (the scalars zeroed first); at most one decoded vector and one workspace are live. */
+#define DVP_SRS_CHECK_EXACT 0x1u
+#define DVP_SRS_VEC_MISSING 1u   /* the file cannot be opened */
+#define DVP_SRS_VEC_LENGTH 2u    /* its entry count is not the expected one, or it is shorter than its count says */
+#define DVP_SRS_VEC_DECODE 3u    /* an encoding the decoder rejects */
+#define DVP_SRS_VEC_BAD_POINT 4u /* DVP_DLOG_BAD_POINT (the decoder cannot produce one) */
+#define DVP_SRS_VEC_WRONG 5u     /* DVP_DLOG_WRONG: well-formed points, not this trapdoor's SRS */
+typedef struct dvp_srs_check_report {
+  uint32_t verdict;      /* 0 = the directory holds the SRS of (tau, delta, epsilon) for its r1cs dump and n_public; else 1 */
+  uint32_t bad_vectors;  /* bit v (0..4 = g_m, g_q, g_k_0, g_k_1, g_k_2): vector v failed */
+  uint32_t path[5];      /* per vector: DVP_DLOG_PATH_*, 0 when the vector never reached the check */
+  uint32_t status[5];    /* per vector: 0 or DVP_SRS_VEC_* */
+  int64_t first_bad[5];  /* per vector: index of its first offending entry, -1 when none */
+  uint64_t count[5];     /* entries expected: n_wires, m, m, m, 2m */
+} dvp_srs_check_report;
+int dvp_srs_check_cache_dir(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const char* cache_dir,
+                            uint32_t n_public, const uint8_t* seed /* 32 bytes or NULL */, uint32_t flags, dvp_srs_check_report* report);
 
 /* prover_prepares_precomputes(cache_dir, validate_precompute) (src/proving.rs:225-325): cache_dir/z_poly must exist (its length
  * fixes m; DVP_EIO when it does not, DVP_EINVAL when m is not a power of two); tree2n is read when present, else generated as a
