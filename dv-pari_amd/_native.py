@@ -37,7 +37,31 @@ class SrsCheckReport(C.Structure):
                 ("first_bad", C.c_int64 * 5), ("count", C.c_uint64 * 5)]
 
 
+class UnsatRow(C.Structure):
+    """dvp_unsat_row (include/dvpari.h)"""
+    _fields_ = [("row", C.c_uint64), ("a", C.c_uint64 * 4), ("b", C.c_uint64 * 4), ("c", C.c_uint64 * 4), ("i", C.c_uint64 * 4)]
+
+
+class SuspectWire(C.Structure):
+    """dvp_suspect_wire (include/dvpari.h)"""
+    _fields_ = [("wire", C.c_uint32), ("n_terms", C.c_uint32)]
+
+
+class WitnessReport(C.Structure):
+    """dvp_witness_report (include/dvpari.h)"""
+    _fields_ = [("n_unsat", C.c_uint64), ("first_unsat", C.c_int64), ("n_noncanonical", C.c_uint64), ("first_noncanonical", C.c_int64),
+                ("n_suspect_wires", C.c_uint64), ("n_rows_listed", C.c_uint32), ("n_wires_listed", C.c_uint32),
+                ("constant_wire_is_one", C.c_uint32)]
+
+
+_WC_TAIL = [C.POINTER(UnsatRow), sz, C.POINTER(SuspectWire), sz, C.POINTER(WitnessReport)]  # rows, rows_cap, wires, wires_cap, report
+
 _SIGS = {
+    "dvp_prover_check_witness_dev": (C.c_int, [vp, vp] + _WC_TAIL + [vp]),
+    "dvp_prover_check_witness": (C.c_int, [vp, u64p, u32, u64p, u32] + _WC_TAIL),
+    "dvp_prover_check_witness_be32": (C.c_int, [vp, u8p, sz] + _WC_TAIL),
+    "dvp_check_witness_cache_dir_witness_file": (C.c_int, [C.c_char_p, u32, C.c_char_p] + _WC_TAIL),
+    "dvp_prover_row_terms": (C.c_int, [vp, C.c_int, u32, vp, vp, sz, C.POINTER(sz)]),
     "dvp_points_check_dlog": (C.c_int, [u64p, u64p, u8p, sz, u8p, u32, C.POINTER(DlogReport)]),
     "dvp_points_check_dlog_dev": (C.c_int, [vp, vp, vp, sz, u8p, u32, vp, sz, C.POINTER(DlogReport), vp]),
     "dvp_points_check_dlog_work_bytes": (sz, [sz]),

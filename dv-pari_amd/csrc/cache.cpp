@@ -508,12 +508,11 @@ extern "C" int dvp_cache_dir_set_binding(const char* cache_dir, uint32_t n_publi
   return DVP_OK;
 }
 
-// dvp_prover_circuit_hash from the R1CS dump of cache_dir alone (Transcript::circuit_info_hash, src/proving.rs:111-134, on the instance
-// update_to_include_vandermode_matrix_d leaves, src/gnark_r1cs.rs:333-386) -- the verifier's way to the value: it ran the setup from
-// the same dump.  The prover dvp_prove_cache_dir keeps for (cache_dir, n_public) on this device is used when it is open (taking its
-// turn like a proof); otherwise a prover without SRS is built from the dump and destroyed: no SRS file is read.
-extern "C" int dvp_circuit_hash_cache_dir(const char* cache_dir, uint32_t n_public, uint8_t out[32]) {
-  if (!cache_dir || !out) return DVP_EINVAL;
+// run(prover) for an entry that needs the circuit and no SRS (the circuit hash, the witness check).  The prover dvp_prove_cache_dir keeps
+// for (cache_dir, n_public) on this device is used when it is open (taking its turn like a proof); otherwise a prover without SRS is
+// built from the R1CS dump of cache_dir alone and destroyed: no SRS file is read.
+template <class F>
+static int on_circuit_prover(const char* cache_dir, uint32_t n_public, F run) {
   std::shared_ptr<OpenEntry> e;
   {
     std::lock_guard<std::mutex> g(g_open_mu);
@@ -526,7 +525,7 @@ extern "C" int dvp_circuit_hash_cache_dir(const char* cache_dir, uint32_t n_publ
       e->slot_cv.wait(g, [&] { return !e->busy[0]; });
       e->busy[0] = true;
     }
-    const int rc = dvp_prover_circuit_hash(e->p, out);
+    const int rc = run(e->p);
     {
       std::lock_guard<std::mutex> g(e->slot_mu);
       e->busy[0] = false;
@@ -566,9 +565,34 @@ extern "C" int dvp_circuit_hash_cache_dir(const char* cache_dir, uint32_t n_publ
   if (rc) return rc;
   rc = dvp_prover_set_coeffs(p, coeffs.data(), v.n_coeffs);
   for (int k = 0; k < 3 && !rc; ++k) rc = dvp_prover_set_matrix(p, k, v.n_rows, rpp[k], wip[k], cip[k]);
-  if (!rc) rc = dvp_prover_circuit_hash(p, out);
+  if (!rc) rc = run(p);
   dvp_prover_destroy(p);
   return rc;
+}
+// dvp_prover_circuit_hash from the R1CS dump of cache_dir alone (Transcript::circuit_info_hash, src/proving.rs:111-134, on the instance
+// update_to_include_vandermode_matrix_d leaves, src/gnark_r1cs.rs:333-386) -- the verifier's way to the value: it ran the setup from
+// the same dump.
+extern "C" int dvp_circuit_hash_cache_dir(const char* cache_dir, uint32_t n_public, uint8_t out[32]) {
+  if (!cache_dir || !out) return DVP_EINVAL;
+  return on_circuit_prover(cache_dir, n_public, [&](dvp_prover* p) { return dvp_prover_circuit_hash(p, out); });
+}
+
+// dvp_prover_check_witness_be32 on a witness file, on the prover dvp_circuit_hash_cache_dir would use: no SRS file is read.  The header
+// is checked as dvp_prove_cache_dir_witness_file checks it, before the prover is looked for; element 0 is left to the report.
+extern "C" int dvp_check_witness_cache_dir_witness_file(const char* cache_dir, uint32_t n_public, const char* witness_path, dvp_unsat_row* rows,
+                                                        size_t rows_cap, dvp_suspect_wire* wires, size_t wires_cap, dvp_witness_report* report) {
+  if (!cache_dir || !report || (rows_cap && !rows) || (wires_cap && !wires)) return DVP_EINVAL;
+  const std::string path = witness_path ? std::string(witness_path) : join(cache_dir, "witness_to_dvsnark");  // src/artifacts.rs
+  MappedFile f;
+  int rc = f.open_ro(path.c_str());
+  if (rc) return rc;
+  if (f.len < 4) return DVP_EIO;
+  const uint32_t cnt = ((uint32_t)f.p[0] << 24) | ((uint32_t)f.p[1] << 16) | ((uint32_t)f.p[2] << 8) | f.p[3];
+  if ((f.len - 4) / 32 < cnt) return DVP_EIO;
+  if (cnt < 1 + (uint64_t)n_public) return DVP_EINVAL;  // [1, public.., private..]
+  return on_circuit_prover(cache_dir, n_public, [&](dvp_prover* p) {
+    return dvp_prover_check_witness_be32(p, f.p + 4, cnt, rows, rows_cap, wires, wires_cap, report);
+  });
 }
 
 // the prover dvp_prove_cache_dir uses for (cache_dir, n_public) on the current device, opened if need be: BORROWED --

@@ -26,6 +26,7 @@
 //   begin       prove_begin.cuh       begin, extend by vector, quotient
 //   MSMs        prove_msm.cuh         prover_msm_partial (table budget), the multi-GPU shards, prove_msm, plan / table / budget entries
 //   challenge   prove_challenge.cuh   vector stages, device and host challenge, _partial / _finish, dvp_prove_finish
+//   check       prove_check.cuh       the witness check (unsatisfied rows, entries >= p, suspect wires) with its own kernels, dvp_prover_row_terms
 //   here        dvp_prove_dev and its two flavours, the host-witness entries, dvp_prover_debug_read, the domain-table entries
 #include <cstdlib>
 #include <algorithm>
@@ -52,6 +53,7 @@ using namespace dvp;
 #include "prove_begin.cuh"
 #include "prove_msm.cuh"
 #include "prove_challenge.cuh"
+#include "prove_check.cuh"
 
 // Proof::prove with the assignment already resident in HBM (the timed configuration of bench.py)
 // Host-transcript flavour (rounds 1-4; still what a device list, n_public > 35 or DVP_PROVE_HOST_TRANSCRIPT=1 gets): the host waits for

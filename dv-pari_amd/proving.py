@@ -93,6 +93,15 @@ def _fr_arg(v) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
 
 
+def _raw_arg(v) -> np.ndarray:
+    """_fr_arg for the witness check: python ints below 2^256 become limbs as they are, NOT reduced mod p"""
+    if isinstance(v, np.ndarray):
+        return np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4)
+    from ._native import ints_to_limbs
+
+    return ints_to_limbs([int(x) for x in v]) if len(v) else np.zeros((0, 4), dtype=np.uint64)
+
+
 def release_cache_dir(cache_dir=None):
     """drop the prover(s) dvp_prove_cache_dir keeps for cache_dir (None: all)"""
     import os
@@ -187,6 +196,51 @@ def circuit_hash_cache_dir(cache_dir, num_public_inputs: int) -> bytes:
     out = np.zeros(32, dtype=np.uint8)
     check(lib.dvp_circuit_hash_cache_dir(os.fspath(cache_dir).encode(), num_public_inputs, ptr(out)), "dvp_circuit_hash_cache_dir")
     return out.tobytes()
+
+
+@dataclass
+class WitnessReport:
+    """dvp_witness_report with its two lists: rows = [{"row", "a", "b", "c", "i"}] (ints; a*b != c + i mod p for each), the first
+    failing rows in row order; wires = [(wire, n_terms)], the first suspect wires in wire order (at least one term in a failing row,
+    none in a satisfied one).  first_* are -1 when there is none."""
+    n_unsat: int
+    first_unsat: int
+    n_noncanonical: int
+    first_noncanonical: int
+    n_suspect_wires: int
+    constant_wire_is_one: bool
+    rows: list
+    wires: list
+
+    @property
+    def ok(self) -> bool:
+        """satisfied, canonical, and the constant wire is 1"""
+        return self.n_unsat == 0 and self.n_noncanonical == 0 and self.constant_wire_is_one
+
+
+def _check_witness(call, max_rows: int, max_wires: int, where: str) -> WitnessReport:
+    """call(rows, rows_cap, wires, wires_cap, report) -> status: one of the dvp_*check_witness* entries behind its own leading arguments"""
+    from ._native import UnsatRow, SuspectWire, WitnessReport as Rep
+
+    rows = (UnsatRow * max_rows)() if max_rows else None
+    wires = (SuspectWire * max_wires)() if max_wires else None
+    rep = Rep()
+    check(call(rows, max_rows, wires, max_wires, C.byref(rep)), where)
+    val = lambda limbs: sum(int(x) << (64 * k) for k, x in enumerate(limbs))
+    return WitnessReport(int(rep.n_unsat), int(rep.first_unsat), int(rep.n_noncanonical), int(rep.first_noncanonical),
+                         int(rep.n_suspect_wires), bool(rep.constant_wire_is_one),
+                         [{"row": int(r.row), "a": val(r.a), "b": val(r.b), "c": val(r.c), "i": val(r.i)} for r in rows[:rep.n_rows_listed]] if rows else [],
+                         [(int(w.wire), int(w.n_terms)) for w in wires[:rep.n_wires_listed]] if wires else [])
+
+
+def check_witness_file(cache_dir, num_public_inputs: int, witness_path=None, max_rows: int = 16, max_wires: int = 16) -> WitnessReport:
+    """dvp_check_witness_cache_dir_witness_file: Prover.check_witness_be32 on a witness file (None = cache_dir/witness_to_dvsnark), on the
+    prover Proof.prove(cache_dir, ..) keeps when it is open, else on one built from the dump without SRS and destroyed"""
+    import os
+
+    wp = None if witness_path is None else os.fspath(witness_path).encode()
+    return _check_witness(lambda *tail: lib.dvp_check_witness_cache_dir_witness_file(os.fspath(cache_dir).encode(), num_public_inputs, wp, *tail),
+                          max_rows, max_wires, "dvp_check_witness_cache_dir_witness_file")
 
 
 class Prover:
@@ -307,6 +361,38 @@ class Prover:
         check(lib.dvp_prove_ark(self._h, ptr(pub) if pub.shape[0] else None, pub.shape[0], ptr(prv) if prv.shape[0] else None,
                                 prv.shape[0], ptr(out)), "dvp_prove_ark")
         return Proof.from_bytes(out.tobytes())
+
+    # ---- explain an unsatisfied witness (needs coefficients and matrices, no SRS) -------------------
+    def check_witness(self, public_inputs, private_inputs, max_rows: int = 16, max_wires: int = 16) -> WitnessReport:
+        """why prove(public_inputs, private_inputs) would answer DVP_EUNSAT: every failing row counted and the first max_rows listed
+        with a, b, c, i; entries >= p counted; the first max_wires suspect wires (dvp_prover_check_witness).  Values may be any
+        integers below 2^256; rows are evaluated on them reduced mod p."""
+        pub, prv = _raw_arg(public_inputs), _raw_arg(private_inputs)
+        return _check_witness(lambda *tail: lib.dvp_prover_check_witness(self._h, ptr(pub) if pub.shape[0] else None, pub.shape[0],
+                                                                         ptr(prv) if prv.shape[0] else None, prv.shape[0], *tail),
+                              max_rows, max_wires, "dvp_prover_check_witness")
+
+    def check_witness_be32(self, raw, max_rows: int = 16, max_wires: int = 16) -> WitnessReport:
+        """the same from the witness as its file holds it (at least n_wires elements of 32 big-endian bytes); element 0 is reported,
+        not refused (dvp_prover_check_witness_be32)"""
+        a = fr._be32_arg(raw)
+        return _check_witness(lambda *tail: lib.dvp_prover_check_witness_be32(self._h, ptr(a) if a.shape[0] else None, a.shape[0], *tail),
+                              max_rows, max_wires, "dvp_prover_check_witness_be32")
+
+    def check_witness_dev(self, d_assignment: int, max_rows: int = 16, max_wires: int = 16, stream: int = 0) -> WitnessReport:
+        """the same with the assignment [1, public.., private..] (n_wires x 4 uint64, any values) already in HBM"""
+        return _check_witness(lambda *tail: lib.dvp_prover_check_witness_dev(self._h, d_assignment, *tail, stream),
+                              max_rows, max_wires, "dvp_prover_check_witness_dev")
+
+    def row_terms(self, which: int, row: int):
+        """[(wire_id, coeff_id)] of row `row` of A / B / C (which = 0 / 1 / 2) from the resident matrices; [] for a padding row"""
+        n = C.c_size_t(0)
+        check(lib.dvp_prover_row_terms(self._h, which, row, None, None, 0, C.byref(n)), "dvp_prover_row_terms")
+        if not n.value:
+            return []
+        w, c = np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32)
+        check(lib.dvp_prover_row_terms(self._h, which, row, ptr(w), ptr(c), n.value, C.byref(n)), "dvp_prover_row_terms")
+        return list(zip(w.tolist(), c.tolist()))
 
     def debug(self, name: str, n: int = None):
         if n is None:

@@ -4,6 +4,11 @@
 //
 //   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3] [--table-budget <bytes>] [--bind-srs] [--bind-circuit | --circuit-hash <hex>]
 //                 [--host-witness] [--repeat N --threads T]
+//   dvp_prove_cli <cache_dir> <n_public> --check-witness [--max-rows N]
+//
+// --check-witness: explain the witness instead of proving (dvp_check_witness_cache_dir_witness_file; needs the dump and the witness
+// file, no SRS file).  Prints the counts, then up to N failing rows and N suspect wires (default 16); exit status 0 when the witness
+// satisfies every row with entries below p, else 2.
 //
 // The witness goes from the file to the proof in one call, dvp_prove_cache_dir_witness_file: the library maps
 // <cache_dir>/witness_to_dvsnark and reduces its elements mod p on the GPU.  --host-witness keeps the two-step path a host used before
@@ -61,6 +66,8 @@ int main(int argc, char** argv) {
   bool bind_srs = false, bind_circuit = false, have_circuit = false, host_witness = false;
   uint8_t srs_hash[32] = {0}, circuit_hash[32] = {0};
   int repeat = 0, threads = 1;  // --repeat N --threads T: N more proofs through dvp_prove_cache_dir from T host threads
+  bool check_witness = false;   // --check-witness [--max-rows N]: explain the witness instead of proving
+  size_t max_rows = 16;
   std::vector<char*> pos;
   bool have_budget = false;
   uint64_t budget = UINT64_MAX;
@@ -80,6 +87,16 @@ int main(int argc, char** argv) {
       bind_circuit = true;
     } else if (std::string(argv[i]) == "--host-witness") {
       host_witness = true;
+    } else if (std::string(argv[i]) == "--check-witness") {
+      check_witness = true;
+    } else if (std::string(argv[i]) == "--max-rows" && i + 1 < argc) {
+      char* end = nullptr;
+      const long v = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end != 0 || v < 0 || v > 1000000) {
+        fprintf(stderr, "--max-rows: expected a count, got '%s'\n", argv[i]);
+        return 2;
+      }
+      max_rows = (size_t)v;
     } else if (std::string(argv[i]) == "--circuit-hash" && i + 1 < argc) {
       if (!parse_hash(argv[++i], circuit_hash)) {
         fprintf(stderr, "--circuit-hash: expected 64 hex digits, got '%s'\n", argv[i]);
@@ -112,7 +129,7 @@ int main(int argc, char** argv) {
   }
   if (bind_circuit && have_circuit) fprintf(stderr, "--bind-circuit and --circuit-hash exclude each other\n");
   if (pos.size() < 2 || (bind_circuit && have_circuit)) {
-    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--bind-circuit | --circuit-hash HEX] [--host-witness] [--repeat N --threads T]\n", argv[0]);
+    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--bind-circuit | --circuit-hash HEX] [--host-witness] [--repeat N --threads T] | --check-witness [--max-rows N]\n", argv[0]);
     return 2;
   }
   argc = (int)pos.size() + 1;
@@ -130,6 +147,38 @@ int main(int argc, char** argv) {
       fprintf(stderr, "--devices: %s\n", dvp_strerror(rcd));
       return 1;
     }
+  }
+  if (check_witness) {
+    // Why would this witness be refused?  dvp_check_witness_cache_dir_witness_file reads the dump and the witness file, no SRS file,
+    // and proves nothing: one line of counts, one line per listed failing row (a*b != c + i) and per suspect wire (a wire whose terms
+    // all lie in failing rows).  Exit status 0 when every row holds and every entry is below p, else 2.
+    std::vector<dvp_unsat_row> rows(max_rows ? max_rows : 1);
+    std::vector<dvp_suspect_wire> wires(max_rows ? max_rows : 1);
+    dvp_witness_report rep;
+    const int rcw = dvp_check_witness_cache_dir_witness_file(dir.c_str(), n_public, nullptr, max_rows ? rows.data() : nullptr, max_rows,
+                                                             max_rows ? wires.data() : nullptr, max_rows, &rep);
+    if (rcw != DVP_OK) {
+      fprintf(stderr, "check %s: %s (index %lld)\n", dir.c_str(), dvp_strerror(rcw), (long long)dvp_last_error_index());
+      return 1;
+    }
+    printf("witness: n_unsat=%llu first_unsat=%lld n_noncanonical=%llu first_noncanonical=%lld n_suspect_wires=%llu constant_wire_is_one=%u\n",
+           (unsigned long long)rep.n_unsat, (long long)rep.first_unsat, (unsigned long long)rep.n_noncanonical,
+           (long long)rep.first_noncanonical, (unsigned long long)rep.n_suspect_wires, rep.constant_wire_is_one);
+    auto hex = [](const uint64_t v[4]) { printf("0x%016llx%016llx%016llx%016llx", (unsigned long long)v[3], (unsigned long long)v[2], (unsigned long long)v[1], (unsigned long long)v[0]); };
+    for (uint32_t k = 0; k < rep.n_rows_listed; ++k) {
+      printf("row %llu a=", (unsigned long long)rows[k].row);
+      hex(rows[k].a);
+      printf(" b=");
+      hex(rows[k].b);
+      printf(" c=");
+      hex(rows[k].c);
+      printf(" i=");
+      hex(rows[k].i);
+      printf("\n");
+    }
+    for (uint32_t k = 0; k < rep.n_wires_listed; ++k) printf("wire %u n_terms=%u\n", wires[k].wire, wires[k].n_terms);
+    dvp_cache_dir_release(nullptr);
+    return rep.n_unsat == 0 && rep.n_noncanonical == 0 && rep.constant_wire_is_one ? 0 : 2;
   }
   const std::string wpath = dir + "/witness_to_dvsnark";
   uint8_t proof[118];

@@ -378,6 +378,64 @@ int dvp_prove_be32(dvp_prover* p, const uint8_t* witness_be32, size_t n, uint8_t
  * NULL pointers are DVP_EINVAL, an unsatisfied witness is DVP_EUNSAT with the same row. */
 int dvp_prove_ark(dvp_prover* p, const uint64_t* public_ark, uint32_t n_public, const uint64_t* private_ark, uint32_t n_private,
                   uint8_t proof[118]);
+
+/* Explain an unsatisfied witness.  dvp_prove answers a witness that does not fit the circuit with DVP_EUNSAT and the smallest failing
+ * row (the reference's assert, src/proving.rs:389-395); the check says how many rows fail, lists the first ones with their values,
+ * counts the entries that are not below p, and names the wires that occur in failing rows only.  It runs on the device over the
+ * prover's resident matrices and needs the coefficients and all three matrices and no SRS (as dvp_prover_circuit_hash).
+ *
+ * The assignment is [1, public.., private..], n_wires elements of any 256-bit value.  An entry >= p is not refused: it is counted
+ * (n_noncanonical, first_noncanonical) and every row is evaluated on the entries reduced mod p, so the report is defined for any input;
+ * constant_wire_is_one says whether entry 0 reduces to 1.
+ *   rows: n_unsat = the number of rows r < m with a*b != C w, the predicate and the arithmetic of dvp_prove, so first_unsat is the
+ *     index DVP_EUNSAT carries (-1 when none); padding rows evaluate to zero and are satisfied.  The first rows_cap failing rows come
+ *     back in increasing row order as {row, a, b, c, i}, canonical, with c = C w - i(d_row) and i = sum_j pub_j d_row^j (the
+ *     reference's c_vals / i_vals), so a*b != c + i holds for each.
+ *   wires: a suspect wire has at least one term of A, B or C (as the dump holds them, without the Vandermonde terms) in a failing row
+ *     and none in a satisfied row.  n_suspect_wires is exact; the first wires_cap of them come back in increasing wire index as
+ *     {wire, n_terms}.  One corrupted wire shows up here; the honest wires that share its rows mostly do not.
+ * Both lists are compactions by rank: a truncated list holds the same records in the same order on every run.
+ *
+ * Returns DVP_OK whenever the check ran -- the answer is in the report, an unsatisfied witness is not an error status here.
+ * DVP_EINVAL, before any device work: a NULL prover / report / assignment, a NULL array with a non-zero cap (cap 0 with NULL gives
+ * the counts alone), a prover without coefficients or matrices, and the count rules of dvp_prove (dvp_prover_check_witness) and of
+ * dvp_prove_be32 (_be32: n < n_wires; a longer buffer is truncated).  rows and wires are HOST arrays in every flavour.
+ *   _dev: the assignment (little-endian limbs) is on the device; enqueues on `stream` and waits for the result -- once for a
+ *     satisfying witness; for an unsatisfied one the listing and the per-term pass run behind the host's look at the count, and the
+ *     call waits a second time.  The per-term pass never runs for a satisfying witness.
+ *   dvp_prover_check_witness / _be32: dvp_prove's / dvp_prove_be32's arguments, staged on the prover's own stream; the limb flavour
+ *     writes the constant wire itself, the be32 flavour reports element 0 as it finds it.
+ * The check borrows the prover's per-proof buffers (which hold nothing between proofs) and allocates its scratch in stream order:
+ * m/8 + 4 m/256 bytes for the rows, 8 bytes per wire when rows fail, plus the listed records.  Call it between proofs, not beside a
+ * proof on the same handle; proofs made afterwards are byte for byte what they were. */
+typedef struct dvp_unsat_row {
+  uint64_t row;
+  uint64_t a[4], b[4], c[4], i[4];
+} dvp_unsat_row;
+typedef struct dvp_suspect_wire {
+  uint32_t wire, n_terms;
+} dvp_suspect_wire;
+typedef struct dvp_witness_report {
+  uint64_t n_unsat;
+  int64_t first_unsat; /* -1 when none */
+  uint64_t n_noncanonical;
+  int64_t first_noncanonical; /* -1 when none */
+  uint64_t n_suspect_wires;
+  uint32_t n_rows_listed, n_wires_listed, constant_wire_is_one;
+} dvp_witness_report;
+int dvp_prover_check_witness_dev(dvp_prover* p, const void* d_assignment, dvp_unsat_row* rows, size_t rows_cap, dvp_suspect_wire* wires,
+                                 size_t wires_cap, dvp_witness_report* report, void* stream);
+int dvp_prover_check_witness(dvp_prover* p, const uint64_t* public_inputs, uint32_t n_public, const uint64_t* private_inputs,
+                             uint32_t n_private, dvp_unsat_row* rows, size_t rows_cap, dvp_suspect_wire* wires, size_t wires_cap,
+                             dvp_witness_report* report);
+int dvp_prover_check_witness_be32(dvp_prover* p, const uint8_t* witness_be32, size_t n, dvp_unsat_row* rows, size_t rows_cap,
+                                  dvp_suspect_wire* wires, size_t wires_cap, dvp_witness_report* report);
+/* One row's (wire_id, coeff_id) terms of A / B / C (which = 0 / 1 / 2) out of the resident CSR, so that a host can print a failing row
+ * without the dump.  *n = the row's term count, of which the first min(cap, *n) are written; a padding row (n_rows <= row < m) gives
+ * *n = 0.  row >= m, a bad `which`, a NULL n, NULL arrays with a non-zero cap or a matrix that was never set: DVP_EINVAL, without a
+ * device call. */
+int dvp_prover_row_terms(dvp_prover* p, int which, uint32_t row, uint32_t* wire_ids, uint32_t* coeff_ids, size_t cap, size_t* n);
+
 /* prove in phases, so that the two MSMs -- the only stages that shard across GPUs -- can be split by
  * index range and their partial sums combined by the caller (all-gather + local add):
  *   begin -> msm_partial(0, lo, hi) -> challenge(commit point) -> msm_partial(1, lo, hi) -> finish */
@@ -686,6 +744,13 @@ int dvp_cache_dir_set_binding(const char* cache_dir, uint32_t n_public, const ui
  * call takes its turn like a proof); otherwise a prover without SRS is built from the dump (log2 m by next_power_of_two of the row
  * count, n_wires as dvp_r1cs_dump_sizes reports it) and destroyed.  DVP_EIO for a missing or malformed dump. */
 int dvp_circuit_hash_cache_dir(const char* cache_dir, uint32_t n_public, uint8_t out[32]);
+/* dvp_prover_check_witness_be32 on a witness file (witness_path == NULL reads <cache_dir>/witness_to_dvsnark), with the prover found
+ * as dvp_circuit_hash_cache_dir finds it: the open prover of (cache_dir, n_public), taking its turn like a proof, or else one built
+ * from the dump without SRS and destroyed -- no SRS file is read.  The file's header follows dvp_prove_cache_dir_witness_file (DVP_EIO
+ * for a missing or short file, DVP_EINVAL for a count below 1 + n_public or below the prover's n_wires; a longer file is truncated);
+ * element 0 is not refused but reported.  NULL report or a NULL array with a non-zero cap: DVP_EINVAL before any file is opened. */
+int dvp_check_witness_cache_dir_witness_file(const char* cache_dir, uint32_t n_public, const char* witness_path, dvp_unsat_row* rows,
+                                             size_t rows_cap, dvp_suspect_wire* wires, size_t wires_cap, dvp_witness_report* report);
 /* the cached prover of (cache_dir, n_public), opened if need be -- borrowed, for inspection only (debug reads, plans) */
 int dvp_cache_dir_prover(const char* cache_dir, uint32_t n_public, dvp_prover** out);
 
