@@ -176,14 +176,21 @@ static std::atomic<size_t> g_ws_need[DVP_MAX_DEVICES];
 // know the lengths the device settled on (off[nkeys], a round's total) when it enqueues, so every copy takes the region's upper bound
 // and the fetch, which waits for the stream, cuts the blob to the lengths the captured offsets name.  A copy that does not fit the
 // arena is not made and the fetch then fails as a whole.  An MSM of a thread that has not armed pays one null check per stage.
-constexpr uint32_t CAPTURE_MAGIC = 0x43505644u, CAPTURE_VERSION = 1, CAPTURE_HDR_WORDS = 104, CAPTURE_MAX_ROUNDS = 40;
+// Behind the buckets the lengths are the host's own: the whole bucket array after every merge level, bucket 0 as level 0 kept it aside,
+// the group sums of k_tail_groups (copied BEFORE k_tail reuses their memory as its ping-pong buffer) and what the last tail kernel wrote.
+constexpr uint32_t CAPTURE_MAGIC = 0x43505644u, CAPTURE_VERSION = 2, CAPTURE_HDR_WORDS = 136, CAPTURE_MAX_ROUNDS = 40, CAPTURE_MAX_LEVELS = 24;
 enum CaptureHdr {  // word indices of the blob's header
   CH_MAGIC = 0, CH_VERSION, CH_HDR_WORDS, CH_FLAVOUR /* bit 0: fixed-base, bit 1: signed digits */, CH_C, CH_W, CH_N_NARROW, CH_NKEYS, CH_SIGN_MASK,
   CH_N_TOTAL, CH_I0, CH_N, CH_RA, CH_RA_PLAN, CH_DENSE, CH_PIPELINE /* 0: per round, 1: side stream, 2: caller's stream */, CH_TPB, CH_AFF_CAP,
-  CH_BMAX, CH_BMIN, CH_ROUTE, CH_K, CH_MAX_CNT, CH_ITEMS_LEN, CH_SHARE /* [40] */, CH_TOTAL = CH_SHARE + CAPTURE_MAX_ROUNDS /* [40] */
+  CH_BMAX, CH_BMIN, CH_ROUTE, CH_K, CH_MAX_CNT, CH_ITEMS_LEN, CH_SHARE /* [40] */, CH_TOTAL = CH_SHARE + CAPTURE_MAX_ROUNDS /* [40] */,
+  // version 2: the merge tree and the tail
+  CH_LEVELS = CH_TOTAL + CAPTURE_MAX_ROUNDS, CH_TAIL /* CaptureTail */, CH_NPARTS, CH_ENC /* an encoding was written */, CH_RULE /* its codec rule */,
+  CH_GROUP = CH_LEVELS + 8 /* [24]: lanes per addition of level j */
 };
-static_assert(CH_TOTAL + CAPTURE_MAX_ROUNDS == CAPTURE_HDR_WORDS, "capture header layout");
+static_assert(CH_LEVELS == 104 && CH_GROUP + CAPTURE_MAX_LEVELS == CAPTURE_HDR_WORDS, "capture header layout");
 enum CaptureRoute { CR_GATHER_ITEMS = 0, CR_GATHER_AFF, CR_BUCKET_PAIRS, CR_REDUCER_FAST, CR_REDUCER_GENERAL };
+enum CaptureTail { CT_HEX_SIGNED = 0 /* k_tail<true>, -3 */, CT_QUAD_SIGNED /* k_tail<false>, -3 */, CT_FROBENIUS /* k_tail<false> alone */,
+                   CT_GROUPS /* k_tail_groups + k_tail<false>, -4 */ };
 struct MsmCapture {
   struct Sec { size_t at, bytes; };  // a region of the arena
   struct Round { Sec ocnt, ooff, desc, pts; };
@@ -197,6 +204,10 @@ struct MsmCapture {
   Sec cnt = {0, 0}, off = {0, 0}, items = {0, 0}, bkt = {0, 0};
   Round rounds[CAPTURE_MAX_ROUNDS] = {};
   uint32_t nrounds = 0;
+  // behind bkt: the bucket array after every merge level, bucket 0 as kept aside, k_tail_groups' sums, what the last tail kernel wrote
+  Sec levels[CAPTURE_MAX_LEVELS] = {}, save0 = {0, 0}, parts = {0, 0}, res_xy = {0, 0}, res_inf = {0, 0}, res_enc = {0, 0};
+  uint32_t nlevels = 0;
+  bool result = false;
   Sec grab(const void* src, size_t bytes, hipStream_t s) {
     const size_t at = Carver::align(wanted);
     wanted = at + bytes;
@@ -211,8 +222,8 @@ struct MsmCapture {
     if (arena) (void)hipFree(arena);
     arena = nullptr;
     cap = used = wanted = 0;
-    armed = taken = false;
-    nrounds = 0;
+    armed = taken = result = false;
+    nrounds = nlevels = 0;
     copy_err = hipSuccess;
   }
 };
@@ -666,9 +677,16 @@ struct MsmRun {
     const uint32_t hex_max = tn.msm_hex_max >= 0 ? (uint32_t)tn.msm_hex_max : MERGE_HEX_MAX;
     for (int j = 0; j < merge_levels; ++j) {
       const uint32_t total = (p.nkeys >> (j + 1)) * (uint32_t)(j + 1);
-      if (total <= hex_max) launch_merge<16>(j, total, EC_LDS_Q, save0);
-      else if (total <= quad_max) launch_merge<4>(j, total, EC_LDS_Q, save0);
+      const uint32_t group = total <= hex_max ? 16u : (total <= quad_max ? 4u : 1u);
+      if (group == 16) launch_merge<16>(j, total, EC_LDS_Q, save0);
+      else if (group == 4) launch_merge<4>(j, total, EC_LDS_Q, save0);
       else launch_merge<1>(j, total, EC_LDS, save0);
+      if (cap && j < (int)CAPTURE_MAX_LEVELS) {  // the whole bucket array as this level left it; bucket 0 as level 0 kept it aside
+        cap->hdr[CH_GROUP + j] = group;
+        cap->levels[j] = cap->grab(b.bkt, (size_t)p.nkeys * sizeof(Ld), st);
+        if (j == 0 && save0) cap->save0 = cap->grab(save0, sizeof(Ld), st);
+        cap->nlevels = (uint32_t)j + 1;
+      }
     }
     const int w_tail = fx ? 1 : p.W;  // fixed-base mode has a single bucket set
     const uint32_t cntT = (uint32_t)(w_tail * p.c);
@@ -676,17 +694,32 @@ struct MsmRun {
     uint32_t *o_xy = (uint32_t*)out.d_out_xy, *o_inf = (uint32_t*)out.d_out_inf;
     uint8_t* o_enc = (uint8_t*)out.d_out_enc;
     const int rule = o_enc ? dvp_codec_get_rule() : 0;
-    if (sign_mask && tn.msm_hex_max != 0)  // c points: one row of 16 lanes each
+    uint32_t tail_shape = CT_FROBENIUS, nparts_cap = 0;
+    if (sign_mask && tn.msm_hex_max != 0) {  // c points: one row of 16 lanes each
+      tail_shape = CT_HEX_SIGNED;
       DVP_LAUNCH(k_tail<true>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, b.bkt, p.c, w_tail, -3, Tsq, ta, o_xy, o_inf, o_enc, rule, b.err, out.d_err_defer);
-    else if (!sign_mask && cntT > 32 && tn.msm_tail_groups != 0) {
+    } else if (!sign_mask && cntT > 32 && tn.msm_tail_groups != 0) {
       // many points (the one-shot MSM's W x c): group sums on cdiv(cntT, 16) workgroups first, then the single-workgroup tail on those
       Ld* part = b.tail + 2 * (size_t)cntT + 1;
       const int nparts = (int)cdiv(cntT, 16);
       DVP_LAUNCH(k_tail_groups, dim3(nparts), dim3(EC_TPB), EC_LDS_Q, st, b.bkt, p.c, w_tail, fx ? 0 : p.n_narrow, Tsq, ta, part);
+      tail_shape = CT_GROUPS;
+      nparts_cap = (uint32_t)nparts;
+      if (cap) cap->parts = cap->grab(part, (size_t)nparts * sizeof(Ld), st);  // before k_tail's ping-pong overwrites them
       DVP_LAUNCH(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, b.bkt, nparts, 1, -4, Tsq, part, o_xy, o_inf, o_enc, rule, b.err, out.d_err_defer);
-    } else
+    } else {
+      if (sign_mask) tail_shape = CT_QUAD_SIGNED;
       DVP_LAUNCH(k_tail<false>, dim3(1), dim3(EC_TPB), EC_LDS_Q, st, b.bkt, p.c, w_tail, sign_mask ? -3 : (fx ? 0 : p.n_narrow), Tsq, ta, o_xy, o_inf,
                  o_enc, rule, b.err, out.d_err_defer);
+    }
+    if (cap) {  // what the last tail kernel wrote
+      uint32_t* h = cap->hdr;
+      h[CH_LEVELS] = (uint32_t)merge_levels; h[CH_TAIL] = tail_shape; h[CH_NPARTS] = nparts_cap; h[CH_ENC] = o_enc ? 1u : 0u; h[CH_RULE] = (uint32_t)rule;
+      cap->res_xy = cap->grab(o_xy, 64, st);
+      cap->res_inf = cap->grab(o_inf, 4, st);
+      if (o_enc) cap->res_enc = cap->grab(o_enc, 30, st);
+      cap->result = true;
+    }
     ps_tail.stop();
   }
   // deferred completion: the workspace stays in use until this point of the stream; nothing here touches the host
@@ -1291,5 +1324,28 @@ extern "C" int dvp_msm_ctx_run(dvp_msm_ctx* c, const uint64_t* scalars, size_t l
   DVP_TRY(ds.up(scalars, (hi - lo) * 32));
   DVP_TRY(sum.init());
   DVP_TRY(msm_fixed_dev(c->fx, ds.p, c->d_inf + lo, (uint32_t)lo, (uint32_t)hi, sum.out(), 0));
+  return sum.down(out_xy, out_is_infinity);
+}
+
+// TEST ONLY (include/dvpari_internal.h; here and not in msm_debug.cuh because it reads dvp_msm_ctx): one MSM whose tail kernel also
+// writes the 30-byte encoding, as a prover's commitment MSMs ask it to -- over the context's bases [lo, hi), or, without a context, a
+// one-shot MSM over bases_xy[0 .. hi)
+extern "C" int dvp_debug_msm_enc(dvp_msm_ctx* c, const uint64_t* scalars, const uint64_t* bases_xy, size_t lo, size_t hi, uint64_t out_xy[8],
+                                 int* out_is_infinity, uint8_t out_enc[30]) {
+  if (!scalars || !out_xy || !out_is_infinity || !out_enc || lo >= hi || (c ? hi > c->n : (lo != 0 || !bases_xy))) return DVP_EINVAL;
+  DevBuf ds, db, denc;
+  MsmResult sum;
+  DVP_TRY(ds.up(scalars, (hi - lo) * 32));
+  DVP_TRY(denc.alloc(32));
+  DVP_TRY(sum.init());
+  MsmOut out = sum.out();
+  out.d_out_enc = denc.p;
+  if (c)
+    DVP_TRY(msm_fixed_dev(c->fx, ds.p, c->d_inf + lo, (uint32_t)lo, (uint32_t)hi, out, 0));
+  else {
+    DVP_TRY(db.up(bases_xy, hi * 64));
+    DVP_TRY(msm_affine_dev(ds.p, db.p, nullptr, hi, out, 0));
+  }
+  DVP_TRY(denc.down(out_enc, 30));
   return sum.down(out_xy, out_is_infinity);
 }

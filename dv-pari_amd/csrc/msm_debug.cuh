@@ -141,7 +141,7 @@ extern "C" int dvp_debug_msm_capture_arm(size_t arena_bytes) {
   DVP_HIP(hipMalloc((void**)&c.arena, arena_bytes));
   c.cap = arena_bytes;
   memset(c.hdr, 0, sizeof c.hdr);
-  c.cnt = c.off = c.items = c.bkt = MsmCapture::Sec{0, 0};
+  c.cnt = c.off = c.items = c.bkt = c.save0 = c.parts = c.res_xy = c.res_inf = c.res_enc = MsmCapture::Sec{0, 0};
   c.armed = true;
   return DVP_OK;
 }
@@ -175,7 +175,13 @@ extern "C" int dvp_debug_msm_capture_fetch(void* out, size_t cap_bytes, size_t* 
   auto word = [&](const MsmCapture::Sec& s, size_t i) { return a[s.at / 4 + i]; };
   const uint32_t nk = c.hdr[CH_NKEYS], ra = c.hdr[CH_RA];
   const bool dense = c.hdr[CH_DENSE] != 0;
+  const uint32_t levels = c.hdr[CH_LEVELS], nparts = c.hdr[CH_NPARTS];
+  const bool has_save0 = c.hdr[CH_SIGN_MASK] != 0, has_enc = c.hdr[CH_ENC] != 0;
   bool ok = ra == c.nrounds && c.bkt.bytes == (size_t)nk * sizeof(Ld);
+  // the merge tree and the tail: every region has the length the host knew when it enqueued the copy
+  ok = ok && c.result && levels == c.nlevels && c.save0.bytes == (has_save0 ? sizeof(Ld) : 0) && c.parts.bytes == (size_t)nparts * sizeof(Ld) &&
+       c.res_xy.bytes == 64 && c.res_inf.bytes == 4 && c.res_enc.bytes == (has_enc ? 30u : 0u);
+  for (uint32_t j = 0; ok && j < levels; ++j) ok = c.levels[j].bytes == (size_t)nk * sizeof(Ld);
   const size_t items_len = word(c.off, nk);
   ok = ok && items_len * 4 <= c.items.bytes;
   size_t words = CAPTURE_HDR_WORDS + (size_t)nk + (nk + 1) + items_len + (size_t)nk * (sizeof(Ld) / 4);
@@ -185,6 +191,7 @@ extern "C" int dvp_debug_msm_capture_fetch(void* out, size_t cap_bytes, size_t* 
     c.hdr[CH_TOTAL + r] = (uint32_t)total;
     words += (size_t)nk + (nk + 1) + dw + total * (sizeof(Aff) / 4);
   }
+  words += (size_t)levels * nk * (sizeof(Ld) / 4) + (has_save0 ? sizeof(Ld) / 4 : 0) + (size_t)nparts * (sizeof(Ld) / 4) + 16 + 1 + (has_enc ? 8 : 0);
   if (!ok) {  // cannot happen: every region was copied at its upper bound
     c.release();
     return DVP_EHIP;
@@ -208,6 +215,16 @@ extern "C" int dvp_debug_msm_capture_fetch(void* out, size_t cap_bytes, size_t* 
     sec(c.rounds[r].pts, total * (sizeof(Aff) / 4));
   }
   sec(c.bkt, (size_t)nk * (sizeof(Ld) / 4));
+  for (uint32_t j = 0; j < levels; ++j) sec(c.levels[j], (size_t)nk * (sizeof(Ld) / 4));
+  if (has_save0) sec(c.save0, sizeof(Ld) / 4);
+  sec(c.parts, (size_t)nparts * (sizeof(Ld) / 4));
+  sec(c.res_xy, 16);
+  sec(c.res_inf, 1);
+  if (has_enc) {  // 30 bytes in 8 words, the last two bytes zero
+    uint32_t enc[8] = {0};
+    memcpy(enc, (const char*)a.data() + c.res_enc.at, 30);
+    put(enc, 8);
+  }
   c.release();
   return DVP_OK;
 }

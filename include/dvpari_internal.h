@@ -49,22 +49,37 @@ int dvp_debug_msm_rest_len(uint32_t* n);
  * allocates a device arena of that size (0 = disarm and free).  That MSM runs as any other, plus device-to-device copies into the arena
  * enqueued on its own stream at the stage boundaries (no kernel, no event, no wait); an MSM of a thread that has not armed does nothing
  * of this.  dvp_debug_msm_capture_fetch waits for that MSM's stream and writes one blob of 32-bit words:
- *   header, 104 words: [0] 0x43505644, [1] version 1, [2] 104, [3] flavour (bit 0 fixed-base, bit 1 signed digits), [4] c, [5] W,
+ *   header, 136 words: [0] 0x43505644, [1] version 2, [2] 136, [3] flavour (bit 0 fixed-base, bit 1 signed digits), [4] c, [5] W,
  *     [6] n_narrow, [7] nkeys, [8] sign mask of an item, [9] n_total (row stride of the table; one-shot: n), [10] i0, [11] n, [12] ra
  *     (pair rounds run), [13] ra_plan, [14] dense descriptors, [15] bookkeeping (0 per round, 1 all rounds on a side stream, 2 all rounds
  *     on the caller's), [16] workgroup size of the rounds, [17] aff_cap (resident round threads), [18] bmax, [19] bmin, [20] leftover
  *     route (0 k_bucket_gather_items, 1 k_bucket_gather_aff, 2 k_bucket_pairs + k_bucket_rest, 3 fan-in-K reducer with the exception-free
  *     first level, 4 with the general one), [21] K, [22] the largest bucket, [23] items_len = off[nkeys], [24 + r] round r shared its
- *     inversions, [64 + r] total_r = output slots of round r;
+ *     inversions, [64 + r] total_r = output slots of round r; since version 2: [104] merge levels run, [105] the tail's shape (0 k_tail<true>
+ *     with n_narrow = -3, 1 k_tail<false> with -3, 2 k_tail<false> alone over the Frobenius powers, 3 k_tail_groups + k_tail<false> with
+ *     -4), [106] nparts = group sums of k_tail_groups (0 unless shape 3), [107] 1 if a 30-byte encoding was written, [108] the codec rule
+ *     it was written under, [109 .. 111] zero, [112 + j] GROUP = lanes per addition of merge level j (1, 4 or 16), j < 24;
  *   after the sort: cnt[nkeys], off[nkeys + 1], items[items_len];
  *   per round r < ra: its output counts [nkeys] and offsets [nkeys + 1], its descriptor words as the kernel read them (round 0: none,
  *     it reads the item list; later rounds total_r words, 2 total_r on the dense path), its output points total_r x 16 words (x, y);
- *   after the leftover reducer: bkt[nkeys] x 24 words, raw (X, Y, Z).
+ *   after the leftover reducer: bkt[nkeys] x 24 words, raw (X, Y, Z);
+ *   per merge level j < levels: the whole bucket array behind that k_merge launch, nkeys x 24 words, lambda-projective (X, L, Z) -- level 0
+ *     converts every bucket on its way in, so no slot of these copies is Lopez-Dahab;
+ *   signed digits (sign mask != 0) only: save0, 24 words: bucket 0 as level 0 kept it aside, raw Lopez-Dahab (X, Y, Z);
+ *   tail shape 3 only: nparts x 24 words, the group sums k_tail_groups left (Lopez-Dahab), copied before k_tail reuses their memory;
+ *   the result as the last tail kernel wrote it: 16 words (x, y), 1 word inf, and, if [107], 8 words holding the 30 encoding bytes (the
+ *     last two bytes zero).
  * fetch(NULL, 0, &need) reports the blob's size and keeps the capture; a buffer smaller than that is DVP_EINVAL, nothing written.  An
  * arena too small for what the MSM had to copy: DVP_EINVAL, no blob at all, dvp_last_error_index() = the arena bytes it wanted.  A
  * fetch without a captured MSM is DVP_EINVAL.  A successful fetch, a failed one and a new arming free the arena. */
 int dvp_debug_msm_capture_arm(size_t arena_bytes);
 int dvp_debug_msm_capture_fetch(void* out, size_t cap_bytes, size_t* need);
+/* TEST ONLY: one MSM whose tail kernel also writes the result's 30-byte encoding under the current codec rule, from the inversion it
+ * shares with the affine conversion -- what a prover asks of its commitment MSMs, here on inputs of the caller's choice.  ctx != NULL: the
+ * context's bases [lo, hi) (bases_xy unused); ctx == NULL: a one-shot MSM over bases_xy[0 .. hi), lo = 0.  scalars: hi - lo canonical
+ * scalars.  A neutral result: out_is_infinity = 1 and 30 zero bytes. */
+int dvp_debug_msm_enc(dvp_msm_ctx* ctx, const uint64_t* scalars, const uint64_t* bases_xy, size_t lo, size_t hi, uint64_t out_xy[8],
+                      int* out_is_infinity, uint8_t out_enc[30]);
 
 /* "msm_affine_round0" split by launch shape: entry k = (pairs of the MSM, summed ms, launches) for every distinct MSM size
  * since the last reset; returns the number of shapes (fills at most `cap`), < 0 on error */

@@ -3,7 +3,8 @@
 is compared, bit for bit, with the plain-Python restatements of tests/msm_stage_cases.py (check_capture):
   (a) cnt / off / items against bucket membership and the sort's layout; (b) every round's counts, offsets and descriptor words;
   (c) every output slot of every pair round against the group law on discrete logarithms (c_oracle.k233_mulgen);
-  (d) every bucket after the leftover reducer; (e) the MSM's own result against the oracle.
+  (d) every bucket after the leftover reducer; (e) the MSM's own result against the oracle;
+  (f) to (i) the bucket array behind every merge level, bucket 0 kept aside, the tail's group sums and the result as the tail kernel wrote it.
 Every expectation of a stage is computed from the captured input of that stage; the order inside a bucket is the sort's own.
 
 The placement matrix (test_placement_matrix) runs placement_input(), whose bucket COUNTS put exceptional pairs at chosen lanes, waves,
@@ -63,14 +64,15 @@ def placement(dvp):
 @pytest.mark.parametrize("tpb", [64, 128, 256])
 def test_placement_matrix(dvp, placement, mg, tpb, share, bmin):
     """placement_input() through every combination of workgroup size, shared inversion, descriptor form and bookkeeping mode, with one
-    and with three slots per thread (at 600 slots a round is far below a chip-full: B = DVP_MSM_AFF_BMIN).  Per run: checks (a) to (e),
+    and with three slots per thread (at 600 slots a round is far below a chip-full: B = DVP_MSM_AFF_BMIN); the bookkeeping per round (0),
+    for all rounds on a side stream (1) and on the caller's stream (2).  Per run: checks (a) to (i),
     six rounds, the route k_bucket_gather_aff, the header's echo of the knobs, and the class coverage condition
     (msm_stage_cases.assert_placement): round 0 holds P + P / P - P at lane 0 and lane 63 of wave 0, lane 0 of a later wave, the last
     lane of a workgroup, the first thread of the second workgroup, the last live thread of the partly filled last workgroup, chain
     positions 0 and B - 1 of one thread, over a whole wave and a whole workgroup (a pair, or the leftover of a bucket of +-P: nothing
     generic); lane 0 of wave 0 and the round's last slot are P - P under any order; every neutral-operand class occurs in a round >= 1."""
     fb, s_np, scalars, logs, exp = placement
-    for pipeline in (0, 2):
+    for pipeline in (0, 1, 2):
         for dense in (0, 1):
             knobs = dict(DVP_MSM_AFF_MIN=1, DVP_MSM_AFF_BMIN=bmin, DVP_MSM_AFF_TPB=tpb, DVP_MSM_AFF_SHARE_INV=share,
                          DVP_MSM_ROUND_DENSE=dense, DVP_MSM_ROUND_PIPELINE=pipeline)
@@ -80,7 +82,7 @@ def test_placement_matrix(dvp, placement, mg, tpb, share, bmin):
             where = (tpb, share, bmin, pipeline, dense)
             assert got == exp, ("result", where)  # (e)
             assert (h["flavour"], h["c"], h["W"], h["n_narrow"], h["nkeys"], h["n_total"], h["i0"], h["n"]) == (3, 8, 30, 6, 128, len(logs), 0, len(logs)), h
-            assert (h["tpb"], h["bmin"], h["pipeline"], h["dense"], h["ra"], h["max_cnt"]) == (tpb, bmin, pipeline, int(dense and pipeline == 2), 6, 33), (h, where)
+            assert (h["tpb"], h["bmin"], h["pipeline"], h["dense"], h["ra"], h["max_cnt"]) == (tpb, bmin, pipeline, int(dense and pipeline != 0), 6, 33), (h, where)
             assert h["share"] == [int(bool(share) and tpb > 64)] * 6 and h["route"] == sc.ROUTES.index("k_bucket_gather_aff"), (h, where)
             try:
                 classes, bucket_logs = sc.check_capture(cap, logs, scalars, mulgen=mg)  # (a) - (d)

@@ -22,7 +22,7 @@ def make_hdr(flavour, c, n, dense=0, tpb=256, bmin=1):
     elif flavour == 0:
         W += (240 - 234 + c - 1) // c
     nkeys = 1 << (c - 1) if flavour == 3 else (1 << c if flavour == 1 else W << c)
-    return dict(magic=sc.MAGIC, version=1, hdr_words=sc.HDR_WORDS, flavour=flavour, c=c, W=W, n_narrow=nn, nkeys=nkeys,
+    return dict(magic=sc.MAGIC, version=sc.VERSION, hdr_words=sc.HDR_WORDS, flavour=flavour, c=c, W=W, n_narrow=nn, nkeys=nkeys,
                 sign_mask=0x80000000 if flavour == 3 else 0, n_total=n, i0=0, n=n, ra=0, ra_plan=40, dense=dense, pipeline=2 if dense else 0,
                 tpb=tpb, aff_cap=196608, bmax=136, bmin=bmin, route=1, K=8, max_cnt=0, items_len=0)
 
@@ -217,3 +217,233 @@ def test_placement_input_reaches_the_named_positions(dense, bmin, order):
     # only the two lowest windows are populated
     rows = {(int(w) & 0x7FFFFFFF) // len(logs) for w in cap.items if int(w) != sc.NONE}
     assert rows == {0, 1} and any(int(w) >> 31 and int(w) != sc.NONE for w in cap.items)
+
+
+# ---- the merge tree and the tails (capture version 2) ----------------------------------------------------------------------------
+
+def test_normalisers_agree_with_the_oracle_points():
+    """a point in lambda-projective and in Lopez-Dahab coordinates with Z != 1 normalises to the oracle's (x, y), one by one and through
+    the shared inversion; Z = 0 is the marker (0, 0)"""
+    rnd = random.Random(3)
+    rows_lam, rows_ld, want = [], [], []
+    for k in (1, 2, 3, R - 1, rnd.randrange(R)):
+        x, y = co.k233_mulgen(k)
+        z = rnd.getrandbits(233) | 1
+        rows_lam.append(np.concatenate([sc.int_to_words(co.gf_mul(x, z)), sc.int_to_words(co.gf_mul(x ^ co.gf_mul(y, co.gf_inv(x)), z)), sc.int_to_words(z)]))
+        rows_ld.append(np.concatenate([sc.int_to_words(co.gf_mul(x, z)), sc.int_to_words(co.gf_mul(y, co.gf_mul(z, z))), sc.int_to_words(z)]))
+        want.append(x.to_bytes(32, "little") + y.to_bytes(32, "little"))
+    zero = np.concatenate([sc.int_to_words(5), sc.int_to_words(7), sc.int_to_words(0)])
+    assert [sc.lam_to_affine_bytes(r) for r in rows_lam] == want == [sc.ld_to_affine_bytes(r) for r in rows_ld]
+    assert sc.to_affine_many(rows_lam + [zero], lam=True) == want + [bytes(64)] == sc.to_affine_many(rows_ld + [zero], lam=False)
+    assert sc.lam_to_affine_bytes(zero) == bytes(64) and sc.to_affine_many([], lam=True) == []
+
+
+def test_merge_levels_end_in_totals_and_bit_sums():
+    """the level rule, applied level after level, keeps the invariant and ends with slot 0 = the total and slot 1 + t = the sum of the
+    buckets with bit t set; its additions are numbered block (j + 1) + slot"""
+    rnd = random.Random(17)
+    start = [rnd.randrange(R) for _ in range(64)]
+    logs = list(start)
+    for j in range(5):  # blocks of 32: two of them
+        logs, adds = sc.merge_level(logs, j)
+        sc.assert_merge_invariant(start, logs, j)
+        assert len(adds) == (64 >> (j + 1)) * (j + 1)
+    for b in (0, 32):
+        assert logs[b] == sum(start[b:b + 32]) % R
+        assert all(logs[b + 1 + t] == sum(start[b + i] for i in range(32) if (i >> t) & 1) % R for t in range(5))
+    with pytest.raises(AssertionError):
+        sc.assert_merge_invariant(start, logs[:5] + [logs[5] ^ 1] + logs[6:], 4)
+    # level 1 of one block of four: (b0 + b1) + (b2 + b3), b1 + b3, T_right = b2 + b3
+    l0, _ = sc.merge_level([1, 2, 4, 8], 0)
+    l1, adds = sc.merge_level(l0, 1)
+    assert l0 == [3, 2, 12, 8] and adds == [(3, 12), (2, 8)] and l1 == [15, 10, 12, 8]
+
+
+def test_tail_points_and_add_tree():
+    """the signed tail weighs slot 1 + t by 2^t and bucket 0 by 2^(c-1); the Frobenius tail weighs slot 1 + t of window w by lambda^(o_w
+    + t); the add tree pairs neighbours and passes an unpaired last entry on"""
+    hdr = make_hdr(3, 8, 4)
+    A = list(range(100, 228))
+    assert sc.tail_points(hdr, A, 7) == [(A[1 + t] << t) % R for t in range(7)] + [7 << 7]
+    hdr = make_hdr(0, 4, 4)
+    A = list(range(1, hdr["nkeys"] + 1))
+    pts = sc.tail_points(hdr, A, 0)
+    starts = sc.window_starts(4, hdr["W"], hdr["n_narrow"])
+    assert len(pts) == hdr["W"] * 4 and all(pts[4 * w + t] == A[16 * w + 1 + t] * pow(sc.LAMBDA, starts[w] + t, R) % R for w in range(hdr["W"]) for t in range(4))
+    hdr = make_hdr(1, 8, 4)
+    assert sc.tail_points(hdr, list(range(256)), 0) == [(1 + t) * pow(sc.LAMBDA, t, R) % R for t in range(8)]
+    total, levels = sc.add_tree([5, 5, 3, R - 3, 0, 9, 4, 0, 0, 0, 11])
+    assert total == 34 and levels[0] == ["P+P", "P-P", "O+Q", "P+O", "O+O", "leftover"] and levels[1] == ["P+O", "generic", "O+Q"]
+    assert levels[2] == ["generic", "leftover"] and levels[3] == ["generic"] and sc.add_tree([]) == (0, []) and sc.add_tree([4]) == (4, [])
+
+
+@pytest.mark.parametrize("flavour,c,tail,enc,rule", [(3, 8, 0, 1, 0), (3, 8, 1, 0, 0), (3, 11, 0, 1, 1), (1, 8, 2, 1, 0), (0, 4, 3, 1, 0), (0, 4, 2, 0, 0)])
+def test_synthetic_version_2_capture(flavour, c, tail, enc, rule):
+    """synthetic_capture's merge levels, save0, group sums and result are accepted, the total is the oracle's MSM, and check_capture
+    returns the merge and tail classes beside the pair it always returned"""
+    n = 40
+    logs, scalars = inputs(n, 200 + flavour + c)
+    hdr = dict(make_hdr(flavour, c, n), tail=tail, enc=enc, rule=rule)
+    cap = sc.synthetic_capture(hdr, logs, scalars, random.Random(2), 2, MG)
+    res = sc.check_capture(cap, logs, scalars, mulgen=MG)
+    classes, bucket_logs = res
+    levels = c - 1 if flavour == 3 else c
+    assert len(res.merge) == levels == cap.hdr["levels"] and all(len(res.merge[j]) == (cap.hdr["nkeys"] >> (j + 1)) * (j + 1) for j in range(levels))
+    assert res.total == sum(s * k for s, k in zip(scalars, logs)) % R == sc.weighted_sum(cap.hdr, bucket_logs)
+    assert res.tail["shape"] == tail and (res.tail["groups"] is not None) == (tail == 3)
+    assert len(res.tail["points"]) == (c if flavour & 1 else cap.hdr["W"] * c)
+    if tail == 3:
+        assert cap.hdr["nparts"] == (cap.hdr["W"] * c + 15) // 16 == len(res.tail["parts"])
+    assert (cap.res_enc is not None) == bool(enc) and (cap.save0 is not None) == (flavour == 3)
+    assert {x for lv in res.merge for x in lv} <= set(sc.MERGE_CLASSES)
+
+
+def test_checker_refuses_one_wrong_word_behind_the_buckets():
+    """a capture that differs from a right one in one word of a merge level, of save0, of a group sum, of the result or of the encoding is
+    refused with that stage named; so is a T_right that a level did not hand over (slot j + 1 stale, j != 1), a save0 that holds the
+    merged slot 0 instead of bucket 0, and an infinity word that contradicts the point"""
+    n = 40
+
+    def refused(hdr, logs, scalars, mutate, stage, where=()):
+        cap = sc.synthetic_capture(hdr, logs, scalars, random.Random(9), 2, MG)
+        sc.check_capture(cap, logs, scalars, mulgen=MG)
+        mutate(cap)
+        with pytest.raises(AssertionError) as ei:
+            sc.check_capture(cap, logs, scalars, mulgen=MG)
+        args = ei.value.args[0]
+        assert args[0] == stage and args[1:1 + len(where)] == where, args
+
+    logs, scalars = inputs(n, 301)
+    signed = dict(make_hdr(3, 8, n), enc=1)
+
+    def flip(section, *idx):
+        def f(cap):
+            a = getattr(cap, section)
+            if idx[:-1]:
+                a = a[idx[0]] if len(idx) == 2 else a[idx[0]][idx[1]]
+            a[idx[-1]] ^= 4
+        return f
+
+    # level 3, block 2 (slots 32 ..), slot 1: a slot the level wrote; a slot it did not write is not compared at that level
+    refused(signed, logs, scalars, flip("levels", 3, 33, 2), "merge", ("level", 3, "block", 2, "slot", 1))
+    refused(signed, logs, scalars, flip("levels", 0, 127, 20), "merge", ("level", 0, "block", 63, "slot", 1))
+    refused(signed, logs, scalars, flip("save0", 9), "save0")
+    refused(signed, logs, scalars, flip("res_xy", 15), "result", ("xy",))
+
+    def flip_inf(cap):
+        cap.res_inf ^= 1
+
+    def flip_enc(cap):
+        cap.res_enc = cap.res_enc[:29] + bytes([cap.res_enc[29] ^ 1])
+
+    refused(signed, logs, scalars, flip_inf, "result", ("inf",))
+    refused(signed, logs, scalars, flip_enc, "encoding")
+    for j in (0, 2, 4, 6):  # slot j + 1 of block 0 as the level before left it
+        def stale(cap, j=j):
+            cap.levels[j][j + 1] = cap.levels[j - 1][j + 1] if j else np.concatenate([cap.bkt[1][:16], sc.int_to_words(1)])
+        refused(signed, logs, scalars, stale, "merge", ("level", j, "block", 0, "slot", j + 1, "T_right"))
+
+    def merged_slot0(cap):  # what slot 0 holds after level 0 (b0 + b1), as a Lopez-Dahab point
+        k = (sc.check_capture(cap, logs, scalars, mulgen=MG)[1][0] + sc.check_capture(cap, logs, scalars, mulgen=MG)[1][1]) % R
+        cap.save0 = np.concatenate([np.frombuffer(MG.words(k), dtype="<u4"), sc.int_to_words(1)])
+
+    refused(signed, logs, scalars, merged_slot0, "save0")
+    one_shot = dict(make_hdr(0, 4, n), enc=1, rule=1)
+    l2, s2 = inputs(n, 302)
+    refused(one_shot, l2, s2, flip("parts", 5, 1), "tail groups", ("group", 5))
+    refused(one_shot, l2, s2, flip("parts", 15, 17), "tail groups", ("group", 15))
+    def flip_t_right(cap):  # the first finite T_right of level 3
+        i = next(i for i in range(4, cap.hdr["nkeys"], 16) if cap.levels[3][i][16:].any())
+        cap.levels[3][i][0] ^= 1
+    refused(one_shot, l2, s2, flip_t_right, "merge", ("level", 3))
+    refused(one_shot, l2, s2, flip_enc, "encoding", ("rule", 1))
+    # a header that names another tail shape than the flavour can run
+    def wrong_shape(cap):
+        cap.hdr["tail"] = 0
+    refused(one_shot, l2, s2, wrong_shape, "tail")
+
+
+# ---- placed inputs for the merge tree and the tails --------------------------------------------------------------------------------
+
+ONE_SHOT_MERGE = dict(require=("classes", "groups", "neighbours", "slots"), require_first=("classes", "neighbours"))
+
+
+def placed_capture(flavour, c, bucket_logs, **hdr_extra):
+    """the synthetic capture of the MSM placed_scalars builds for these bucket logarithms: no pair round, one item per bucket"""
+    base_logs, scalars, keys = sc.placed_scalars(flavour, c, bucket_logs)
+    hdr = dict(make_hdr(flavour, c, len(base_logs)), route=0, **hdr_extra)
+    assert (hdr["W"], hdr["n_narrow"], hdr["nkeys"]) == sc.plan_windows(flavour, c)
+    cap = sc.synthetic_capture(hdr, base_logs, scalars, random.Random(1), 0, MG)
+    return cap, base_logs, scalars
+
+
+@pytest.mark.parametrize("flavour,c", [(3, 8), (3, 11), (0, 4)])
+def test_merge_placement_is_reached_by_the_restatement_alone(flavour, c):
+    """merge_placed_logs through placed_scalars (every scalar's window property asserted there, with the signed recoding or the oracle's
+    tau-adic digits) puts the chosen logarithm into every bucket, and the schedule meets assert_merge_placement for 1, 4 and 16 lanes
+    per addition: in full at 128 buckets; at 1 024 all but a last addition in a partly filled workgroup of level 0 (two full ones), with
+    level 2's last addition, the last lane of workgroup 0 and the first of workgroup 1 named; one-shot at c = 4 what its windows allow"""
+    runs = []
+    for variant in ("pp", "mm", "o0"):
+        want = sc.merge_placed_logs(flavour, c, variant)
+        cap, base_logs, scalars = placed_capture(flavour, c, want)
+        assert cap.hdr["max_cnt"] == 1
+        res = sc.check_capture(cap, base_logs, scalars, mulgen=MG)
+        assert res[1] == want and res.merge == sc.merge_classes(flavour, c, want)
+        runs.append(res.merge)
+    for G in (1, 4, 16):
+        with_g = [([G] * len(m), m) for m in runs]
+        if flavour == 0:
+            found = sc.assert_merge_placement(with_g, **ONE_SHOT_MERGE)
+        elif c == 8:
+            found = sc.assert_merge_placement(with_g)
+        else:
+            found = sc.assert_merge_placement(with_g, require_first=tuple(x for x in sc.MERGE_CONDITIONS if x != "last addition"))
+        assert set(found) == {(G, True), (G, False)}
+    if c == 11:
+        assert 384 % 256 and [m[2][383] for m in runs] == ["P+P", "P+O", "P-P"]
+        assert [(m[0][255], m[0][256]) for m in runs] == [("P+P", "P+P"), ("P-P", "P-P"), ("P+P", "P+P")]
+    if flavour == 3:  # addition 0 of level 0, the lane that keeps bucket 0 aside
+        assert [m[0][0] for m in runs] == ["P+P", "P-P", "O+Q"]
+
+
+def test_merge_placement_fails_when_a_class_is_missing():
+    rnd = random.Random(4)
+    merge = sc.merge_classes(3, 8, [rnd.randrange(1, R) for _ in range(128)])
+    assert {x for lv in merge for x in lv} == {"generic"}
+    with pytest.raises(AssertionError):
+        sc.assert_merge_placement([([16] * 7, merge)])
+    good = [([4] * 7, sc.merge_classes(3, 8, sc.merge_placed_logs(3, 8, v))) for v in ("pp", "mm", "o0")]
+    sc.assert_merge_placement(good)
+    for drop in ("pp", "mm", "o0"):  # every variant is needed
+        with pytest.raises(AssertionError):
+            sc.assert_merge_placement([g for g, v in zip(good, ("pp", "mm", "o0")) if v != drop])
+
+
+TAIL_SHAPES = [(3, 8, 0), (3, 8, 1), (3, 11, 0), (3, 11, 1), (1, 8, 2), (0, 4, 2), (0, 4, 3), (0, 6, 3)]
+
+
+@pytest.mark.parametrize("flavour,c,shape", TAIL_SHAPES)
+def test_tail_placement_is_reached_by_the_restatement_alone(flavour, c, shape):
+    """tail_targets through tail_placed_logs and placed_scalars makes the tail's points exactly the targets, and the four variants meet
+    assert_tail_placement for every tail shape.  Parity is met by c = 8 and c = 11 together.  The single-workgroup Frobenius tail of a
+    one-shot MSM has its last first-level pair in the overflow windows, which no scalar reaches.  W c is a multiple of 16 at c = 6 only
+    (c = 4 .. 15: 244, 245, 240, 245, 248, 243, 250, 253, 252, 247, 252, 255): there the last group is full"""
+    runs = []
+    for variant in sc.TAIL_VARIANTS if c != 6 else ("a",):
+        E = sc.tail_targets(flavour, c, variant)
+        cap, base_logs, scalars = placed_capture(flavour, c, sc.tail_placed_logs(flavour, c, E), tail=shape, enc=1, rule=variant == "b")
+        res = sc.check_capture(cap, base_logs, scalars, mulgen=MG)
+        assert res.tail["points"] == E and res.tail["shape"] == shape and (res.total == 0) == (variant == "z")
+        runs.append(res.tail)
+    if c == 6:
+        assert len(E) % 16 == 0 and [W * cc % 16 == 0 for cc in range(4, 16) for W in [sc.plan_windows(0, cc)[0]]] == [cc == 6 for cc in range(4, 16)]
+        return
+    skip = {"parity"} | ({"last pair"} if (flavour, shape) == (0, 2) else set())
+    found = sc.assert_tail_placement(runs, tuple(x for x in sc.TAIL_CONDITIONS if x not in skip))
+    assert found["parity"] == [c & 1 if flavour & 1 else 0]
+    with pytest.raises(AssertionError):  # the variants are needed: "a" alone has no neutral result
+        sc.assert_tail_placement(runs[:1], ("result",))
+    if flavour == 3 and shape == 0:
+        both = runs + [sc.tail_restated(dict(flavour=3, c=19 - c), sc.merged_array(3, 19 - c, sc.tail_placed_logs(3, 19 - c, sc.tail_targets(3, 19 - c, "a"))), 1, 0)]
+        sc.assert_tail_placement(both)
