@@ -233,6 +233,10 @@ _SIGS = {
     "dvp_verify_batch_dev": (C.c_int, [u64p, u64p, u64p, vp, u32, vp, sz, vp, vp]),
     "dvp_verify_batch_rlc": (C.c_int, [u64p, u64p, u64p, u64p, u32, u8p, sz, u8p, u8p, C.POINTER(C.c_uint32)]),
     "dvp_verify_batch_rlc_dev": (C.c_int, [u64p, u64p, u64p, vp, u32, vp, sz, u8p, vp, vp, vp]),
+    "dvp_simulate_batch": (C.c_int, [u64p, u64p, u64p, u64p, u32, sz, u8p, C.c_uint64, u8p, u64p, u8p, u8p, u64p]),
+    "dvp_simulate_batch_dev": (C.c_int, [u64p, u64p, u64p, vp, u32, sz, u8p, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+    "dvp_verify_trace_batch": (C.c_int, [u64p, u64p, u64p, u64p, u32, u8p, sz, vp]),
+    "dvp_verify_trace_batch_dev": (C.c_int, [u64p, u64p, u64p, vp, u32, vp, sz, vp, vp]),
     "dvp_sp1_public_input": (C.c_int, [C.c_uint64, u64p]),
 }
 EXPORTED = []

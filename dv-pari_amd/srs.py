@@ -350,6 +350,88 @@ def verify_device(td: Trapdoor, public_inputs, proof) -> bool:
     return bool(acc.value)
 
 
+# ---- verifier-side vectors (csrc/simulate.hip): accepted proofs from the trapdoor, and the verifier's stage values per proof ---------
+SIM_GENERIC, SIM_T_HALF, SIM_P_ZERO, SIM_U0_ZERO, SIM_K_PLUS_G, SIM_K_MINUS_G, SIM_K_ZERO = range(7)
+SIM_CASES = ("generic", "t_half", "p_zero", "u0_zero", "k_plus_g", "k_minus_g", "k_zero")  # SIM_CASES[SIM_T_HALF] == "t_half"
+SIM_OK, SIM_V0_ZERO, SIM_BAD_PUBLIC, SIM_BAD_CASE, SIM_BAD_B0 = 0x00, 0x01, 0x02, 0x04, 0x08
+
+_FR_FIELDS = ("alpha", "i0", "r0", "u0", "v0")
+_POINT_FIELDS = ("p", "k", "vk", "ug", "sum")
+VERIFY_TRACE_DTYPE = np.dtype([(f, "<u8", (4,)) for f in _FR_FIELDS] + [(f + "_xy", "<u8", (8,)) for f in _POINT_FIELDS]
+                              + [(f + "_inf", "u1") for f in _POINT_FIELDS] + [("verdict", "u1"), ("pad", "u1", (2,))])
+assert VERIFY_TRACE_DTYPE.itemsize == 488  # dvp_verify_trace, include/dvpari.h
+
+
+def simulate_batch(td: Trapdoor, public_inputs, seed=None, index_base: int = 0, cases=None, b0=None, return_dlogs: bool = False):
+    """dvp_simulate_batch: one accepted proof per row of public_inputs, made from the trapdoor alone (include/dvpari.h states the
+    construction).  seed: 32 bytes, or None for the key derived from the trapdoor; cases: SIM_* per proof (None = all generic);
+    b0: ints or n x 4 uint64 limbs (None = drawn).  Returns (proofs n x 118 uint8, status n uint8[, dlogs n x 2 x 4 uint64: p then k]);
+    a proof with a nonzero status (SIM_V0_ZERO) is zero bytes."""
+    from ._native import lib, check, ptr
+
+    rows = public_inputs if isinstance(public_inputs, np.ndarray) else [list(r) for r in public_inputs]
+    n = len(rows)
+    pub = _public_array(rows, n)
+    keep, (t, d, e) = _trapdoor_args(td)
+    sd = curve._seed_arg(seed)
+    cs = None if cases is None else np.ascontiguousarray(cases, dtype=np.uint8).reshape(n)
+    if b0 is not None and not (isinstance(b0, np.ndarray) and b0.dtype == np.uint64):
+        b0 = np.stack([_raw_limbs(v) for v in b0]) if n else np.zeros((0, 4), dtype=np.uint64)
+    bb = None if b0 is None else np.ascontiguousarray(b0).reshape(n, 4)
+    proofs = np.zeros((n, 118), dtype=np.uint8)
+    status = np.zeros(n, dtype=np.uint8)
+    dlogs = np.zeros((n, 2, 4), dtype=np.uint64)
+    pub_buf = pub if pub.size else np.zeros(4, dtype=np.uint64)
+    opt = lambda a: None if a is None else ptr(a)  # noqa: E731
+    check(lib.dvp_simulate_batch(t, d, e, ptr(pub_buf), pub.shape[1] if n else 0, n, opt(sd), index_base, opt(cs), opt(bb),
+                                 ptr(proofs) if n else None, ptr(status) if n else None, ptr(dlogs) if (n and return_dlogs) else None),
+          "dvp_simulate_batch")
+    return (proofs, status, dlogs) if return_dlogs else (proofs, status)
+
+
+def verify_trace(td: Trapdoor, public_inputs, proofs) -> np.ndarray:
+    """dvp_verify_trace_batch: the arguments of verify_batch; one VERIFY_TRACE_DTYPE record per proof -- alpha, i0, r0, u0, v0 as limbs,
+    the decoded points p (commit_p) and k (kzg_k), vk = v0 K, ug = u0 G and sum = vk + ug as *_xy / *_inf, and verdict, verify_batch's
+    byte.  A record with a validity bit in its verdict is zero elsewhere."""
+    from ._native import lib, check, ptr
+
+    pa = _proofs_array(proofs)
+    n = pa.shape[0]
+    pub = _public_array(public_inputs, n)
+    keep, (t, d, e) = _trapdoor_args(td)
+    out = np.zeros(n, dtype=VERIFY_TRACE_DTYPE)
+    if n == 0:
+        return out
+    pub_buf = pub if pub.size else np.zeros(4, dtype=np.uint64)
+    check(lib.dvp_verify_trace_batch(t, d, e, ptr(pub_buf), pub.shape[1], ptr(pa), n, ptr(out)), "dvp_verify_trace_batch")
+    return out
+
+
+def format_verify_trace(rec) -> str:
+    """one verify_trace record as text, one `name = hex` line per field (what examples/dvp_verify_cli --trace prints): scalars and
+    coordinates as big-endian hex numbers, flags and the verdict as two hex digits"""
+    lines = [f"{f} = {fr.to_int(rec[f]):064x}" for f in _FR_FIELDS]
+    for f in _POINT_FIELDS:
+        xy = np.asarray(rec[f + "_xy"])
+        lines += [f"{f}_x = {fr.to_int(xy[:4]):064x}", f"{f}_y = {fr.to_int(xy[4:]):064x}"]
+    lines += [f"{f}_inf = {int(rec[f + '_inf']):02x}" for f in _POINT_FIELDS]
+    lines.append(f"verdict = {int(rec['verdict']):02x}")
+    return "\n".join(lines)
+
+
+def parse_verify_trace(text: str) -> np.ndarray:
+    """format_verify_trace's (and the CLI's) lines back into one record; lines without ` = ` are skipped"""
+    vals = dict(ln.split(" = ") for ln in text.splitlines() if " = " in ln)
+    rec = np.zeros((), dtype=VERIFY_TRACE_DTYPE)
+    for f in _FR_FIELDS:
+        rec[f] = _raw_limbs(int(vals[f], 16))
+    for f in _POINT_FIELDS:
+        rec[f + "_xy"] = np.concatenate([_raw_limbs(int(vals[f + "_x"], 16)), _raw_limbs(int(vals[f + "_y"], 16))])
+        rec[f + "_inf"] = int(vals[f + "_inf"], 16)
+    rec["verdict"] = int(vals["verdict"], 16)
+    return rec
+
+
 def sp1_public_input(raw: int) -> int:
     """sp1_generate_scalar_from_raw_public_input, src/gnark_r1cs.rs:214-229 (dvp_sp1_public_input)"""
     from ._native import lib, check, ptr

@@ -604,6 +604,73 @@ int dvp_verify_batch_rlc(const uint64_t tau[4], const uint64_t delta[4], const u
 int dvp_verify_batch_rlc_dev(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const void* d_public_inputs,
                              uint32_t n_public, const void* d_proofs, size_t n, const uint8_t seed[32], void* d_verdicts,
                              void* d_report /* optional u32 */, void* stream);
+
+/* Accepted proofs from the trapdoor alone, without a circuit, an SRS or a witness (test vectors for a verifier, distinct proofs for a
+ * benchmark): for proof j the discrete logs are chosen and the verifier's equation is solved for them, one lane per proof, one kernel
+ * launch per call once the generator table of the device exists.  Deterministic:
+ *   key        = seed (32 bytes), or for seed == NULL BLAKE3("dv-pari simulate v1" || tau || delta || epsilon), each as 32 LE bytes
+ *   draw(j, g) = the first 29 bytes of BLAKE3(key || LE64(index_base + j) || g), g one byte, read little-endian, masked to 230 bits
+ *   p = draw(j, 1), or 1 if that is 0;  b0 = draw(j, 2) unless the caller gives b0;  t = draw(j, 3)
+ *   the case:    P_ZERO p = 0;  T_HALF t = p / 2;  U0_ZERO t = 0;  K_ZERO t = p
+ *   commit_p   = enc(p G) under the codec rule in force;  alpha = the verifier's transcript over commit_p and row j of the public
+ *                inputs under the binding dvp_verify_set_binding holds;  v0 = (tau - alpha) epsilon;  v0 = 0: status DVP_SIM_V0_ZERO
+ *   the case:    K_PLUS_G t = p - v0;  K_MINUS_G t = p + v0
+ *   kzg_k      = enc(k G), k = (p - t) / v0;  i0 = sum_i pub_i alpha^i;  if 1 + delta^2 b0 = 0 then b0 := b0 + 1;
+ *   a0         = (t / epsilon - delta b0 + delta^2 i0) / (1 + delta^2 b0)
+ *   proof j    = commit_p[30] | kzg_k[30] | a0 as 29 LE bytes | b0 as 29 LE bytes
+ * so that u0 = t and v0 K + u0 G = (p - t) G + t G = P: dvp_verify_batch accepts every proof with status DVP_SIM_OK, under the
+ * trapdoor, public inputs, binding and codec rule it was made with.  The cases reach the exceptional branches of the verifier's
+ * addition chain.  dlogs (optional): p then k per proof, canonical.  A proof with a nonzero status is 118 zero bytes and its
+ * discrete logs are zero.  DVP_EINVAL before any device work: a trapdoor element >= p, epsilon = 0 (u0 = v0 = 0 leaves nothing to
+ * solve), n_public > DVP_VERIFY_MAX_PUBLIC, a NULL required pointer, and in the host flavour a non-canonical public input
+ * (dvp_last_error_index() = its flat index), a case byte > 6 or a non-canonical b0 (= the proof's index).  n = 0 is DVP_OK and
+ * touches nothing. */
+#define DVP_SIM_GENERIC 0   /* P, b0, u0 drawn from the key */
+#define DVP_SIM_T_HALF 1    /* u0 = p/2: v0 K == u0 G, the final addition is a doubling */
+#define DVP_SIM_P_ZERO 2    /* P = O: v0 K == -u0 G */
+#define DVP_SIM_U0_ZERO 3
+#define DVP_SIM_K_PLUS_G 4  /* K = G */
+#define DVP_SIM_K_MINUS_G 5 /* K = -G */
+#define DVP_SIM_K_ZERO 6    /* K = O */
+#define DVP_SIM_OK 0x00u
+#define DVP_SIM_V0_ZERO 0x01u    /* alpha == tau: no K exists for this P; the 118 bytes are zero */
+#define DVP_SIM_BAD_PUBLIC 0x02u /* _dev only */
+#define DVP_SIM_BAD_CASE 0x04u   /* _dev only */
+#define DVP_SIM_BAD_B0 0x08u     /* _dev only */
+int dvp_simulate_batch(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4],
+                       const uint64_t* public_inputs /* n x n_public x 4 */, uint32_t n_public, size_t n,
+                       const uint8_t seed[32] /* NULL: key from the trapdoor */, uint64_t index_base,
+                       const uint8_t* cases /* n bytes, NULL = all generic */, const uint64_t* b0 /* n x 4, NULL = drawn */,
+                       uint8_t* proofs /* n x 118 */, uint8_t* status /* n */, uint64_t* dlogs /* optional, n x 8: p then k */);
+/* the same on device buffers, enqueued on `stream` on the current device; only the first call on a device waits (it builds the
+ * generator table).  The three input faults are status bits of their proof here, which is then zero bytes; its neighbours are
+ * not affected. */
+int dvp_simulate_batch_dev(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const void* d_public_inputs,
+                           uint32_t n_public, size_t n, const uint8_t seed[32], uint64_t index_base, const void* d_cases,
+                           const void* d_b0, void* d_proofs, void* d_status, void* d_dlogs /* optional */, void* stream);
+
+/* The stage values of SRS::verify per proof, for whoever has to find where a prover and a verifier part (or writes this verifier a
+ * second time): the arguments and errors of dvp_verify_batch(_dev) with one record per proof in place of the verdict byte.
+ * `verdict` is exactly dvp_verify_batch's byte.  With a validity bit set every other field is zero.  Otherwise the record holds the
+ * transcript challenge alpha, i0 = sum_i pub_i alpha^i, r0 = a0 b0 - i0, u0 and v0 (canonical limbs), the decoded commit_p and
+ * kzg_k, and v0 K, u0 G and their sum, every point in the affine form used everywhere in this header (x then y), a point at infinity
+ * with zero coordinates and its flag set; DVP_VERIFY_EQUATION is set exactly when (sum_inf, sum_xy) != (p_inf, p_xy). */
+typedef struct dvp_verify_trace {
+  uint64_t alpha[4], i0[4], r0[4], u0[4], v0[4]; /* canonical limbs */
+  uint64_t p_xy[8], k_xy[8];                     /* decoded commit_p, kzg_k */
+  uint64_t vk_xy[8], ug_xy[8], sum_xy[8];        /* v0 K, u0 G, v0 K + u0 G */
+  uint8_t p_inf, k_inf, vk_inf, ug_inf, sum_inf, verdict, pad[2];
+} dvp_verify_trace;
+#ifdef __cplusplus
+static_assert(sizeof(dvp_verify_trace) == 488, "dvp_verify_trace is 488 bytes");
+#else
+_Static_assert(sizeof(dvp_verify_trace) == 488, "dvp_verify_trace is 488 bytes");
+#endif
+int dvp_verify_trace_batch(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const uint64_t* public_inputs,
+                           uint32_t n_public, const uint8_t* proofs, size_t n, dvp_verify_trace* out);
+/* the same on device buffers (d_out: n x 488 bytes), enqueued on `stream`; a non-canonical public input is DVP_VERIFY_BAD_PUBLIC */
+int dvp_verify_trace_batch_dev(const uint64_t tau[4], const uint64_t delta[4], const uint64_t epsilon[4], const void* d_public_inputs,
+                               uint32_t n_public, const void* d_proofs, size_t n, void* d_out, void* stream);
 /* sp1_generate_scalar_from_raw_public_input (src/gnark_r1cs.rs:214-229), host only: BLAKE3 of the 8-byte LE raw value, digest
  * bytes 0..3 cleared, read big-endian (< 2^224, canonical) */
 int dvp_sp1_public_input(uint64_t raw, uint64_t out[4]);

@@ -1,6 +1,6 @@
 """dvp_verify_batch_dev throughput and dvp_verify latency (csrc/verify.hip).
 
-    python tools/verify_bench.py [--reps 5] [--pool 4096] [--max-log 20] [--rlc]
+    python tools/verify_bench.py [--reps 5] [--pool 4096] [--max-log 20] [--rlc] [--simulate]
 
 Valid proofs (n_public = 2) are built once without a prover (tests/verify_cases.py, library encodings and transcript), a pool of
 --pool distinct proofs tiled to each batch size -- every lane does the full work of a valid proof whatever repeats.  Batches of
@@ -11,7 +11,11 @@ script (tools/README.md).
 
 --rlc: the same batches also through dvp_verify_batch_rlc_dev (one random-linear-combination MSM, the per-lane kernel gated off), timed
 the same way right after the per-lane leg of each size, every report checked to be COMBINED; then a 2^16 batch (or the largest
-size run) with one invalid proof, which takes the combined check plus the per-lane fallback, for both entries."""
+size run) with one invalid proof, which takes the combined check plus the per-lane fallback, for both entries.
+
+--simulate: the proofs come from dvp_simulate_batch (srs.simulate_batch) instead: 2^max-log DISTINCT proofs, every batch a prefix of
+them, nothing tiled: the combined check's MSM then runs over 2^21 distinct points (tools/README.md, "Simulated proofs", has it
+beside the tiled pool)."""
 import argparse
 import ctypes as C
 import importlib
@@ -55,6 +59,17 @@ def pool(n):
     return td, dvp.srs._public_array(pubs, n), proofs
 
 
+def simulated(n):
+    """n DISTINCT valid proofs (n_public = 2) from dvp_simulate_batch: the trapdoor of pool(), public inputs below 2^230"""
+    rng = random.Random(1)
+    td = (rng.randrange(1, o.P), rng.randrange(1, o.P), rng.randrange(1, o.P))
+    pub = np.random.default_rng(2).integers(0, 1 << 62, size=(n, 2, 4), dtype=np.uint64)
+    pub[:, :, 3] &= np.uint64((1 << 38) - 1)
+    proofs, status = dvp.srs.simulate_batch(dvp.srs.Trapdoor(*td), pub)
+    assert not status.any()
+    return td, pub, proofs
+
+
 def timed(a, s, tv, trep, fn, args, n, want_report, label, lg, bad_at=None):
     """one warm-up call, then --reps calls between device events on stream s; every verdict checked (0, or EQUATION at bad_at only)
     and, for the combined check, the report word"""
@@ -92,8 +107,11 @@ def main():
     ap.add_argument("--pool", type=int, default=4096)
     ap.add_argument("--max-log", type=int, default=20)
     ap.add_argument("--rlc", action="store_true", help="time dvp_verify_batch_rlc_dev beside dvp_verify_batch_dev")
+    ap.add_argument("--simulate", action="store_true", help="distinct proofs from dvp_simulate_batch instead of a tiled pool")
     a = ap.parse_args()
-    td, pub, proofs = pool(a.pool)
+    if a.simulate:
+        a.pool = 1 << min(20, a.max_log)  # every batch is a prefix of one run of distinct proofs
+    td, pub, proofs = simulated(a.pool) if a.simulate else pool(a.pool)
     keep, (t, d, e) = dvp.srs._trapdoor_args(dvp.srs.Trapdoor(*td))
     dev = torch.device("cuda:0")
     s = torch.cuda.Stream(device=dev)
