@@ -7,7 +7,7 @@
 HIPCC  ?= /opt/rocm/bin/hipcc
 ARCH   ?= gfx950
 CSRC   := dv-pari_amd/csrc
-SRCS   := capi.cpp cache.cpp tree_io.cpp ecfft.hip msm.hip codec.hip fr_ops.hip fr_debug.hip gf_debug.hip prove.hip setup.hip verify.hip simulate.hip blake3_tree.hip points_mul.hip msm_segments.hip fr_wire.hip circuit_hash.hip fr_ark.hip srs_check.hip
+SRCS   := capi.cpp cache.cpp tree_io.cpp ecfft.hip msm.hip codec.hip fr_ops.hip fr_debug.hip gf_debug.hip prove.hip setup.hip verify.hip simulate.hip blake3_tree.hip points_mul.hip msm_segments.hip fr_wire.hip circuit_hash.hip fr_ark.hip srs_check.hip fr_digest.hip
 OBJS   := $(addprefix $(CSRC)/,$(addsuffix .o,$(basename $(SRCS))))
 HDRS   := $(wildcard $(CSRC)/*.h $(CSRC)/*.cuh include/*.h)
 LIB    := dv-pari_amd/libdvpari_hip.so

@@ -54,6 +54,30 @@ class WitnessReport(C.Structure):
                 ("constant_wire_is_one", C.c_uint32)]
 
 
+class TracePoint(C.Structure):
+    """dvp_trace_point (include/dvpari.h)"""
+    _fields_ = [("xy", C.c_uint64 * 8), ("enc", C.c_uint8 * 30), ("inf", C.c_uint8), ("pad", C.c_uint8)]
+
+
+TRACE_SCALARS = ("alpha", "z_alpha", "a0", "b0", "i0", "r0")
+TRACE_POINTS = ("msm_gm", "msm_q", "commit_p", "kzg_a", "kzg_b", "kzg_r", "kzg_k")
+# the digests in the struct's order: (field, the name src/proving.rs gives the vector)
+TRACE_DIGESTS = (("assignment", "assignment"), ("evals_a", "evals.a"), ("evals_b", "evals.b"), ("evals_c", "evals.c"), ("evals_i", "evals.i"),
+                 ("evals2_a", "evals2.a"), ("evals2_b", "evals2.b"), ("evals2_c", "evals2.c"), ("evals2_i", "evals2.i"),
+                 ("r_vals2", "r_vals2"), ("q_vals2", "q_vals2"), ("denom_invs", "denom_invs"), ("denom_invs2", "denom_invs2"),
+                 ("k_scalar_a", "k_scalar_a"), ("k_scalar_b", "k_scalar_b"), ("k_scalar_r", "k_scalar_r"))
+TRACE_HEADER = ("log2_m", "n_wires", "n_public", "codec_rule", "parts", "mismatch")
+
+
+class ProveTrace(C.Structure):
+    """dvp_prove_trace (include/dvpari.h)"""
+    _fields_ = ([(f, C.c_uint32) for f in TRACE_HEADER] + [(f, C.c_uint64 * 4) for f in TRACE_SCALARS] + [(f, TracePoint) for f in TRACE_POINTS]
+                + [(f, C.c_uint8 * 32) for f, _ in TRACE_DIGESTS])
+
+
+PROVE_TRACE_BYTES = 1400  # the header's static_assert
+
+
 _WC_TAIL = [C.POINTER(UnsatRow), sz, C.POINTER(SuspectWire), sz, C.POINTER(WitnessReport)]  # rows, rows_cap, wires, wires_cap, report
 
 _SIGS = {
@@ -238,6 +262,9 @@ _SIGS = {
     "dvp_verify_trace_batch": (C.c_int, [u64p, u64p, u64p, u64p, u32, u8p, sz, vp]),
     "dvp_verify_trace_batch_dev": (C.c_int, [u64p, u64p, u64p, vp, u32, vp, sz, vp, vp]),
     "dvp_sp1_public_input": (C.c_int, [C.c_uint64, u64p]),
+    "dvp_fr_vec_digest": (C.c_int, [u64p, sz, u8p]),
+    "dvp_fr_vec_digest_dev": (C.c_int, [vp, sz, C.c_int, vp, vp]),
+    "dvp_prover_trace_last": (C.c_int, [vp, u32, C.POINTER(ProveTrace), vp]),
 }
 EXPORTED = []
 for _name, (_res, _args) in _SIGS.items():

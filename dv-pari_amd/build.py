@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdvpari_hip.so")
-SOURCES = ["capi.cpp", "cache.cpp", "tree_io.cpp", "ecfft.hip", "msm.hip", "codec.hip", "fr_ops.hip", "fr_debug.hip", "gf_debug.hip", "prove.hip", "setup.hip", "verify.hip", "simulate.hip", "blake3_tree.hip", "points_mul.hip", "msm_segments.hip", "fr_wire.hip", "circuit_hash.hip", "fr_ark.hip", "srs_check.hip"]
+SOURCES = ["capi.cpp", "cache.cpp", "tree_io.cpp", "ecfft.hip", "msm.hip", "codec.hip", "fr_ops.hip", "fr_debug.hip", "gf_debug.hip", "prove.hip", "setup.hip", "verify.hip", "simulate.hip", "blake3_tree.hip", "points_mul.hip", "msm_segments.hip", "fr_wire.hip", "circuit_hash.hip", "fr_ark.hip", "srs_check.hip", "fr_digest.hip"]
 HEADERS = ["common.h", "fr.cuh", os.path.join("..", "..", "include", "dvpari.h")]
 
 

@@ -150,6 +150,7 @@ static constexpr Knob kKnobs[] = {
     {"DVP_MSM_SEG_PIECE", &Tune::msm_seg_piece},
     {"DVP_CIRCUIT_HASH_WINDOW", &Tune::circuit_hash_window},
     {"DVP_MSM_ALIGNED_SIGNED", &Tune::msm_aligned_signed},
+    {"DVP_FR_DIGEST_WINDOW", &Tune::fr_digest_window},
 };
 static_assert(sizeof(Tune) == sizeof(kKnobs) / sizeof(kKnobs[0]) * sizeof(long long), "every field of Tune needs exactly one row of kKnobs");
 

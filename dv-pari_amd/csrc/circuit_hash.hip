@@ -120,6 +120,8 @@ __global__ void __launch_bounds__(CH_TPB) k_ch_find_minus_one(const Fr* __restri
 // last dword), the workgroup's 7424 dwords meet in LDS (stride 29: no bank conflict) and leave in order, each only if inside [lo, hi).
 // A Vandermonde entry -(d_i^j): the thread's first one by square-and-multiply (at most 2 x 32 products, whatever k), the next three by
 // one product each (or a load of d_(i+1) at a row's end), so a record's cost does not grow with j.
+// k_frd_pack (fr_digest.hip) holds a second copy of the packing loop and of the LDS hand-over (why two: there): a fix to one belongs in
+// the other.
 __global__ void __launch_bounds__(CH_TPB)
 k_ch_coeffs(const Fr* __restrict__ coeffs_m, uint32_t n0, uint64_t n1 /* 2^32 at most */, const Fr* __restrict__ dom_m, uint32_t m, uint32_t k, uint64_t N,
             uint64_t group0, uint64_t lo, uint64_t hi, uint32_t* __restrict__ out) {

@@ -253,6 +253,7 @@ struct Tune {
   long long msm_seg_piece = 4;         // DVP_MSM_SEG_PIECE: operands one lane of dvp_msm_segments' reduction sums per level, the piece length P (2 ..= 64; anything else = the default)
   long long circuit_hash_window = 0;   // DVP_CIRCUIT_HASH_WINDOW: 1 KiB chunks of the staging window dvp_prover_circuit_hash generates its stream into (0 or less = the default, 61440 chunks = 60 MiB, the SRS hash's window; at most 2^21); the digest does not depend on it
   long long msm_aligned_signed = 1;   // DVP_MSM_ALIGNED_SIGNED: the aligned-window tables hold 2^(c w) P and the windows are signed binary digits (0 = the tau-adic aligned windows over rows tau^(o_w) P)
+  long long fr_digest_window = 0;     // DVP_FR_DIGEST_WINDOW: 1 KiB chunks of the staging window dvp_fr_vec_digest packs its stream into (0 or less = the default, 61440 chunks = 60 MiB; at most 2^21; never more than the stream has); the digest does not depend on it
 };
 Tune& tune();
 

@@ -100,6 +100,12 @@ int b3_single_chunk_dev(const uint8_t* d_data, size_t len, uint32_t* d_out32, hi
 size_t b3_reduce_tmp_bytes(size_t n);
 int b3_reduce_dev(uint32_t* d_cvs, size_t n, uint32_t* d_tmp, uint32_t* d_out32, hipStream_t st);
 
+// ---- fr_digest.hip -----------------------------------------------------------------------------------------------------------
+// dvp_fr_vec_digest_dev with the scratch in the caller's hands (a prover's trace digests sixteen vectors through one): d_work holds
+// fr_digest_work_bytes(n) bytes, 256-byte aligned, and is free again when the work enqueued on st has run
+size_t fr_digest_work_bytes(size_t n);
+int fr_vec_digest_dev(const Fr* d_fr, size_t n, bool montgomery, void* d_work, uint32_t* d_out32, hipStream_t st);
+
 // ---- circuit_hash.hip --------------------------------------------------------------------------------------------------------
 // what the generator reads of the three matrices: row pointers and coefficient ids (never the wire ids)
 struct ChCsr {

@@ -27,6 +27,7 @@
 //   MSMs        prove_msm.cuh         prover_msm_partial (table budget), the multi-GPU shards, prove_msm, plan / table / budget entries
 //   challenge   prove_challenge.cuh   vector stages, device and host challenge, _partial / _finish, dvp_prove_finish
 //   check       prove_check.cuh       the witness check (unsatisfied rows, entries >= p, suspect wires) with its own kernels, dvp_prover_row_terms
+//   trace       prove_trace.cuh       dvp_prover_trace_last: scalars, partial commitments and vector digests of the last proof
 //   here        dvp_prove_dev and its two flavours, the host-witness entries, dvp_prover_debug_read, the domain-table entries
 #include <cstdlib>
 #include <algorithm>
@@ -54,6 +55,7 @@ using namespace dvp;
 #include "prove_msm.cuh"
 #include "prove_challenge.cuh"
 #include "prove_check.cuh"
+#include "prove_trace.cuh"
 
 // Proof::prove with the assignment already resident in HBM (the timed configuration of bench.py)
 // Host-transcript flavour (rounds 1-4; still what a device list, n_public > 35 or DVP_PROVE_HOST_TRANSCRIPT=1 gets): the host waits for
@@ -123,6 +125,7 @@ static int prove_dev_device_transcript(dvp_prover* p, const void* d_assignment, 
   if (f[1] != ~0ull) { g_last_error_index = (int64_t)f[1]; return DVP_ECHALLENGE; }
   if (rc_k != DVP_OK) { g_last_error_index = k_idx; return rc_k; }
   assemble_proof(p, h->enc + 30, proof);
+  p->trace_mark();
   return DVP_OK;
 }
 extern "C" int dvp_prove_dev(dvp_prover* p, const void* d_assignment, uint8_t proof[118], void* stream) {

@@ -33,6 +33,7 @@ static int prove_begin_impl(dvp_prover* p, const void* d_assignment, int need_ex
   if (!p || !d_assignment || !prover_ready(p)) return DVP_EINVAL;
   p->last_begin_extended = false;  // set by dvp_prove_quotient once every extended vector is in place
   p->ext_filled = 0;
+  p->trace_ok = p->challenge_sliced = false;
   p->enc_fused[0] = p->enc_fused[1] = false;  // a staged caller may have abandoned a proof after an MSM into the prover's own slot
   hipStream_t st = (hipStream_t)stream;
   const uint32_t m = p->m;
@@ -85,6 +86,7 @@ extern "C" int dvp_prove_extend_vectors(dvp_prover* p, uint32_t mask, void* stre
   hipStream_t st = (hipStream_t)stream;
   const uint32_t m = p->m, n_ext = prover_n_ext(p);
   if (mask >> n_ext) return DVP_EINVAL;
+  p->trace_ok = false;  // E2 is rewritten
   // runs of consecutive selected vectors share one batched extend (the matrices are read once per run)
   for (uint32_t v = 0; v < n_ext;) {
     if (!((mask >> v) & 1)) { ++v; continue; }
@@ -112,6 +114,7 @@ extern "C" int dvp_prove_quotient(dvp_prover* p, void* stream) {
   const uint32_t m = p->m;
   const size_t nw = p->n_wires;
   if (p->ext_filled != (1u << prover_n_ext(p)) - 1) return DVP_EINVAL;  // a missed broadcast would otherwise give a silently wrong q2
+  p->trace_ok = false;  // r2, q2 and (by Horner) E2's fourth vector are rewritten
   dim3 gm(cdiv(m, PT)), bt(PT);
   if (prover_n_ext(p) == 3)
     DVP_LAUNCH(k_quotient<true>, gm, bt, 0, st, p->E2, p->z2inv, m, p->SA, p->dD2, p->n_pub, p->r2, p->SA + nw);

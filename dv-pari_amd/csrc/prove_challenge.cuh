@@ -62,6 +62,7 @@ static int challenge_alpha_host(dvp_prover* p, const void* d_commit_xy, const vo
 // phase 2 (src/proving.rs:515-654): commit_p -> alpha -> a0,b0,i0,r0 -> K scalars SK.
 extern "C" int dvp_prove_challenge(dvp_prover* p, const void* d_commit_xy, const void* d_commit_inf, void* stream) {
   if (!p || !d_commit_xy || !d_commit_inf) return DVP_EINVAL;
+  p->trace_ok = false;  // den, SK and the block are rewritten: dvp_prove_finish marks the proof again
   hipStream_t st = (hipStream_t)stream;
   ProverBlock* h = p->fin_host;  // its (alpha_m, neg_z) are pinned staging, rewritten only after this proof's final synchronisation
   DVP_TRY(challenge_alpha_host(p, d_commit_xy, d_commit_inf, st, &h->alpha_m, &h->neg_z));
@@ -81,6 +82,8 @@ extern "C" int dvp_prove_challenge_partial(dvp_prover* p, const void* d_commit_x
   if (!p || !d_commit_xy || !d_commit_inf || !d_record_out) return DVP_EINVAL;
   const uint32_t m = p->m;
   if (d_lo > d_hi || d_hi > m || k_lo > k_hi || k_hi > 4 * (size_t)m) return DVP_EINVAL;
+  p->challenge_sliced = true;
+  p->trace_ok = false;
   hipStream_t st = (hipStream_t)stream;
   dim3 bt(PT);
   Fr alpha_m;
@@ -130,6 +133,7 @@ extern "C" int dvp_prove_challenge_finish(dvp_prover* p, const void* d_records, 
   if (!p || !d_records || !n_records) return DVP_EINVAL;
   const uint32_t m = p->m;
   if (k_lo > k_hi || k_hi > 4 * (size_t)m) return DVP_EINVAL;
+  p->trace_ok = false;
   hipStream_t st = (hipStream_t)stream;
   DVP_LAUNCH(k_bary3_from_records, dim3(1), dim3(64), 0, st, (const Fr*)d_records, n_records, p->neg_z_alpha_m, p->blk->abir0, p->blk->flags + 1);
   if (k_lo < k_hi)
@@ -166,5 +170,6 @@ extern "C" int dvp_prove_finish(dvp_prover* p, const void* d_kzg_xy, const void*
     return DVP_ECHALLENGE;  // alpha in D u D', src/proving.rs:548-556
   }
   assemble_proof(p, h->enc + 30, proof);
+  if (p->last_begin_extended && !p->challenge_sliced) p->trace_mark();
   return DVP_OK;
 }

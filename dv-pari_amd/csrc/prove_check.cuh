@@ -232,6 +232,7 @@ static int check_witness_impl(dvp_prover* p, const void* d_in, bool be, dvp_unsa
   DVP_HIP(hipMemsetAsync(blk->first, 0xff, sizeof(blk->first), st));
   DVP_HIP(hipMemsetAsync(blk->count, 0, sizeof(WcBlock) - sizeof(blk->first), st));
   Fr* w = p->SA;  // the reduced assignment, where a proof keeps its own: the next begin overwrites it
+  p->trace_ok = false;  // SA no longer holds the last proof's assignment: that proof has no trace any more
   if (be) DVP_LAUNCH(k_wc_reduce<true>, dim3(nbw), dim3(PT), 0, st, (const uint32_t*)d_in, nw, w, blk);
   else DVP_LAUNCH(k_wc_reduce<false>, dim3(nbw), dim3(PT), 0, st, (const uint32_t*)d_in, nw, w, blk);
   DVP_LAUNCH(k_wc_rows, dim3(nb), dim3(PT), 0, st, A, B, C, p->coeffs_m, w, m, bits, cnt, blk);

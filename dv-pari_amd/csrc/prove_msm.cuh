@@ -109,7 +109,10 @@ static int prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, vo
   return msm_affine_dev(sc + lo, bs + lo, inf + lo, hi - lo, out, st);
 }
 extern "C" int dvp_prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, void* d_out_xy, void* d_out_inf, void* stream) {
-  if (p && (which == 0 || which == 1) && d_out_xy == (void*)(p->pts + which)) p->enc_fused[which] = false;  // the point changes, its encoding does not follow
+  if (p && (which == 0 || which == 1) && d_out_xy == (void*)(p->pts + which)) {
+    p->enc_fused[which] = false;  // the point changes, its encoding does not follow
+    p->trace_ok = false;          // nor does a trace describe the proof whose point this was
+  }
   return prover_msm_partial(p, which, lo, hi, d_out_xy, d_out_inf, nullptr, stream);
 }
 

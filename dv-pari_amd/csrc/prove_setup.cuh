@@ -166,7 +166,9 @@ static int srs_slot(dvp_prover* p, int which, size_t n, Aff** base, uint8_t** in
     case 4: *base = p->bases_k + 2 * m; *inf = p->inf_k + 2 * m; want = 2 * m; break;
     default: return DVP_EINVAL;
   }
-  return n == want ? DVP_OK : DVP_EINVAL;
+  if (n != want) return DVP_EINVAL;
+  p->trace_ok = false;  // the caller overwrites the slot: the last proof's commitments are not sums over these bases
+  return DVP_OK;
 }
 // how every setter closes.  Its copies / fills ran on the default stream; proofs run on other (non-blocking) streams, which do not order
 // themselves behind it: nothing of a setter may still be in flight when it returns

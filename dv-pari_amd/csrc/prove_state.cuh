@@ -54,6 +54,17 @@ struct dvp_prover {
   char* mix = nullptr;
   bool last_begin_extended = false;            // dvp_prove_begin_partial(need_extend): q2 / k_r are valid only if true
   uint32_t ext_filled = 0;                     // bit v: extended vector v of this proof is in E2 (extended here, or received and marked)
+  // dvp_prover_trace_last (prove_trace.cuh): the buffers hold a COMPLETE proof -- set by trace_mark where a whole proof succeeds, cleared
+  // by every entry that writes what the trace reads (SA, E, E2, r2, den, SK, the block, the result points) or replaces a base vector:
+  // every begin and staged phase entry, the witness check (it reduces its argument into SA), the SRS setters.
+  // challenge_sliced: this proof's challenge phase ran by index slices (den / SK are partial), so finishing it does not set trace_ok.
+  // trace_rule: the codec rule the proof's two encodings were written under; a trace under another rule is refused
+  bool trace_ok = false, challenge_sliced = false;
+  int trace_rule = 0;
+  void trace_mark() {
+    trace_ok = true;
+    trace_rule = codec_rule_now();
+  }
   // in-library multi-GPU (dvp_set_devices): one shard per listed device, each with its slice of both base vectors
   struct Shard {
     int device = 0;

@@ -76,6 +76,31 @@ def batch_inverse(a):
     return a
 
 
+def vec_digest(v) -> bytes:
+    """BLAKE3 of Vec<Fr>::serialize_uncompressed of v (uint64 [n, 4] canonical, or ints): the u64 count, then 29 bytes little-endian
+    per entry -- the bytes io_utils.write_fr_vec_to_file writes; packed and hashed on the GPU (dvp_fr_vec_digest).  An entry >= p
+    raises DvpError (DVP_EINVAL) with its index."""
+    a = _c(v) if isinstance(v, np.ndarray) else (vec(v) if len(v) else np.zeros((0, 4), dtype=np.uint64))
+    out = np.zeros(32, dtype=np.uint8)
+    check(lib.dvp_fr_vec_digest(ptr(a) if a.shape[0] else None, a.shape[0], ptr(out)), "dvp_fr_vec_digest")
+    return out.tobytes()
+
+
+def vec_digest_dev(d_fr: int, n: int, montgomery: bool = False, stream: int = 0) -> bytes:
+    """the same over n x 32 bytes at the device address d_fr (dvp_fr_vec_digest_dev; montgomery: the entries are a R mod p and are
+    converted first).  The low 29 bytes of every entry are hashed unchecked.  The call only enqueues on `stream`; this wrapper then
+    waits for the 32 bytes."""
+    import torch
+
+    out = torch.empty(32, dtype=torch.uint8, device="cuda")
+    check(lib.dvp_fr_vec_digest_dev(d_fr or None, n, int(bool(montgomery)), out.data_ptr(), stream or None), "dvp_fr_vec_digest_dev")
+    if stream:
+        torch.cuda.ExternalStream(stream).synchronize()
+    else:
+        torch.cuda.synchronize()
+    return out.cpu().numpy().tobytes()
+
+
 def _be32_arg(raw) -> np.ndarray:
     """n x 32 big-endian bytes (bytes-like, or a uint8 array of shape [n, 32] / [32 n]) as a contiguous uint8 [n, 32]"""
     a = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else np.asarray(raw)

@@ -243,6 +243,74 @@ def check_witness_file(cache_dir, num_public_inputs: int, witness_path=None, max
                           max_rows, max_wires, "dvp_check_witness_cache_dir_witness_file")
 
 
+TRACE_SCALARS, TRACE_DIGESTS, TRACE_POINTS, TRACE_ALL = 0x1, 0x2, 0x4, 0x7  # DVP_TRACE_*
+TRACE_MISMATCH_COMMIT, TRACE_MISMATCH_KZG = 0x1, 0x2
+
+
+def _trace_record(t) -> dict:
+    """a dvp_prove_trace as a plain dict: header fields and scalars as ints, a point as {"x", "y", "inf", "enc"}, a digest as 32 bytes
+    under the name src/proving.rs gives its vector ("evals2.i", "k_scalar_r", ..)"""
+    from . import _native as nat
+
+    rec = {f: int(getattr(t, f)) for f in nat.TRACE_HEADER}
+    for f in nat.TRACE_SCALARS:
+        rec[f] = sum(int(x) << (64 * k) for k, x in enumerate(getattr(t, f)))
+    for f in nat.TRACE_POINTS:
+        pt = getattr(t, f)
+        rec[f] = {"x": sum(int(x) << (64 * k) for k, x in enumerate(pt.xy[:4])), "y": sum(int(x) << (64 * k) for k, x in enumerate(pt.xy[4:])),
+                  "inf": int(pt.inf), "enc": bytes(pt.enc)}
+    for f, name in nat.TRACE_DIGESTS:
+        rec[name] = bytes(getattr(t, f))
+    return rec
+
+
+def format_prove_trace(rec) -> str:
+    """one prove-trace record as text, one `name = hex` line per field (what examples/dvp_prove_cli --trace prints): header words as
+    eight hex digits, scalars and coordinates as big-endian hex numbers, flags as two hex digits, encodings and digests byte by byte"""
+    from . import _native as nat
+
+    lines = [f"{f} = {rec[f]:08x}" for f in nat.TRACE_HEADER]
+    lines += [f"{f} = {rec[f]:064x}" for f in nat.TRACE_SCALARS]
+    for f in nat.TRACE_POINTS:
+        pt = rec[f]
+        lines += [f"{f}_x = {pt['x']:064x}", f"{f}_y = {pt['y']:064x}", f"{f}_inf = {pt['inf']:02x}", f"{f}_enc = {pt['enc'].hex()}"]
+    lines += [f"{name} = {rec[name].hex()}" for _, name in nat.TRACE_DIGESTS]
+    return "\n".join(lines)
+
+
+def parse_prove_trace(text: str) -> dict:
+    """format_prove_trace's (and the CLI's) lines back into a record; lines without ` = ` are skipped"""
+    from . import _native as nat
+
+    vals = dict(ln.split(" = ") for ln in text.splitlines() if " = " in ln)
+    rec = {f: int(vals[f], 16) for f in nat.TRACE_HEADER + nat.TRACE_SCALARS}
+    for f in nat.TRACE_POINTS:
+        rec[f] = {"x": int(vals[f + "_x"], 16), "y": int(vals[f + "_y"], 16), "inf": int(vals[f + "_inf"], 16),
+                  "enc": bytes.fromhex(vals[f + "_enc"].strip())}
+    for _, name in nat.TRACE_DIGESTS:
+        rec[name] = bytes.fromhex(vals[name].strip())
+    return rec
+
+
+def _trace_last(handle, parts: int, stream: int = 0) -> dict:
+    from ._native import ProveTrace
+
+    t = ProveTrace()
+    check(lib.dvp_prover_trace_last(handle, parts, C.byref(t), stream or None), "dvp_prover_trace_last")
+    return _trace_record(t)
+
+
+def trace_cache_dir(cache_dir, num_public_inputs: int, parts: int = TRACE_ALL) -> dict:
+    """Prover.trace_last on the prover Proof.prove(cache_dir, ..) keeps for the directory (dvp_cache_dir_prover): the stages of the last
+    proof made from cache_dir.  The handle is borrowed and the call does not take a turn: do not prove from cache_dir on another thread
+    meanwhile."""
+    import os
+
+    h = C.c_void_p()
+    check(lib.dvp_cache_dir_prover(os.fspath(cache_dir).encode(), num_public_inputs, C.byref(h)), "dvp_cache_dir_prover")
+    return _trace_last(h, parts)
+
+
 class Prover:
     """The artefacts Proof::prove reads from cache_dir (R1CS dump, SRS point vectors, TREE_2N and the
     prover precomputes, src/proving.rs:435-511,562-565,666-672), loaded once and kept in HBM."""
@@ -361,6 +429,17 @@ class Prover:
         check(lib.dvp_prove_ark(self._h, ptr(pub) if pub.shape[0] else None, pub.shape[0], ptr(prv) if prv.shape[0] else None,
                                 prv.shape[0], ptr(out)), "dvp_prove_ark")
         return Proof.from_bytes(out.tobytes())
+
+    # ---- the stages of the last proof -----------------------------------------------------------------------
+    def trace_last(self, parts: int = TRACE_ALL, stream: int = 0) -> dict:
+        """dvp_prover_trace_last: scalars, partial commitments and vector digests of this prover's last complete proof (the record of
+        format_prove_trace); DvpError (DVP_EINVAL) when there is none.  Costs more than the proof; changes nothing a later proof reads."""
+        return _trace_last(self._h, parts, stream)
+
+    def prove_trace(self, public_inputs, private_inputs, parts: int = TRACE_ALL):
+        """prove, then trace_last: (Proof, record)"""
+        proof = self.prove(public_inputs, private_inputs)
+        return proof, self.trace_last(parts)
 
     # ---- explain an unsatisfied witness (needs coefficients and matrices, no SRS) -------------------
     def check_witness(self, public_inputs, private_inputs, max_rows: int = 16, max_wires: int = 16) -> WitnessReport:

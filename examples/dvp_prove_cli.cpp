@@ -3,7 +3,7 @@
 // (src/proving.rs:426) from files alone:
 //
 //   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3] [--table-budget <bytes>] [--bind-srs] [--bind-circuit | --circuit-hash <hex>]
-//                 [--host-witness] [--repeat N --threads T]
+//                 [--host-witness] [--repeat N --threads T] [--trace]
 //   dvp_prove_cli <cache_dir> <n_public> --check-witness [--max-rows N]
 //
 // --check-witness: explain the witness instead of proving (dvp_check_witness_cache_dir_witness_file; needs the dump and the witness
@@ -15,6 +15,11 @@
 // that entry existed: dvp_file_witness_read (reduction on one host thread) + dvp_prover_open_cache_dir + dvp_prove.  Same bytes.
 // --repeat N --threads T: N more proofs through dvp_prove_cache_dir with the witness as limbs in host memory, whichever way the first
 // proof went; the witness is read and reduced on the host only for this leg or under --host-witness.
+//
+// --trace: after the proof line, the stages of that proof (dvp_prover_trace_last with DVP_TRACE_ALL) as `name = hex` lines -- the header
+// words, alpha, z_alpha, a0, b0, i0, r0, the seven points (x, y, infinity flag, 30-byte encoding) and the sixteen vector digests under
+// the names src/proving.rs gives the vectors: what a host compares field by field when its reference prover's bytes differ
+// ("When the bytes differ").  Single device only; it costs more than the proof.
 //
 // --bind-srs: bind the proof's challenge to the SRS (dvp_prover_srs_hash + dvp_prover_set_transcript_binding); the SRS hash used goes
 // to stderr -- the verifier needs it (dvp_verify_cli --srs-hash).  --circuit-hash <64 hex digits>: the circuit half of the binding
@@ -61,6 +66,40 @@ static bool parse_hash(const char* s, uint8_t out[32]) {
   return true;
 }
 
+// the record as `name = hex` lines: header words, scalars and coordinates as big-endian numbers, encodings and digests byte by byte
+static void print_trace(const dvp_prove_trace& t) {
+  const struct { const char* name; uint32_t v; } hdr[] = {{"log2_m", t.log2_m}, {"n_wires", t.n_wires}, {"n_public", t.n_public},
+                                                            {"codec_rule", t.codec_rule}, {"parts", t.parts}, {"mismatch", t.mismatch}};
+  for (const auto& h : hdr) printf("%s = %08x\n", h.name, h.v);
+  auto num = [](const char* name, const char* suffix, const uint64_t v[4]) {
+    printf("%s%s = %016llx%016llx%016llx%016llx\n", name, suffix, (unsigned long long)v[3], (unsigned long long)v[2], (unsigned long long)v[1],
+           (unsigned long long)v[0]);
+  };
+  auto bytes = [](const char* name, const char* suffix, const uint8_t* b, int n) {
+    printf("%s%s = ", name, suffix);
+    for (int i = 0; i < n; ++i) printf("%02x", b[i]);
+    printf("\n");
+  };
+  const struct { const char* name; const uint64_t* v; } sc[] = {{"alpha", t.alpha}, {"z_alpha", t.z_alpha}, {"a0", t.a0},
+                                                                 {"b0", t.b0},       {"i0", t.i0},           {"r0", t.r0}};
+  for (const auto& s : sc) num(s.name, "", s.v);
+  const struct { const char* name; const dvp_trace_point* p; } pt[] = {{"msm_gm", &t.msm_gm}, {"msm_q", &t.msm_q}, {"commit_p", &t.commit_p},
+                                                                        {"kzg_a", &t.kzg_a},   {"kzg_b", &t.kzg_b}, {"kzg_r", &t.kzg_r},
+                                                                        {"kzg_k", &t.kzg_k}};
+  for (const auto& q : pt) {
+    num(q.name, "_x", q.p->xy);
+    num(q.name, "_y", q.p->xy + 4);
+    printf("%s_inf = %02x\n", q.name, q.p->inf);
+    bytes(q.name, "_enc", q.p->enc, 30);
+  }
+  const struct { const char* name; const uint8_t* d; } dg[] = {
+      {"assignment", t.assignment}, {"evals.a", t.evals_a},         {"evals.b", t.evals_b},         {"evals.c", t.evals_c},
+      {"evals.i", t.evals_i},       {"evals2.a", t.evals2_a},       {"evals2.b", t.evals2_b},       {"evals2.c", t.evals2_c},
+      {"evals2.i", t.evals2_i},     {"r_vals2", t.r_vals2},         {"q_vals2", t.q_vals2},         {"denom_invs", t.denom_invs},
+      {"denom_invs2", t.denom_invs2}, {"k_scalar_a", t.k_scalar_a}, {"k_scalar_b", t.k_scalar_b},   {"k_scalar_r", t.k_scalar_r}};
+  for (const auto& d : dg) bytes(d.name, "", d.d, 32);
+}
+
 int main(int argc, char** argv) {
   std::vector<int> devices;
   bool bind_srs = false, bind_circuit = false, have_circuit = false, host_witness = false;
@@ -68,6 +107,8 @@ int main(int argc, char** argv) {
   int repeat = 0, threads = 1;  // --repeat N --threads T: N more proofs through dvp_prove_cache_dir from T host threads
   bool check_witness = false;   // --check-witness [--max-rows N]: explain the witness instead of proving
   size_t max_rows = 16;
+  bool trace = false;           // --trace: print the stages of the proof behind the proof line
+  dvp_prove_trace tr;
   std::vector<char*> pos;
   bool have_budget = false;
   uint64_t budget = UINT64_MAX;
@@ -87,6 +128,8 @@ int main(int argc, char** argv) {
       bind_circuit = true;
     } else if (std::string(argv[i]) == "--host-witness") {
       host_witness = true;
+    } else if (std::string(argv[i]) == "--trace") {
+      trace = true;
     } else if (std::string(argv[i]) == "--check-witness") {
       check_witness = true;
     } else if (std::string(argv[i]) == "--max-rows" && i + 1 < argc) {
@@ -129,7 +172,7 @@ int main(int argc, char** argv) {
   }
   if (bind_circuit && have_circuit) fprintf(stderr, "--bind-circuit and --circuit-hash exclude each other\n");
   if (pos.size() < 2 || (bind_circuit && have_circuit)) {
-    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--bind-circuit | --circuit-hash HEX] [--host-witness] [--repeat N --threads T] | --check-witness [--max-rows N]\n", argv[0]);
+    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--bind-circuit | --circuit-hash HEX] [--host-witness] [--repeat N --threads T] [--trace] | --check-witness [--max-rows N]\n", argv[0]);
     return 2;
   }
   argc = (int)pos.size() + 1;
@@ -206,7 +249,7 @@ int main(int argc, char** argv) {
     // load_witness_from_file + Proof::prove as ONE call: the library maps the file and reduces its elements mod p on the GPU.  The
     // prover is the one the library keeps for this directory, so the budget and the binding go to that one.
     dvp_prover* cp = nullptr;
-    if (have_budget || bind_srs || bind_circuit) {
+    if (have_budget || bind_srs || bind_circuit || trace) {
       rc = dvp_cache_dir_prover(dir.c_str(), n_public, &cp);
       if (rc != DVP_OK) {
         fprintf(stderr, "open %s: %s (index %lld)\n", dir.c_str(), dvp_strerror(rc), (long long)dvp_last_error_index());
@@ -245,6 +288,10 @@ int main(int argc, char** argv) {
     rc = dvp_prove_cache_dir_witness_file(dir.c_str(), n_public, nullptr, proof, nullptr);
     if (rc != DVP_OK) {
       fprintf(stderr, "prove from %s: %s (index %lld)\n", wpath.c_str(), dvp_strerror(rc), (long long)dvp_last_error_index());
+      return 1;
+    }
+    if (trace && (rc = dvp_prover_trace_last(cp, DVP_TRACE_ALL, &tr, nullptr)) != DVP_OK) {
+      fprintf(stderr, "--trace: %s\n", dvp_strerror(rc));
       return 1;
     }
     if (have_budget)
@@ -327,6 +374,11 @@ int main(int argc, char** argv) {
                   (unsigned long long)dvp_prover_msm_table_bytes(p, which, nullptr),
                   reason == 1 ? ", limited by the budget" : reason == 2 ? ", table refused by the runtime" : "");
       }
+    if (trace && rc == DVP_OK && (rc = dvp_prover_trace_last(p, DVP_TRACE_ALL, &tr, nullptr)) != DVP_OK) {
+      fprintf(stderr, "--trace: %s\n", dvp_strerror(rc));
+      dvp_prover_destroy(p);
+      return 1;
+    }
     dvp_prover_destroy(p);
     if (rc != DVP_OK) {
       fprintf(stderr, "prove: %s (index %lld)\n", dvp_strerror(rc), (long long)dvp_last_error_index());
@@ -335,6 +387,7 @@ int main(int argc, char** argv) {
   }
   for (int i = 0; i < 118; ++i) printf("%02x", proof[i]);
   printf("\n");
+  if (trace) print_trace(tr);
   if (repeat > 0) {
     // Throughput through the reference's own signature (Proof::prove(cache_dir, public, private) = dvp_prove_cache_dir): `threads`
     // host threads share `repeat` proofs; with two or more, the library keeps two proofs in flight on the GPU.  Every proof must

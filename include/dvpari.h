@@ -675,6 +675,69 @@ int dvp_verify_trace_batch_dev(const uint64_t tau[4], const uint64_t delta[4], c
  * bytes 0..3 cleared, read big-endian (< 2^224, canonical) */
 int dvp_sp1_public_input(uint64_t raw, uint64_t out[4]);
 
+/* BLAKE3 of an Fr vector in the reference's serialisation, Vec<Fr>::serialize_uncompressed: n as u64 little-endian, then every entry
+ * as 29 bytes little-endian canonical -- byte for byte the file dvp_file_fr_vec_write writes, so one blake3::hash per Vec<Fr> on the
+ * Rust side compares a whole vector.  n = 0 hashes the 8 count bytes.  The stream is never materialised: it is packed on the device
+ * from the 32-byte entries into a bounded window of whole 1 KiB chunks (DVP_FR_DIGEST_WINDOW of them, 61440 = 60 MiB by default, never
+ * more than the stream needs) and hashed chunk-parallel as dvp_blake3_dev hashes; device scratch = that window + 32 bytes per chunk.
+ * Host entry: limbs = n x 4 u64 canonical; an entry >= p is DVP_EINVAL with dvp_last_error_index() = its index. */
+int dvp_fr_vec_digest(const uint64_t* limbs, size_t n, uint8_t out[32]);
+/* the same over n x 32 bytes on the device, enqueued on `stream` (scratch comes from and returns to the stream's pool; nothing waits).
+ * montgomery != 0: the entries are a R mod p and are converted on their way into the stream.  Nothing is range-checked: the low 29
+ * bytes of every (converted) entry are hashed as they are.  d_out32: 32 bytes on the device. */
+int dvp_fr_vec_digest_dev(const void* d_fr, size_t n, int montgomery, void* d_out32, void* stream);
+
+/* The stages of a prover's LAST proof, the mirror of dvp_verify_trace for Proof::prove (src/proving.rs:426-688): when the 118 bytes of
+ * this library and of the reference differ, the record says at which stage they part.  Nothing on the proof path produces it: the call
+ * reads what a completed proof leaves resident in the prover.
+ *   header   log2_m, n_wires, n_public, the codec rule in force (dvp_codec_get_rule), parts as delivered, mismatch
+ *   scalars  (DVP_TRACE_SCALARS) canonical limbs: the challenge alpha, z_alpha = Z_D(alpha), a0, b0, i0, r0
+ *   points   (DVP_TRACE_POINTS) msm_gm = <assignment, g_m>, msm_q = <q_vals2, g_q>, commit_p; kzg_a = <k_scalar_a, g_k_0>, kzg_b =
+ *            <k_scalar_b, g_k_1>, kzg_r = <k_scalar_r, g_k_2>, kzg_k.  commit_p and kzg_k are the proof's own (their encodings are its
+ *            bytes 0..59); the five partial commitments are computed now, through the one-shot MSM (dvp_msm_affine_dev's path) over
+ *            sub-ranges of the resident bases and scalars -- never through the fixed-base tables, so no table is built and no budget
+ *            touched, and the table path is checked against an independent one: mismatch bit 0 = commit_p != msm_gm + msm_q, bit 1 =
+ *            kzg_k != kzg_a + kzg_b + kzg_r, both sums taken on the device with the complete addition.
+ *   digests  (DVP_TRACE_DIGESTS) dvp_fr_vec_digest_dev of every intermediate vector under the name src/proving.rs gives it:
+ *            assignment (n_wires entries), evals.a/b/c/i on D and evals2.a/b/c/i on D' (m each; c is the matrix C with the Vandermonde
+ *            fold, as the reference's updated instance has it; evals2.i is in place on the Horner route too, written by the quotient
+ *            kernel), r_vals2, q_vals2, denom_invs, denom_invs2, k_scalar_a, k_scalar_b (m each), k_scalar_r (2m, interleaved
+ *            [D_i, D'_i] as :644-654).  r_vals on D is never materialised here (the K scalars fold it in) and is not part of the record.
+ * A part that was not asked for is zero.  Valid only while the prover holds a COMPLETE proof: dvp_prove / _dev / _be32 / _ark /
+ * _cache_dir* and dvp_prove_finish (behind a full begin and dvp_prove_challenge) mark it on success, every begin clears it; DVP_EINVAL
+ * before the first proof, after any proof that returned an error (DVP_EUNSAT, DVP_ECHALLENGE, ..), after dvp_prove_challenge_partial /
+ * an extend-free begin (their vectors are partial), after any call since the proof that overwrote what it left -- a staged phase entry,
+ * dvp_prover_check_witness* (it reduces its argument into the assignment's buffer; also through dvp_check_witness_cache_dir_witness_file
+ * on an open prover), dvp_prover_set_srs_* (the commitments are no longer sums over the resident bases) --, after a
+ * dvp_codec_set_rule to another rule than the proof's (its two encodings and the five made now would disagree; codec_rule in the
+ * header is the one rule of all seven), for parts == 0 or unknown bits, and under dvp_set_devices with more than one device (the
+ * sharded prover is out of scope).  The call runs on `stream`, waits for it, changes nothing a later proof reads, and two
+ * traces of one proof are identical.  It costs more than the proof: five one-shot MSMs and about 17 m x 29 bytes of hashing. */
+#define DVP_TRACE_SCALARS 0x1u
+#define DVP_TRACE_DIGESTS 0x2u
+#define DVP_TRACE_POINTS 0x4u
+#define DVP_TRACE_ALL 0x7u
+#define DVP_TRACE_MISMATCH_COMMIT 0x1u /* commit_p != msm_gm + msm_q */
+#define DVP_TRACE_MISMATCH_KZG 0x2u    /* kzg_k != kzg_a + kzg_b + kzg_r */
+typedef struct dvp_trace_point {
+  uint64_t xy[8];  /* affine x then y; zero for the point at infinity */
+  uint8_t enc[30]; /* under the codec rule of the header */
+  uint8_t inf, pad;
+} dvp_trace_point;
+typedef struct dvp_prove_trace {
+  uint32_t log2_m, n_wires, n_public, codec_rule, parts, mismatch;
+  uint64_t alpha[4], z_alpha[4], a0[4], b0[4], i0[4], r0[4];
+  dvp_trace_point msm_gm, msm_q, commit_p, kzg_a, kzg_b, kzg_r, kzg_k;
+  uint8_t assignment[32], evals_a[32], evals_b[32], evals_c[32], evals_i[32], evals2_a[32], evals2_b[32], evals2_c[32], evals2_i[32],
+      r_vals2[32], q_vals2[32], denom_invs[32], denom_invs2[32], k_scalar_a[32], k_scalar_b[32], k_scalar_r[32];
+} dvp_prove_trace;
+#ifdef __cplusplus
+static_assert(sizeof(dvp_trace_point) == 96 && sizeof(dvp_prove_trace) == 1400, "dvp_prove_trace is 1400 bytes");
+#else
+_Static_assert(sizeof(dvp_trace_point) == 96 && sizeof(dvp_prove_trace) == 1400, "dvp_prove_trace is 1400 bytes");
+#endif
+int dvp_prover_trace_last(dvp_prover* p, uint32_t parts, dvp_prove_trace* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* cache_dir formats: the files the reference's setup / prover exchange.          */
 /* Host-only code; the counted readers take out == NULL to query the element count.            */
