@@ -265,6 +265,21 @@ _SIGS = {
     "dvp_fr_vec_digest": (C.c_int, [u64p, sz, u8p]),
     "dvp_fr_vec_digest_dev": (C.c_int, [vp, sz, C.c_int, vp, vp]),
     "dvp_prover_trace_last": (C.c_int, [vp, u32, C.POINTER(ProveTrace), vp]),
+    "dvp_prover_srs_slot_add": (C.c_int, [vp, C.POINTER(u32)]),
+    "dvp_prover_srs_slot_select": (C.c_int, [vp, u32]),
+    "dvp_prover_srs_slot_active": (u32, [vp]),
+    "dvp_prover_srs_slot_count": (u32, [vp]),
+    "dvp_prover_srs_slot_drop": (C.c_int, [vp, u32]),
+    "dvp_prover_srs_slot_bytes": (C.c_int, [vp, u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dvp_prove_multi_dev": (C.c_int, [vp, vp, u32, vp, u8p, vp, vp]),
+    "dvp_prove_multi": (C.c_int, [vp, vp, u32, u64p, u32, u64p, u32, u8p, vp]),
+    "dvp_prove_multi_be32": (C.c_int, [vp, vp, u32, u8p, sz, u8p, vp]),
+    "dvp_prove_multi_ark": (C.c_int, [vp, vp, u32, u64p, u32, u64p, u32, u8p, vp]),
+    "dvp_cache_dir_add_srs_dir": (C.c_int, [C.c_char_p, u32, C.c_char_p, C.POINTER(u32)]),
+    "dvp_cache_dir_slot_set_binding": (C.c_int, [C.c_char_p, u32, u32, u8p, u8p, C.c_int]),
+    "dvp_prove_cache_dir_multi": (C.c_int, [C.c_char_p, u32, vp, u32, u64p, u64p, u32, u8p, vp]),
+    "dvp_prove_cache_dir_multi_ark": (C.c_int, [C.c_char_p, u32, vp, u32, u64p, u64p, u32, u8p, vp]),
+    "dvp_prove_cache_dir_multi_witness_file": (C.c_int, [C.c_char_p, u32, vp, u32, C.c_char_p, u8p, vp, u64p]),
 }
 EXPORTED = []
 for _name, (_res, _args) in _SIGS.items():

@@ -163,6 +163,9 @@ struct OpenEntry {
   bool bind_has[2] = {false, false};
   uint8_t bind_hash[2][32];
   uint64_t bind_gen = 0, applied_gen[2] = {0, 0};
+  // dvp_cache_dir_add_srs_dir (under the first prover's turn): the SRS directories loaded into further slots of `p`, by path.  The second
+  // prover holds slot 0 only, so every multi-slot call takes the first.
+  std::map<std::string, uint32_t> srs_dirs;
   ~OpenEntry() {
     if (p) dvp_prover_destroy(p);
     if (p2) dvp_prover_destroy(p2);
@@ -372,13 +375,14 @@ extern "C" int dvp_prover_open_cache_dir(const char* cache_dir, uint32_t n_publi
 
 // one proof on the entry of (cache_dir, n_public): takes a prover of the entry (waiting its turn), brings its binding up to date, runs
 // prove(prover), gives the prover back.  Shared by the limb flavour and the witness-file flavour of Proof::prove(cache_dir, ..).
+// first_only: the proof needs the first prover (the one that holds the further SRS slots) and waits for that one.
 template <class F>
-static int prove_on_entry(const char* cache_dir, uint32_t n_public, F prove) {
+static int prove_on_entry(const char* cache_dir, uint32_t n_public, F prove, bool first_only = false) {
   std::shared_ptr<OpenEntry> e;
   int rc = open_entry(cache_dir, n_public, &e);
   if (rc) return rc;
   long long replicas = 1;
-  (void)dvp_tune_get("DVP_CACHE_REPLICAS", &replicas);
+  if (!first_only) (void)dvp_tune_get("DVP_CACHE_REPLICAS", &replicas);
   int slot = -1;
   {
     std::unique_lock<std::mutex> g(e->slot_mu);
@@ -593,6 +597,144 @@ extern "C" int dvp_check_witness_cache_dir_witness_file(const char* cache_dir, u
   return on_circuit_prover(cache_dir, n_public, [&](dvp_prover* p) {
     return dvp_prover_check_witness_be32(p, f.p + 4, cnt, rows, rows_cap, wires, wires_cap, report);
   });
+}
+
+// ---- one prover, many verifiers (SRS per Trapdoor, src/srs.rs:31-50,177): further SRS directories in slots of the entry's first prover ----
+// run(first prover) with the prover's turn taken, like a proof
+template <class F>
+static int on_first_prover(const std::shared_ptr<OpenEntry>& e, F run) {
+  {
+    std::unique_lock<std::mutex> g(e->slot_mu);
+    e->slot_cv.wait(g, [&] { return !e->busy[0]; });
+    e->busy[0] = true;
+  }
+  const int rc = run(e->p);
+  {
+    std::lock_guard<std::mutex> g(e->slot_mu);
+    e->busy[0] = false;
+  }
+  e->slot_cv.notify_all();
+  return rc;
+}
+extern "C" int dvp_cache_dir_add_srs_dir(const char* cache_dir, uint32_t n_public, const char* srs_dir, uint32_t* slot) {
+  if (!cache_dir || !srs_dir || !slot) return DVP_EINVAL;
+  std::shared_ptr<OpenEntry> e;
+  int rc = open_entry(cache_dir, n_public, &e);
+  if (rc) return rc;
+  // srs_dir's own circuit, if it carries a dump: hashed before the turn is taken (srs_dir may be an open entry itself, cache_dir even)
+  uint8_t h_other[32];
+  bool has_dump = false;
+  {
+    MappedFile dump;
+    has_dump = dump.open_ro(join(srs_dir, "r1cs_to_dvsnark").c_str()) == DVP_OK;
+  }
+  if (has_dump) {
+    rc = dvp_circuit_hash_cache_dir(srs_dir, n_public, h_other);
+    if (rc) return rc;
+  }
+  return on_first_prover(e, [&](dvp_prover* p) -> int {
+    auto known = e->srs_dirs.find(srs_dir);
+    if (known != e->srs_dirs.end()) {
+      *slot = known->second;
+      return DVP_OK;
+    }
+    if (has_dump) {
+      uint8_t h_own[32];
+      int r = dvp_prover_circuit_hash(p, h_own);
+      if (r) return r;
+      if (memcmp(h_own, h_other, 32)) return DVP_EINVAL;  // an SRS for another circuit
+    }
+    static const char* const names[5] = {"g_m", "g_q", "g_k_0", "g_k_1", "g_k_2"};  // src/artifacts.rs:18-27
+    const size_t m = dvp_prover_msm_size(p, 1) / 4, n_wires = dvp_prover_msm_size(p, 0) - m;
+    const size_t want[5] = {n_wires, m, m, m, 2 * m};
+    MappedFile srs[5];
+    const uint8_t* payload[5];
+    size_t cnt[5];
+    for (int i = 0; i < 5; ++i) {
+      int r = srs[i].open_ro(join(srs_dir, names[i]).c_str());
+      if (r) return r;
+      r = counted_payload(srs[i], 30, &payload[i], &cnt[i]);
+      if (r) return r;
+    }
+    for (int i = 0; i < 5; ++i)
+      if (cnt[i] != want[i]) return DVP_EINVAL;
+    uint32_t k = 0;
+    int r = dvp_prover_srs_slot_add(p, &k);
+    if (r) return r;
+    const uint32_t back = dvp_prover_srs_slot_active(p);
+    r = dvp_prover_srs_slot_select(p, k);
+    for (int i = 0; i < 5 && !r; ++i) r = dvp_prover_set_srs_encoded(p, i, payload[i], cnt[i]);  // decoder and strict mode as for cache_dir's own
+    (void)dvp_prover_srs_slot_select(p, back);
+    if (r) {
+      (void)dvp_prover_srs_slot_drop(p, k);
+      return r;
+    }
+    e->srs_dirs[srs_dir] = k;
+    *slot = k;
+    return DVP_OK;
+  });
+}
+// the binding of one slot of the entry's first prover.  Slot 0 is the entry's own SRS: dvp_cache_dir_set_binding, second prover included.
+extern "C" int dvp_cache_dir_slot_set_binding(const char* cache_dir, uint32_t n_public, uint32_t slot, const uint8_t* srs_hash,
+                                              const uint8_t* circuit_hash, int bind_srs) {
+  if (!cache_dir) return DVP_EINVAL;
+  if (slot == 0) return dvp_cache_dir_set_binding(cache_dir, n_public, srs_hash, circuit_hash, bind_srs);
+  std::shared_ptr<OpenEntry> e;
+  int rc = open_entry(cache_dir, n_public, &e);
+  if (rc) return rc;
+  return on_first_prover(e, [&](dvp_prover* p) -> int {
+    const uint32_t back = dvp_prover_srs_slot_active(p);
+    int r = dvp_prover_srs_slot_select(p, slot);
+    if (r) return r;
+    uint8_t computed[32];
+    const uint8_t* sh = srs_hash;
+    if (bind_srs && !sh) {
+      r = dvp_prover_srs_hash(p, computed);
+      sh = computed;
+    }
+    if (!r) r = dvp_prover_set_transcript_binding(p, sh, circuit_hash);
+    (void)dvp_prover_srs_slot_select(p, back);
+    return r;
+  });
+}
+extern "C" int dvp_prove_cache_dir_multi(const char* cache_dir, uint32_t n_public, const uint32_t* slots, uint32_t n_slots,
+                                         const uint64_t* public_inputs, const uint64_t* private_inputs, uint32_t n_private, uint8_t* proofs,
+                                         int32_t* status) {
+  if (!cache_dir || !slots || !n_slots || !proofs || !status) return DVP_EINVAL;
+  return prove_on_entry(cache_dir, n_public, [&](dvp_prover* pv) {
+    return dvp_prove_multi(pv, slots, n_slots, public_inputs, n_public, private_inputs, n_private, proofs, status);
+  }, /*first_only=*/true);
+}
+extern "C" int dvp_prove_cache_dir_multi_ark(const char* cache_dir, uint32_t n_public, const uint32_t* slots, uint32_t n_slots,
+                                             const uint64_t* public_ark, const uint64_t* private_ark, uint32_t n_private, uint8_t* proofs,
+                                             int32_t* status) {
+  if (!cache_dir || !slots || !n_slots || !proofs || !status) return DVP_EINVAL;
+  return prove_on_entry(cache_dir, n_public, [&](dvp_prover* pv) {
+    return dvp_prove_multi_ark(pv, slots, n_slots, public_ark, n_public, private_ark, n_private, proofs, status);
+  }, /*first_only=*/true);
+}
+// the header checks of dvp_prove_cache_dir_witness_file, before cache_dir is opened
+extern "C" int dvp_prove_cache_dir_multi_witness_file(const char* cache_dir, uint32_t n_public, const uint32_t* slots, uint32_t n_slots,
+                                                      const char* witness_path, uint8_t* proofs, int32_t* status, uint64_t* public_inputs_out) {
+  if (!cache_dir || !slots || !n_slots || !proofs || !status) return DVP_EINVAL;
+  const std::string path = witness_path ? std::string(witness_path) : join(cache_dir, "witness_to_dvsnark");  // src/artifacts.rs
+  MappedFile f;
+  int rc = f.open_ro(path.c_str());
+  if (rc) return rc;
+  if (f.len < 4) return DVP_EIO;
+  const uint32_t cnt = ((uint32_t)f.p[0] << 24) | ((uint32_t)f.p[1] << 16) | ((uint32_t)f.p[2] << 8) | f.p[3];
+  if ((f.len - 4) / 32 < cnt) return DVP_EIO;
+  if (cnt < 1 + (uint64_t)n_public) return DVP_EINVAL;  // [1, public.., private..]
+  const uint8_t* payload = f.p + 4;
+  if (!dvp::fr_be32_is_one(payload)) {  // the constant wire (src/proving.rs:449-452)
+    dvp::g_last_error_index = 0;
+    return DVP_EINVAL;
+  }
+  rc = prove_on_entry(cache_dir, n_public, [&](dvp_prover* pv) { return dvp_prove_multi_be32(pv, slots, n_slots, payload, cnt, proofs, status); },
+                      /*first_only=*/true);
+  if (rc == DVP_OK && public_inputs_out)
+    for (uint32_t i = 0; i < n_public; ++i) be32_to_fr(payload + 32 * (1 + (size_t)i), public_inputs_out + 4 * (size_t)i);
+  return rc;
 }
 
 // the prover dvp_prove_cache_dir uses for (cache_dir, n_public) on the current device, opened if need be: BORROWED --

@@ -176,6 +176,11 @@ std::vector<int> mgpu_devices() {
   std::lock_guard<std::mutex> g(g_dev_mu);
   return g_devices;
 }
+static int g_multi_slot_provers = 0;  // under g_dev_mu, as the list it excludes
+void multi_slot_provers_add(int delta) {
+  std::lock_guard<std::mutex> g(g_dev_mu);
+  g_multi_slot_provers += delta;
+}
 Tune& tune() {
   static Tune t = [] { Tune x; tune_from_env(x); return x; }();
   return t;
@@ -309,6 +314,7 @@ extern "C" int dvp_device_count(void) {
 // In-library multi-GPU: the devices dvp_prove / dvp_prove_dev / dvp_prove_cache_dir spread the two MSMs of a proof over
 // (one host thread per entry).  ids[0] should be the device the prover was created on (its "home"); an id may repeat
 // (that is how the path is tested on a one-GPU box).  n <= 1 (or ids == NULL) switches back to single-device proving.
+// A list of more than one device while a prover holds a second SRS slot is DVP_EINVAL (the shards hold per-device slices of ONE SRS).
 extern "C" int dvp_set_devices(const int* ids, int n) {
   int cnt = 0;
   DVP_HIP(hipGetDeviceCount(&cnt));
@@ -316,6 +322,7 @@ extern "C" int dvp_set_devices(const int* ids, int n) {
   for (int i = 0; i < n; ++i)
     if (ids[i] < 0 || ids[i] >= cnt) return DVP_EINVAL;
   std::lock_guard<std::mutex> g(dvp::g_dev_mu);
+  if (n > 1 && dvp::g_multi_slot_provers > 0) return DVP_EINVAL;
   dvp::g_devices.assign(ids, ids + (n > 1 ? n : 0));
   return DVP_OK;
 }

@@ -259,6 +259,8 @@ Tune& tune();
 
 // devices of the in-library multi-GPU mode (dvp_set_devices); empty = single device (whatever is current)
 std::vector<int> mgpu_devices();
+// provers that hold more than one SRS slot (prove_slots.cuh): while there is one, dvp_set_devices refuses a list of more than one device
+void multi_slot_provers_add(int delta);
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 

@@ -21,6 +21,7 @@
 // unit and counted as "prove.hip:<kernel>" (common.h: DVP_LAUNCH).  Phase -> text:
 //   kernels     prove_kernels.cuh     every __global__ kernel and device helper of the stage map above
 //   state       prove_state.cuh       DevCsr, the result block, struct dvp_prover, PT, HORNER_MAX_PUB, host_vanish, prover_ready
+//   slots       prove_slots.cuh       SRS slots: the state model, add / select / drop / bytes
 //   setup       prove_setup.cuh       create / init / destroy, set_coeffs, set_matrix, the SRS setters
 //   transcript  prove_transcript.cuh  host transcript, challenge entries, binding, SRS / circuit hash, dvp_blake3
 //   begin       prove_begin.cuh       begin, extend by vector, quotient
@@ -28,6 +29,7 @@
 //   challenge   prove_challenge.cuh   vector stages, device and host challenge, _partial / _finish, dvp_prove_finish
 //   check       prove_check.cuh       the witness check (unsatisfied rows, entries >= p, suspect wires) with its own kernels, dvp_prover_row_terms
 //   trace       prove_trace.cuh       dvp_prover_trace_last: scalars, partial commitments and vector digests of the last proof
+//   multi       prove_multi.cuh       dvp_prove_multi*: one begin, then the rest of a proof once per SRS slot
 //   here        dvp_prove_dev and its two flavours, the host-witness entries, dvp_prover_debug_read, the domain-table entries
 #include <cstdlib>
 #include <algorithm>
@@ -49,6 +51,7 @@
 using namespace dvp;
 
 #include "prove_state.cuh"
+#include "prove_slots.cuh"
 #include "prove_setup.cuh"
 #include "prove_transcript.cuh"
 #include "prove_begin.cuh"
@@ -60,12 +63,14 @@ using namespace dvp;
 // Proof::prove with the assignment already resident in HBM (the timed configuration of bench.py)
 // Host-transcript flavour (rounds 1-4; still what a device list, n_public > 35 or DVP_PROVE_HOST_TRANSCRIPT=1 gets): the host waits for
 // the commitment MSM, hashes, and enqueues the challenge phase.
-static int prove_dev_host_transcript(dvp_prover* p, const void* d_assignment, uint8_t proof[118], void* stream) {
+// Both flavours are begin + rest: dvp_prove_multi_dev (prove_multi.cuh) runs the begin once and the rest once per SRS slot.
+// *witness_fault (optional) is set where the failure is the witness's own -- an unsatisfied row, a scalar >= p in the commitment
+// MSM -- and not the slot's (alpha in D u D', the K MSM's status).
+static int prove_dev_host_rest(dvp_prover* p, ProfScope& ps, uint8_t proof[118], void* stream, bool* witness_fault = nullptr) {
   hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(PROF_PROVE_TOTAL, st);
-  DVP_TRY(prove_begin_impl(p, d_assignment, 1, stream, true));
   {
     const int rc = prove_msm(p, 0, p->pts, p->pts_inf32, stream);
+    if (witness_fault) *witness_fault = true;
     if (rc == DVP_OK && p->enc_fused[0]) {  // fin_host = [a0 b0 i0 r0 | flags | encodings] as of the MSM's end
       const unsigned long long f0 = p->fin_host->flags[0];
       if (f0 != ~0ull) {
@@ -74,13 +79,20 @@ static int prove_dev_host_transcript(dvp_prover* p, const void* d_assignment, ui
       }
     } else {  // sharded MSM (no block on the host), or an MSM error: the unsatisfied row is reported first, as before
       DVP_TRY(prove_check_unsat(p, st));
+      if (witness_fault) *witness_fault = rc == DVP_EINVAL;  // the MSM's scalar-range check; any other status is the slot's
       DVP_TRY(rc);
     }
+    if (witness_fault) *witness_fault = false;
   }
   DVP_TRY(dvp_prove_challenge(p, p->pts, p->pts_inf32, stream));
   DVP_TRY(prove_msm(p, 1, p->pts + 1, p->pts_inf32 + 1, stream));
   ps.stop();
   return dvp_prove_finish(p, p->pts + 1, p->pts_inf32 + 1, proof, stream);
+}
+static int prove_dev_host_transcript(dvp_prover* p, const void* d_assignment, uint8_t proof[118], void* stream) {
+  ProfScope ps(PROF_PROVE_TOTAL, (hipStream_t)stream);
+  DVP_TRY(prove_begin_impl(p, d_assignment, 1, stream, true));
+  return prove_dev_host_rest(p, ps, proof, stream);
 }
 // Device-transcript flavour (round 5, the default on one device): begin -> commitment MSM (deferred: no final synchronisation, its
 // tail kernel leaves commit_p's 30 bytes and its scalar-range word in the prover's block) -> k_transcript -> challenge phase -> K MSM,
@@ -89,11 +101,9 @@ static int prove_dev_host_transcript(dvp_prover* p, const void* d_assignment, ui
 // bucket on a side stream while the first pair round runs; that read never idles the GPU.)  Errors are reported in the reference's
 // order from that block: unsatisfied row (src/proving.rs:389-395), scalar >= p in the witness (multi_scalar_mul's fr_to_le_bytes),
 // alpha in D u D' (:548-556), then the K MSM's own status.
-static int prove_dev_device_transcript(dvp_prover* p, const void* d_assignment, uint8_t proof[118], void* stream) {
+static int prove_dev_device_rest(dvp_prover* p, ProfScope& ps, uint8_t proof[118], void* stream, bool* witness_fault = nullptr) {
   hipStream_t st = (hipStream_t)stream;
-  if (!p->shards.empty()) shards_release(p);
-  ProfScope ps(PROF_PROVE_TOTAL, st);
-  DVP_TRY(prove_begin_impl(p, d_assignment, 1, stream, true, /*pub_to_host=*/false));
+  if (witness_fault) *witness_fault = false;
   DVP_TRY(prover_msm_partial(p, 0, 0, dvp_prover_msm_size(p, 0), p->pts, p->pts_inf32, p->blk->enc, stream, p->blk->msm_err));
   // from here on the commitment MSM is in flight on `st` and in its workspace: every error return below drains the stream first
   {
@@ -120,6 +130,7 @@ static int prove_dev_device_transcript(dvp_prover* p, const void* d_assignment, 
   memcpy(p->abir0_host, h->abir0, sizeof(h->abir0));
   memcpy(p->commit_p_host, h->enc, 30);
   p->alpha_canon = h->alpha;
+  if (witness_fault) *witness_fault = f[0] != ~0ull || e0 != ~0ull;
   if (f[0] != ~0ull) { g_last_error_index = (int64_t)f[0]; return DVP_EUNSAT; }
   if (e0 != ~0ull) { g_last_error_index = (int64_t)(e0 & 0xffffffffull); return DVP_EINVAL; }
   if (f[1] != ~0ull) { g_last_error_index = (int64_t)f[1]; return DVP_ECHALLENGE; }
@@ -128,10 +139,19 @@ static int prove_dev_device_transcript(dvp_prover* p, const void* d_assignment, 
   p->trace_mark();
   return DVP_OK;
 }
+static int prove_dev_device_transcript(dvp_prover* p, const void* d_assignment, uint8_t proof[118], void* stream) {
+  if (!p->shards.empty()) shards_release(p);
+  ProfScope ps(PROF_PROVE_TOTAL, (hipStream_t)stream);
+  DVP_TRY(prove_begin_impl(p, d_assignment, 1, stream, true, /*pub_to_host=*/false));
+  return prove_dev_device_rest(p, ps, proof, stream);
+}
+// the flavour of a proof on this prover now: the device transcript on one device, up to TRANSCRIPT_DEV_MAX_PUB public inputs
+static bool prove_flavour_device(const dvp_prover* p) {
+  return mgpu_devices().size() <= 1 && p->n_pub <= TRANSCRIPT_DEV_MAX_PUB && !tune().prove_host_transcript;
+}
 extern "C" int dvp_prove_dev(dvp_prover* p, const void* d_assignment, uint8_t proof[118], void* stream) {
   if (!p || !d_assignment || !proof) return DVP_EINVAL;
-  if (mgpu_devices().size() <= 1 && p->n_pub <= TRANSCRIPT_DEV_MAX_PUB && !tune().prove_host_transcript)
-    return prove_dev_device_transcript(p, d_assignment, proof, stream);
+  if (prove_flavour_device(p)) return prove_dev_device_transcript(p, d_assignment, proof, stream);
   return prove_dev_host_transcript(p, d_assignment, proof, stream);
 }
 
@@ -190,6 +210,8 @@ extern "C" int dvp_prove_ark(dvp_prover* p, const uint64_t* public_ark, uint32_t
   DVP_TRY(dvp_fr_from_ark_dev(p->w + 1, (size_t)p->n_wires - 1, p->w + 1, p->own_stream));
   return dvp_prove_dev(p, p->w, proof, p->own_stream);
 }
+
+#include "prove_multi.cuh"
 
 // Parity-test access to the intermediates of the last dvp_prove call.  name in:
 //  "a","b","c","i" (m each), "a2","b2","c2","i2", "r2", "q2", "ka","kb" (m), "kr" (2m),

@@ -18,6 +18,7 @@ static int prover_msm_partial(dvp_prover* p, int which, size_t lo, size_t hi, vo
   const Fr* sc = which ? p->SK : p->SA;
   const Aff* bs = which ? p->bases_k : p->bases_a;
   const uint8_t* inf = which ? p->inf_k : p->inf_a;
+  if (!bs) return DVP_EINVAL;  // an added SRS slot that no setter has touched yet holds no bases
   // after an extend-free begin (dvp_prove_begin_partial(need_extend = 0)) q2 and the r2 inside k_r were never computed:
   // a range that reads them would silently sum garbage
   if (!p->last_begin_extended && hi > lo && hi > (which ? 2 * (size_t)p->m : (size_t)p->n_wires)) return DVP_EINVAL;

@@ -1,9 +1,7 @@
 // The prover's lifetime and inputs: init / create / destroy, set_coeffs, set_matrix, the SRS setters.
 // Part of prove.hip's translation unit: included once, at global scope behind its `using namespace dvp` (map: top of prove.hip).
 #pragma once
-#include "prove_state.cuh"
-
-static void shards_release(dvp_prover* p);  // prove_msm.cuh, with the shards it releases
+#include "prove_slots.cuh"
 
 static int prover_init(dvp_prover* p, uint32_t log2_m, uint32_t n_public, uint32_t n_wires) {
   p->log_m = log2_m;
@@ -96,6 +94,10 @@ extern "C" void dvp_prover_destroy(dvp_prover* p) {
   }
   msm_fixed_destroy(p->fx[0]);
   msm_fixed_destroy(p->fx[1]);
+  const bool multi = slots_live(p) > 1;
+  for (uint32_t k = 0; k < p->slots.size(); ++k)  // the parked slots; the active one's fields are released above
+    if (k != p->active_slot) slot_free(&p->slots[k]);
+  if (multi) multi_slot_provers_add(-1);
   shards_release(p);
   if (p->mg_parts) (void)hipFree(p->mg_parts);
   if (p->tree) dvp_ecfft_destroy(p->tree);
@@ -157,6 +159,8 @@ static void srs_changed(dvp_prover* p, int slot) {
 // how every setter opens: the slot of vector `which`, which must be n points long
 static int srs_slot(dvp_prover* p, int which, size_t n, Aff** base, uint8_t** inf) {
   const size_t m = p->m, nw = p->n_wires;
+  if (which < 0 || which > 4 || n != (which == 0 ? nw : which == 4 ? 2 * m : m)) return DVP_EINVAL;
+  DVP_TRY(slot_alloc_bases(p));  // an added SRS slot gets its base vectors with its first setter
   size_t want;
   switch (which) {
     case 0: *base = p->bases_a; *inf = p->inf_a; want = nw; break;

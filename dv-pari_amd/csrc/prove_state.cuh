@@ -1,4 +1,4 @@
-// The prover's state: DevCsr, the result block (ProverBlock), struct dvp_prover, the shared constants, host_vanish, prover_ready.
+// The prover's state: DevCsr, the result block (ProverBlock), SrsSlot, struct dvp_prover, the shared constants, host_vanish, prover_ready.
 // Part of prove.hip's translation unit: included once, at global scope behind its `using namespace dvp` (map: top of prove.hip).
 #pragma once
 #include "prove_kernels.cuh"
@@ -27,6 +27,21 @@ static_assert(offsetof(ProverBlock, flags) == 128 && offsetof(ProverBlock, enc) 
               offsetof(ProverBlock, msm_err) == 240 && FIN_BYTES == 256 && offsetof(ProverBlock, neg_z) == 288 && sizeof(ProverBlock) == 320,
               "the layout the one copy per proof has always had: no padding, the host part first");
 static constexpr size_t MIX_OFF_INF = 128, MIX_OFF_ERR = 136, MIX_OFF_ERR_OUT = 152, MIX_BYTES = 160;  // dvp_prover::mix
+// An SRS slot (prove_slots.cuh): everything of a prover that depends on the SRS -- one verifier's SRS (SRS per Trapdoor,
+// src/srs.rs:31-50,177) beside the circuit and the work buffers, which do not.  The prover's own fields of these names ARE the active
+// slot, so every entry reads and writes them as it always has; the inactive slots are parked in dvp_prover::slots and selecting one
+// swaps these fields on the host.  `live` = false: an index handed out and dropped again, reusable.
+struct SrsSlot {
+  Aff *bases_a = nullptr, *bases_k = nullptr;
+  uint8_t *inf_a = nullptr, *inf_k = nullptr;
+  bool have_srs[5] = {false, false, false, false, false};
+  MsmFixedCtx* fx[2] = {nullptr, nullptr};
+  size_t fx_lo[2] = {0, 0}, fx_hi[2] = {0, 0};
+  uint64_t table_budget = UINT64_MAX;
+  bool table_refused[2] = {false, false};
+  b3d::Words8 h_ct;
+  bool live = true;
+};
 struct dvp_prover {
   uint32_t log_m = 0, m = 0, n_pub = 0, n_wires = 0;
   dvp_ecfft* tree = nullptr;  // 2m leaves (tree2n)
@@ -102,6 +117,10 @@ struct dvp_prover {
   // H(srs_hash || circuit_hash), the compile-time half of the transcript.  Default: both are hashes of empty buffers, as in the
   // reference (src/proving.rs:86-105,113-132); dvp_prover_set_transcript_binding replaces them.  Every path that derives alpha reads it.
   b3d::Words8 h_ct;
+  // the SRS slots (prove_slots.cuh): one entry per index ever handed out; slots[active_slot] is a placeholder whose content lives in
+  // the fields above (bases_a .. table_refused, h_ct) while it is active
+  std::vector<SrsSlot> slots = std::vector<SrsSlot>(1);
+  uint32_t active_slot = 0;
 };
 
 static const int PT = 256;
@@ -121,11 +140,15 @@ static Fr host_vanish(const dvp_prover* p, int which, const Fr& x_m) {
   return fr_sub(u, fr_mul(p->ctop_host[which], v));
 }
 
-static bool prover_ready(dvp_prover* p) {
-  for (int k = 0; k < 5; ++k)
-    if (!p->have_srs[k]) return false;
+// the half of prover_ready that does not depend on the SRS: coefficients and all three matrices
+static bool circuit_ready(const dvp_prover* p) {
   if (!(p->coeffs_m && p->mat[0].row_ptr && p->mat[1].row_ptr && p->mat[2].row_ptr)) return false;
   for (int k = 0; k < 3; ++k)  // whatever order set_coeffs / set_matrix were called in, every stored id must be in the table
     if (p->mat[k].nnz && p->mat[k].max_coeff_id >= p->n_coeffs) return false;
   return true;
+}
+static bool prover_ready(dvp_prover* p) {
+  for (int k = 0; k < 5; ++k)
+    if (!p->have_srs[k]) return false;
+  return circuit_ready(p);
 }

@@ -79,6 +79,32 @@ class Proof:
               "dvp_prove_cache_dir_witness_file")
         return Proof.from_bytes(out.tobytes()), pub[:num_public_inputs]
 
+    @staticmethod
+    def prove_multi(cache_dirs, public_inputs, private_inputs) -> list:
+        """one witness, one proof per verifier: cache_dirs[0] is the primary directory (circuit and its own SRS), every further
+        directory the SRS of another verifier, loaded into a slot of the primary's prover (add_srs_dir).  Phase 1 runs once
+        (dvp_prove_cache_dir_multi).  Returns a list in the order of cache_dirs: a Proof, or the DvpError of that verifier's slot."""
+        primary, slots = _multi_dirs(cache_dirs, len(_fr_arg(public_inputs)))
+        pub, prv = _fr_arg(public_inputs), _fr_arg(private_inputs)
+        out, st = np.zeros((len(slots), 118), dtype=np.uint8), np.zeros(len(slots), dtype=np.int32)
+        check(lib.dvp_prove_cache_dir_multi(primary, pub.shape[0], ptr(slots), len(slots), ptr(pub) if pub.shape[0] else None,
+                                            ptr(prv) if prv.shape[0] else None, prv.shape[0], ptr(out), ptr(st)), "dvp_prove_cache_dir_multi")
+        return _multi_results(out, st, "dvp_prove_cache_dir_multi")
+
+    @staticmethod
+    def prove_multi_witness_file(cache_dirs, num_public_inputs: int, witness_path=None):
+        """prove_multi from a witness file (None = cache_dirs[0]/witness_to_dvsnark; dvp_prove_cache_dir_multi_witness_file): returns
+        (list of Proof or DvpError, public_inputs as uint64 [num_public_inputs, 4])"""
+        import os
+
+        primary, slots = _multi_dirs(cache_dirs, num_public_inputs)
+        out, st = np.zeros((len(slots), 118), dtype=np.uint8), np.zeros(len(slots), dtype=np.int32)
+        pub = np.zeros((max(num_public_inputs, 1), 4), dtype=np.uint64)
+        wp = None if witness_path is None else os.fspath(witness_path).encode()
+        check(lib.dvp_prove_cache_dir_multi_witness_file(primary, num_public_inputs, ptr(slots), len(slots), wp, ptr(out), ptr(st), ptr(pub)),
+              "dvp_prove_cache_dir_multi_witness_file")
+        return _multi_results(out, st, "dvp_prove_cache_dir_multi_witness_file"), pub[:num_public_inputs]
+
     def a0_fr(self):
         v = int.from_bytes(self.a0, "little")
         return (v, True) if v < P else (0, False)  # FrBits::to_fr, src/curve.rs:43-59
@@ -100,6 +126,66 @@ def _raw_arg(v) -> np.ndarray:
     from ._native import ints_to_limbs
 
     return ints_to_limbs([int(x) for x in v]) if len(v) else np.zeros((0, 4), dtype=np.uint64)
+
+
+def _expand_slots(slots, live) -> np.ndarray:
+    """the `slots` argument of the prove_multi forms as uint32: None = every slot of `live` (the non-empty slots, in index order)"""
+    if slots is None:
+        slots = list(live)
+    elif isinstance(slots, (str, bytes)) or not hasattr(slots, "__iter__"):
+        raise TypeError("slots must be a sequence of slot indices or None")
+    vals = [int(k) for k in slots]
+    if any(k < 0 or k >= 1 << 32 for k in vals):
+        raise ValueError("a slot index is a uint32")
+    return np.array(vals, dtype=np.uint32)
+
+
+def _multi_results(proofs, status, where) -> list:
+    """per slot: the Proof, or the DvpError of its status (returned, not raised: the other slots' proofs stand)"""
+    from ._native import DvpError
+
+    proofs = np.asarray(proofs, dtype=np.uint8).reshape(-1, 118)
+    return [Proof.from_bytes(proofs[j].tobytes()) if int(s) == 0 else DvpError(int(s), f"{where}[{j}]") for j, s in enumerate(status)]
+
+
+def _dirs_arg(cache_dirs) -> list:
+    """a non-empty list / tuple of directories as bytes; a single path is refused (it would be read as its characters)"""
+    import os
+
+    if isinstance(cache_dirs, (str, bytes, os.PathLike)) or not isinstance(cache_dirs, (list, tuple)):
+        raise TypeError("cache_dirs must be a list of directories, the primary first")
+    if not cache_dirs:
+        raise ValueError("cache_dirs is empty")
+    return [os.fspath(d).encode() if not isinstance(d, bytes) else d for d in cache_dirs]
+
+
+def _multi_dirs(cache_dirs, num_public_inputs: int):
+    """(primary directory, slots as uint32): slot 0 for the primary, add_srs_dir's slot for every further directory"""
+    dirs = _dirs_arg(cache_dirs)
+    slots = [0] + [add_srs_dir(dirs[0], num_public_inputs, d) if d != dirs[0] else 0 for d in dirs[1:]]
+    return dirs[0], np.array(slots, dtype=np.uint32)
+
+
+def add_srs_dir(cache_dir, num_public_inputs: int, srs_dir) -> int:
+    """dvp_cache_dir_add_srs_dir: the five SRS point files of srs_dir (another verifier's SRS for the same circuit) into a new slot of the
+    prover Proof.prove(cache_dir, ..) keeps; returns the slot (the one it already has when srs_dir was added before)"""
+    import os
+
+    k = C.c_uint32(0)
+    cd = cache_dir if isinstance(cache_dir, bytes) else os.fspath(cache_dir).encode()
+    sd = srs_dir if isinstance(srs_dir, bytes) else os.fspath(srs_dir).encode()
+    check(lib.dvp_cache_dir_add_srs_dir(cd, num_public_inputs, sd, C.byref(k)), "dvp_cache_dir_add_srs_dir")
+    return int(k.value)
+
+
+def set_cache_dir_slot_binding(cache_dir, num_public_inputs: int, slot: int, srs_hash=None, circuit_hash=None, bind_srs: bool = False):
+    """dvp_cache_dir_slot_set_binding: set_cache_dir_binding for one SRS slot of cache_dir's prover"""
+    import os
+
+    ks, s = _hash_arg(srs_hash, "srs_hash")
+    kc, c = _hash_arg(circuit_hash, "circuit_hash")
+    check(lib.dvp_cache_dir_slot_set_binding(os.fspath(cache_dir).encode(), num_public_inputs, slot, s, c, int(bool(bind_srs))),
+          "dvp_cache_dir_slot_set_binding")
 
 
 def release_cache_dir(cache_dir=None):
@@ -359,6 +445,81 @@ class Prover:
         """payload of a reference point-vector file (n x 30 bytes, src/io_utils.rs:83-111)"""
         e = np.ascontiguousarray(enc, dtype=np.uint8).reshape(-1, 30)
         check(lib.dvp_prover_set_srs_encoded(self._h, which, ptr(e), e.shape[0]), "dvp_prover_set_srs_encoded")
+
+    # ---- SRS slots: one SRS per verifier on one prover (include/dvpari.h, dvp_prover_srs_slot_*) ------------
+    def add_srs(self, srs_or_encoded=None) -> int:
+        """a new SRS slot (or a dropped index reused); not selected.  srs_or_encoded: an SRS (set_srs) or the five encoded payloads
+        [g_m, g_q, g_k_0, g_k_1, g_k_2] (set_srs_encoded), loaded into the slot; None leaves it empty"""
+        k = C.c_uint32(0)
+        check(lib.dvp_prover_srs_slot_add(self._h, C.byref(k)), "dvp_prover_srs_slot_add")
+        slot = int(k.value)
+        self._dropped_slots().discard(slot)
+        if srs_or_encoded is not None:
+            back = self.active_srs()
+            self.select_srs(slot)
+            try:
+                if hasattr(srs_or_encoded, "as_list"):
+                    self.set_srs(srs_or_encoded)
+                else:
+                    for which, enc in enumerate(srs_or_encoded):
+                        self.set_srs_encoded(which, enc)
+            finally:
+                self.select_srs(back)
+        return slot
+
+    def _dropped_slots(self) -> set:
+        if not hasattr(self, "_dropped"):
+            self._dropped = set()
+        return self._dropped
+
+    def select_srs(self, slot: int):
+        """make `slot` the active one: every other method (set_srs, prove, srs_hash, msm_plan, set_table_budget, ..) acts on it"""
+        check(lib.dvp_prover_srs_slot_select(self._h, slot), "dvp_prover_srs_slot_select")
+
+    def active_srs(self) -> int:
+        return int(lib.dvp_prover_srs_slot_active(self._h))
+
+    def srs_slots(self) -> list:
+        """the slot indices in use (handed out and not dropped through this object), in index order"""
+        return [k for k in range(int(lib.dvp_prover_srs_slot_count(self._h))) if k not in self._dropped_slots()]
+
+    def drop_srs(self, slot: int):
+        """free the slot's bases and tables; the index is reused by a later add_srs.  The active slot cannot be dropped"""
+        check(lib.dvp_prover_srs_slot_drop(self._h, slot), "dvp_prover_srs_slot_drop")
+        self._dropped_slots().add(int(slot))
+
+    def srs_slot_bytes(self, slot: int):
+        """(bases, tables): bytes of HBM the slot holds now (tables are built by its first proof)"""
+        b, t = C.c_uint64(0), C.c_uint64(0)
+        check(lib.dvp_prover_srs_slot_bytes(self._h, slot, C.byref(b), C.byref(t)), "dvp_prover_srs_slot_bytes")
+        return int(b.value), int(t.value)
+
+    def _multi(self, slots, call, where) -> list:
+        sl = _expand_slots(slots, self.srs_slots())
+        n = len(sl)
+        out, st = np.zeros((max(n, 1), 118), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.int32)
+        check(call(ptr(sl) if n else None, n, ptr(out), ptr(st)), where)
+        return _multi_results(out[:n], st[:n], where)
+
+    def prove_multi(self, public_inputs, private_inputs, slots=None) -> list:
+        """one witness, one proof per SRS slot: phase 1 once, the MSMs and the challenge phase per slot (dvp_prove_multi).  slots:
+        the slot indices in the order wanted (None = every slot in use).  Returns a list: a Proof, or the DvpError of a slot that
+        could not be proven (the others stand); a failure of the witness itself (DVP_EUNSAT, ..) raises"""
+        pub, prv = _fr_arg(public_inputs), _fr_arg(private_inputs)
+        return self._multi(slots, lambda s, n, out, st: lib.dvp_prove_multi(self._h, s, n, ptr(pub) if pub.shape[0] else None, pub.shape[0],
+                                                                           ptr(prv) if prv.shape[0] else None, prv.shape[0], out, st),
+                           "dvp_prove_multi")
+
+    def prove_multi_be32(self, raw, slots=None) -> list:
+        """prove_multi from the witness as its file holds it (prove_be32's argument; dvp_prove_multi_be32)"""
+        a = fr._be32_arg(raw)
+        return self._multi(slots, lambda s, n, out, st: lib.dvp_prove_multi_be32(self._h, s, n, ptr(a) if a.shape[0] else None, a.shape[0], out, st),
+                           "dvp_prove_multi_be32")
+
+    def prove_multi_dev(self, d_assignment: int, slots=None, stream: int = 0) -> list:
+        """prove_multi with the assignment already in HBM (prove_dev's argument; dvp_prove_multi_dev)"""
+        return self._multi(slots, lambda s, n, out, st: lib.dvp_prove_multi_dev(self._h, s, n, d_assignment, out, st, stream),
+                           "dvp_prove_multi_dev")
 
     def srs_hash(self) -> bytes:
         """BLAKE3 of to_bytes() of g_k[0], g_k[1], g_k[2], g_q, g_m in that order (the stream Transcript::srs_hash would hash,

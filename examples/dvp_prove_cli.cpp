@@ -3,7 +3,7 @@
 // (src/proving.rs:426) from files alone:
 //
 //   dvp_prove_cli <cache_dir> <n_public> [<proof_out>] [--devices 0,1,2,3] [--table-budget <bytes>] [--bind-srs] [--bind-circuit | --circuit-hash <hex>]
-//                 [--host-witness] [--repeat N --threads T] [--trace]
+//                 [--host-witness] [--repeat N --threads T] [--trace] [--also <srs_dir>]...
 //   dvp_prove_cli <cache_dir> <n_public> --check-witness [--max-rows N]
 //
 // --check-witness: explain the witness instead of proving (dvp_check_witness_cache_dir_witness_file; needs the dump and the witness
@@ -20,6 +20,14 @@
 // words, alpha, z_alpha, a0, b0, i0, r0, the seven points (x, y, infinity flag, 30-byte encoding) and the sixteen vector digests under
 // the names src/proving.rs gives the vectors: what a host compares field by field when its reference prover's bytes differ
 // ("When the bytes differ").  Single device only; it costs more than the proof.
+//
+// --also <srs_dir> (repeatable): one witness, one proof per verifier.  Each <srs_dir> holds another verifier's SRS for the same circuit
+// (its g_m, g_q, g_k_0..2; an R1CS dump there must be the same circuit): dvp_cache_dir_add_srs_dir puts it into a slot of cache_dir's
+// prover and dvp_prove_cache_dir_multi_witness_file proves for cache_dir's own SRS and then for each --also, in order, with the
+// first phase of the proof, which does not depend on the SRS, computed once.  Prints one line per verifier, `<directory>
+// <118 bytes in hex>`; exit status 0 only if every proof was made.  --table-budget, the bindings, <proof_out> and --trace keep acting
+// on the first proof, cache_dir's own (under --trace that proof is made last, so that the trace is its trace).  Excludes
+// --host-witness, --repeat and --devices.
 //
 // --bind-srs: bind the proof's challenge to the SRS (dvp_prover_srs_hash + dvp_prover_set_transcript_binding); the SRS hash used goes
 // to stderr -- the verifier needs it (dvp_verify_cli --srs-hash).  --circuit-hash <64 hex digits>: the circuit half of the binding
@@ -110,6 +118,7 @@ int main(int argc, char** argv) {
   bool trace = false;           // --trace: print the stages of the proof behind the proof line
   dvp_prove_trace tr;
   std::vector<char*> pos;
+  std::vector<std::string> also;  // --also <srs_dir>: further verifiers' SRS directories
   bool have_budget = false;
   uint64_t budget = UINT64_MAX;
   for (int i = 1; i < argc; ++i) {
@@ -122,6 +131,8 @@ int main(int argc, char** argv) {
       }
       budget = (uint64_t)v;
       have_budget = true;
+    } else if (std::string(argv[i]) == "--also" && i + 1 < argc) {
+      also.push_back(argv[++i]);
     } else if (std::string(argv[i]) == "--bind-srs") {
       bind_srs = true;
     } else if (std::string(argv[i]) == "--bind-circuit") {
@@ -171,8 +182,10 @@ int main(int argc, char** argv) {
     }
   }
   if (bind_circuit && have_circuit) fprintf(stderr, "--bind-circuit and --circuit-hash exclude each other\n");
-  if (pos.size() < 2 || (bind_circuit && have_circuit)) {
-    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--bind-circuit | --circuit-hash HEX] [--host-witness] [--repeat N --threads T] [--trace] | --check-witness [--max-rows N]\n", argv[0]);
+  const bool also_clash = !also.empty() && (host_witness || repeat > 0 || !devices.empty());
+  if (also_clash) fprintf(stderr, "--also excludes --host-witness, --repeat and --devices\n");
+  if (pos.size() < 2 || (bind_circuit && have_circuit) || also_clash) {
+    fprintf(stderr, "usage: %s <cache_dir> <n_public> [<proof_out>] [--devices 0,1,..] [--table-budget BYTES] [--bind-srs] [--bind-circuit | --circuit-hash HEX] [--host-witness] [--repeat N --threads T] [--trace] [--also SRS_DIR]... | --check-witness [--max-rows N]\n", argv[0]);
     return 2;
   }
   argc = (int)pos.size() + 1;
@@ -285,10 +298,47 @@ int main(int argc, char** argv) {
         fprintf(stderr, "\n");
       }
     }
-    rc = dvp_prove_cache_dir_witness_file(dir.c_str(), n_public, nullptr, proof, nullptr);
+    std::vector<uint8_t> more(118 * also.size());  // the proofs for the --also directories, in their order
+    if (also.empty()) {
+      rc = dvp_prove_cache_dir_witness_file(dir.c_str(), n_public, nullptr, proof, nullptr);
+    } else {
+      // slot 0 is cache_dir's own SRS; under --trace it goes last, so that the prover's last proof is the one the trace is asked for
+      std::vector<uint32_t> slots(1 + also.size(), 0);
+      const size_t first = trace ? also.size() : 0, others = trace ? 0 : 1;
+      for (size_t k = 0; k < also.size(); ++k) {
+        rc = dvp_cache_dir_add_srs_dir(dir.c_str(), n_public, also[k].c_str(), &slots[others + k]);
+        if (rc != DVP_OK) {
+          fprintf(stderr, "--also %s: %s\n", also[k].c_str(), dvp_strerror(rc));
+          return 1;
+        }
+      }
+      std::vector<uint8_t> all(118 * slots.size());
+      std::vector<int32_t> status(slots.size(), DVP_OK);
+      rc = dvp_prove_cache_dir_multi_witness_file(dir.c_str(), n_public, slots.data(), (uint32_t)slots.size(), nullptr, all.data(), status.data(),
+                                                  nullptr);
+      for (size_t k = 0; rc == DVP_OK && k < slots.size(); ++k)
+        if (status[k] != DVP_OK) {
+          fprintf(stderr, "prove for %s: %s\n", k == first ? dir.c_str() : also[k - others].c_str(), dvp_strerror(status[k]));
+          rc = status[k];
+        }
+      if (rc == DVP_OK) {
+        memcpy(proof, all.data() + 118 * first, 118);
+        memcpy(more.data(), all.data() + 118 * others, more.size());
+      }
+    }
     if (rc != DVP_OK) {
       fprintf(stderr, "prove from %s: %s (index %lld)\n", wpath.c_str(), dvp_strerror(rc), (long long)dvp_last_error_index());
       return 1;
+    }
+    if (!also.empty()) {
+      printf("%s ", dir.c_str());
+      for (int i = 0; i < 118; ++i) printf("%02x", proof[i]);
+      printf("\n");
+      for (size_t k = 0; k < also.size(); ++k) {
+        printf("%s ", also[k].c_str());
+        for (int i = 0; i < 118; ++i) printf("%02x", more[118 * k + i]);
+        printf("\n");
+      }
     }
     if (trace && (rc = dvp_prover_trace_last(cp, DVP_TRACE_ALL, &tr, nullptr)) != DVP_OK) {
       fprintf(stderr, "--trace: %s\n", dvp_strerror(rc));
@@ -385,8 +435,10 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  for (int i = 0; i < 118; ++i) printf("%02x", proof[i]);
-  printf("\n");
+  if (also.empty()) {
+    for (int i = 0; i < 118; ++i) printf("%02x", proof[i]);
+    printf("\n");
+  }
   if (trace) print_trace(tr);
   if (repeat > 0) {
     // Throughput through the reference's own signature (Proof::prove(cache_dir, public, private) = dvp_prove_cache_dir): `threads`

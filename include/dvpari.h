@@ -379,6 +379,60 @@ int dvp_prove_be32(dvp_prover* p, const uint8_t* witness_be32, size_t n, uint8_t
 int dvp_prove_ark(dvp_prover* p, const uint64_t* public_ark, uint32_t n_public, const uint64_t* private_ark, uint32_t n_private,
                   uint8_t proof[118]);
 
+/* One witness, many verifiers.  DV-Pari is designated-verifier: every verifier runs the setup with a trapdoor of its own and so has
+ * an SRS of its own (SRS per Trapdoor, src/srs.rs:31-50,177), while the circuit, the witness and everything a proof computes before
+ * its first MSM do not depend on the SRS.  A prover therefore holds SRS SLOTS.  A slot is what depends on the SRS: the five base
+ * vectors, their fixed-base tables and table budget, and the transcript binding (bind-srs makes it a function of the SRS).  A new
+ * prover has slot 0 and it is active; every other entry of this header -- the SRS setters, every prove form, the staged begin ..
+ * finish entries, dvp_prover_srs_hash, dvp_prover_set_transcript_binding, dvp_prover_msm_plan / _coverage / _table_bytes /
+ * _partial, dvp_prover_set_table_budget, dvp_prover_trace_last -- acts on the ACTIVE slot and does what it did before slots existed.
+ *
+ * dvp_prover_srs_slot_add     (src/srs.rs:31-50,177) a new empty slot, or a dropped index reused: no bases (its first setter allocates
+ *                             them), no table limit, the reference's binding (hashes of empty buffers).  Not selected.
+ * dvp_prover_srs_slot_select  (src/srs.rs:31-50,177) makes `slot` active: a swap of host-side fields, no device work and no wait.
+ *                             Unless the slot is active already, dvp_prover_trace_last answers afterwards as after an SRS setter.
+ * dvp_prover_srs_slot_active / _count  (src/srs.rs:31-50,177) the active index / the number of indices ever handed out.
+ * dvp_prover_srs_slot_drop    (src/srs.rs:31-50,177) waits for the device (every stream), frees the slot's bases and tables and
+ *                             leaves the index empty and reusable.  The active slot or an unknown index: DVP_EINVAL.
+ * dvp_prover_srs_slot_bytes   (src/srs.rs:31-50,177) what the slot holds on the device now: the base vectors with their flag bytes
+ *                             (65 bytes per point, 0 before the first setter) and the tables (built by the slot's first proof, so 0
+ *                             before it; 0 for ever under a budget of 0).  A dropped index answers (0, 0).
+ *
+ * The table budget is per slot: the device total is the SUM over the slots (dvp_prover_msm_coverage on each selected slot says what
+ * that slot got).  Limit: slots and a device list do not combine.  With a list of more than one device in force (dvp_set_devices)
+ * dvp_prover_srs_slot_add is DVP_EINVAL, and while any prover holds more than one slot such a list is DVP_EINVAL: the shards hold
+ * per-device slices of one SRS. */
+int dvp_prover_srs_slot_add(dvp_prover* p, uint32_t* slot);
+int dvp_prover_srs_slot_select(dvp_prover* p, uint32_t slot);
+uint32_t dvp_prover_srs_slot_active(const dvp_prover* p);
+uint32_t dvp_prover_srs_slot_count(const dvp_prover* p);
+int dvp_prover_srs_slot_drop(dvp_prover* p, uint32_t slot);
+int dvp_prover_srs_slot_bytes(const dvp_prover* p, uint32_t slot, uint64_t* bases, uint64_t* tables);
+/* Proof::prove (src/proving.rs:426-688) of ONE witness for the SRS of every listed slot (src/srs.rs:31-50,177): phase 1 -- the R1CS
+ * rows, the unsatisfied-row check, the extends, the quotient -- runs once; then, per slot in the order given, exactly what
+ * dvp_prove_dev runs after it: the commitment MSM over the slot's bases, the transcript under the slot's binding, the challenge
+ * phase, the K MSM, and the 118 bytes into proofs + 118 j.  The flavour (device or host transcript) is chosen as dvp_prove_dev
+ * chooses it.  A slot may repeat (same bytes twice).
+ *   Arguments: NULL pointers and n_slots == 0 are DVP_EINVAL; a slot index never handed out or dropped is DVP_EINVAL with
+ *     dvp_last_error_index() = its position in `slots`; both before any device work.
+ *   The witness: DVP_EUNSAT with its row, or DVP_EINVAL with the index of a scalar >= p, shows at the first slot's wait as in a
+ *     single proof; the call returns it, proves no further slot and leaves `proofs` untouched.
+ *   A slot: status[j] = DVP_OK, DVP_EINVAL for a slot that lacks one of its five vectors, DVP_ECHALLENGE, or an MSM's status; the
+ *     other slots are proven all the same and the call returns DVP_OK.  proofs + 118 j is written only where status[j] == DVP_OK.
+ *   On return the slot that was active at the call is active again; dvp_prover_trace_last is valid only if the last listed slot is
+ *     that slot and its proof succeeded, and otherwise answers as after an SRS setter.
+ *   Host waits: what dvp_prove_dev waits, once per slot, and none for phase 1: in the device-transcript flavour one stream wait per
+ *     slot (plus one per MSM that is too small for a first pair round, as in a single proof).
+ * The host forms stage the witness once, as dvp_prove / dvp_prove_be32 / dvp_prove_ark do, and run on the prover's own stream. */
+int dvp_prove_multi_dev(dvp_prover* p, const uint32_t* slots, uint32_t n_slots, const void* d_assignment, uint8_t* proofs /* n_slots x 118 */,
+                        int32_t* status /* n_slots */, void* stream);
+int dvp_prove_multi(dvp_prover* p, const uint32_t* slots, uint32_t n_slots, const uint64_t* public_inputs, uint32_t n_public,
+                    const uint64_t* private_inputs, uint32_t n_private, uint8_t* proofs, int32_t* status);
+int dvp_prove_multi_be32(dvp_prover* p, const uint32_t* slots, uint32_t n_slots, const uint8_t* witness_be32, size_t n, uint8_t* proofs,
+                         int32_t* status);
+int dvp_prove_multi_ark(dvp_prover* p, const uint32_t* slots, uint32_t n_slots, const uint64_t* public_ark, uint32_t n_public,
+                        const uint64_t* private_ark, uint32_t n_private, uint8_t* proofs, int32_t* status);
+
 /* Explain an unsatisfied witness.  dvp_prove answers a witness that does not fit the circuit with DVP_EUNSAT and the smallest failing
  * row (the reference's assert, src/proving.rs:389-395); the check says how many rows fail, lists the first ones with their values,
  * counts the entries that are not below p, and names the wires that occur in failing rows only.  It runs on the device over the
@@ -881,6 +935,28 @@ int dvp_circuit_hash_cache_dir(const char* cache_dir, uint32_t n_public, uint8_t
  * element 0 is not refused but reported.  NULL report or a NULL array with a non-zero cap: DVP_EINVAL before any file is opened. */
 int dvp_check_witness_cache_dir_witness_file(const char* cache_dir, uint32_t n_public, const char* witness_path, dvp_unsat_row* rows,
                                              size_t rows_cap, dvp_suspect_wire* wires, size_t wires_cap, dvp_witness_report* report);
+/* One prover, many verifiers, from directories (SRS per Trapdoor, src/srs.rs:31-50,177): the SRS of a further verifier -- the point files
+ * g_m, g_q, g_k_0, g_k_1, g_k_2 of srs_dir (src/artifacts.rs:18-27), same reader and decoder as dvp_prover_open_cache_dir, strict-points
+ * mode honoured -- goes into a new SRS slot of the FIRST prover dvp_prove_cache_dir keeps for (cache_dir, n_public), opened if need be;
+ * *slot = its index (slot 0 is cache_dir's own SRS).  Adding the same srs_dir (same path string) again returns the slot it has.  If
+ * srs_dir holds an R1CS dump, its dvp_circuit_hash_cache_dir must equal cache_dir's: DVP_EINVAL otherwise.  A missing or short point
+ * file is DVP_EIO, a count that is not cache_dir's DVP_EINVAL; after any failure no slot has been added.  Takes the prover's turn
+ * like a proof.  A release of the entry drops the slots with it. */
+int dvp_cache_dir_add_srs_dir(const char* cache_dir, uint32_t n_public, const char* srs_dir, uint32_t* slot);
+/* dvp_cache_dir_set_binding for ONE slot (src/srs.rs:31-50,177: the binding is a function of the SRS under bind_srs): slot 0 is
+ * dvp_cache_dir_set_binding itself; any other slot is bound at once, on the first prover, taking its turn; bind_srs != 0 with
+ * srs_hash == NULL binds dvp_prover_srs_hash of that slot.  An unknown slot is DVP_EINVAL. */
+int dvp_cache_dir_slot_set_binding(const char* cache_dir, uint32_t n_public, uint32_t slot, const uint8_t* srs_hash,
+                                   const uint8_t* circuit_hash, int bind_srs);
+/* dvp_prove_multi / dvp_prove_multi_ark / dvp_prove_multi_be32 (Proof::prove, src/proving.rs:426-688, once per SRS, src/srs.rs:31-50,177)
+ * on the first prover of (cache_dir, n_public), under the locking rules of dvp_prove_cache_dir (never on a second prover: it holds slot 0
+ * only).  The witness-file form checks the file as dvp_prove_cache_dir_witness_file does, before cache_dir is opened. */
+int dvp_prove_cache_dir_multi(const char* cache_dir, uint32_t n_public, const uint32_t* slots, uint32_t n_slots, const uint64_t* public_inputs,
+                              const uint64_t* private_inputs, uint32_t n_private, uint8_t* proofs /* n_slots x 118 */, int32_t* status);
+int dvp_prove_cache_dir_multi_ark(const char* cache_dir, uint32_t n_public, const uint32_t* slots, uint32_t n_slots, const uint64_t* public_ark,
+                                  const uint64_t* private_ark, uint32_t n_private, uint8_t* proofs, int32_t* status);
+int dvp_prove_cache_dir_multi_witness_file(const char* cache_dir, uint32_t n_public, const uint32_t* slots, uint32_t n_slots,
+                                           const char* witness_path, uint8_t* proofs, int32_t* status, uint64_t* public_inputs_out);
 /* the cached prover of (cache_dir, n_public), opened if need be -- borrowed, for inspection only (debug reads, plans) */
 int dvp_cache_dir_prover(const char* cache_dir, uint32_t n_public, dvp_prover** out);
 

@@ -192,6 +192,20 @@ static void fuzz_witness_entry(const std::string& dir, int iters) {
   if (dvp_prove_cache_dir_witness_file(cd.c_str(), 2, (dir + "/no_such_file").c_str(), nullptr, nullptr) != DVP_EINVAL) FAIL();
   uint8_t proof[118];
   if (dvp_prove_cache_dir_witness_file(cd.c_str(), 2, (dir + "/no_such_file").c_str(), proof, nullptr) != DVP_EIO) FAIL();
+  // the many-verifiers form judges the same header before cache_dir is opened; dvp_cache_dir_add_srs_dir stops at the opening
+  const uint32_t slots[2] = {0, 1};
+  uint8_t proofs2[2 * 118];
+  int32_t status2[2];
+  for (int it = 0; it < iters / 4 + 2; ++it) {
+    write_file(other, it < 2 ? good : damage(good, it));
+    uint64_t pub[8];
+    const int rc = dvp_prove_cache_dir_multi_witness_file(cd.c_str(), 2, slots, 2, other.c_str(), proofs2, status2, it % 3 ? pub : nullptr);
+    if (rc == DVP_OK || (it < 2 && rc != DVP_EHIP)) FAIL();
+  }
+  if (dvp_prove_cache_dir_multi_witness_file(cd.c_str(), 2, slots, 0, other.c_str(), proofs2, status2, nullptr) != DVP_EINVAL) FAIL();
+  uint32_t slot = 0;
+  if (dvp_cache_dir_add_srs_dir(cd.c_str(), 2, cd.c_str(), &slot) != DVP_EHIP) FAIL();
+  if (dvp_cache_dir_add_srs_dir(cd.c_str(), 2, nullptr, &slot) != DVP_EINVAL) FAIL();
   dvp_cache_dir_release(nullptr);
   printf("witness file entry: %d cases; statuses EINVAL %d (element 0: %d) EHIP(reached the device entry) %d EIO %d\n", iters, rcs[1], idx0, rcs[4], rcs[6]);
   if (!rcs[1] || !rcs[4] || !rcs[6] || !idx0) FAIL();

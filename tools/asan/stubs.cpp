@@ -24,6 +24,14 @@ int dvp_prove(dvp_prover*, const uint64_t*, uint32_t, const uint64_t*, uint32_t,
 int dvp_prove_be32(dvp_prover*, const uint8_t*, size_t, uint8_t*) { return DVP_EHIP; }
 int dvp_prove_ark(dvp_prover*, const uint64_t*, uint32_t, const uint64_t*, uint32_t, uint8_t*) { return DVP_EHIP; }
 int dvp_prover_check_witness_be32(dvp_prover*, const uint8_t*, size_t, dvp_unsat_row*, size_t, dvp_suspect_wire*, size_t, dvp_witness_report*) { return DVP_EHIP; }
+int dvp_prover_srs_slot_add(dvp_prover*, uint32_t*) { return DVP_EHIP; }
+int dvp_prover_srs_slot_select(dvp_prover*, uint32_t) { return DVP_EHIP; }
+uint32_t dvp_prover_srs_slot_active(const dvp_prover*) { return 0; }
+int dvp_prover_srs_slot_drop(dvp_prover*, uint32_t) { return DVP_EHIP; }
+size_t dvp_prover_msm_size(const dvp_prover*, int) { return 0; }
+int dvp_prove_multi(dvp_prover*, const uint32_t*, uint32_t, const uint64_t*, uint32_t, const uint64_t*, uint32_t, uint8_t*, int32_t*) { return DVP_EHIP; }
+int dvp_prove_multi_be32(dvp_prover*, const uint32_t*, uint32_t, const uint8_t*, size_t, uint8_t*, int32_t*) { return DVP_EHIP; }
+int dvp_prove_multi_ark(dvp_prover*, const uint32_t*, uint32_t, const uint64_t*, uint32_t, const uint64_t*, uint32_t, uint8_t*, int32_t*) { return DVP_EHIP; }
 int dvp_tune_get(const char*, long long* v) { if (v) *v = 1; return DVP_OK; }
 hipError_t hipGetDevice(int* d) { if (d) *d = 0; return hipSuccess; }
 hipError_t hipMemGetInfo(size_t* f, size_t* t) { if (f) *f = 0; if (t) *t = 0; return hipSuccess; }
