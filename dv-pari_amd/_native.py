@@ -215,6 +215,7 @@ _SIGS = {
     "dvp_prove_finish": (C.c_int, [vp, vp, vp, u8p, vp]),
     "dvp_prover_debug_read": (C.c_int, [vp, C.c_char_p, u64p, sz]),
     "dvp_prover_debug_transcript_dev": (C.c_int, [vp, u8p, u64p, u32, u64p, u64p]),
+    "dvp_prover_debug_force_alpha": (C.c_int, [vp, u64p]),
     "dvp_prover_domains": (C.c_int, [vp, u64p, u64p]),
     "dvp_prover_domain_tables": (C.c_int, [vp, C.c_int, u64p, u64p]),
     "dvp_ecfft_domain_tables": (C.c_int, [vp, C.c_int, u64p, u64p]),

@@ -8,11 +8,15 @@
 //   begin -> [commitment MSM, possibly partial per rank] -> challenge -> [K MSM] -> finish
 // and dvp_prove / dvp_prove_dev run the phases back to back on one device.
 
-// vectors a proof extends: a, b, c', and i unless its few coefficients make Horner on D' cheaper (k_quotient<HORNER>)
+// vectors a proof extends: a, b, c', and i unless its few coefficients make Horner on D' cheaper (k_quotient<HORNER>).
+// Horner is the extend's value only while i(X) has degree < m: with n_pub > m the reference extends the m evaluations of i on D
+// (src/proving.rs:369-376, 415), i.e. the interpolant of degree < m, which is NOT i on D' -- so such a circuit always extends i,
+// whatever the knob says, and gets the reference's proof (one its verifier rejects).  This is the ONE place the route is chosen:
+// the extends by vector, the quotient, dvp_prove_multi* and the trace's digests all follow it.
 static uint32_t prover_n_ext(const dvp_prover* p) {
   uint32_t hmax = HORNER_MAX_PUB;
   if (tune().horner_max_pub >= 0) hmax = (uint32_t)tune().horner_max_pub;  // tests force either route
-  return p->n_pub <= hmax ? 3u : 4u;
+  return p->n_pub <= hmax && p->n_pub <= p->m ? 3u : 4u;
 }
 // the host's look at the unsatisfied-row flag (assert_eq!(a*b, c+i), src/proving.rs:389-395)
 static int prove_check_unsat(dvp_prover* p, hipStream_t st) {

@@ -25,7 +25,12 @@ static int challenge_vector_stages(dvp_prover* p, hipStream_t st, bool z_on_side
 // the same phase with the transcript on the device: commit_p's 30 bytes are where the commitment MSM's tail kernel wrote them
 // (the block's enc), the public inputs in the witness vector; no host round trip
 static int challenge_dev(dvp_prover* p, hipStream_t st) {
-  DVP_LAUNCH(k_transcript, dim3(1), dim3(64), 0, st, (const uint32_t*)p->blk->enc, p->SA + 1, p->n_pub, p->h_ct, &p->blk->alpha, &p->blk->alpha_m);
+  if (p->alpha_forced) {  // dvp_prover_debug_force_alpha: the pair where k_transcript would have left it (the prover outlives the copies)
+    DVP_HIP(hipMemcpyAsync(&p->blk->alpha, &p->alpha_forced_pair[0], sizeof(Fr), hipMemcpyHostToDevice, st));
+    DVP_HIP(hipMemcpyAsync(&p->blk->alpha_m, &p->alpha_forced_pair[1], sizeof(Fr), hipMemcpyHostToDevice, st));
+  } else {
+    DVP_LAUNCH(k_transcript, dim3(1), dim3(64), 0, st, (const uint32_t*)p->blk->enc, p->SA + 1, p->n_pub, p->h_ct, &p->blk->alpha, &p->blk->alpha_m);
+  }
   DVP_HIP(hipEventRecord(p->ev_alpha, st));
   DVP_HIP(hipStreamWaitEvent(p->side, p->ev_alpha, 0));
   DVP_LAUNCH(k_zalpha, dim3(1), dim3(64), 0, p->side, &p->blk->alpha_m, p->tree->d_x0, p->tree->d_t, (int)p->log_m, p->tree->layer((int)p->log_m),
@@ -53,6 +58,7 @@ static int challenge_alpha_host(dvp_prover* p, const void* d_commit_xy, const vo
   transcript_challenge(p->commit_p_host, p->pub_host.data(), p->n_pub, (const uint8_t*)p->h_ct.w, ch);
   Fr alpha;
   (void)fr_load(ch, &alpha);  // 224 bits: always below p
+  if (p->alpha_forced) alpha = p->alpha_forced_pair[0];  // dvp_prover_debug_force_alpha
   p->alpha_canon = alpha;
   *alpha_m = fr_to_mont(alpha);
   *neg_z = fr_neg(host_vanish(p, 0, *alpha_m));

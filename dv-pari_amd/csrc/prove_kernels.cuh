@@ -85,7 +85,9 @@ k_r1cs_eval(Csr A, Csr B, Csr C, const Fr* __restrict__ coeffs_m, const Fr* __re
 
 // r2 = a2 b2 - i2 ; q2 = (r2 - c2) * z2inv        (src/proving.rs:492-508)
 // HORNER: i has only npub coefficients, so for a short public input i2 = i(d'_i) is evaluated directly (the same
-// canonical value the extend of i's evaluations yields, at npub products instead of an ECFFT pass).
+// canonical value the extend of i's evaluations yields, at npub products instead of an ECFFT pass).  Rule: HORNER only with
+// npub <= m.  Beyond that i(X) has degree >= m, the extend of its m evaluations on D is another polynomial (the interpolant of
+// degree < m), and the reference proves with that one (src/proving.rs:369-376, 415): prover_n_ext then takes the fourth extend.
 template <bool HORNER>
 __global__ void __launch_bounds__(256)
 k_quotient(Fr* __restrict__ E2, const Fr* __restrict__ z2inv_m, uint32_t m, const Fr* __restrict__ w, const Fr* __restrict__ dom2_m,

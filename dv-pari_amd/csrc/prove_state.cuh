@@ -108,6 +108,9 @@ struct dvp_prover {
   // last-proof intermediates kept for parity tests
   Fr alpha_canon, abir0_host[4];
   Fr neg_z_alpha_m;  // -Z_D(alpha), kept between dvp_prove_challenge_partial and dvp_prove_challenge_finish
+  // dvp_prover_debug_force_alpha (tests): this alpha (canonical, Montgomery) instead of the transcript's output
+  bool alpha_forced = false;
+  Fr alpha_forced_pair[2];
   std::vector<uint64_t> pub_host;
   uint8_t commit_p_host[30];
   ProverBlock* fin_host = nullptr;  // pinned mirror of the block (its device-only part: staging for alpha_m, -Z(alpha)) + a mixed MSM's merged word

@@ -121,6 +121,21 @@ extern "C" int dvp_prover_debug_transcript_dev(dvp_prover* p, const uint8_t comm
   return DVP_OK;
 }
 
+// test access to the refusal of alpha in D u D' (include/dvpari_internal.h): challenge_alpha_host and challenge_dev read the pair
+extern "C" int dvp_prover_debug_force_alpha(dvp_prover* p, const uint64_t alpha[4]) {
+  if (!p) return DVP_EINVAL;
+  if (!alpha) {
+    p->alpha_forced = false;
+    return DVP_OK;
+  }
+  Fr a;
+  if (!fr_load((const uint8_t*)alpha, &a)) return DVP_EINVAL;  // >= p
+  p->alpha_forced_pair[0] = a;
+  p->alpha_forced_pair[1] = fr_to_mont(a);
+  p->alpha_forced = true;
+  return DVP_OK;
+}
+
 extern "C" int dvp_blake3(const uint8_t* data, size_t len, uint8_t out[32]) {
   if ((len && !data) || !out) return DVP_EINVAL;
   b3::hash(data, len, out);

@@ -650,6 +650,12 @@ class Prover:
               "dvp_prover_debug_transcript_dev")
         return fr.to_int(a), fr.to_int(z)
 
+    def force_alpha(self, alpha):
+        """TEST ONLY (dvp_prover_debug_force_alpha): every later proof on this prover takes this alpha (an int below p) instead of
+        the transcript's output -- the way to a challenge inside D u D', which the library refuses with DVP_ECHALLENGE; None clears it"""
+        a = None if alpha is None else _raw_arg([alpha])
+        check(lib.dvp_prover_debug_force_alpha(self._h, None if a is None else ptr(a)), "dvp_prover_debug_force_alpha")
+
     # ---- device-resident / phased flavours --------------------------------------------------------------
     def prove_dev(self, d_assignment: int, stream: int = 0) -> Proof:
         """assignment = [1, public.., private..] as n_wires x 4 uint64 already in HBM (device pointer)."""

@@ -161,6 +161,13 @@ int dvp_setup_cache_dir_ex(const uint64_t tau[4], const uint64_t delta[4], const
 int dvp_prover_debug_transcript_dev(dvp_prover* p, const uint8_t commit_p[30], const uint64_t* public_inputs, uint32_t n_public,
                                     uint64_t out_alpha[4], uint64_t out_neg_z_alpha[4]);
 
+/* TEST ONLY: a canonical alpha (four LE u64, below p) replaces the transcript's output in every later proof on this prover -- every
+ * entry that derives alpha: dvp_prove*, dvp_prove_multi*, dvp_prove_challenge, dvp_prove_challenge_partial -- so that the refusal of a
+ * challenge in D u D' (DVP_ECHALLENGE, src/proving.rs:548-556), which a 224-bit hash never meets, can be reached.  NULL clears it;
+ * alpha >= p is DVP_EINVAL.  Host-side only: the host flavour swaps the value it hashed, the device flavour copies alpha and its
+ * Montgomery form into the prover's block in the place of k_transcript's launch; everything downstream runs unchanged. */
+int dvp_prover_debug_force_alpha(dvp_prover* p, const uint64_t alpha[4]);
+
 /* TEST ONLY: the two halves of dvp_blake3_dev apart, so that a long stream can be hashed piecewise (what dvp_prover_srs_hash does with
  * its staging windows).  leaves: the chaining values of the 1 KiB chunks of d_data[0, len), len > 0, a piece of a stream that starts at
  * chunk `chunk_base` of it (so at a multiple of 1024 bytes; every piece but the last is a multiple of 1024 bytes long) -> d_cvs, 32
